@@ -14,9 +14,11 @@ JSON line rank 0 prints, and exits non-zero if any rank fails.  Under torch.dist
 rank and WORLD_SIZE must equal --gpus.  Rank 0 prints ONE JSON line.
 
 Output (benchlib/line.py): the LAST line of stdout is the record -- the contract's top-level keys, `config` of <= 25 scalars, flat `roofline`
-and `cpu_baseline`, strict JSON, < 4 KB.  At N = 1 everything else measured outside the timed loop (`cpu_baseline_torch_sparse`, configs[2]'s
-kernels with per-kernel rooflines, the configs[3] / configs[4] shards, Walk-SAT, Reinforce, training, solved fractions) is printed BEFORE it as
-short `{"detail": name, "data": ...}` lines and written unrounded to gpurun_out/bench_detail.json.  Helpers: tools/benchlib/."""
+and `cpu_baseline`, strict JSON, < 4 KB.  A plain run sets up, warms up, times the K steps and prints it (`cpu_baseline` null).  With --full, at
+N = 1 everything else measured outside the timed loop (both CPU baselines, configs[2]'s kernels with per-kernel rooflines, the configs[3] /
+configs[4] shards, Walk-SAT, Reinforce, training, the fast build, solved fractions, the HIP events around the whole solve call) is measured
+too, printed BEFORE the record as short `{"detail": name, "data": ...}` lines and written unrounded to the side file bench_detail.json
+(benchlib/line.py; $PDP_BENCH_DETAIL).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.  Helpers: tools/benchlib/."""
 
 import argparse
 import json
@@ -36,6 +38,11 @@ from benchlib.neural import bench_neural                                        
 from benchlib.line import emit                                                                        # noqa: E402
 from benchlib.secondary import (fast_build_measurement, secondary_measurements, config_shard_measurements, big_instance_measurements,   # noqa: E402
                                 solved_fractions, driver_summary)
+from benchlib.outputs import sample_rows, write_outputs                                               # noqa: E402
+
+# initial states (q, fs, active mask, decimator: 24 B per edge, 0.30 GB on configs[1]) held at once; a longer run is timed in chunks of this
+# many steps and the states are refilled between the chunks, outside the clock
+STATE_POOL = 64
 
 
 # =====================================================================================================================
@@ -148,7 +155,14 @@ def main():
     ap.add_argument('--train-batch', type=int, default=400, help='instances of the training-step measurement (n = --n)')
     ap.add_argument('--config4-instances', type=int, default=600, help='instances (before the 4 replicas) of the configs[4] shard measurement')
     ap.add_argument('--selftest-collective', action='store_true', help='the N-rank plumbing only (no GPU work); used by the gloo test')
+    ap.add_argument('--full', action='store_true', help='measure everything next to the headline as well: CPU baselines, config.secondary, the '
+                    'fast build, solved fractions, the events around the whole solve call, detail lines and side file (off: the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last one computed as '
+                    'DIR/<name>.npy (finite float32 / float64, NaN entries flagged in <name>_nonfinite.npy; a seeded sample of the '
+                    'edge-wise arrays; rank 0)')
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_secondary = args.no_fast_build = True
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -185,14 +199,18 @@ def main():
     torch.cuda.synchronize(); setup_ms = 1e3 * (time.perf_counter() - t_setup)   # reported, never part of `value`
     E, V, F, B = prob.E, prob.V, prob.F, prob.B
     # the inputs of every step are resident before the timed region starts: one initial state (get_init_state(randomized=False),
-    # pdp_propagate.py:233-235), active mask and decimator per step -- 0.25 GB each
-    n_states = args.warmup + args.steps + 3          # + the three steps with events around the whole call
-    states = []
-    for _ in range(n_states):
-        q_ = torch.full((E, 3), 1.0, device=dev); q_.div_(3.0)
-        fs_ = torch.zeros(E, 2, device=dev); fs_[:, 0] = 0.5
-        states.append((q_, fs_, torch.ones(B, dtype=torch.uint8, device=dev), native.Decimator(prob)))
-    q, fs, am, dec = states[0]
+    # pdp_propagate.py:233-235), active mask and decimator per step -- 0.30 GB each, at most STATE_POOL of them at once
+    n_extra = 3 if args.full else 0                   # --full: the three steps with events around the whole call
+    n_states = min(args.warmup + args.steps + n_extra, STATE_POOL)
+
+    def fill_state(st=None):
+        q_, fs_, am_ = st[:3] if st is not None else (torch.empty(E, 3, device=dev), torch.empty(E, 2, device=dev),
+                                                        torch.empty(B, dtype=torch.uint8, device=dev))
+        q_.fill_(1.0); q_.div_(3.0)
+        fs_.zero_(); fs_[:, 0] = 0.5
+        am_.fill_(1)
+        return (q_, fs_, am_, native.Decimator(prob))
+    states = [fill_state() for _ in range(n_states)]
     L = native.lib()
     ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
     call_ms, iters_done, paths, launches = [], [], [], []
@@ -201,6 +219,12 @@ def main():
     # (the five state arrays and the stream do not change from step to step: their ctypes forms are made once)
     bind_args = (native.ptr(prob.active_variables), native.ptr(prob.active_functions), native.ptr(prob.solution), native.ptr(prob.is_sat),
                  native.ptr(prob.edge_mask), native._stream())
+
+    def refill():
+        "untimed: once every state of the pool has been used, fresh inputs for the next n_states steps"
+        if step_no[0] and step_no[0] % n_states == 0:
+            states[:] = [fill_state(st) for st in states]
+            torch.cuda.synchronize()
 
     def step(record, call_events=False):
         # a fresh SATProblem (solver.py:49-54: the library resets the problem's state arrays) + simplify(), then the solver on this step's
@@ -230,26 +254,42 @@ def main():
             dist.barrier()
 
     for _ in range(args.warmup):
-        step(False)
-    barrier(); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
-    torch.cuda.synchronize(); barrier()
-    elapsed = time.perf_counter() - t0
+        refill(); step(False)
+    elapsed, done = 0.0, 0
+    while done < args.steps:                            # one chunk unless the steps outnumber the state pool
+        refill()
+        chunk = min(args.steps - done, n_states - step_no[0] % n_states)
+        barrier(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(chunk):
+            step(True)
+        torch.cuda.synchronize(); barrier()
+        elapsed += time.perf_counter() - t0
+        done += chunk
     total_iters = float(sum(iters_done))
-    for _ in range(3):                                  # untimed: HIP events around the whole pdp_sp_solve call (config.solve_call_ms)
-        step(False, call_events=True)
+    if args.dump_outputs and rank == 0:
+        # what the caller of pdp_sp_solve holds after the last timed step: the message state q / fs (sampled edges), the problem's edge
+        # mask and partial assignment, the active mask, and the executed iterations of every timed step
+        q, fs, am, _ = states[(step_no[0] - 1) % n_states]
+        dump = sample_rows({'q': q, 'fs': fs, 'edge_mask': prob.edge_mask.view(-1)}, 'edge_index')
+        dump.update(sample_rows({'solution': prob.solution}, 'variable_index'))
+        dump.update(sample_rows({'active_mask': am}, 'instance_index'))
+        dump['iterations'] = np.array(iters_done, dtype=np.float64)
+        write_outputs(args.dump_outputs, dump)
+    for _ in range(n_extra):                            # untimed: HIP events around the whole pdp_sp_solve call (config.solve_call_ms)
+        refill(); step(False, call_events=True)
     del states[:]
     torch.cuda.empty_cache()
 
-    # ---- untimed: finish the forward pass once (random fill + Walk-SAT) for the solved fraction ------------------
-    prob.random_fill(seed=12345 + rank)
-    out, ws_steps = prob.local_search(prob.solution.clone(), args.walksat, 0.5, seed=999 + rank)
-    pred = prob.update_solution(out.reshape(-1).contiguous())
-    solved, unsat = prob.cnf_eval(pred.reshape(-1).contiguous())
-    stats = torch.tensor([float(B), float(solved.sum().item()), float(unsat.sum().item()), elapsed, total_iters],
-                         dtype=torch.float64, device=args.coll_dev)
+    solved = unsat = ws_steps = None
+    if args.full:
+        # ---- untimed: finish the forward pass once (random fill + Walk-SAT) for the solved fraction ------------------
+        prob.random_fill(seed=12345 + rank)
+        out, ws_steps = prob.local_search(prob.solution.clone(), args.walksat, 0.5, seed=999 + rank)
+        pred = prob.update_solution(out.reshape(-1).contiguous())
+        solved, unsat = prob.cnf_eval(pred.reshape(-1).contiguous())
+    n_solved_rank, n_unsat_rank = (float(solved.sum().item()), float(unsat.sum().item())) if args.full else (0.0, 0.0)
+    stats = torch.tensor([float(B), n_solved_rank, n_unsat_rank, elapsed, total_iters], dtype=torch.float64, device=args.coll_dev)
     ranks = 1
     if grouped():
         import torch.distributed as dist
@@ -262,7 +302,7 @@ def main():
 
     if rank == 0:
         value = iters_all / elapsed
-        kms = float(np.mean(call_ms))                   # HIP-event time of one pdp_sp_solve call (all its launches), three steps behind the timed ones
+        kms = float(np.mean(call_ms)) if call_ms else None   # HIP-event time of one pdp_sp_solve call (all its launches), three steps behind the timed ones (--full)
         it_mean = float(np.mean(iters_done))
         n_launch = float(np.mean([l['launches'] for l in launches]))
         n_replay = float(np.mean([l['replays'] for l in launches]))
@@ -270,10 +310,10 @@ def main():
         # on the launch stream around every launch; algorithmic bytes = bytes/iteration x iterations per launch
         launch_ms = float(np.mean([l['solve_kernel_ms'] for l in launches])) / n_launch
         if launch_ms <= 0.0:                            # HBM-resident fallback kernel (instances too large for the LDS): no per-launch events,
-            launch_ms = kms / max(n_launch, 1.0)        # the events around the whole call divided by its launches
+            launch_ms = kms / max(n_launch, 1.0) if kms is not None else None   # the events around the whole call divided by its launches
         replay_ms = float(np.mean([l['replay_kernel_ms'] for l in launches]))
         bytes_launch = algorithmic_bytes_per_iteration(E, V, F) * it_mean / n_launch
-        achieved = bytes_launch / (launch_ms * 1e-3) / 1e9
+        achieved = bytes_launch / (launch_ms * 1e-3) / 1e9 if launch_ms else None
         # measured HBM traffic and VALU instruction count per launch: NOT measured in this run -- read from the committed rocprofv3 PMC
         # summary of the same kernel and labelled with their source
         traffic, valu, src = None, None, None
@@ -286,7 +326,7 @@ def main():
                 scale = float(pj.get('launches_per_call', 9.0)) / max(n_launch, 1.0)
                 traffic = pj.get('k_sp_solve_lds_bytes_per_launch')
                 if traffic: traffic = float(traffic) * scale
-                if pj.get('SQ_INSTS_VALU_per_launch'):
+                if pj.get('SQ_INSTS_VALU_per_launch') and launch_ms:
                     # what binds the LDS-resident kernel: wave-level VALU instructions against the issue slots of 1024 SIMDs over the measured
                     # launch time.  A wave64 fp32 instruction occupies its SIMD for 2 cycles when the same wave has an independent instruction
                     # next and ~4 in a dependent chain (tools/micro/pk_rate.hip: 2.2 / 4.3 measured; MI355X_MICROARCH.md: 2 cycles) -- both given
@@ -302,11 +342,13 @@ def main():
         config = {'workload': "configs[1]: 'p-d-p' survey propagation, random 3-SAT n=%d m=%d batch=%d T=%d per GPU" % (args.n, m, args.batch, args.iters),
                   'E': E, 'V': V, 'F': F, 'iterations_per_step': it_mean, 'path': paths[0] if paths else None,
                   'instance_iterations_per_sec': value * args.batch, 'edge_updates_per_sec': value * 2 * E,
-                  'solve_call_ms': kms, 'kernel_launches_per_call': n_launch, 'kernel_ms_per_launch': launch_ms,
+                  'kernel_launches_per_call': n_launch, 'kernel_ms_per_launch': launch_ms,
                   'poison_replay_launches_per_call': n_replay, 'poison_replay_ms_per_call': replay_ms,
-                  'algorithmic_bytes_per_launch': bytes_launch, 'setup_ms_upload_and_layout': setup_ms, 'solved_fraction': n_solved / n_inst, 'unsat_clauses_total': n_unsat,
-                  'walksat_steps': ws_steps, 'tolerance': args.tolerance, 't_max': args.t_max, 'parallelism': 'instances sharded, dp%d' % world,
+                  'algorithmic_bytes_per_launch': bytes_launch, 'setup_ms_upload_and_layout': setup_ms,
+                  'tolerance': args.tolerance, 't_max': args.t_max, 'parallelism': 'instances sharded, dp%d' % world,
                   'semantics': 'isolated instances' if args.isolated else "reference (batch-wide couplings reproduced)"}
+        if args.full:
+            config.update(solve_call_ms=kms, solved_fraction=n_solved / n_inst, unsat_clauses_total=n_unsat, walksat_steps=ws_steps)
         if world == 1 and not args.no_secondary:
             config['solved'] = solved_fractions(args, dev, b, native, rank)
             config['secondary'] = secondary_measurements(args, dev, b, prob, native, items)
@@ -321,7 +363,7 @@ def main():
                 config['fast_build'] = fast_build_measurement(args, dev, native, host_batch, items, n_solved / n_inst)
             except Exception as ex:
                 config['fast_build'] = dict(error=repr(ex))
-        summary = driver_summary(config)                # flat scalars of every BASELINE config (detail line "summary"; ten of them in the final line)
+        summary = driver_summary(config) if args.full else {}   # flat scalars of every BASELINE config (detail line "summary"; ten of them in the final line)
         full = {
             'metric': 'pdp_iterations_per_sec', 'value': value,
             'unit': 'iterations/s (each iteration sweeps a batch of %d instances)' % args.batch,
@@ -329,7 +371,7 @@ def main():
             'ms_per_step': 1e3 * elapsed / args.steps,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'config': config,
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS if achieved else None,
                          'traffic': traffic, 'traffic_source': src, 'valu_issue': valu, 'kernel': solve_kernel_name,
                          'note': 'achieved = streaming-model algorithmic bytes (41E+36V+8F per iteration) x iterations per launch / '
                                  'average launch duration (HIP events on the launch stream, this run); the instance state is LDS-resident, '
@@ -338,7 +380,7 @@ def main():
             'cpu_baseline': cpu, 'cpu_baseline_torch_sparse': cpu_ts,
             'summary': summary,
         }
-        emit(full, side_file=(world == 1))              # short {"detail": ...} lines, then the compact record as the LAST line of stdout
+        emit(full, side_file=(world == 1 and args.full))   # short {"detail": ...} lines, then the compact record as the LAST line of stdout
     if grouped():
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -1,10 +1,12 @@
-"""bench.py on the GPU box: the line's contract fields at N = 1 (with the secondary measurements and both CPU baselines on a small
-workload) and the launcher at N = 2 (two gloo ranks sharing the box's single GPU: RCCL wants one GPU per rank)."""
+"""bench.py on the GPU box: the line's contract fields at N = 1 (--full: with the secondary measurements and both CPU baselines on a small
+workload), a plain run with --dump-outputs (the headline only, the outputs of its last timed step the same from run to run) and the
+launcher at N = 2 (two gloo ranks sharing the box's single GPU: RCCL wants one GPU per rank)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from helpers import REPO
@@ -41,7 +43,7 @@ def _bench(env_extra, *argv, detail=None):
 
 
 def test_bench_line_small_workload(tmp_path):
-    rec, line = _bench({}, '--steps', '2', '--warmup', '1', '--batch', '600', '--iters', '40', '--cpu-cores', '8', '--secondary-walksat-steps', '200',
+    rec, line = _bench({}, '--full', '--steps', '2', '--warmup', '1', '--batch', '600', '--iters', '40', '--cpu-cores', '8', '--secondary-walksat-steps', '200',
                        '--config3-batch', '200', '--config4-instances', '30', detail=tmp_path / 'detail.json')
     assert tuple(rec.keys()) == ('metric', 'value', 'unit', 'n_gpus', 'rccl_ranks', 'collective_backend', 'steps', 'warmup', 'ms_per_step', 'higher_is_better',
                                  'scaling', 'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline')
@@ -102,6 +104,37 @@ def test_bench_line_small_workload(tmp_path):
     assert 'fast_build_configs2_frac_mfma_f32' not in sm          # bf16x3 products are never priced against the fp32 MFMA peak
     assert abs(sm['configs2_np_nd_np_h128_frac_mfma_f32'] - sec['neural']['roofline']['frac']) < 1e-9 and abs(rec['config']['configs2_frac_mfma_f32'] - sm['configs2_np_nd_np_h128_frac_mfma_f32']) < 1e-5
     assert abs(sm['configs3_shard_n400_frac_mfma_f32'] - c3['roofline']['frac']) < 1e-9 and abs(sm['fast_build_it_per_s'] - fb['value']) < 1e-6 * fb['value']
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run measures the headline only: no CPU baseline, no secondary measurements, no side file.  --steps sets the timed steps also
+    past the state pool (70 steps: two chunks), and --dump-outputs writes the last timed step's results, equal from one run to the next."""
+    argv = ('--steps', '70', '--warmup', '1', '--batch', '600', '--iters', '40')
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ('dump%d' % k)
+        rec, _ = _bench({'PDP_BENCH_DETAIL': str(tmp_path / 'detail.json')}, *(argv + ('--dump-outputs', str(out))))
+        assert rec['steps'] == 70 and rec['warmup'] == 1 and rec['ms_per_step'] > 0 and rec['value'] > 0 and rec['cpu_baseline'] is None
+        assert abs(rec['value'] - 70 * rec['config']['iterations_per_step'] / (70 * rec['ms_per_step'] * 1e-3)) < 1e-3 * rec['value']
+        assert rec['config']['path'] == 'persistent-lds' and 'configs2_it_per_s' not in rec['config'] and 'solved_fraction' not in rec['config']
+        assert not (tmp_path / 'detail.json').exists()
+        files = {f.name[:-4]: np.load(str(f)) for f in out.iterdir()}
+        base = {'q', 'fs', 'edge_mask', 'edge_index', 'solution', 'variable_index', 'active_mask', 'instance_index', 'iterations'}
+        assert base <= set(files) and set(files) - base <= {n + '_nonfinite' for n in ('q', 'fs', 'edge_mask', 'solution', 'active_mask')}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        for name in set(files) - base:                         # NaN poisoning: the entries that were not finite, flagged beside the array
+            assert files[name].shape == files[name[:-len('_nonfinite')]].shape and set(np.unique(files[name])) <= {0.0, 1.0, 2.0, 3.0}
+        E, V = rec['config']['E'], rec['config']['V']
+        rows = files['edge_index'].astype(np.int64)            # a seeded sample of the edges when there are more than 2**19
+        assert len(rows) == min(E, 1 << 19) and np.all(np.diff(rows) > 0) and 0 <= rows[0] and rows[-1] < E
+        assert files['q'].shape == (len(rows), 3) and files['fs'].shape == (len(rows), 2) and files['edge_mask'].shape == (len(rows),)
+        assert files['solution'].shape == (V,) and np.array_equal(files['variable_index'], np.arange(V))
+        assert files['active_mask'].shape == (600,) and files['iterations'].shape == (70,)
+        assert abs(float(files['iterations'].mean()) - rec['config']['iterations_per_step']) < 1e-4 * rec['config']['iterations_per_step']
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name], equal_nan=True), name
 
 
 def test_bench_launcher_two_ranks_on_one_gpu():

@@ -472,3 +472,37 @@ def test_bench_final_line_is_compact_strict_json():
     slim['config'] = {k: v for k, v in full['config'].items() if not isinstance(v, dict)}
     rec2 = strict(line.emit(slim, out=io.StringIO(), side_file=False))
     assert rec2['cpu_baseline'] is None and 'configs2_it_per_s' not in rec2['config']
+
+
+def test_bench_output_dump_is_a_fixed_float_sample(tmp_path):
+    """bench.py --dump-outputs (tools/benchlib/outputs.py): arrays longer than the row limit are cut to one seeded sample of rows, the same
+    for every array of a group and from call to call, with the rows kept beside them; only finite float32 / float64 is written, at most 64 MB."""
+    import torch
+    _bench_line_module()
+    from benchlib import outputs
+    a = torch.arange(3000, dtype=torch.float32).reshape(1000, 3)
+    m = torch.arange(1000, dtype=torch.uint8)
+    d1 = outputs.sample_rows({'a': a, 'm': m}, 'idx', max_rows=100)
+    d2 = outputs.sample_rows({'a': a, 'm': m}, 'idx', max_rows=100)
+    idx = d1['idx'].astype(np.int64)
+    assert d1['idx'].dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0) and idx[-1] < 1000
+    assert np.array_equal(d1['a'], a.numpy()[idx]) and np.array_equal(d1['m'], m.numpy()[idx].astype(np.float32)) and d1['m'].dtype == np.float32
+    assert all(np.array_equal(d1[k], d2[k]) for k in d1)
+    whole = outputs.sample_rows({'a': a}, 'idx', max_rows=1000)
+    assert np.array_equal(whole['a'], a.numpy()) and np.array_equal(whole['idx'], np.arange(1000))
+    with pytest.raises(ValueError):
+        outputs.sample_rows({'a': a, 'b': torch.zeros(10)}, 'idx')
+    assert outputs.write_outputs(str(tmp_path / 'out'), d1) == sum(v.nbytes for v in d1.values())
+    assert np.array_equal(np.load(str(tmp_path / 'out' / 'a.npy')), d1['a'])
+    # the NaN poisoning the solver reproduces: non-finite entries are written as 0 and flagged beside the array, every file stays finite
+    x = np.array([[0.5, np.nan], [np.inf, -np.inf]], dtype=np.float32)
+    outputs.write_outputs(str(tmp_path / 'nf'), {'x': x, 'y': np.ones(3)})
+    got = {f.name[:-4]: np.load(str(f)) for f in (tmp_path / 'nf').iterdir()}
+    assert set(got) == {'x', 'x_nonfinite', 'y'} and all(np.isfinite(v).all() for v in got.values())
+    assert got['x'].dtype == np.float32 and np.array_equal(got['x'], [[0.5, 0.0], [0.0, 0.0]])
+    assert got['x_nonfinite'].dtype == np.float32 and np.array_equal(got['x_nonfinite'], [[0, 1], [2, 3]]) and np.array_equal(got['y'], np.ones(3))
+    with pytest.raises(TypeError):
+        outputs.write_outputs(str(tmp_path / 'bad'), {'i': np.zeros(4, dtype=np.int32)})
+    with pytest.raises(ValueError):
+        outputs.write_outputs(str(tmp_path / 'big'), {'x': np.zeros((outputs.MAX_BYTES >> 3) + 1)})
+    assert not (tmp_path / 'bad').exists() and not (tmp_path / 'big').exists()

@@ -8,6 +8,7 @@ import time
 import numpy as np
 
 from .cpu_baselines import cpu_baseline_neural
+from .outputs import sample_rows, write_outputs
 from . import REPO, HBM_PEAK_GBS, MFMA_F32_PEAK_TFLOPS, N_SIMD, CLOCK_HZ, algorithmic_bytes_per_iteration, grouped
 
 
@@ -47,15 +48,18 @@ def make_neural_model(args, T, model_type='np-nd-np', hidden=None):
     return tr, tr._model_list[0]
 
 
-def neural_step(tr, model, b, T, replication=1):
+def neural_step(tr, model, b, T, replication=1, keep=None):
+    "one forward of the model on the resident batch; the variable prediction it returns goes to keep['prediction'] when `keep` is a dict"
     import torch
     from pdp.nn.solver import OwnedState
     gm, bvm, bfm, ef = b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature']
     with torch.no_grad():
         # exactly what FactorGraphTrainerBase._predict_batch does: the initial state is handed over, not kept
-        model.forward(init_state=OwnedState(model.get_init_state(gm, bvm, bfm, ef, None, randomized=False, batch_replication=replication)),
-                      graph_map=gm, batch_variable_map=bvm, batch_function_map=bfm, edge_feature=ef, meta_data=None,
-                      is_training=False, iteration_num=T, check_termination=tr._check_recurrence_termination, batch_replication=replication)
+        out = model.forward(init_state=OwnedState(model.get_init_state(gm, bvm, bfm, ef, None, randomized=False, batch_replication=replication)),
+                            graph_map=gm, batch_variable_map=bvm, batch_function_map=bfm, edge_feature=ef, meta_data=None,
+                            is_training=False, iteration_num=T, check_termination=tr._check_recurrence_termination, batch_replication=replication)
+    if keep is not None:
+        keep['prediction'] = out[0][0]
     return model.last_run['iterations']
 
 
@@ -263,10 +267,11 @@ def bench_neural(args, dev, rank, world):
     tr, model = make_neural_model(args, T)
     E, V, F = b['graph_map'].size(1), b['batch_variable_map'].numel(), b['batch_function_map'].numel()
     iters_done, step_ms = [], []
+    last = {} if (args.dump_outputs and rank == 0) else None
 
     def step(record):
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        it = neural_step(tr, model, b, T)
+        it = neural_step(tr, model, b, T, keep=last)
         torch.cuda.synchronize()
         if record:
             step_ms.append(1e3 * (time.perf_counter() - t0)); iters_done.append(it)
@@ -283,6 +288,11 @@ def bench_neural(args, dev, rank, world):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timing = native.kernel_timing_read(); native.kernel_timing(False)
+    if last is not None:
+        # what the forward of the last timed step returned to its caller: the variable prediction, and the executed iterations of every step
+        dump = sample_rows({'prediction': last['prediction'].reshape(last['prediction'].shape[0], -1)}, 'variable_index')
+        dump['iterations'] = np.array(iters_done, dtype=np.float64)
+        write_outputs(args.dump_outputs, dump)
     tot = torch.tensor([float(sum(iters_done)), elapsed], dtype=torch.float64, device=args.coll_dev)
     ranks = 1
     if grouped():
