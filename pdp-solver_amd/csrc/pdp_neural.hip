@@ -17,9 +17,12 @@
 //                       full tiles run k_agg_post_wave, a wave per tile)
 //   hidden 128          k_gru_pipe (in-wave pipelined MFMA chains and activation slices; also the 4- / 3-input cells of p-nd-np)
 //   hidden 150          k_gru_wave (a wave owns a 32-edge tile through all five column blocks: one software pipeline per tile)
+//   any width to 512    k_gru_wide, k_agg_pre_wide, k_agg_post_wide, k_predict_wide (the shapes the generic kernels cannot hold: 32-row tiles,
+//                       next tile's rows by LDS-DMA)
 // What bounds them: on gfx950 the f32 MFMA and the VALU share issue time on a SIMD -- their times add up whichever wave issues them --
 // so beyond keeping every MFMA's operands in registers ahead of time, instruction count is what counts.
 #include "pdp_common.hpp"
+#include <initializer_list>
 
 #define ST(s) ((hipStream_t)(s))
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -2192,6 +2195,308 @@ __global__ void k_edge_active(int E, const int32_t *__restrict__ gm, const int32
         out[e] = amask ? (0.0f + (0.0f + (float)amask[var_inst[gm[e]]])) : 1.0f;
 }
 
+// ---- wide shapes: every layer width up to PDP_NEURAL_MAX_WIDTH ------------------------------------------------------------------------------
+// The generic kernels keep a 64-row tile of every layer of an operator in LDS, and k_gru / k_agg_pre_res prefetch the next tile's rows into
+// registers (at most 192 columns).  The wide kernels serve the shapes neither takes: a tile of TR = 32 MB rows (MB = 1 for the GRU and the
+// aggregator, whose 64-row tiles are exactly what the generic kernels could not fit; the predictor takes 64 where its aliased buffers fit; two
+// 32-row layers at width 512 are 132 KB), persistent over tiles, the next tile's rows brought in by LDS-DMA
+// (global_load_lds_dword: a wave-uniform LDS row base, lane-linear columns, no registers) into the buffer the current tile has finished with,
+// while the current tile's remaining chains run.  Only waves 0-3 (one per SIMD) issue the DMA: vector-memory results return in order, so such
+// a wave waits for its rows at its next weight fragment, and the SIMD's other wave keeps the matrix pipe busy (as in k_gru_pipe).  The columns
+// that do not come from a row copy (edge sign, zero pad) are written by wave 4.  Every output column is the k-ascending chain of mfma_chain
+// (the generic kernels' chain) and every epilogue the generic kernels' expression, so the results are theirs and the oracle's, bit for bit.
+#define WIDE_FETCHERS 4
+#define WIDE_SIDE 4        /* the wave that writes the sign / pad columns */
+
+__device__ __forceinline__ void dma_row(float *lds_row /* wave-uniform */, const float *src, int n)
+{
+    const int l = threadIdx.x & 63;
+    for (int c = 0; c < n; c += 64)
+        if (c + l < n)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + c + l),
+                                             (__attribute__((address_space(3))) void *)(lds_row + c), 4, 0, 0);
+}
+
+// lds_layer on a tile of 32 MB rows
+template <int MB>
+__device__ __forceinline__ void wide_layer(const float *in, int ldi, int Kp, const float *Wt, int Np, const float *bias, int n_valid, int act,
+                                           float *out, int ldo)
+{
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int nblocks = (Np / 32) * MB;
+    for (int blk = wave; blk < nblocks; blk += NWAVES) {
+        const int nb = blk / MB, mb = blk % MB;
+        const f32x16 acc = mfma_block(in, ldi, Kp, Wt, Np, nb, mb, bias);
+        const int col = 32 * nb + (l & 31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = 32 * mb + acc_row(r, l);
+            out[row * ldo + col] = (col < n_valid) ? act_apply(acc[r], act) : 0.0f;
+        }
+    }
+}
+
+// aggregator first half (k_agg_pre): the next tile's input rows arrive during layer 2
+template <int MB>
+__global__ void __launch_bounds__(NTN) k_agg_pre_wide(int E, const float *__restrict__ state, int sd, const float *__restrict__ sign,
+                                                      const float *__restrict__ emask, AggW w, float *__restrict__ h2out, int ntiles)
+{
+    constexpr int TR = 32 * MB;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int ld0 = w.Kp1 + 1, ld1 = w.Np1 + 1;
+    float *X = sm, *H1 = sm + TR * ld0;
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+    float psg = 0.0f;
+    auto fetch = [&](int tile) {
+        const int e0 = tile * TR;
+        if (wave < WIDE_FETCHERS)
+            for (int r = wave; r < TR; r += WIDE_FETCHERS)
+                if (e0 + r < E) dma_row(X + r * ld0, state + (size_t)(e0 + r) * sd, sd);
+        if (wave == WIDE_SIDE) psg = (l < TR && e0 + l < E) ? sign[e0 + l] : 0.0f;
+    };
+    auto deposit = [&]() {                                 // [state | sign | zero pad]
+        if (wave == WIDE_SIDE && l < TR) {
+            X[l * ld0 + sd] = psg;
+            for (int c = sd + 1; c < w.Kp1; ++c) X[l * ld0 + c] = 0.0f;
+        }
+    };
+    int tile = blockIdx.x;
+    if (tile < ntiles) { fetch(tile); deposit(); }
+    for (; tile < ntiles; tile += gridDim.x) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's LDS-DMA requests have landed; the barrier publishes them
+        __syncthreads();
+        wide_layer<MB>(X, ld0, w.Kp1, w.Wt1m, w.Np1, w.b1m, w.m1, ACT_LOGSIGMOID, H1, ld1);
+        __syncthreads();                                   // H1 complete, X free
+        const int next = tile + gridDim.x;
+        if (next < ntiles) fetch(next);
+        const int e0 = tile * TR;
+        const int nblocks = (w.Np2 / 32) * MB;
+        for (int blk = wave; blk < nblocks; blk += NWAVES) {
+            const int nb = blk / MB, mb = blk % MB;
+            const f32x16 acc = mfma_block(H1, ld1, w.Kp2, w.Wt2m, w.Np2, nb, mb, nullptr);
+            const int col = 32 * nb + (l & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int e = e0 + 32 * mb + acc_row(r, l);
+                if (e < E && col < w.a) {
+                    float v = pdp_logsigmoidf(acc[r]);
+                    if (emask) v = v * emask[e];
+                    h2out[(size_t)e * w.a + col] = v;
+                }
+            }
+        }
+        if (next < ntiles) deposit();
+    }
+}
+
+// aggregator second half (k_agg_post): the next tile's gathered rows agg[row(e)] arrive during layer 4; the own message is taken off at the
+// start of the tile (r = (0 + agg[row(e)]) - h2[e] * edge_mask, as in k_agg_post)
+template <int MB>
+__global__ void __launch_bounds__(NTN) k_agg_post_wide(int E, const float *__restrict__ agg, const int32_t *__restrict__ edge_row,
+                                                       const float *__restrict__ h2, const float *__restrict__ sign,
+                                                       const float *__restrict__ emask, const float *__restrict__ rowmask /*[E] or NULL*/,
+                                                       const float *__restrict__ old, AggW w, float *__restrict__ out, int ntiles)
+{
+    if (loop_stopped(rowmask, E)) return;                  // a device-driven loop has ended: this sweep writes nothing (k_edge_active)
+    constexpr int TR = 32 * MB;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int ld0 = w.Kp3 + 1, ld1 = w.Np3 + 1;
+    float *Rt = sm, *G1 = sm + TR * ld0;
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int A = w.a;
+    float psg = 0.0f;
+    auto fetch = [&](int tile) {
+        const int e0 = tile * TR;
+        if (wave < WIDE_FETCHERS) {
+            // the rows this wave copies: lane j holds the aggregate row of tile row wave + 4 j
+            const int rj = wave + WIDE_FETCHERS * l;
+            const int myrow = (l < TR / WIDE_FETCHERS && e0 + rj < E) ? edge_row[e0 + rj] : 0;
+            for (int j = 0; j < TR / WIDE_FETCHERS; ++j) {
+                const int r = wave + WIDE_FETCHERS * j;
+                const int row = __builtin_amdgcn_readlane(myrow, j);
+                if (e0 + r < E) dma_row(Rt + r * ld0, agg + (size_t)row * A, A);
+            }
+        }
+        if (wave == WIDE_SIDE) psg = (w.fd && l < TR && e0 + l < E) ? sign[e0 + l] : 0.0f;
+    };
+    auto deposit = [&]() {                                 // [r | sign (fd) | zero pad]
+        if (wave == WIDE_SIDE && l < TR)
+            for (int c = A; c < w.Kp3; ++c) Rt[l * ld0 + c] = (c == A && w.fd) ? psg : 0.0f;
+    };
+    int tile = blockIdx.x;
+    if (tile < ntiles) { fetch(tile); deposit(); }
+    for (; tile < ntiles; tile += gridDim.x) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                   // the gathered rows are in place
+        const int e0 = tile * TR;
+#pragma unroll
+        for (int q = 0; q < TR / NWAVES; ++q) {            // a wave per row, a lane per column
+            const int r = wave + NWAVES * q, e = e0 + r;
+            if (e < E) {
+                const float em = emask ? emask[e] : 1.0f;
+                for (int c = l; c < A; c += 64) {
+                    const float v = h2[(size_t)e * A + c];
+                    Rt[r * ld0 + c] = (0.0f + Rt[r * ld0 + c]) - (emask ? v * em : v);
+                }
+            }
+        }
+        __syncthreads();
+        wide_layer<MB>(Rt, ld0, w.Kp3, w.Wt1a, w.Np3, w.b1a, w.g, ACT_LOGSIGMOID, G1, ld1);
+        __syncthreads();                                   // G1 complete, Rt free
+        const int next = tile + gridDim.x;
+        if (next < ntiles) fetch(next);
+        const int nblocks = (w.Np4 / 32) * MB;
+        for (int blk = wave; blk < nblocks; blk += NWAVES) {
+            const int nb = blk / MB, mb = blk % MB;
+            const f32x16 acc = mfma_block(G1, ld1, w.Kp4, w.Wt2a, w.Np4, nb, mb, nullptr);
+            const int col = 32 * nb + (l & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int e = e0 + 32 * mb + acc_row(r, l);
+                if (e < E && col < w.out) {
+                    const float nv = pdp_logsigmoidf(acc[r]);
+                    const float mk = rowmask ? rowmask[e] : 1.0f;
+                    out[(size_t)e * w.out + col] = mk * nv + (1.0f - mk) * old[(size_t)e * w.out + col];
+                }
+            }
+        }
+        if (next < ntiles) deposit();
+    }
+}
+
+// predictor tail (k_predict_rows): rows -> G1 -> O -> head layer C1 -> Perceptron output.  G1 and C1 share a buffer; the input rows R have
+// their own when it fits (SEP: the next tile's rows arrive during the output and head layers), else they share O's (they arrive during the
+// head's last step, the dot product)
+template <int MB>
+__global__ void __launch_bounds__(NTN) k_predict_wide(int V, const float *__restrict__ agg, AggW w, HeadW hd, float *__restrict__ pred, int ntiles,
+                                                      int sep)
+{
+    constexpr int TR = 32 * MB;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int ldr = w.Kp3 + 1, ldo = w.Np4 + 1, ldg = (w.Np3 > hd.Np ? w.Np3 : hd.Np) + 1;
+    const int ra = (w.Kp3 > w.Np4 ? w.Kp3 : w.Np4) + 1;
+    float *R = sm, *O = sep ? sm + TR * ldr : sm, *GC = sep ? O + TR * ldo : sm + TR * ra;
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int A = w.a;
+    auto fetch = [&](int tile) {
+        const int v0 = tile * TR;
+        if (wave < WIDE_FETCHERS)
+            for (int r = wave; r < TR; r += WIDE_FETCHERS)
+                if (v0 + r < V) dma_row(R + r * ldr, agg + (size_t)(v0 + r) * A, A);
+    };
+    auto deposit = [&]() {                                 // zero pad (O's values when the buffer is shared)
+        if (wave == WIDE_SIDE && l < TR)
+            for (int c = A; c < w.Kp3; ++c) R[l * ldr + c] = 0.0f;
+    };
+    int tile = blockIdx.x;
+    if (tile < ntiles) { fetch(tile); deposit(); }
+    for (; tile < ntiles; tile += gridDim.x) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        const int next = tile + gridDim.x;
+        wide_layer<MB>(R, ldr, w.Kp3, w.Wt1a, w.Np3, w.b1a, w.g, ACT_LOGSIGMOID, GC, ldg);
+        __syncthreads();                                   // G1 complete, R free
+        if (sep && next < ntiles) fetch(next);
+        wide_layer<MB>(GC, ldg, w.Kp4, w.Wt2a, w.Np4, nullptr, w.out, ACT_LOGSIGMOID, O, ldo);
+        __syncthreads();                                   // O complete, G1 free
+        wide_layer<MB>(O, ldo, hd.Kp, hd.Wt1, hd.Np, hd.b1, hd.C, ACT_RELU, GC, ldg);
+        __syncthreads();                                   // C1 complete, O free
+        if (!sep && next < ntiles) fetch(next);
+        const int v0 = tile * TR;
+        if (threadIdx.x < TR && v0 + (int)threadIdx.x < V) {
+            float acc = 0.0f;
+            for (int k = 0; k < hd.C; ++k) acc = fmaf(GC[threadIdx.x * ldg + k], hd.w2[k], acc);
+            pred[v0 + threadIdx.x] = act_apply(acc, hd.out_act);
+        }
+        if (next < ntiles) deposit();
+    }
+}
+
+// GRU cell (k_gru) on 32-row tiles.  A wave owns the column blocks wave and wave + 8 (Hp <= 512) of all three gates; the three input
+// accumulators of a block are carried from its input products to its hidden products, one block at a time (two at once spill).
+__global__ void __launch_bounds__(NTN) k_gru_wide(int E, const float *__restrict__ state, const float *__restrict__ sign,
+                                                  const float *__restrict__ hprev, const float *__restrict__ rowmask, GruW g, float *__restrict__ out,
+                                                  int ntiles)
+{
+    if (loop_stopped(rowmask, E)) return;                  // a device-driven loop has ended: this sweep writes nothing (k_edge_active)
+    constexpr int TR = 32;
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int ldx = g.Kpx + 1, ldh = g.Kph + 1;
+    float *X = sm, *Hs = sm + TR * ldx;
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const int dx = g.dx, H = g.H;
+    const int hb = g.Hp / 32, N3 = 3 * g.Hp, nj = (hb + NWAVES - 1) / NWAVES;
+    float psg = 0.0f;
+    auto fetch_x = [&](int tile) {
+        const int e0 = tile * TR;
+        if (wave < WIDE_FETCHERS)
+            for (int r = wave; r < TR; r += WIDE_FETCHERS)
+                if (e0 + r < E) dma_row(X + r * ldx, state + (size_t)(e0 + r) * dx, dx);
+        if (wave == WIDE_SIDE) psg = (l < TR && e0 + l < E) ? sign[e0 + l] : 0.0f;
+    };
+    auto deposit_x = [&]() {                               // [state | sign | zero pad]
+        if (wave == WIDE_SIDE && l < TR)
+            for (int c = dx; c < g.Kpx; ++c) X[l * ldx + c] = c == dx ? psg : 0.0f;
+    };
+    auto fetch_h = [&](int tile) {
+        const int e0 = tile * TR;
+        if (wave < WIDE_FETCHERS)
+            for (int r = wave; r < TR; r += WIDE_FETCHERS)
+                if (e0 + r < E) dma_row(Hs + r * ldh, hprev + (size_t)(e0 + r) * H, H);
+    };
+    if (threadIdx.x < TR && g.Kph > H) Hs[threadIdx.x * ldh + H] = 0.0f;   // zero pad column of an odd width (never overwritten)
+    const int col_l = l & 31;
+    int tile = blockIdx.x;
+    if (tile < ntiles) { fetch_x(tile); deposit_x(); }
+    for (; tile < ntiles; tile += gridDim.x) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                   // X in place, Hs free
+        fetch_h(tile);
+        const int next = tile + gridDim.x, e0 = tile * TR;
+        // a pass per column block of this wave (two at Hp > 256): the input products of its three gates (the first pass: while the hidden
+        // rows arrive), then the hidden products and the epilogue (the last pass: while the next tile's input rows arrive)
+#pragma unroll 1
+        for (int j = 0; j < nj; ++j) {
+            const int nb = wave + NWAVES * j;
+            // gate order r, z, n (torch.nn.GRUCell); input and hidden products stay separate sums (hgates + igates)
+            f32x16 ia[3][1];
+            if (nb < hb) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) mfma_chain<1, 8>(X, ldx, g.Kpx, g.Wt_ih, N3, q * hb + nb, 0, g.b_ih, ia[q]);
+            }
+            if (j == 0 || j == nj - 1) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();                           // first pass: Hs in place; last pass: X free
+            }
+            if (j == nj - 1 && next < ntiles) fetch_x(next);
+            if (nb < hb) {
+                const int col = 32 * nb + col_l;
+                f32x16 ha[1], rg, zg;
+                mfma_chain<1, 8>(Hs, ldh, g.Kph, g.Wt_hh, N3, nb, 0, g.b_hh, ha);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) rg[r] = pdp_sigmoidf(ha[0][r] + ia[0][0][r]);
+                mfma_chain<1, 8>(Hs, ldh, g.Kph, g.Wt_hh, N3, hb + nb, 0, g.b_hh, ha);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) zg[r] = pdp_sigmoidf(ha[0][r] + ia[1][0][r]);
+                mfma_chain<1, 8>(Hs, ldh, g.Kph, g.Wt_hh, N3, 2 * hb + nb, 0, g.b_hh, ha);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = acc_row(r, l);
+                    const int e = e0 + row;
+                    if (e < E && col < H) {
+                        const float ng = pdp_tanhf_abs(ia[2][0][r] + ha[0][r] * rg[r]);
+                        const float hp = Hs[row * ldh + col];
+                        const float hnew = (hp - ng) * zg[r] + ng;
+                        const float mk = rowmask ? rowmask[e] : 1.0f;
+                        out[(size_t)e * H + col] = mk * hnew + (1.0f - mk) * hp;
+                    }
+                }
+            }
+        }
+        if (next < ntiles) deposit_x();
+    }
+}
+
 // ---- C ABI ----------------------------------------------------------------------------------------------------------------------------
 static AggW make_agg(const pdp_agg_desc *d)
 {
@@ -2253,6 +2558,27 @@ static int persistent_grid()
     return pdp_device_cus();
 }
 
+// The widest layer the neural operators take: every width of a model (hidden, message, aggregator and classifier layers) runs on one of the
+// kernels above up to this, the wide kernels' two 32-row layers then filling 132 KB of LDS.
+#define PDP_NEURAL_MAX_WIDTH 512
+static int check_widths(const char *what, std::initializer_list<int> widths)
+{
+    for (int n : widths)
+        if (n < 1 || n > PDP_NEURAL_MAX_WIDTH) {
+            pdp_set_error("%s: layer width %d is not supported (the neural operators take widths 1 to %d)", what, n, PDP_NEURAL_MAX_WIDTH);
+            return PDP_ERR_UNSUPPORTED;
+        }
+    return PDP_OK;
+}
+static int check_agg_widths(const pdp_agg_desc *d) { return check_widths("aggregator", {d->din - 1, d->m1, d->a, d->g, d->out}); }
+// a persistent wide kernel: 32 MB-row tiles, one grid of at most what stays resident
+static int wide_grid(const void *fn, size_t lds, int tiles)
+{
+    int per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NTN, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    return tiles < per_cu * persistent_grid() ? tiles : per_cu * persistent_grid();
+}
+
 // aggregator pre-transform: wave-private form (default); resident-weight persistent form when both matrices and the tile fit the LDS, tile-per-workgroup form otherwise
 static int launch_agg_pre(int E, const float *state, const float *sign, const float *edge_mask, const AggW &w, float *h2, hipStream_t st, uint32_t *bf3_ws = nullptr)
 {
@@ -2302,10 +2628,17 @@ static int launch_agg_pre(int E, const float *state, const float *sign, const fl
         const int grid = tiles < persistent_grid() ? tiles : persistent_grid();
         pdp_note_kernel(PDP_TK_AGG_PRE, "k_agg_pre_res");
         hipLaunchKernelGGL(k_agg_pre_res, dim3(grid), dim3(NTN), res1, st, E, state, w.din - 1, sign, edge_mask, w, h2, tiles);
-    } else {
+    } else if (lds1 <= LDS_RES_LIMIT) {
         int s = set_lds((const void *)k_agg_pre, lds1); if (s != PDP_OK) return s;
         pdp_note_kernel(PDP_TK_AGG_PRE, "k_agg_pre");
         hipLaunchKernelGGL(k_agg_pre, dim3(tiles), dim3(NTN), lds1, st, E, state, w.din - 1, sign, edge_mask, w, h2);
+    } else {
+        // wider than any of the above: 32-row tiles of the two layers (a 64-row tile would need the generic kernel's lds1)
+        const size_t ldsw = sizeof(float) * (size_t)32 * ((w.Kp1 + 1) + (w.Np1 + 1));
+        const int wt = (E + 31) / 32, grid = wide_grid((const void *)k_agg_pre_wide<1>, ldsw, wt);
+        int s = set_lds((const void *)k_agg_pre_wide<1>, ldsw); if (s != PDP_OK) return s;
+        pdp_note_kernel(PDP_TK_AGG_PRE, "k_agg_pre_wide<1>");
+        hipLaunchKernelGGL(k_agg_pre_wide<1>, dim3(grid), dim3(NTN), ldsw, st, E, state, w.din - 1, sign, edge_mask, w, h2, wt);
     }
     return PDP_OK;
 }
@@ -2317,16 +2650,14 @@ extern "C" int pdp_neural_aggregate_edges(pdp_problem *p, const pdp_agg_desc *d,
                                           const float *edge_mask, const uint8_t *active_mask, const float *old, float *out, void *stream)
 {
     PDP_REQUIRE(p && d && state && old && out, "NULL argument");
+    int s = check_agg_widths(d); if (s != PDP_OK) return s;
     hipStream_t st = ST(stream);
     const AggW w = make_agg(d);
     const int E = p->E, R = by_variable ? p->V : p->F;
     float *h2 = neural_ws(p, 0, (size_t)E * w.a), *agg = neural_ws(p, 1, (size_t)R * w.a), *rowmask = neural_ws(p, 2, (size_t)E + 4);
     if (!h2 || !agg || !rowmask) return PDP_ERR_HIP;
     const int tiles = (E + TM - 1) / TM;
-    const size_t lds1 = sizeof(float) * (size_t)TM * ((w.Kp1 + 1) + (w.Np1 + 1));
     const size_t lds3 = sizeof(float) * (size_t)TM * ((w.Kp3 + 1) + (w.Np3 + 1));
-    int s = set_lds((const void *)k_agg_pre, lds1); if (s != PDP_OK) return s;
-    s = set_lds((const void *)k_agg_post, lds3); if (s != PDP_OK) return s;
     hipLaunchKernelGGL(k_edge_active, dim3(1024), dim3(256), 0, st, E, p->graph_map, p->var_inst, active_mask, rowmask, p->flags + FL_LOOP_STOP);
 #ifdef PDP_FAST_MATH
     s = launch_agg_pre(E, state, p->edge_sign, edge_mask, w, h2, st, bf3_workspace(p, 2, st)); if (s != PDP_OK) return s;
@@ -2386,9 +2717,17 @@ extern "C" int pdp_neural_aggregate_edges(pdp_problem *p, const pdp_agg_desc *d,
             pdp_note_kernel(PDP_TK_AGG_POST, "k_agg_post_pf<26, 4, 50, 5>");
             hipLaunchKernelGGL((k_agg_post_pf<26, 4, 50, 5>), dim3(tiles), dim3(NTN), ldsp, st, E, agg, edge_row, h2, p->edge_sign, edge_mask, rowmask, old, w, out);
         }
-    } else {
+    } else if (lds3 <= LDS_RES_LIMIT) {
+        s = set_lds((const void *)k_agg_post, lds3); if (s != PDP_OK) return s;
         pdp_note_kernel(PDP_TK_AGG_POST, "k_agg_post");
         hipLaunchKernelGGL(k_agg_post, dim3(tiles), dim3(NTN), lds3, st, E, agg, edge_row, h2, p->edge_sign, edge_mask, rowmask, old, w, out);
+    } else {
+        // wider than the workgroup-tile kernel: 32-row tiles of the two layers (a 64-row tile would need its lds3)
+        const size_t ldsw = sizeof(float) * (size_t)32 * ((w.Kp3 + 1) + (w.Np3 + 1));
+        const int wt = (E + 31) / 32, grid = wide_grid((const void *)k_agg_post_wide<1>, ldsw, wt);
+        s = set_lds((const void *)k_agg_post_wide<1>, ldsw); if (s != PDP_OK) return s;
+        pdp_note_kernel(PDP_TK_AGG_POST, "k_agg_post_wide<1>");
+        hipLaunchKernelGGL(k_agg_post_wide<1>, dim3(grid), dim3(NTN), ldsw, st, E, agg, edge_row, h2, p->edge_sign, edge_mask, rowmask, old, w, out, wt);
     }
     PDP_LAUNCH_CHECK();
     return PDP_OK;
@@ -2400,6 +2739,7 @@ extern "C" int pdp_neural_gru(pdp_problem *p, const pdp_gru_desc *d, const float
 {
     PDP_REQUIRE(p && d && state && h && out, "NULL argument");
     PDP_REQUIRE(out != h, "output must not alias the hidden state");
+    int s = check_widths("GRU", {d->dx, d->H}); if (s != PDP_OK) return s;
     hipStream_t st = ST(stream);
     GruW g;
     g.Wt_ih = d->Wt_ih; g.Wt_hh = d->Wt_hh; g.b_ih = d->b_ih; g.b_hh = d->b_hh; g.dx = d->dx; g.H = d->H;
@@ -2408,8 +2748,19 @@ extern "C" int pdp_neural_gru(pdp_problem *p, const pdp_gru_desc *d, const float
     float *rowmask = neural_ws(p, 2, (size_t)E + 4);
     if (!rowmask) return PDP_ERR_HIP;
     const size_t lds = sizeof(float) * (size_t)TM * ((g.Kpx + 1) + (g.Kph + 1));
-    PDP_REQUIRE(g.Kpx <= 64 * PRE_C && g.Kph <= 64 * PRE_C, "GRU wider than 192 inputs is not supported by the tile prefetch");
-    int s = set_lds((const void *)k_gru, lds); if (s != PDP_OK) return s;
+    if (g.Kpx > 64 * PRE_C || g.Kph > 64 * PRE_C) {
+        // wider than the generic kernel's register prefetch: 32-row tiles, the rows by LDS-DMA
+        const size_t ldsw = sizeof(float) * (size_t)32 * ((g.Kpx + 1) + (g.Kph + 1));
+        s = set_lds((const void *)k_gru_wide, ldsw); if (s != PDP_OK) return s;
+        hipLaunchKernelGGL(k_edge_active, dim3(1024), dim3(256), 0, st, E, p->graph_map, p->var_inst, active_mask, rowmask, p->flags + FL_LOOP_STOP);
+        pdp_timed_scope timed(PDP_TK_GRU, st);
+        const int wt = (E + 31) / 32, grid = wide_grid((const void *)k_gru_wide, ldsw, wt);
+        pdp_note_kernel(PDP_TK_GRU, "k_gru_wide");
+        hipLaunchKernelGGL(k_gru_wide, dim3(grid), dim3(NTN), ldsw, st, E, state, p->edge_sign, h, rowmask, g, out, wt);
+        PDP_LAUNCH_CHECK();
+        return PDP_OK;
+    }
+    s = set_lds((const void *)k_gru, lds); if (s != PDP_OK) return s;
     hipLaunchKernelGGL(k_edge_active, dim3(1024), dim3(256), 0, st, E, p->graph_map, p->var_inst, active_mask, rowmask, p->flags + FL_LOOP_STOP);
     pdp_timed_scope timed(PDP_TK_GRU, st);
     const bool plain = generic_forced();
@@ -2519,6 +2870,7 @@ extern "C" int pdp_neural_predict(pdp_problem *p, const pdp_agg_desc *d, const p
                                   float *pred, void *stream)
 {
     PDP_REQUIRE(p && d && hd && state && pred, "NULL argument");
+    int s = check_agg_widths(d); if (s == PDP_OK) s = check_widths("predictor head", {hd->H, hd->C}); if (s != PDP_OK) return s;
     hipStream_t st = ST(stream);
     const AggW w = make_agg(d);
     HeadW h;
@@ -2527,10 +2879,7 @@ extern "C" int pdp_neural_predict(pdp_problem *p, const pdp_agg_desc *d, const p
     const int E = p->E, V = p->V;
     float *h2 = neural_ws(p, 0, (size_t)E * w.a), *agg = neural_ws(p, 1, (size_t)V * w.a);
     if (!h2 || !agg) return PDP_ERR_HIP;
-    const size_t lds1 = sizeof(float) * (size_t)TM * ((w.Kp1 + 1) + (w.Np1 + 1));
     const size_t lds4 = sizeof(float) * (size_t)TM * ((w.Kp3 + 1) + (w.Np3 + 1) + (w.Np4 + 1) + (h.Np + 1));
-    int s = set_lds((const void *)k_agg_pre, lds1); if (s != PDP_OK) return s;
-    s = set_lds((const void *)k_predict_rows, lds4); if (s != PDP_OK) return s;
 #ifdef PDP_FAST_MATH
     s = launch_agg_pre(E, state, p->edge_sign, edge_mask, w, h2, st, bf3_workspace(p, 2, st)); if (s != PDP_OK) return s;
 #else
@@ -2546,9 +2895,27 @@ extern "C" int pdp_neural_predict(pdp_problem *p, const pdp_agg_desc *d, const p
           s = set_lds((const void *)k_predict_rows_pf<26, 4, 50, 4>, ldsp); if (s != PDP_OK) return s;
           pdp_note_kernel(PDP_TK_PREDICT_HEAD, "k_predict_rows_pf<26, 4, 50, 4>");
           hipLaunchKernelGGL((k_predict_rows_pf<26, 4, 50, 4>), dim3((V + TM - 1) / TM), dim3(NTN), ldsp, st, V, agg, w, h, pred);
-      } else {
+      } else if (lds4 <= LDS_RES_LIMIT) {
+          s = set_lds((const void *)k_predict_rows, lds4); if (s != PDP_OK) return s;
           pdp_note_kernel(PDP_TK_PREDICT_HEAD, "k_predict_rows");
           hipLaunchKernelGGL(k_predict_rows, dim3((V + TM - 1) / TM), dim3(NTN), lds4, st, V, agg, w, h, pred);
+      } else {
+          // wider than the workgroup-tile kernel: 64- or 32-row tiles; the input rows get a buffer of their own when it fits
+          const size_t rs = (size_t)w.Kp3 + 1, os = (size_t)w.Np4 + 1, gs = (size_t)(w.Np3 > h.Np ? w.Np3 : h.Np) + 1;
+          const size_t ra = (w.Kp3 > w.Np4 ? w.Kp3 : w.Np4) + 1;
+          int mb = 0, sep = 0;                              // (at width 512 the 32-row shared form takes 132 KB)
+          for (int m = 2; m >= 1 && !mb; --m)
+              for (int sp = 1; sp >= 0 && !mb; --sp)
+                  if (sizeof(float) * 32 * m * (sp ? rs + os + gs : ra + gs) <= LDS_RES_LIMIT) { mb = m; sep = sp; }
+          if (!mb) mb = 1;
+          const size_t ldsw = sizeof(float) * 32 * mb * (sep ? rs + os + gs : ra + gs);
+          const int wt = (V + 32 * mb - 1) / (32 * mb);
+          const void *fn = mb == 2 ? (const void *)k_predict_wide<2> : (const void *)k_predict_wide<1>;
+          s = set_lds(fn, ldsw); if (s != PDP_OK) return s;
+          const int grid = wide_grid(fn, ldsw, wt);
+          pdp_note_kernel(PDP_TK_PREDICT_HEAD, mb == 2 ? "k_predict_wide<2>" : "k_predict_wide<1>");
+          if (mb == 2) hipLaunchKernelGGL(k_predict_wide<2>, dim3(grid), dim3(NTN), ldsw, st, V, agg, w, h, pred, wt, sep);
+          else hipLaunchKernelGGL(k_predict_wide<1>, dim3(grid), dim3(NTN), ldsw, st, V, agg, w, h, pred, wt, sep);
       } }
     PDP_LAUNCH_CHECK();
     return PDP_OK;
