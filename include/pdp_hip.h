@@ -23,7 +23,8 @@ extern "C" {
 #endif
 
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
- * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops */
+ * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
+ * pdp_exact_solve is an addition that changes no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -185,6 +186,24 @@ int pdp_local_search(pdp_problem *p, const float *pred, int iterations, float ep
 /* replaces: _deduplicate (solver.py:401-431, with the integer-division fix): pred [V] -> out [V/R],
  * chosen replica per original instance [B/R] (may be NULL) */
 int pdp_deduplicate(pdp_problem *p, const float *pred, float *out, int32_t *chosen, void *stream);
+
+/* ---- batched complete solver ---------------------------------------------------------------------------
+ * replaces: the reference's labelling hook is_sat (src/pdp/generator.py:15-17, "invoke your SAT solver of choice"), which PDP itself
+ * cannot fill: PDP is incomplete and never proves an instance unsatisfiable.  DPLL with unit propagation and chronological backtracking,
+ * no clause learning, one wave per instance ("Complete solver").
+ * Reads the topology only (instance offsets, e_var / e_sgn in clause order); bound state, simplify(), decimation and edge masks are
+ * ignored.  Any instance the layout holds is accepted (unit, empty and tautological clauses, repeated literals, variables without
+ * occurrences, instances without clauses); small instances run from LDS, the others from HBM working arrays (routing decided once per
+ * problem from the instance sizes: the only host synchronisation).  A replicated problem (R > 1) -> PDP_ERR_UNSUPPORTED.
+ * Outputs: status [B] = 1 satisfiable, 0 unsatisfiable, -1 undecided within the budget; model [V] (0 / 1) satisfies every clause of each
+ * status-1 instance and is 0 elsewhere (also for variables the search never had to assign); work [B] (may be NULL) = clause-literal reads.
+ * budget: clause-literal reads per instance, checked before every unit-propagation pass; an instance stops with -1 at the first check
+ * with work >= budget, so work < budget + 3 * (edges of the instance) (a pass reads at most every literal once, the branching scan after it
+ * at most twice).  budget <= 0 means PDP_EXACT_DEFAULT_BUDGET.
+ * Deterministic and instance-local: status, model and work of an instance do not depend on the batch around it, its position, the call
+ * or the library build.  Asynchronous on `stream`; calls on one problem must not overlap (they share its working arrays). */
+#define PDP_EXACT_DEFAULT_BUDGET (((int64_t)1) << 32)
+int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream);
 
 /* ---- persistent solve: the whole _forward_core loop in one launch ------------------------------------
  * replaces: PropagatorDecimatorSolverBase._forward_core (solver.py:355-386) for the classical

@@ -138,6 +138,10 @@ struct pdp_problem {
     int ws_route_ready, ws_nfit, ws_nbig, ws_fit_n, ws_fit_m, ws_fit_e;
     int32_t *ws_fit_list, *ws_big_list; int64_t *ws_big_off; int64_t ws_big_E, ws_big_V, ws_big_F;
     hipStream_t ws_side_stream; hipEvent_t ws_side_ev[2];
+    // complete solver (pdp_exact.hip::ex_prepare): instance order (HBM-routed first, by edges descending), "next instance" counter and the
+    // HBM route's working arrays, one block allocated on first use
+    int ex_ready, ex_nbig; size_t ex_lds_bytes;
+    char *ex_blob; int32_t *ex_order; uint32_t *ex_next; uint32_t *ex_h_lit;
     uint32_t *team_ws;          // barrier counters and reduction mailboxes of the workgroup teams (k_sp_solve<NT, true>)
     hipStream_t res_side_stream; hipEvent_t res_side_ev[2];   // the big instances' launches overlap the LDS-resident kernel on a stream of their own
     float *nws[4]; size_t nws_floats[4];             // neural workspaces (grow on demand)

@@ -1,0 +1,352 @@
+// pdp_exact.hip -- batched complete solver: labels every instance of a problem satisfiable / unsatisfiable (pdp_exact_solve).
+// The reference leaves this to "your SAT solver of choice" (src/pdp/generator.py:16); PDP itself is incomplete and cannot prove UNSAT.
+//
+// DPLL with unit propagation and chronological backtracking, no clause learning.  One wave64 (one 64-thread workgroup) per instance; a
+// persistent grid pulls instance ids from a host-sorted list (HBM-routed instances first, then by edge count descending) through one
+// global counter, so a few hard instances do not hold up a launch of easy ones.  Nothing couples two instances.
+//
+// Search state of one instance (instance-local variable ids; a literal is coded (v << 1) | negative):
+//   lit  [e]    clause-major literal codes        cptr [m+1] clause offsets into lit
+//   val  [n]    0 unassigned, 1 true, 2 false     pend [n]   polarity bits raised by unit clauses in the current pass (bit 0 true, bit 1 false)
+//   cnt  [2n]   branching counters (by literal)   trail [n]  assigned variables in assignment order
+//   mark [n+1]  trail length at each decision     dvar [n+1] decision variable of each level, bit 31 = second polarity in progress
+// Instances whose state fits EX_LDS_LIMIT run from a slab of LDS (u16 literals and offsets); the others run the same search on working
+// arrays in HBM indexed by the problem's own ids (u32 literals, the problem's int32 clause offsets).
+//
+// One propagation pass reads every clause (lane l takes clauses l, l+64, ...; a clause stops at its first true literal): a clause whose
+// literals are all false is a conflict, a clause with no true literal whose unassigned literals are all the same literal is a unit and
+// raises that literal's bit in pend with an atomic OR.  At the end of the pass every pending variable is assigned at once (both bits:
+// conflict), so the outcome of a pass does not depend on lane or wave order; only the trail order within a level does, and nothing reads
+// it.  The work counter (clause-literal reads) is a sum of per-clause counts, the branching counters are integer atomic adds, the branch
+// variable is a max of unique keys: every output is a function of the instance alone.
+#include "pdp_common.hpp"
+#include <algorithm>
+#include <vector>
+
+#define ST(s) ((hipStream_t)(s))
+
+namespace {
+
+constexpr int EX_NT = 64;                       // one wave per instance
+constexpr size_t EX_LDS_LIMIT = 48 * 1024;      // per-instance slab: at least three instances per CU (160 KiB of LDS)
+
+struct ExLds { size_t pend, cnt, trail, mark, dvar, lit, cptr, val, bytes; };
+
+// 4-byte arrays first, then the 2-byte literals and offsets, then the value bytes
+__host__ __device__ inline ExLds ex_lds_layout(int n, int m, int e)
+{
+    ExLds L;
+    size_t o = 0;
+    L.pend = o;  o += 4 * (size_t)n;
+    L.cnt = o;   o += 8 * (size_t)n;
+    L.trail = o; o += 4 * (size_t)n;
+    L.mark = o;  o += 4 * ((size_t)n + 1);
+    L.dvar = o;  o += 4 * ((size_t)n + 1);
+    L.lit = o;   o += 2 * (size_t)e;
+    L.cptr = o;  o += 2 * ((size_t)m + 1);
+    L.val = o;   o += (size_t)n;
+    L.bytes = (o + 15) & ~(size_t)15;
+    return L;
+}
+// u16 literal codes need n < 32768, u16 clause offsets e <= 65535
+inline bool ex_fits_lds(int n, int m, int e) { return n < 32768 && e <= 65535 && ex_lds_layout(n, m, e).bytes <= EX_LDS_LIMIT; }
+
+struct ExParams {
+    const int32_t *order;       // [B] instance ids: the nbig HBM-routed ones first, then the LDS-routed ones, each by edges descending
+    int nbig, B;
+    uint32_t *next;             // the "next instance" counter (zeroed before the launch)
+    int64_t budget;
+    int8_t *status; float *model; int64_t *work;
+    // working arrays of the HBM route, indexed by the problem's global ids (only the HBM-routed instances' slices are used)
+    uint32_t *h_lit;            // [E]
+    uint8_t *h_val;             // [V]
+    uint32_t *h_pend, *h_cnt;   // [V], [2V]
+    int32_t *h_trail;           // [V]
+    int32_t *h_mark;            // [V+B] (instance b at v0 + b: n+1 entries)
+    uint32_t *h_dvar;           // [V+B]
+};
+
+template <typename LitT, typename PtrT>
+struct ExInst {
+    LitT *lit; const PtrT *cptr;
+    uint8_t *val; uint32_t *pend, *cnt; int32_t *trail, *mark; uint32_t *dvar;
+    int n, m, e;
+};
+
+// Between two phases of the search every lane must see what the others wrote: a barrier of the (one-wave) workgroup; the HBM route also
+// needs the agent-scope fence (waits for the stores, invalidates the CU's L1) so that plain loads see the other lanes' stores.
+template <bool HBM>
+__device__ __forceinline__ void ex_sync()
+{
+    if constexpr (HBM) __threadfence();
+    __syncthreads();
+}
+
+__device__ __forceinline__ int ex_sum(int x)
+{
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+__device__ __forceinline__ int ex_min(int x)
+{
+    for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_xor(x, o); x = y < x ? y : x; }
+    return x;
+}
+__device__ __forceinline__ unsigned long long ex_max64(unsigned long long x)
+{
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long y = __shfl_xor(x, o); x = y > x ? y : x; }
+    return x;
+}
+
+// The DPLL search of one instance by the calling wave.  Returns 1 (satisfiable: val holds a model), 0 (unsatisfiable) or -1 (budget spent);
+// *work_out = the clause-literal reads made.  The budget is checked before every propagation pass.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t *work_out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int level = 0, tlen = 0;
+    int64_t work = 0;
+    int result = -1;
+    for (;;) {
+        if (work >= budget) break;
+        // ---- one unit-propagation pass
+        int reads = 0, conflict = 0, unit = 0, wmin = 0x7fffffff;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat) continue;
+            if (nfree == 0) conflict = 1;
+            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
+            else wmin = nfree < wmin ? nfree : wmin;
+        }
+        work += ex_sum(reads);
+        bool any_conflict = __ballot(conflict) != 0ull;
+        const bool any_unit = __ballot(unit) != 0ull;
+        if (any_unit) {
+            // assign the pending set of the pass; a variable asked for both polarities is a conflict
+            ex_sync<HBM>();
+            int bad = 0;
+            for (int base = 0; base < X.n; base += EX_NT) {
+                const int v = base + lane;
+                const uint32_t bits = v < X.n ? X.pend[v] : 0u;
+                const unsigned long long mask = __ballot(bits != 0u);
+                if (bits) {
+                    X.pend[v] = 0u;
+                    X.val[v] = (bits & 1u) ? 1 : 2;
+                    bad |= bits == 3u;
+                    X.trail[tlen + __popcll(mask & below)] = v;
+                }
+                tlen += __popcll(mask);
+            }
+            any_conflict = any_conflict || __ballot(bad) != 0ull;
+            ex_sync<HBM>();
+        }
+        if (any_conflict) {
+            // chronological backtracking: undo levels until one whose second polarity is untried
+            bool resumed = false;
+            while (level > 0) {
+                const uint32_t d = X.dvar[level];
+                const int v = (int)(d & 0x7fffffffu);
+                const int from = X.mark[level];
+                const uint32_t first = X.val[v];
+                ex_sync<HBM>();                                     // every lane has read the level before it is undone
+                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
+                tlen = from;
+                if (!(d & 0x80000000u)) {
+                    ex_sync<HBM>();
+                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
+                    ++tlen;
+                    ex_sync<HBM>();
+                    resumed = true;
+                    break;
+                }
+                --level;
+            }
+            if (!resumed) { result = 0; break; }
+            continue;
+        }
+        if (any_unit) continue;
+        wmin = ex_min(wmin);
+        if (wmin == 0x7fffffff) { result = 1; break; }          // no open clause: every clause is satisfied
+        // ---- branching: the unassigned variable with the most occurrences in the open clauses of minimum width
+        reads = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) ++nfree;
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat || nfree != wmin) continue;
+            for (int j = a; j < z; ++j) {
+                const uint32_t L = X.lit[j];
+                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+            }
+            reads += z - a;
+        }
+        work += ex_sum(reads);
+        ex_sync<HBM>();
+        unsigned long long best = 0ull;
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+            if (p | q) {
+                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+                // score, then the lower index, then the polarity (true when its occurrences are at least as many)
+                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                               (p >= q ? 1ull : 0ull);
+                best = key > best ? key : best;
+            }
+        }
+        best = ex_max64(best);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        const int v =(int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        ++level;
+        ex_sync<HBM>();
+        if (lane == 0) { X.mark[level] = tlen; X.dvar[level] = (uint32_t)v; X.val[v] = (best & 1ull) ? 1 : 2; X.trail[tlen] = v; }
+        ++tlen;
+        ex_sync<HBM>();
+    }
+    *work_out = work;
+    return result;
+}
+
+// copy the instance's literals in clause order (f_ptr / f_edges: any edge order of the problem), clear the state, search, write the results
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve(const PView &pv, const ExParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill)
+{
+    const int lane = (int)threadIdx.x;
+    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+    for (int k = lane; k < I.e; k += EX_NT) {
+        const int ed = I.f_edges[k];
+        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+    }
+    for (int v = lane; v < I.n; v += EX_NT) { X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u; }
+    ex_sync<HBM>();
+    int64_t work = 0;
+    const int st = ex_search<HBM>(X, xp.budget, &work);
+    for (int v = lane; v < I.n; v += EX_NT) xp.model[I.v0 + v] = (st == 1 && X.val[v] == 1) ? 1.0f : 0.0f;
+    if (lane == 0) {
+        xp.status[I.b] = (int8_t)st;
+        if (xp.work) xp.work[I.b] = work;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact(PView pv, ExParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        if (i < xp.nbig) {
+            ExInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
+            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
+            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve<true, uint32_t, int32_t>(pv, xp, I, X, (int32_t *)nullptr);
+        } else {
+            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
+            ExInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
+            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
+            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve<false, uint16_t, uint16_t>(pv, xp, I, X, (uint16_t *)(ex_slab + L.cptr));
+        }
+    }
+}
+
+// Routing, instance order and working arrays: once per problem (the only host synchronisation of the entry point).
+int ex_prepare(pdp_problem *p)
+{
+    if (p->ex_ready) return PDP_OK;
+    const size_t B = p->B;
+    std::vector<int32_t> v0(B + 1), f0(B + 1), e0(B + 1);
+    PDP_HIP_CHECK(hipMemcpy(v0.data(), p->inst_v0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(f0.data(), p->inst_f0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(e0.data(), p->inst_e0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> big, fit;
+    size_t lds = 0;
+    for (size_t b = 0; b < B; ++b) {
+        const int n = v0[b + 1] - v0[b], m = f0[b + 1] - f0[b], e = e0[b + 1] - e0[b];
+        if (ex_fits_lds(n, m, e)) { fit.push_back((int32_t)b); lds = std::max(lds, ex_lds_layout(n, m, e).bytes); }
+        else big.push_back((int32_t)b);
+    }
+    auto by_edges = [&](int32_t a, int32_t b) { const int ea = e0[a + 1] - e0[a], eb = e0[b + 1] - e0[b]; return ea != eb ? ea > eb : a < b; };
+    std::sort(big.begin(), big.end(), by_edges);
+    std::sort(fit.begin(), fit.end(), by_edges);
+    std::vector<int32_t> order(big);
+    order.insert(order.end(), fit.begin(), fit.end());
+    // one block: order [B] | counter | (HBM route) lit [E] | pend [V] | cnt [2V] | trail [V] | mark [V+B] | dvar [V+B] | val [V]
+    const size_t V = p->V, E = p->E;
+    size_t bytes = (B + 1) * 4;
+    if (!big.empty()) bytes += E * 4 + V * 16 + (V + B) * 8 + V;
+    char *blk = nullptr;
+    { const int st_ = pdp_dev_alloc((void **)&blk, (bytes + 15) & ~(size_t)15); if (st_ != PDP_OK) return st_; }
+    p->ex_blob = blk;
+    p->ex_order = (int32_t *)blk;
+    p->ex_next = (uint32_t *)(blk + B * 4);
+    PDP_HIP_CHECK(hipMemcpy(p->ex_order, order.data(), B * 4, hipMemcpyHostToDevice));
+    p->ex_nbig = (int)big.size();
+    p->ex_lds_bytes = lds;
+    p->ex_h_lit = nullptr;
+    if (!big.empty()) p->ex_h_lit = (uint32_t *)(blk + (B + 1) * 4);
+    p->ex_ready = 1;
+    return PDP_OK;
+}
+
+} // namespace
+
+extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
+{
+    PDP_REQUIRE(p && status && model, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_solve: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    ExParams xp;
+    xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.status = status; xp.model = model; xp.work = work;
+    const size_t V = p->V, E = p->E, B = p->B;
+    if (p->ex_h_lit) {
+        char *q = (char *)p->ex_h_lit;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_pend = (uint32_t *)q;           q += V * 4;
+        xp.h_cnt = (uint32_t *)q;            q += V * 8;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
+        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
+        xp.h_val = (uint8_t *)q;
+    } else {
+        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
+        xp.h_val = nullptr;
+    }
+    const int lds = (int)p->ex_lds_bytes;
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu);
+    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    return PDP_OK;
+}

@@ -87,18 +87,50 @@ def remove_subsumed(signed_vars, clause_ids):
     return np.asarray(out_sv, dtype=np.int32), np.asarray(out_ci, dtype=np.int32)
 
 
-def json_line(path, label, propagate=False):
-    "One output line; the text is read by the native parser of libpdp_hip.so (pdp_dimacs_open, include/pdp_hip.h)."
+def compact_instance(path, propagate=False):
+    "(var_num, clause_num, signed_vars, clause_ids) of one output line, read by the native parser of libpdp_hip.so (pdp_dimacs_open)"
     from pdp import native
     var_num, clause_num, signed_vars, clause_ids = native.dimacs_parse(path)
     if propagate:
         signed_vars, clause_ids = remove_subsumed(signed_vars, clause_ids)
         clause_num = int(clause_ids.max()) if clause_ids.size else 0
+    return var_num, clause_num, signed_vars, clause_ids
+
+
+def json_line(path, label, propagate=False):
+    "One output line; the text is read by the native parser of libpdp_hip.so (pdp_dimacs_open, include/pdp_hip.h)."
+    var_num, clause_num, signed_vars, clause_ids = compact_instance(path, propagate)
     return generator.format_json_line(var_num, clause_num, signed_vars, clause_ids, label=label, name=os.path.split(path)[1])
 
 
-def convert_directory(dimacs_dir, output_file, propagate=False, only_positive=False):
+def exact_labels(instances, budget=0):
+    """Labels of compact instances ((var_num, clause_num, signed_vars, clause_ids) as written to the lines) from the complete GPU solver
+    (pdp.exact), all instances in a few launches: 1.0 satisfiable, 0.0 unsatisfiable, -1 undecided within the budget (the converter's
+    "no label" value)."""
+    import numpy as np
+    from pdp import exact
+    items = []
+    for var_num, clause_num, signed_vars, clause_ids in instances:
+        sv, ci = np.asarray(signed_vars, dtype=np.int64), np.asarray(clause_ids, dtype=np.int64)
+        graph_map = np.stack((np.abs(sv) - 1, ci - 1)).astype(np.int32).reshape(2, -1)
+        items.append((int(var_num), int(clause_num), graph_map, np.sign(sv).astype(np.float32), -1.0, []))
+    status, _, _ = exact.solve_items(items, budget=budget)
+    return [1.0 if s == 1 else (0.0 if s == 0 else -1) for s in status]
+
+
+def convert_directory(dimacs_dir, output_file, propagate=False, only_positive=False, label='name', budget=0):
+    """label 'name': the reference's rule (the last digit of the file stem, else -1); 'exact': the complete solver's answer for the
+    instance the line holds (exact_labels).  Every other byte of a line is the same either way."""
     file_list = [os.path.join(dimacs_dir, f) for f in os.listdir(dimacs_dir) if os.path.isfile(os.path.join(dimacs_dir, f))]
+    if label == 'exact':
+        paths = [p for p in file_list if os.path.splitext(p)[1].lower() in ('.dimacs', '.cnf')]
+        instances = [compact_instance(p, propagate) for p in paths]
+        with open(output_file, 'w') as f:
+            for path, inst, lab in zip(paths, instances, exact_labels(instances, budget) if instances else []):
+                if only_positive and lab == 0:
+                    continue
+                f.write(generator.format_json_line(*inst, label=lab, name=os.path.split(path)[1]) + '\n')
+        return
     with open(output_file, 'w') as f:
         for path in file_list:
             name, ext = os.path.splitext(path)
@@ -120,11 +152,18 @@ def convert_file(file_name, output_file, propagate=False):
         f.write(json_line(file_name, label, propagate) + '\n')
 
 
-if __name__ == '__main__':
+def cli_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('in_dir', action='store', type=str)
     parser.add_argument('out_file', action='store', type=str)
     parser.add_argument('-s', '--simplify', help='Propagate binary constraints', required=False, action='store_true', default=False)
     parser.add_argument('-p', '--positive', help='Output only positive examples', required=False, action='store_true', default=False)
-    args = vars(parser.parse_args())
-    convert_directory(args['in_dir'], args['out_file'], args['simplify'], args['positive'])
+    parser.add_argument('--label', choices=('name', 'exact'), default='name',
+                        help="name: the last digit of the file name (the reference's rule); exact: solve every instance on the GPU")
+    parser.add_argument('--budget', type=int, default=0, help="clause-literal reads per instance for --label exact (0: the library default)")
+    return parser
+
+
+if __name__ == '__main__':
+    args = vars(cli_parser().parse_args())
+    convert_directory(args['in_dir'], args['out_file'], args['simplify'], args['positive'], args['label'], args['budget'])

@@ -108,8 +108,15 @@ class CNFGeneratorBase(object):
     def _to_dimacs(n, m, clause_list):
         return 'p cnf %d %d\n' % (n, m) + ''.join(' '.join(str(int(l)) for l in clause) + ' 0\n' for clause in clause_list)
 
-    def generate_dataset(self, size, output_dimacs_path, json_output, name, sat_only=True):
-        "``alpha_resolution`` JSON files + DIMACS directories, one per alpha slice (generator.py:53-93)"
+    def generate_dataset(self, size, output_dimacs_path, json_output, name, sat_only=True, labeller=None, label_batch=None):
+        """``alpha_resolution`` JSON files + DIMACS directories, one per alpha slice (generator.py:53-93).
+
+        ``labeller``: a function [(n, clause_list), ...] -> [True / False / None, ...] (pdp.exact.label_clause_lists) that replaces the
+        stub ``is_sat``; None keeps the stub.  A candidate labelled None is a failed trial.  Candidates are drawn ahead and labelled in
+        batches (``label_batch`` candidates at most per call; None: as many as the slice still needs), and the files and the numpy
+        global random state afterwards are those of a run that asks the labeller one candidate at a time."""
+        if labeller is not None:
+            return self._generate_labelled(size, output_dimacs_path, json_output, name, sat_only, labeller, label_batch)
         os.makedirs(output_dimacs_path, exist_ok=True)
         os.makedirs(json_output, exist_ok=True)
         dimacs_base, json_base = os.path.join(output_dimacs_path, name), os.path.join(json_output, name)
@@ -130,6 +137,57 @@ class CNFGeneratorBase(object):
                             g.write(self._to_dimacs(n, m, clause_list) + '\n')
                     sys.stdout.write("Dataset {:2d}/{:2d}: {:.2f} % complete  \r".format(j + 1, self._alpha_resolution, 100 * float(i + 1) / size))
                     sys.stdout.flush()
+            self._alpha += self._alpha_inc
+
+    def _generate_labelled(self, size, output_dimacs_path, json_output, name, sat_only, labeller, label_batch):
+        os.makedirs(output_dimacs_path, exist_ok=True)
+        os.makedirs(json_output, exist_ok=True)
+        dimacs_base, json_base = os.path.join(output_dimacs_path, name), os.path.join(json_output, name)
+        for j in range(self._alpha_resolution):
+            postfix = '_%d_%s_%s' % (j, self._alpha, self._alpha + self._alpha_inc)
+            os.makedirs(dimacs_base + postfix, exist_ok=True)
+            # the candidate stream of this slice: candidate c is drawn from snapshot[c] (the global state before it); the labeller draws
+            # nothing, so drawing ahead does not change the stream, and the state is rewound to the first candidate the loop left unused
+            cands, labels, snapshot = [], [], []
+            used, counts = 0, {True: 0, False: 0, None: 0}
+
+            def candidate(c, remaining):
+                while c >= len(cands):
+                    accepted = max(1, sum(1 for x in labels[:used] if x is True or (x is False and not sat_only)))
+                    ahead = int(np.ceil(remaining * max(1.0, used / float(accepted))))
+                    ahead = max(1, min(ahead, 50 * remaining, label_batch or 4096))
+                    fresh = []
+                    for _ in range(ahead):
+                        snapshot.append(np.random.get_state())
+                        fresh.append(self.generate_complete())
+                    got = list(labeller([(cand[0], cand[6]) for cand in fresh]))
+                    if len(got) != len(fresh):
+                        raise ValueError("labeller returned %d labels for %d instances" % (len(got), len(fresh)))
+                    cands.extend(fresh)
+                    labels.extend(None if x is None else bool(x) for x in got)
+                return cands[c], labels[c]
+
+            with open(json_base + postfix + ".json", 'w') as f:
+                for i in range(size):
+                    found = False
+                    for _ in range(50):
+                        (n, m, graph_map, edge_feature, _, _, clause_list), label = candidate(used, size - i)
+                        used += 1
+                        counts[label] += 1
+                        if label is not None and ((not sat_only) or label):
+                            found = True
+                            break
+                    if found:
+                        f.write(str(self._to_json(n, m, graph_map, edge_feature, label)).replace("'", '"') + '\n')
+                        with open(os.path.join(dimacs_base + postfix, 'dimacs_%d_sat=%s.DIMACS' % (i, label)), 'w') as g:
+                            g.write(self._to_dimacs(n, m, clause_list) + '\n')
+                    sys.stdout.write("Dataset {:2d}/{:2d}: {:.2f} % complete  \r".format(j + 1, self._alpha_resolution, 100 * float(i + 1) / size))
+                    sys.stdout.flush()
+            if used < len(snapshot):
+                np.random.set_state(snapshot[used])
+            sys.stdout.write("\nDataset {:2d}/{:2d}: {} candidates labelled: {} SAT, {} UNSAT, {} undecided\n".format(
+                j + 1, self._alpha_resolution, used, counts[True], counts[False], counts[None]))
+            sys.stdout.flush()
             self._alpha += self._alpha_inc
 
 

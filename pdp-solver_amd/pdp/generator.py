@@ -7,7 +7,9 @@ the DIMACS writer used by the CLI tests.  Everything is driven by ``numpy.random
 the same (seed, n, m, k) always yields the same instance on every machine.
 """
 
+import argparse
 import os
+import sys
 
 import numpy as np
 
@@ -139,3 +141,50 @@ try:
                                     VariableModularCNFGenerator, is_sat)
 except ImportError:      # this file loaded on its own next to another `pdp` package (tests/golden/generate_golden.py does that)
     pass
+
+
+def make_generator(method, args):
+    "the generator class the dataset CLI names (uniform is the default, like the reference's)"
+    from pdp.cnf_generators import ModularCNFGenerator, UniformCNFGenerator, VariableModularCNFGenerator
+    if method == 'modular':
+        return ModularCNFGenerator(k=args.min_k, min_n=args.min_n, max_n=args.max_n, min_q=args.min_q, max_q=args.max_q, min_c=args.min_c,
+                                   max_c=args.max_c, min_alpha=args.min_a, max_alpha=args.max_a, alpha_resolution=args.res)
+    if method == 'v-modular':
+        return VariableModularCNFGenerator(min_k=args.min_k, max_k=args.max_k, min_n=args.min_n, max_n=args.max_n, min_q=args.min_q,
+                                           max_q=args.max_q, min_c=args.min_c, max_c=args.max_c, min_alpha=args.min_a, max_alpha=args.max_a,
+                                           alpha_resolution=args.res)
+    return UniformCNFGenerator(min_n=args.min_n, max_n=args.max_n, min_k=args.min_k, max_k=args.max_k, min_alpha=args.min_a,
+                               max_alpha=args.max_a, alpha_resolution=args.res)
+
+
+def cli_parser():
+    "the reference's dataset CLI (positional arguments and flags of src/pdp/generator.py run as a script) plus --label / --budget"
+    p = argparse.ArgumentParser(description="Generate a labelled CNF dataset: one JSON file and one DIMACS directory per alpha slice.")
+    p.add_argument('out_dir', type=str)
+    p.add_argument('out_json', type=str)
+    p.add_argument('name', type=str)
+    p.add_argument('size', type=int)
+    p.add_argument('method', type=str, help="uniform (default), modular or v-modular")
+    for flag, typ, default in (('min_n', int, 40), ('max_n', int, 40), ('min_c', int, 10), ('max_c', int, 40), ('min_q', float, 0.3),
+                               ('max_q', float, 0.9), ('min_k', int, 3), ('max_k', int, 5), ('min_a', float, 2), ('max_a', float, 10),
+                               ('res', int, 5)):
+        p.add_argument('--' + flag, dest=flag, type=typ, default=default)
+    p.add_argument('-s', '--sat_only', help='Include SAT examples only', action='store_true', default=False)
+    p.add_argument('--label', choices=('exact', 'none'), default='exact',
+                   help="exact: label every candidate with the complete GPU solver (pdp.exact); none: the reference's stub labels (always False)")
+    p.add_argument('--budget', type=int, default=0, help="clause-literal reads per instance for --label exact (0: the library default)")
+    return p
+
+
+def main(argv=None):
+    args = cli_parser().parse_args(argv)
+    labeller = None
+    if args.label == 'exact':
+        from pdp import exact
+        labeller = lambda instances: exact.label_clause_lists(instances, budget=args.budget)  # noqa: E731
+    make_generator(args.method, args).generate_dataset(args.size, args.out_dir, args.out_json, args.name, args.sat_only, labeller=labeller)
+
+
+if __name__ == '__main__':
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    main()

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     'pdp_train_linear', 'pdp_train_linear_backward', 'pdp_train_linear_s_supported', 'pdp_train_linear_s', 'pdp_train_linear_s_backward', 'pdp_train_row_sum', 'pdp_train_row_spread', 'pdp_train_gru', 'pdp_train_gru_fused', 'pdp_train_gru_backward', 'pdp_train_gru_backward_s',
     'pdp_sat_loss_grad', 'pdp_train_sp_adapted_backward',
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
+    'pdp_exact_solve',
 ]
 
 
@@ -404,6 +405,17 @@ class Problem(object):
         out = torch.empty(self.V, 1, dtype=torch.float32, device=self.device)
         check(lib().pdp_reinforce_predict(self._h, ptr(fs, torch.float32, 2 * self.E), ptr(out), _stream()))
         return out
+
+    # -- complete solver ---------------------------------------------------------------------------------------
+    def exact_solve(self, budget=0):
+        """Label every instance with the batched DPLL solver (pdp_exact_solve): (status int8 [B]: 1 SAT, 0 UNSAT, -1 undecided within
+        ``budget`` clause-literal reads per instance, 0 = the library default; model float [V]: a satisfying 0/1 assignment of every status-1
+        instance, 0 elsewhere; work int64 [B]: the clause-literal reads of each search).  Asynchronous on the current stream."""
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        model = torch.empty(self.V, dtype=torch.float32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_solve(self._h, C.c_int64(int(budget)), ptr(status), ptr(model), ptr(work), _stream()))
+        return status, model, work
 
     # -- K14 ---------------------------------------------------------------------------------------------------
     def energy(self, assignment):
