@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """Randomised parity soak of pdp_sp_solve and pdp_local_search against the CPU oracle (strict reference semantics, bit for bit): random batch
 compositions (tiny to mid-size instances, mixed k, optionally one or two instances past the LDS limit, single-instance and very small
-batches), both model types, random T / tolerance / t_max / alpha, so that every routing decision of the library is hit: LDS-resident,
-per-instance routing with workgroup teams, exact single-instance mode, lock-step launch, Walk-SAT routing.  Test infrastructure (uses oracle/).
+batches, a batch of one structured family of tests/families.py: hubs, long clauses, sparse regular graphs, ...), both model types,
+random T / tolerance / t_max / alpha, so that every routing decision of the library is hit: LDS-resident, per-instance
+routing with workgroup teams, exact single-instance mode, lock-step launch, Walk-SAT routing.  Test infrastructure (uses oracle/).
 usage: python tools/parity_soak.py [seconds] [seed]"""
 import os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, 'pdp-solver_amd')); sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, 'pdp-solver_amd')); sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, 'tests'))
 import numpy as np, torch
 from pdp import native, generator
 from pdp.factorgraph import dataset
 from oracle import binding
+import families
 binding.build()
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -21,7 +23,7 @@ paths = {}
 t_end = time.time() + budget
 runs = 0
 while time.time() < t_end:
-    kind = rng.choice(['small', 'tiny', 'single', 'mixed', 'bigs'])
+    kind = rng.choice(['small', 'tiny', 'single', 'mixed', 'bigs', 'family'])
     items = []
     def inst(n, alpha, k=None):
         kk = int(k or rng.choice([3, 3, 3, 4, 5, 2]))
@@ -38,12 +40,13 @@ while time.time() < t_end:
         items = [inst(int(rng.randint(10, 80)), alpha) for _ in range(int(rng.randint(10, 60)))]
         for _ in range(int(rng.randint(1, 3))):
             items.insert(int(rng.randint(0, len(items) + 1)), inst(int(rng.randint(1500, 3500)), float(rng.choice([3.5, 3.8, 4.2])), 3))
-    else:
+    elif kind == 'bigs':
         items = [inst(int(rng.randint(1500, 3000)), float(rng.choice([3.5, 4.0])), 3) for _ in range(int(rng.randint(2, 5)))]
-    b = dataset.collate_segment(items)
+    family = str(rng.choice(families.NAMES)) if kind == 'family' else ''
+    b = families.batch(family) if family else dataset.collate_segment(items)
     model = 'reinforce' if rng.rand() < 0.3 else 'p-d-p'
     T = int(rng.choice([1, 7, 13, 30, 60, 100]))
-    if kind in ('single', 'mixed', 'bigs'):
+    if kind in ('single', 'mixed', 'bigs', 'family'):
         T = min(T, 40)
     tol = float(rng.choice([0.02, 0.05, 0.1])); t_max = float(rng.choice([4, 8, 100]))
     hp = native.Problem(t(b['graph_map']), t(b['batch_variable_map']), t(b['batch_function_map']), t(b['edge_feature']))
@@ -51,7 +54,7 @@ while time.time() < t_end:
     hp.simplify()
     q = torch.full((hp.E, 3), 1.0, device=dev) / 3.0; fs = torch.zeros(hp.E, 2, device=dev); fs[:, 0] = 0.5
     am = torch.ones(hp.B, dtype=torch.uint8, device=dev); dec = native.Decimator(hp)
-    desc = '%s %s B=%d E=%d T=%d tol=%g tmax=%g alpha=%g' % (kind, model, hp.B, hp.E, T, tol, t_max, alpha)
+    desc = '%s %s B=%d E=%d T=%d tol=%g tmax=%g alpha=%g' % (family or kind, model, hp.B, hp.E, T, tol, t_max, alpha)
     try:
         if model == 'p-d-p':
             res = op.forward('p-d-p', T, local_search_iterations=0, tolerance=tol, t_max=t_max, seed=5, trace=True)
