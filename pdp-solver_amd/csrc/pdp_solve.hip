@@ -834,7 +834,7 @@ static size_t lds2_bytes_for(int n, int m, int e)
 struct LdsArrays {
     float *QU, *EA, *EB, *X, *Y;
     uint16_t *pvv, *pcc, *e2p, *v_ptr, *f_ptr;
-    float *S, *af, *av, *sol, *Pv, *Nv, *xv1, *xv2, *coeff;
+    float *S, *af, *av, *sol, *PN, *xv1, *xv2, *coeff, *EX;
     uint8_t *flag_v;
     uint16_t *vord;      // variables in order of descending degree: a wave of 64 consecutive entries runs loops of similar length
 };
@@ -845,8 +845,25 @@ __device__ __forceinline__ LdsArrays carve_all(unsigned char *cp, int n, int m, 
     L.pvv = carve<uint16_t>(cp, ne); L.pcc = carve<uint16_t>(cp, ne); L.e2p = carve<uint16_t>(cp, ne);
     L.v_ptr = carve<uint16_t>(cp, n + 1); L.f_ptr = carve<uint16_t>(cp, m + 1);
     L.S = carve<float>(cp, m + 8); L.af = carve<float>(cp, m);
-    L.av = carve<float>(cp, n); L.sol = carve<float>(cp, n); L.Pv = carve<float>(cp, n); L.Nv = carve<float>(cp, n);
+    L.av = carve<float>(cp, n); L.sol = carve<float>(cp, n);
+    // The five per-variable float arrays of lds2_bytes_for (P, N, xv1, xv2, coeff), none of them part of the instance record:
+    // * PN, the first two: the row sums of R1 as one pair {P, N} per variable (8 n bytes of the 2 a16(4 n)), so that a slot reads "its" sum at
+    //   2 v + [negative literal] and the other one at that index ^ 1 -- no select on the sign.  Live from R1 to the exit path (which forms
+    //   q_s / q_dc from them); lds_ghost_bad, behind the write-back, overwrites them.
+    // * xv1: P4's per-variable codes for P5b; deg of the simplification routines.
+    // * EX, over xv2 and coeff: {exp1_sum(N), exp1_sum(P)} per variable -- the exp of the OPPOSITE row sum at the same index 2 v + [negative
+    //   literal] (instantiations without a force only; see R1).  Live from R1 to the barrier that ends E2 of the same sweep, and only there:
+    //   everything else that uses these bytes runs behind P5's barrier or at the exit -- lds_decimate (score / sdeg in xv2, assign in coeff, also
+    //   through d_simplify / d_peel / d_set_variable_core), lds_reinforce_step (codev in xv2; forced instantiations, which have no EX) --,
+    //   P5b, the exact gate and the mask pass behind a refresh touch X / Y / the q_u array / xv1 only, and EVERY sweep (poisoned or not, the first
+    //   of a launch, of the replay pass, behind a decimation or a Reinforce step) runs R1 and its barrier before E2: the values are rebuilt
+    //   after whatever clobbered them, never carried from one sweep to the next.  A wave that enters the next sweep's R1 early (a sweep without E1
+    //   has no barrier in front of it) writes EX while slower waves finish the previous sweep: behind the last barrier of a sweep those
+    //   read none of these bytes (a decimation that fixed a variable ends with the refresh barrier; one that did not returns behind its
+    //   arg-max barrier and reads only the shared record).
+    L.PN = carve<float>(cp, n); carve<float>(cp, n);
     L.xv1 = carve<float>(cp, n); L.xv2 = carve<float>(cp, n); L.coeff = carve<float>(cp, n);
+    L.EX = L.xv2;
     L.flag_v = carve<uint8_t>(cp, n);
     L.vord = carve<uint16_t>(cp, n);
     return L;
@@ -1187,7 +1204,7 @@ __device__ __noinline__ int lds_ghost_bad(uint32_t smem_off, uint32_t cold_off, 
             P = P + (negative ? 0.0f : 1.0f) * y;
             N = N + (negative ? 1.0f : 0.0f) * y;
         }
-        L.Pv[v] = P; L.Nv[v] = N;
+        L.PN[2 * v] = P; L.PN[2 * v + 1] = N;
     }
     __syncthreads();
     for (int p = tid; p < ne; p += nt) {
@@ -1195,7 +1212,7 @@ __device__ __noinline__ int lds_ghost_bad(uint32_t smem_off, uint32_t cold_off, 
         const float agg = (0.0f + L.S[L.pcc[p] & 0x3fff]) - s0[p];
         const float eta_new = pdp_safe_exp(agg);
         const int v = pw & vmask;
-        const SpOut o = d_sp_edge(slot_sign(pw), L.Pv[v], L.Nv[v], s3[p], has_force ? frc_of(pw) : 0.0f, L0h, L1h);
+        const SpOut o = d_sp_edge(slot_sign(pw), L.PN[2 * v], L.PN[2 * v + 1], s3[p], has_force ? frc_of(pw) : 0.0f, L0h, L1h);
         if (!pdp_finite(eta_new) || !pdp_finite(o.qu) || !pdp_finite(o.qs) || !pdp_finite(o.dc)) bad = 1;
     }
     __syncthreads();
@@ -1705,7 +1722,7 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
         // ---- R1: per-clause sums (through e2p) and per-variable sums (contiguous), ascending edge id ------------
         {
             const uint16_t *const e2p = L.e2p, *const f_ptr = L.f_ptr, *const v_ptr = L.v_ptr;
-            float *const S = L.S, *const Pv = L.Pv, *const Nv = L.Nv;
+            float *const S = L.S;
             // Work is handed out per wave in items of 64 rows.  A variable row is a sequential sum over ~|E|/n terms and costs
             // about two clause rows, so the waves that take a variable item skip the first two rounds of clause items.
             const int nvi = (n + 63) >> 6, nci = (m + 63) >> 6;
@@ -1753,7 +1770,15 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
 #pragma unroll
                     for (int j = 0; j < 3; ++j) if (p + j < bnd) acc(y[j], sg[j]);
                 }
-                Pv[v] = P + 0.0f * N; Nv[v] = N + 0.0f * P;
+                const float Ps = P + 0.0f * N, Ns = N + 0.0f * P;
+                reinterpret_cast<float2 *>(L.PN)[v] = make_float2(Ps, Ns);
+                // Without an external force the "opposite" sum of a slot is Ps or Ns itself, one of two values per variable: their exps are
+                // taken here, once per variable, with the function E2 would use on the same bits (the same result bits, NaN included), and E2
+                // reads them -- one exp per slot less in the phase that is bound by VALU issue, two per variable more in this one, whose
+                // critical path is the clause waves.  Stored crosswise: a slot's index 2 v + [negative literal] finds the exp of the OTHER sum.
+                // (With a force the opposite sum also carries L0 / L1 by the slot's own force code -- up to four values per variable for
+                // two spare floats: those instantiations keep their four exps per slot.)
+                if constexpr (!FORCE) reinterpret_cast<float2 *>(L.EX)[v] = make_float2(exp1_sum(Ns), exp1_sum(Ps));
             };
             // Clause rows are a three-level dependent LDS chain (f_ptr -> e2p -> X): a lane takes up to four rows at once so that the
             // chain is paid once per group, not once per row; the straight-line form needs 3-literal clauses in all of the lane's rows.
@@ -1828,7 +1853,7 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
         const uint32_t log_em_or = use_em ? 0u : PC_EM;      // without an edge mask every slot counts
         // one slot's update: reads the slot's words, the three row sums and its own logs, stores the new survey and returns the new values
         struct SlotNew { float qu, eta, eta_old, total; uint16_t cw; };
-        const float *const S_ = L.S, *const Pv_ = L.Pv, *const Nv_ = L.Nv;
+        const float *const S_ = L.S, *const PN_ = L.PN, *const EX_ = L.EX;
         auto slot_update = [&](int p) __attribute__((always_inline)) {
             const uint16_t pw = pvv[p], cw = pcc[p];
             const int v = pw & VM, c = cw & 0x3fff;
@@ -1837,25 +1862,32 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
             const float xp = X[p];
             const float agg = S_[c] - xp;                       // the reference's 0 + S is a no-op: a sum that starts at +0 is never -0
             const float force = FORCE ? frc_of(pw) : 0.0f;
-            const float pos = Pv_[v], neg = Nv_[v];
             // The reference's (0.5 (1 + s)) * pos + (0.5 (1 - s)) * neg has coefficients 1 and 0: one product is the sum itself, the other an
-            // exact zero.  R1 stores Pv / Nv so that they are never -0 (sums that start at +0), never infinite (sums of clamped logs) and NaN
-            // only together (each gets 0 * the other): x + (+-0) == x then, so the expression is the SELECTED sum -- two selects on the slot's
-            // sign bit instead of the coefficient arithmetic, two packed multiplies and the adds.
+            // exact zero.  R1 stores P / N so that they are never -0 (sums that start at +0), never infinite (sums of clamped logs) and NaN
+            // only together (each gets 0 * the other): x + (+-0) == x then, so the expression is the SELECTED sum -- and with the pair
+            // {P, N} per variable the selection on the slot's sign bit is the index 2 v + [negative literal]: no coefficient arithmetic, no select.
+            // (with a force: the pair in one read and two selects, as before the pair layout -- the index form costs those instantiations scratch)
+            const uint32_t iv = ((uint32_t)v << 1) | ((uint32_t)pw >> 15);
             const bool neg_lit = (pw & 0x8000u) != 0;
-            float same = neg_lit ? neg : pos;
+            float2 pn = make_float2(0.0f, 0.0f);
+            if constexpr (FORCE) pn = reinterpret_cast<const float2 *>(PN_)[v];
+            float same = FORCE ? (neg_lit ? pn.y : pn.x) : PN_[iv];
             same = same - Y[p];
             // without an external force both log terms are log(1) = +0: adding it can only turn a -0 into +0, which exp ignores
             if constexpr (FORCE) same = same + ((force == s) ? L1 : L0);
-            float opp = neg_lit ? pos : neg;
+            float opp = FORCE ? (neg_lit ? pn.x : pn.y) : PN_[iv ^ 1u];
             if constexpr (FORCE) opp = opp + ((force == -s) ? L1 : L0);
 #ifndef PDP_E2_PACKED_EXPS
             // (four scalar chains: a packed fp32 instruction holds the SIMD as long as two plain ones and waits a state behind the packed step it
             //  depends on, so the 4-vector form buys nothing here -- measured in round 5: -2.3 % on the launch, the logs likewise -1.8 %)
             const float so = same + opp;
-            const f4v ex = {exp1_sum(agg), exp1_sum(so), exp1_sum(same), exp1_sum(opp)};
+            // (without a force exp(opp) is one of the two exps R1 took for the variable: three exps per slot)
+            float eopp;
+            if constexpr (FORCE) eopp = exp1_sum(opp); else eopp = EX_[iv];
+            const f4v ex = {exp1_sum(agg), exp1_sum(so), exp1_sum(same), eopp};
 #else
-            const f4v ex = exp4_sum((f4v){agg, same + opp, same, opp});
+            f4v ex = exp4_sum((f4v){agg, same + opp, same, FORCE ? opp : same});     // A/B switch: 3 + 1 without a force
+            if constexpr (!FORCE) ex.w = EX_[iv];
 #endif
             // mask * new + (1 - mask) * old with mask == 1: (+0) * old + new as ONE fused operation -- the product is an exact zero (or NaN),
             // so fusing rounds nothing differently; the unfused form is a multiply and an add per slot
@@ -2209,7 +2241,7 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
             float y = pdp_safe_log_fin(1.0f - Eprev[p], PDP_SP_EPS);
             if (last_use_em) y = y * ((cw & PC_EM_USED) ? 1.0f : 0.0f);
             const float force = RF ? (rf_last_flip ? (qu_is_delta ? QU[p] : X[p]) : frc_of(pw)) : (FORCE ? frc_of(pw) : 0.0f);
-            const float pos = 0.0f + L.Pv[v], neg = 0.0f + L.Nv[v];
+            const float pos = 0.0f + L.PN[2 * v], neg = 0.0f + L.PN[2 * v + 1];
             float same = (0.5f * (1.0f + s)) * pos + (0.5f * (1.0f - s)) * neg;
             same = same - y;
             same = same + ((force == s) ? L1 : L0);

@@ -8,7 +8,7 @@ change instruction selection or scheduling), walks the kernel's assembly, attrib
 phase whose source lines (the `// ---- E1` ... markers inside k_sp_solve_lds) the last `.loc` of the kernel body
 named, and classifies it:
 
-    fp    v_{add,sub,mul,fma,fmac,pk_*}_f32               the arithmetic the reference asks for
+    fp    v_{add,sub,mul,fma,fmac,fmaak,fmamk,pk_*}_f32   the arithmetic the reference asks for
     fpx   other float VALU: max/min, ldexp, frexp, cvt, rcp, div_*, cmp_*_f32, cndmask, trans
     int   integer / bit / move VALU (index unpack, address arithmetic, selects on integers)
     xl    cross-lane VALU (dpp moves, readlane / writelane, permlane)
@@ -33,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "pdp-solver_amd", "csrc", "pdp_solve.hip")
 HEADLINE = "_Z14k_sp_solve_ldsILb0ELb0ELb0ELb1EEv5PView11SolveParams"      # <false, false, false, true>: pass 1 through the dispatch list (round 5)
 
-FP = re.compile(r"^v_(pk_)?(add|sub|subrev|mul|fma|fmac|mac|mad)_(f32|legacy_f32)")
+FP = re.compile(r"^v_(pk_)?(add|sub|subrev|mul|fma|fmac|fmaak|fmamk|mac|mad|madak|madmk)_(f32|legacy_f32)")
 XL = re.compile(r"^v_(readlane|writelane|readfirstlane|permlane|mov_b32_dpp|bpermute)|dpp|row_|quad_perm")
 FPX = re.compile(r"^v_(max|min|ldexp|frexp|cvt|rcp|rsq|sqrt|exp|log|div|cmp\w*_f32|cmpx\w*_f32|cndmask|trunc|rndne|floor|ceil|fract|med3_f32|max3_f32|min3_f32|pk_max|pk_min)")
 
