@@ -24,7 +24,7 @@ extern "C" {
 
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
- * pdp_exact_solve is an addition that changes no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_solve and pdp_exact_solve_hinted are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -204,6 +204,23 @@ int pdp_deduplicate(pdp_problem *p, const float *pred, float *out, int32_t *chos
  * or the library build.  Asynchronous on `stream`; calls on one problem must not overlap (they share its working arrays). */
 #define PDP_EXACT_DEFAULT_BUDGET (((int64_t)1) << 32)
 int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream);
+
+/* The same search with phase hints: an assignment that violates few clauses (a PDP prediction) steers the search towards itself.
+ * hint [V], one float per variable in the problem's variable order: h > 0.5 = "true first", any other finite value = "false first",
+ * NaN = "no hint for this variable" (the reference's poisoning leaves NaN predictions).  hint == NULL behaves as all-NaN.
+ * For one instance the search is pdp_exact_solve's with two additions:
+ *   1. Check pass, only if none of the instance's hints is NaN: every clause is read up to and including its first literal that is true
+ *      under the thresholded hint, and these reads count into work.  If every clause has such a literal the instance is done: status 1,
+ *      model[v] = (h[v] > 0.5) for all of its variables, work = the reads of this pass.  Otherwise the search starts from the empty
+ *      assignment as in pdp_exact_solve, keeping the reads already counted.  An instance with a NaN hint skips the pass and reads nothing.
+ *   2. Polarity: at a decision on variable v the first polarity is the hint's when h[v] is not NaN, else pdp_exact_solve's (true when
+ *      its occurrences are at least as many).  The choice of v and everything else are unchanged.
+ * The budget is checked where pdp_exact_solve checks it; the check pass runs before the first check, at work = 0, and reads at most every
+ * literal once, so work < budget + 3 * (edges of the instance) holds as before.  Status, model and work are a function of the instance
+ * and its own hints only.  Consequences: hints never change the status of a search that runs to its end; an unsatisfiable instance's work
+ * is pdp_exact_solve's plus the check-pass reads; with pdp_exact_solve's model as the hint the check pass accepts it and work is at most
+ * pdp_exact_solve's; all-NaN hints give pdp_exact_solve's three outputs exactly.  R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules. */
+int pdp_exact_solve_hinted(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream);
 
 /* ---- persistent solve: the whole _forward_core loop in one launch ------------------------------------
  * replaces: PropagatorDecimatorSolverBase._forward_core (solver.py:355-386) for the classical

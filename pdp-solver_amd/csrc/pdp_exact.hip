@@ -19,6 +19,12 @@
 // conflict), so the outcome of a pass does not depend on lane or wave order; only the trail order within a level does, and nothing reads
 // it.  The work counter (clause-literal reads) is a sum of per-clause counts, the branching counters are integer atomic adds, the branch
 // variable is a max of unique keys: every output is a function of the instance alone.
+//
+// pdp_exact_solve_hinted is the same search with phase hints (one float per variable: > 0.5 true first, any other finite value false first,
+// NaN no hint).  Two additions, both in the HINT = true instantiation only (HINT = false is the code above, unchanged): a check pass that
+// tries the thresholded hint as a whole assignment before the search when no hint of the instance is NaN, and the first polarity of a
+// decision taken from the hint.  The hint code of a variable (0 none, 1 true, 2 false) lives in bits 8-9 of pend[v], next to the counters
+// the decision reads anyway: no array is added to the slab, and the routing and ex_prepare's cached decision stay as they are.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <vector>
@@ -64,6 +70,7 @@ struct ExParams {
     int32_t *h_trail;           // [V]
     int32_t *h_mark;            // [V+B] (instance b at v0 + b: n+1 entries)
     uint32_t *h_dvar;           // [V+B]
+    const float *hint;          // [V] phase hints, read by k_exact<true> only (NULL: none); last, so the fields above keep their offsets
 };
 
 template <typename LitT, typename PtrT>
@@ -98,16 +105,45 @@ __device__ __forceinline__ unsigned long long ex_max64(unsigned long long x)
     return x;
 }
 
+constexpr uint32_t EX_HINT_SHIFT = 8;            // bits 8-9 of pend[v]: the hint code of v (0 none, 1 true, 2 false); bits 0-1 are the unit bits
+
 // The DPLL search of one instance by the calling wave.  Returns 1 (satisfiable: val holds a model), 0 (unsatisfiable) or -1 (budget spent);
 // *work_out = the clause-literal reads made.  The budget is checked before every propagation pass.
-template <bool HBM, typename LitT, typename PtrT>
-__device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t *work_out)
+// HINT: pend[v] carries the hint codes; `check` (wave-uniform: every variable has a hint) asks for the check pass, which runs before the
+// first budget check: the hint is written into val and every clause is read up to its first true literal; if every clause has one, that
+// assignment is the model, otherwise val is cleared and the search starts from nothing with the reads counted.
+template <bool HBM, bool HINT, typename LitT, typename PtrT>
+__device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, bool check, int64_t *work_out)
 {
     const int lane = (int)threadIdx.x;
     const unsigned long long below = (1ull << lane) - 1ull;
+    // the unit bits of pend[v]; without hints they are the whole word
+    constexpr uint32_t UNIT = HINT ? 3u : ~0u;
     int level = 0, tlen = 0;
     int64_t work = 0;
     int result = -1;
+    if constexpr (HINT) {
+        if (check) {
+            for (int v = lane; v < X.n; v += EX_NT) X.val[v] = (uint8_t)((X.pend[v] >> EX_HINT_SHIFT) & 3u);
+            ex_sync<HBM>();
+            int reads = 0, open = 0;
+            for (int c = lane; c < X.m; c += EX_NT) {
+                const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+                int sat = 0, k = a;
+                for (; k < z; ++k) {
+                    const uint32_t L = X.lit[k];
+                    if (X.val[L >> 1] == 1u + (L & 1u)) { sat = 1; ++k; break; }
+                }
+                reads += k - a;
+                open |= !sat;
+            }
+            work += ex_sum(reads);
+            if (__ballot(open) == 0ull) { *work_out = work; return 1; }
+            ex_sync<HBM>();                                         // every lane has read val before it is cleared
+            for (int v = lane; v < X.n; v += EX_NT) X.val[v] = 0;
+            ex_sync<HBM>();
+        }
+    }
     for (;;) {
         if (work >= budget) break;
         // ---- one unit-propagation pass
@@ -137,10 +173,11 @@ __device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t *w
             int bad = 0;
             for (int base = 0; base < X.n; base += EX_NT) {
                 const int v = base + lane;
-                const uint32_t bits = v < X.n ? X.pend[v] : 0u;
+                const uint32_t word = v < X.n ? X.pend[v] : 0u;
+                const uint32_t bits = word & UNIT;
                 const unsigned long long mask = __ballot(bits != 0u);
                 if (bits) {
-                    X.pend[v] = 0u;
+                    X.pend[v] = word & ~UNIT;
                     X.val[v] = (bits & 1u) ? 1 : 2;
                     bad |= bits == 3u;
                     X.trail[tlen + __popcll(mask & below)] = v;
@@ -203,9 +240,14 @@ __device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t *w
             const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
             if (p | q) {
                 X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
-                // score, then the lower index, then the polarity (true when its occurrences are at least as many)
+                // score, then the lower index, then the polarity (true when its occurrences are at least as many; the hint's if v has one)
+                bool pos = p >= q;
+                if constexpr (HINT) {
+                    const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
+                    if (code) pos = code == 1u;
+                }
                 const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
-                                               (p >= q ? 1ull : 0ull);
+                                               (pos ? 1ull : 0ull);
                 best = key > best ? key : best;
             }
         }
@@ -222,8 +264,9 @@ __device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t *w
     return result;
 }
 
-// copy the instance's literals in clause order (f_ptr / f_edges: any edge order of the problem), clear the state, search, write the results
-template <bool HBM, typename LitT, typename PtrT>
+// copy the instance's literals in clause order (f_ptr / f_edges: any edge order of the problem), clear the state (HINT: pend starts as the
+// hint codes), search, write the results
+template <bool HBM, bool HINT, typename LitT, typename PtrT>
 __device__ void ex_solve(const PView &pv, const ExParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill)
 {
     const int lane = (int)threadIdx.x;
@@ -232,10 +275,22 @@ __device__ void ex_solve(const PView &pv, const ExParams &xp, const Inst &I, ExI
         const int ed = I.f_edges[k];
         X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
     }
-    for (int v = lane; v < I.n; v += EX_NT) { X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u; }
+    bool check = false;
+    if constexpr (HINT) {
+        int none = xp.hint == nullptr;
+        for (int v = lane; v < I.n; v += EX_NT) {
+            uint32_t code = 0u;
+            if (xp.hint) { const float h = xp.hint[I.v0 + v]; code = h != h ? 0u : (h > 0.5f ? 1u : 2u); }
+            none |= code == 0u;
+            X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        }
+        check = __ballot(none) == 0ull;
+    } else {
+        for (int v = lane; v < I.n; v += EX_NT) { X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u; }
+    }
     ex_sync<HBM>();
     int64_t work = 0;
-    const int st = ex_search<HBM>(X, xp.budget, &work);
+    const int st = ex_search<HBM, HINT>(X, xp.budget, check, &work);
     for (int v = lane; v < I.n; v += EX_NT) xp.model[I.v0 + v] = (st == 1 && X.val[v] == 1) ? 1.0f : 0.0f;
     if (lane == 0) {
         xp.status[I.b] = (int8_t)st;
@@ -244,6 +299,7 @@ __device__ void ex_solve(const PView &pv, const ExParams &xp, const Inst &I, ExI
     ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
 }
 
+template <bool HINT>
 __global__ void __launch_bounds__(EX_NT) k_exact(PView pv, ExParams xp)
 {
     extern __shared__ __align__(16) unsigned char ex_slab[];
@@ -259,7 +315,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact(PView pv, ExParams xp)
             X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
             X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
             X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve<true, uint32_t, int32_t>(pv, xp, I, X, (int32_t *)nullptr);
+            ex_solve<true, HINT, uint32_t, int32_t>(pv, xp, I, X, (int32_t *)nullptr);
         } else {
             const ExLds L = ex_lds_layout(I.n, I.m, I.e);
             ExInst<uint16_t, uint16_t> X;
@@ -267,7 +323,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact(PView pv, ExParams xp)
             X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
             X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
             X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve<false, uint16_t, uint16_t>(pv, xp, I, X, (uint16_t *)(ex_slab + L.cptr));
+            ex_solve<false, HINT, uint16_t, uint16_t>(pv, xp, I, X, (uint16_t *)(ex_slab + L.cptr));
         }
     }
 }
@@ -311,21 +367,16 @@ int ex_prepare(pdp_problem *p)
     return PDP_OK;
 }
 
-} // namespace
-
-extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
+// the launch of both entry points: HINT = false is pdp_exact_solve's kernel, HINT = true reads xp.hint
+template <bool HINT>
+int ex_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
 {
-    PDP_REQUIRE(p && status && model, "NULL argument");
-    if (p->R != 1) {
-        pdp_set_error("pdp_exact_solve: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
-        return PDP_ERR_UNSUPPORTED;
-    }
     { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
     const hipStream_t st = ST(stream);
     ExParams xp;
     xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
     xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
-    xp.status = status; xp.model = model; xp.work = work;
+    xp.status = status; xp.model = model; xp.work = work; xp.hint = hint;
     const size_t V = p->V, E = p->E, B = p->B;
     if (p->ex_h_lit) {
         char *q = (char *)p->ex_h_lit;
@@ -341,12 +392,34 @@ extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, f
         xp.h_val = nullptr;
     }
     const int lds = (int)p->ex_lds_bytes;
-    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact<HINT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact<HINT>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     const int64_t grid = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu);
     PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    hipLaunchKernelGGL(k_exact<HINT>, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
     return PDP_OK;
+}
+
+} // namespace
+
+extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
+{
+    PDP_REQUIRE(p && status && model, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_solve: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return ex_launch<false>(p, nullptr, budget, status, model, work, stream);
+}
+
+extern "C" int pdp_exact_solve_hinted(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
+{
+    PDP_REQUIRE(p && status && model, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_solve_hinted: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return ex_launch<true>(p, hint, budget, status, model, work, stream);
 }

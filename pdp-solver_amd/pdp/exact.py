@@ -1,4 +1,4 @@
-"""SAT / UNSAT labels from the batched complete solver on the GPU (pdp_exact_solve, include/pdp_hip.h; DESIGN.md "Complete solver").
+"""SAT / UNSAT labels from the batched complete solver on the GPU (pdp_exact_solve and pdp_exact_solve_hinted, include/pdp_hip.h; DESIGN.md "Complete solver").
 
 PDP is incomplete: it finds assignments but never proves an instance unsatisfiable, so the reference leaves labelling to "your SAT solver
 of choice" (src/pdp/generator.py:15-17).  This module fills that hook: ``label_clause_lists`` labels many instances in a few launches,
@@ -43,11 +43,19 @@ def _segments(items, max_edges):
     return runs
 
 
-def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES):
+def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
     """Solve loader items ((n, m, graph_map, edge_feature, label, misc) tuples: dataset.instance_from_clauses, dataset.random_ksat_items,
     dataset.parse_line, raw_item).  Returns numpy (status int8 [N] in {1, 0, -1}, models: a float32 0/1 array of n_i values per instance,
-    work int64 [N]).  Instances are packed into problems of at most ``max_edges`` edges; nothing couples two instances."""
+    work int64 [N]).  Instances are packed into problems of at most ``max_edges`` edges; nothing couples two instances.
+    ``hints``: per instance an array of n_i phase hints (> 0.5 true first, other finite values false first, NaN none) or None (no hints for
+    that instance); the search is then pdp_exact_solve_hinted's (include/pdp_hip.h)."""
     native.require_gpu()
+    if hints is not None:
+        if len(hints) != len(items):
+            raise ValueError("hints: one entry per instance (%d), got %d" % (len(items), len(hints)))
+        for it, h in zip(items, hints):
+            if h is not None and np.asarray(h).size != int(it[0]):
+                raise ValueError("hints: instance %r has %d variables, its hints %d values" % (it[5], int(it[0]), np.asarray(h).size))
     device = torch.device('cuda:0') if device is None else torch.device(device)
     N = len(items)
     status = np.zeros(N, dtype=np.int8)
@@ -61,11 +69,19 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES):
             for i, it in zip(seg, part):
                 status[i] = 1 if int(it[1]) == 0 else 0
                 models[i] = np.zeros(int(it[0]), dtype=np.float32)
+                h = None if hints is None or hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
+                if status[i] == 1 and h is not None and not np.isnan(h).any():
+                    models[i] = (h > 0.5).astype(np.float32)           # the check pass accepts a complete hint: no clause objects
             continue
         b = dataset.to_torch(dataset.collate_segment(part), device)
         with torch.cuda.device(device):
             prob = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(part))
-            st, model, wk = prob.exact_solve(budget)
+            hint = None
+            if hints is not None:
+                flat = [np.full(int(it[0]), np.nan, dtype=np.float32) if hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
+                        for i, it in zip(seg, part)]
+                hint = torch.from_numpy(np.concatenate(flat)).to(device)
+            st, model, wk = prob.exact_solve(budget, hints=hint)
             st, model, wk = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
         del prob
         off = 0

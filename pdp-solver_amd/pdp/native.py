@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = [
     'pdp_train_linear', 'pdp_train_linear_backward', 'pdp_train_linear_s_supported', 'pdp_train_linear_s', 'pdp_train_linear_s_backward', 'pdp_train_row_sum', 'pdp_train_row_spread', 'pdp_train_gru', 'pdp_train_gru_fused', 'pdp_train_gru_backward', 'pdp_train_gru_backward_s',
     'pdp_sat_loss_grad', 'pdp_train_sp_adapted_backward',
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
-    'pdp_exact_solve',
+    'pdp_exact_solve', 'pdp_exact_solve_hinted',
 ]
 
 
@@ -407,14 +407,25 @@ class Problem(object):
         return out
 
     # -- complete solver ---------------------------------------------------------------------------------------
-    def exact_solve(self, budget=0):
+    def exact_solve(self, budget=0, hints=None):
         """Label every instance with the batched DPLL solver (pdp_exact_solve): (status int8 [B]: 1 SAT, 0 UNSAT, -1 undecided within
         ``budget`` clause-literal reads per instance, 0 = the library default; model float [V]: a satisfying 0/1 assignment of every status-1
-        instance, 0 elsewhere; work int64 [B]: the clause-literal reads of each search).  Asynchronous on the current stream."""
+        instance, 0 elsewhere; work int64 [B]: the clause-literal reads of each search).  Asynchronous on the current stream.
+        ``hints`` (float32, V elements, on the problem's device): phase hints, pdp_exact_solve_hinted -- > 0.5 true first, other finite values
+        false first, NaN no hint; an instance whose hints are all finite and satisfy it is answered by one pass over its clauses."""
+        if hints is not None:
+            if not torch.is_tensor(hints) or hints.dtype != torch.float32 or hints.numel() != self.V:
+                raise ValueError("hints must be a float32 tensor of %d elements (one per variable), got %s"
+                                 % (self.V, '%s of %d' % (hints.dtype, hints.numel()) if torch.is_tensor(hints) else type(hints).__name__))
+            hints = hints.reshape(-1).contiguous()
         status = torch.empty(self.B, dtype=torch.int8, device=self.device)
         model = torch.empty(self.V, dtype=torch.float32, device=self.device)
         work = torch.empty(self.B, dtype=torch.int64, device=self.device)
-        check(lib().pdp_exact_solve(self._h, C.c_int64(int(budget)), ptr(status), ptr(model), ptr(work), _stream()))
+        if hints is None:
+            check(lib().pdp_exact_solve(self._h, C.c_int64(int(budget)), ptr(status), ptr(model), ptr(work), _stream()))
+        else:
+            check(lib().pdp_exact_solve_hinted(self._h, ptr(hints, torch.float32, self.V, 'hints'), C.c_int64(int(budget)), ptr(status), ptr(model),
+                                               ptr(work), _stream()))
         return status, model, work
 
     # -- K14 ---------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Model factory + prediction post-processing for PDP SAT solvers (reference: src/pdp/trainer.py).
 
 The inference side of ``SatFactorGraphTrainer``: ``_build_graph`` (model_type -> solver class,
-trainer.py:48-99), ``_check_recurrence_termination`` (:150-162), ``_post_process_predictions`` (:125-148) and the test-mode
+trainer.py:48-99), ``_check_recurrence_termination`` (:150-162), ``_post_process_predictions`` (:125-148; ``_post_process_complete``: the same rows
+decided by the hinted exact search, satyr.py --complete) and the test-mode
 metrics ``_compute_evaluation_metrics`` (:108-123: accuracy / recall errors of the clause check and the energy loss), and the training
 loss ``_compute_loss`` (:100-106) used by ``FactorGraphTrainerBase._train_batch``.
 """
@@ -10,6 +11,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from pdp import native
 from pdp.factorgraph.base import FactorGraphTrainerBase
 from pdp.nn import solver, util
 
@@ -99,10 +101,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                                           sat_problem=sat_problem).unsqueeze(0)
         return torch.cat([accuracy, recall.reshape(1), loss_value], 0)
 
-    def _post_process_predictions(self, model, prediction, graph_map, batch_variable_map, batch_function_map,
-                                  edge_feature, graph_feat, label, misc_data):
-        """JSON result rows (reference: trainer.py:125-148).  The reference scans ``batch_variable_map == i`` for every
-        instance (O(B*V)); instance slices come from one prefix sum here."""
+    def _prediction_rows(self, model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label, misc_data):
+        "the result rows of a forward as dictionaries (the reference's five keys in its order) and the variable offsets of the instances"
         sat_problem = getattr(model, '_last_problem', None)
         solved, unsat = self._cnf_evaluator(prediction[0], graph_map, batch_variable_map, batch_function_map, edge_feature,
                                             graph_feat, sat_problem=sat_problem)
@@ -114,19 +114,58 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         offs = np.concatenate(([0], np.cumsum(counts)))
         rows = []
         for i in range(output.shape[0]):
-            instance = {
+            rows.append({
                 'ID': misc_data[i][0] if len(misc_data[i]) > 0 else "",
                 'label': int(labs[i, 0]),
                 'solved': int(output[i].flatten()[0] == 1),
                 'unsat_clauses': int(unsat_clause_num[i].flatten()[0]),
                 'solution': bits[offs[i]:offs[i + 1]].astype(int).tolist()
-            }
-            rows.append(str(instance).replace("'", '"') + "\n")
-            self._counter += 1
+            })
+        return rows, offs
+
+    def _write_rows(self, rows):
+        "the rows as text, counted as written"
+        self._counter += len(rows)
         if hasattr(self, '_run_stats'):
-            self._run_stats[0] += int(output.shape[0]); self._run_stats[1] += int((output.reshape(output.shape[0], -1)[:, 0] == 1).sum())
-            self._run_stats[2] += int(unsat_clause_num.sum())
-        return "".join(rows)
+            self._run_stats[0] += len(rows); self._run_stats[1] += sum(r['solved'] for r in rows)
+            self._run_stats[2] += sum(r['unsat_clauses'] for r in rows)
+        return "".join(str(r).replace("'", '"') + "\n" for r in rows)
+
+    def _post_process_predictions(self, model, prediction, graph_map, batch_variable_map, batch_function_map,
+                                  edge_feature, graph_feat, label, misc_data):
+        """JSON result rows (reference: trainer.py:125-148).  The reference scans ``batch_variable_map == i`` for every
+        instance (O(B*V)); instance slices come from one prefix sum here."""
+        rows, _ = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
+                                        misc_data)
+        return self._write_rows(rows)
+
+    def _post_process_complete(self, model, prediction, graph_map, batch_variable_map, batch_function_map,
+                               edge_feature, graph_feat, label, misc_data):
+        """The rows of ``_post_process_predictions`` completed by the exact search (satyr.py --complete): the prediction is the phase hint of
+        pdp_exact_solve_hinted on the unreplicated instances of the forward.  Every row gains "complete" (1 satisfiable, 0 unsatisfiable, -1
+        undecided within config['complete_budget'] clause-literal reads), "pdp_solved" (what "solved" is without the search) and "work" (the
+        reads of the search).  A satisfiable row gets solved 1, unsat_clauses 0 and the search's model -- PDP's own assignment where PDP had
+        solved the instance, because the check pass accepts it; every other row keeps its five reference keys."""
+        rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
+                                           misc_data)
+        sat_problem = getattr(model, '_last_problem', None)
+        handle = None
+        if sat_problem is not None and sat_problem._orig[0] is graph_map:
+            handle = sat_problem._native if sat_problem._batch_replication == 1 else sat_problem._native_unreplicated()
+        if handle is None or handle.R != 1 or handle.V != int(offs[-1]):
+            handle = native.Problem(graph_map, batch_variable_map, batch_function_map, edge_feature, batch_size=len(rows))
+        hint = prediction[0].detach().reshape(-1).to(torch.float32).contiguous()
+        status, solution, work = handle.exact_solve(int(self._config.get('complete_budget', 0) or 0), hints=hint)
+        status, work = status.cpu().numpy(), work.cpu().numpy()
+        solution = solution.cpu().numpy().astype(int)
+        for i, row in enumerate(rows):
+            row['complete'], row['pdp_solved'], row['work'] = int(status[i]), row['solved'], int(work[i])
+            if status[i] == 1:
+                row['solved'], row['unsat_clauses'], row['solution'] = 1, 0, solution[offs[i]:offs[i + 1]].tolist()
+        if hasattr(self, '_complete_stats'):
+            for k, s in enumerate((1, 0, -1)):
+                self._complete_stats[k] += int((status == s).sum())
+        return self._write_rows(rows)
 
     def _check_recurrence_termination(self, active, prediction, sat_problem):
         "De-activates the instances the model has already solved (reference: trainer.py:150-162)."

@@ -4,7 +4,9 @@
 Same positionals, flags, YAML keys and output format as the reference CLI (reference: satyr.py:45-109).
 Additions: ``--rng {torch,philox}`` (torch = the reference's CPU random stream, bit-compatible results for the
 same ``-s`` seed; philox = on-device counters, fastest), ``--stepwise`` (disable the one-launch persistent loop) and ``--isolated``
-(every instance on its own instead of the reference's batch-wide couplings).
+(every instance on its own instead of the reference's batch-wide couplings), and ``--complete`` / ``--complete-budget N``: every instance
+is then decided by the batched exact search with the model's assignment as its phase hints (pdp_exact_solve_hinted), and a row gains
+"complete" (1 satisfiable, 0 unsatisfiable, -1 undecided within the budget), "pdp_solved" and "work".
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -24,6 +26,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import dimacs2json  # noqa: E402
+from pdp import native  # noqa: E402
 from pdp.trainer import SatFactorGraphTrainer  # noqa: E402
 
 
@@ -38,6 +41,11 @@ def _open_output(path):
 
 def run(config, logger, output):
     "Seeds the two random sources, builds the model of config['model_type'] and writes one result row per input instance."
+    complete = bool(config.get('complete'))
+    if complete and config.get('split_forward'):
+        raise native.NativeError("--complete does not run together with --split-forward: the exact search needs whole segments on one rank")
+    if complete and config.get('isolated') and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        raise native.NativeError("--complete does not run together with --isolated on several ranks: the exact search needs whole segments on one rank")
     seed = config['random_seed']
     np.random.seed(seed)
     torch.manual_seed(seed)
@@ -45,14 +53,18 @@ def run(config, logger, output):
     say("Building the computational graph...")
     solver = SatFactorGraphTrainer(config=config, use_cuda=not config['cpu_mode'], logger=logger)
     solver._counter = 0
+    solver._complete_stats = [0, 0, 0]                  # satisfiable, unsatisfiable, undecided (this rank's units)
     say("Starting the prediction phase...")
     sink, owned = _open_output(output)
     try:
         solver.predict(test_list=config['test_path'], out_file=sink, import_path_base=config['model_path'],
-                       post_processor=solver._post_process_predictions, batch_replication=config['batch_replication'])
+                       post_processor=solver._post_process_complete if complete else solver._post_process_predictions,
+                       batch_replication=config['batch_replication'])
     finally:
         if owned:
             sink.close()
+    if complete:
+        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d" % tuple(solver._complete_stats))
     return solver
 
 
@@ -78,6 +90,11 @@ def main(argv=None):
                         '(global minima, NaN poisoning of the whole batch); p-d-p only, results differ from the reference where those couplings act.  On several ranks (torch.distributed.run) '
                         'the instances of every forward are then spread over all GPUs',
                         action='store_true')
+    parser.add_argument('--complete', help='Decide every instance with the batched exact search, the model\'s assignment as its phase hints: rows gain '
+                        '"complete" (1 satisfiable, 0 unsatisfiable, -1 undecided), "pdp_solved" and "work"; not with --split-forward, nor with --isolated on several ranks',
+                        action='store_true')
+    parser.add_argument('--complete-budget', dest='complete_budget', help='Clause-literal reads per instance of the --complete search (0 = the library default, 2^32)',
+                        type=int, default=0)
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')

@@ -2,9 +2,19 @@
 the one-time routing preparation is not in it), instances per second, SAT / UNSAT / undecided counts, median / p99 / max work
 (clause-literal reads per instance), literal reads per second, and the wall time of labelling the batch from loader items (collate,
 problem set-up, the first call with its preparation, results back on the host).
-Usage: python tools/exact_time.py [row ...]   (rows a b c d e; default all)"""
+Usage: python tools/exact_time.py [row ...]   (rows a b c d e; default all)
+
+Hinted rows (pdp_exact_solve_hinted; never part of the default): ``ha`` / ``hb`` = row (a) / (b) with the assignment of one p-d-p forward
+(T = 100, -w 100, philox) as phase hints: kernel time of the unhinted and the hinted solve on the same problem, total and median work over
+the satisfiable instances, the count PDP had solved, and the work sums over the unsatisfiable ones (they differ by the check-pass reads
+only).  ``wa`` = wall time of ``satyr.py`` on row (a)'s instances with and without ``--complete``."""
+import io
+import json
+import logging
 import os
+import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -82,7 +92,83 @@ def run(key):
         print("    planted n=20000 instance: status %d  work %d" % (int(status[big]), int(work[big])), flush=True)
 
 
+def _write_json(items, path):
+    from pdp import generator
+    with open(path, 'w') as f:
+        for it in items:
+            sv = ((it[2][0] + 1) * it[3]).astype(int)
+            f.write(generator.format_json_line(it[0], it[1], sv, it[2][1] + 1, label=-1, name=it[5][0]) + '\n')
+
+
+def _timed(p, hints):
+    "kernel ms (device events) and the outputs of the second call on the problem"
+    p.exact_solve(hints=hints)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    st, _, wk = p.exact_solve(hints=hints)
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]), st.cpu().numpy(), wk.cpu().numpy()
+
+
+def run_hinted(key):
+    "the prediction of one p-d-p forward (one segment: the batch is the loader batch) as the hints of the search on the same instances"
+    from pdp.trainer import SatFactorGraphTrainer
+    title, make = ROWS[key[1:]]
+    items = make()
+    cfg = dict(model_type='p-d-p', model_name='exact-time', verbose=False, local_search_iteration=100, epsilon=0.5, tolerance=0.02,
+               t_max=100, pi=0.01, decimation_probability=0.5, rng='philox', random_seed=0, hidden_dim=3, test_batch_limit=40000000,
+               batch_size=len(items), test_recurrence_num=100)
+    tr = SatFactorGraphTrainer(cfg, use_cuda=True, logger=logging.getLogger('exact-time'))
+    grabbed = []
+
+    def grab(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label, misc_data):
+        grabbed.append((prediction[0].detach().reshape(-1).to(torch.float32).clone(), graph_map, batch_variable_map, batch_function_map, edge_feature))
+        return ""
+    with tempfile.TemporaryDirectory() as tmp:
+        _write_json(items, os.path.join(tmp, 'in.json'))
+        tr.predict(os.path.join(tmp, 'in.json'), io.StringIO(), import_path_base=None, post_processor=grab, batch_replication=1)
+    assert len(grabbed) == 1, "expected one forward, got %d" % len(grabbed)
+    hint, gm, bvm, bfm, ef = grabbed[0]
+    p = native.Problem(gm, bvm, bfm, ef, batch_size=len(items))
+    pdp_solved = int(p.cnf_eval(hint.contiguous())[0].sum().item())
+    ms0, st0, wk0 = _timed(p, None)
+    ms1, st1, wk1 = _timed(p, hint)
+    assert np.array_equal(st0, st1), "hints changed a status"
+    sat, unsat = st0 == 1, st0 == 0
+    print("(%s) %s, hints = p-d-p forward T=100 -w 100 philox (PDP solved %d of %d satisfiable): kernel %.2f ms unhinted, %.2f ms hinted  "
+          "work over the satisfiable: total %d -> %d (ratio %.3f), median %d -> %d  hinted work below / equal / above the unhinted: %d / %d / %d  "
+          "work over the %d unsatisfiable: %d -> %d (difference = check-pass reads)"
+          % (key, title, pdp_solved, int(sat.sum()), ms0, ms1, int(wk0[sat].sum()), int(wk1[sat].sum()), float(wk1[sat].sum()) / float(wk0[sat].sum()),
+             int(np.median(wk0[sat])), int(np.median(wk1[sat])), int((wk1[sat] < wk0[sat]).sum()), int((wk1[sat] == wk0[sat]).sum()),
+             int((wk1[sat] > wk0[sat]).sum()), int(unsat.sum()), int(wk0[unsat].sum()), int(wk1[unsat].sum())), flush=True)
+
+
+def run_wall(key):
+    "wall time of the command line on the row's instances, without and with --complete (a fresh process each)"
+    title, make = ROWS[key[1:]]
+    items = make()
+    satyr = os.path.join(REPO, 'pdp-solver_amd', 'satyr.py')
+    yaml = os.path.join(REPO, 'config', 'Predict', 'PDP-p-d-p-sp-pytorch.yaml')
+    with tempfile.TemporaryDirectory() as tmp:
+        _write_json(items, os.path.join(tmp, 'in.json'))
+        took = {}
+        for name, extra in (('plain', []), ('complete', ['--complete'])):
+            out = os.path.join(tmp, name + '.jsonl')
+            t0 = time.perf_counter()
+            subprocess.check_call([sys.executable, satyr, yaml, os.path.join(tmp, 'in.json'), '100', '-z', str(len(items)), '-w', '100', '--rng', 'philox',
+                                   '-s', '0', '-o', out] + extra, stdout=subprocess.DEVNULL, timeout=600)
+            took[name] = time.perf_counter() - t0
+            rows = [json.loads(l) for l in open(out) if l.strip()]
+            took[name + '_solved'] = sum(r['solved'] for r in rows)
+            if extra:
+                took['unsat'] = sum(r['complete'] == 0 for r in rows)
+                took['undecided'] = sum(r['complete'] == -1 for r in rows)
+    print("(%s) %s: satyr.py T=100 -w 100 philox wall %.2f s (solved %d), with --complete %.2f s (satisfiable %d, unsatisfiable %d, undecided %d)"
+          % (key, title, took['plain'], took['plain_solved'], took['complete'], took['complete_solved'], took['unsat'], took['undecided']), flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
-        run(k)
+        {'h': run_hinted, 'w': run_wall}.get(k[0], run)(k)
