@@ -24,7 +24,8 @@ extern "C" {
 
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
- * pdp_exact_solve and pdp_exact_solve_hinted are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn and pdp_exact_learn_reductions are additions that change no existing entry point or structure, so the
+ * version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -221,6 +222,39 @@ int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model
  * is pdp_exact_solve's plus the check-pass reads; with pdp_exact_solve's model as the hint the check pass accepts it and work is at most
  * pdp_exact_solve's; all-NaN hints give pdp_exact_solve's three outputs exactly.  R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules. */
 int pdp_exact_solve_hinted(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream);
+
+/* The same search with conflict clause learning and backjumping instead of chronological backtracking (opt-in: the two entry points above
+ * are unchanged).  hint as in pdp_exact_solve_hinted (may be NULL); arena = 16-bit-word budget for learned clauses per instance (a clause
+ * of len literals takes len + 1 words), 0 = four words per literal (edge) of the instance, at most 2^30; learned [B] (may be NULL) = the
+ * clauses learned per instance, deleted ones included.  Literal coding, the pass structure (a clause stops reading at its first true
+ * literal, units are applied at the end of the pass), the branching rule, hint codes, the check pass, the budget check before every pass
+ * and work = clause-literal reads are pdp_exact_solve_hinted's.  New per instance: lev[v], the decision level of an assigned variable,
+ * rsn[v], the clause that implied it (none for a decision), and the learned clauses, which get the indices m, m + 1, ... in learning
+ * order and take part in every pass and every branching scan after the original ones.
+ *   Propagation pass over all live clauses in ascending index.  A clause with no true and no unassigned literal is falsified; the conflict
+ *     clause is the lowest-index one, and the pending units of that pass are dropped.  Otherwise a unit clause on literal (v, pol) records
+ *     the lowest clause index asking for (v, pol).  At the end of the pass let v* be the lowest variable asked for in both polarities, if
+ *     any: v* becomes true with its positive request's clause as reason, and its negative request's clause is the conflict clause; other
+ *     both-polarity variables stay unassigned.  Every single-polarity variable is assigned with its clause as reason.  All of them enter
+ *     the trail in ascending variable order at the current level.
+ *   Conflict at level 0: status 0.  Otherwise first-UIP analysis: start from the conflict clause and resolve backwards along the trail
+ *     with the reason of the latest seen current-level variable until exactly one current-level literal (the UIP) is left; literals
+ *     assigned at level 0 are dropped; work grows by the length of the conflict clause and of every reason resolved with.  The learned
+ *     clause is [not UIP, then the remaining literals ascending by variable]; the backjump level bl is the highest level among the
+ *     remaining literals (0 if none); every assignment above bl is undone, level = bl, then the clause is stored.  It is not asserted: the
+ *     next pass finds it unit.
+ *   Arena: if used + len + 1 > arena after the backjump, every learned clause that is not the reason of an assigned variable is deleted,
+ *     the others keep their order and are renumbered.  If the clause still does not fit: status -1 with the work so far.
+ * Per loop iteration the work added is at most one pass, one scan (twice a pass) and one analysis (every live literal at most once), so
+ * work < budget + 4 * (e + arena) for every instance (e = its edges).  Status, model, work and learned are a function of the instance,
+ * its hints, the budget and the arena size alone: the same alone, at any batch position, on repeated calls and in both library builds.
+ * All-NaN hints equal hint == NULL.  R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules; the routing and the HBM route's arenas are
+ * prepared once per problem and arena size (a call with another arena size synchronises the device and rebuilds them). */
+int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work,
+                          int32_t *learned, void *stream);
+/* reductions [B] (device) = how often each instance's arena was reduced in the last pdp_exact_solve_learn call on the problem, ordered
+ * after it on `stream`; PDP_ERR_INVALID before the first such call.  A function of the same inputs as the other outputs. */
+int pdp_exact_learn_reductions(pdp_problem *p, int32_t *reductions, void *stream);
 
 /* ---- persistent solve: the whole _forward_core loop in one launch ------------------------------------
  * replaces: PropagatorDecimatorSolverBase._forward_core (solver.py:355-386) for the classical

@@ -142,6 +142,9 @@ struct pdp_problem {
     // HBM route's working arrays, one block allocated on first use
     int ex_ready, ex_nbig; size_t ex_lds_bytes;
     char *ex_blob; int32_t *ex_order; uint32_t *ex_next; uint32_t *ex_h_lit;
+    // learning complete solver (pdp_exact.hip::exl_prepare): the same for its own routing, with the HBM route's arenas (exl_words words);
+    // rebuilt when the arena size of the call changes
+    int exl_ready, exl_nbig; int64_t exl_arena; size_t exl_lds_bytes, exl_words; char *exl_blob;
     uint32_t *team_ws;          // barrier counters and reduction mailboxes of the workgroup teams (k_sp_solve<NT, true>)
     hipStream_t res_side_stream; hipEvent_t res_side_ev[2];   // the big instances' launches overlap the LDS-resident kernel on a stream of their own
     float *nws[4]; size_t nws_floats[4];             // neural workspaces (grow on demand)

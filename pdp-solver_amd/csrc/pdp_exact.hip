@@ -402,6 +402,497 @@ int ex_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status,
     return PDP_OK;
 }
 
+// ---- pdp_exact_solve_learn: the same passes, branching rule, hints and budget with conflict clause learning and backjumping -------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_learn_model.py).  Its own state, search, kernel and launch path: nothing
+// above is touched.  On top of the DPLL state an instance has
+//   lev [n]   decision level of an assigned variable        rsn [n]   clause that implied it (EXL_NONE: a decision)
+//   req [2n]  per literal, the lowest clause index that asked for it as a unit in the current pass (EXL_NONE between passes)
+//   ar  [A]   the arena: the learned clauses' literals grow from word 0, their end offsets from word A - 1 downwards (clause j ends at
+//             ar[A - 1 - j]), so a clause of len literals takes len + 1 words and clause m + j is the j-th live learned clause
+// and pend[v] keeps the hint code (bits 8-9) and the two marks of the conflict analysis.  On the LDS route the arena follows lit in the
+// slab as u16 words; on the HBM route it is a block of u32 words per instance.  Everything a lane decides is wave-uniform or a function of
+// the variable / clause it holds, and every reduction is a sum, a minimum or a maximum: the outputs do not depend on lane order.
+constexpr uint32_t EXL_NONE = 0xffffffffu;
+constexpr uint32_t EXL_SEEN = 4u, EXL_OUT = 8u;  // pend[v]: met by the analysis / goes into the learned clause (a level below the current one)
+constexpr int EXL_INF = 0x7fffffff;
+constexpr int64_t EXL_MAX_ARENA = (int64_t)1 << 30;
+
+__host__ __device__ inline int exl_arena(int64_t arena, int e)
+{
+    const int64_t a = arena > 0 ? arena : 4 * (int64_t)e;
+    return (int)(a < EXL_MAX_ARENA ? a : EXL_MAX_ARENA);
+}
+
+struct ExlLds { size_t pend, cnt, req, trail, mark, lev, rsn, lit, cptr, val, bytes; };
+
+// 4-byte arrays first, then the 2-byte literals (the instance's e, then the arena's A) and offsets, then the value bytes
+__host__ __device__ inline ExlLds exl_lds_layout(int n, int m, int e, int A)
+{
+    ExlLds L;
+    size_t o = 0;
+    L.pend = o;  o += 4 * (size_t)n;
+    L.cnt = o;   o += 8 * (size_t)n;
+    L.req = o;   o += 8 * (size_t)n;
+    L.trail = o; o += 4 * (size_t)n;
+    L.mark = o;  o += 4 * ((size_t)n + 1);
+    L.lev = o;   o += 4 * (size_t)n;
+    L.rsn = o;   o += 4 * (size_t)n;
+    L.lit = o;   o += 2 * ((size_t)e + (size_t)A);
+    L.cptr = o;  o += 2 * ((size_t)m + 1);
+    L.val = o;   o += (size_t)n;
+    L.bytes = (o + 15) & ~(size_t)15;
+    return L;
+}
+// u16 literal codes with the top bit free (the arena reduction marks a clause there) need n < 16384, u16 offsets e + A <= 65535
+inline bool exl_fits_lds(int n, int m, int e, int A)
+{
+    return n < 16384 && (int64_t)e + A <= 65535 && exl_lds_layout(n, m, e, A).bytes <= EX_LDS_LIMIT;
+}
+
+struct ExlParams {
+    const int32_t *order;       // as ExParams: the nbig HBM-routed instances first
+    int nbig, B;
+    uint32_t *next;
+    int64_t budget, arena;      // arena: words per instance, 0 = 4 e
+    int8_t *status; float *model; int64_t *work; int32_t *learned;
+    int32_t *reductions;        // [B] arena reductions per instance of the last call (kept on the problem: pdp_exact_learn_reductions)
+    const float *hint;
+    // working arrays of the HBM route, indexed by the problem's global ids
+    uint32_t *h_lit;            // [E]
+    uint8_t *h_val;             // [V]
+    uint32_t *h_pend, *h_cnt, *h_req, *h_rsn;   // [V], [2V], [2V], [V]
+    int32_t *h_trail, *h_lev;   // [V]
+    int32_t *h_mark;            // [V+B]
+    uint32_t *h_arena;          // the HBM-routed instances' arenas
+    const int64_t *h_aoff;      // [B] by instance id: where an HBM-routed instance's arena starts
+};
+
+template <typename LitT, typename PtrT>
+struct ExlInst {
+    LitT *lit; const PtrT *cptr; LitT *ar;
+    uint8_t *val; uint32_t *pend, *cnt, *req, *rsn; int32_t *trail, *mark, *lev;
+    int n, m, e, A;
+};
+
+__device__ __forceinline__ int ex_max(int x)
+{
+    for (int o = 32; o > 0; o >>= 1) { const int y = __shfl_xor(x, o); x = y > x ? y : x; }
+    return x;
+}
+
+// literals of clause c: an original one (c < m) or the live learned clause c - m
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ const LitT *exl_span(const ExlInst<LitT, PtrT> &X, int c, int &len)
+{
+    if (c < X.m) { const int a = (int)X.cptr[c]; len = (int)X.cptr[c + 1] - a; return X.lit + a; }
+    const int j = c - X.m;
+    const int s = j ? (int)X.ar[X.A - j] : 0;
+    len = (int)X.ar[X.A - 1 - j] - s;
+    return X.ar + s;
+}
+
+// Arena reduction: every learned clause that is not the reason of an assigned variable goes, the others move up in order and the
+// reasons are renumbered.  A kept clause is marked in the free top bit of its first literal; it is the reason of exactly one variable,
+// the one of its only true literal.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void exl_reduce(const ExlInst<LitT, PtrT> &X, int tlen, int &nl, int &lits)
+{
+    constexpr LitT TOP = (LitT)((LitT)1 << (8 * sizeof(LitT) - 1));
+    const int lane = (int)threadIdx.x;
+    for (int t = lane; t < tlen; t += EX_NT) {
+        const uint32_t r = X.rsn[X.trail[t]];
+        if (r != EXL_NONE && r >= (uint32_t)X.m) { const int j = (int)r - X.m; X.ar[j ? (int)X.ar[X.A - j] : 0] |= TOP; }
+    }
+    ex_sync<HBM>();
+    int kept = 0, w = 0;
+    for (int base = 0; base < nl; base += EX_NT) {
+        const int j = base + lane;
+        int s = 0, z = 0, keep = 0;
+        if (j < nl) { s = j ? (int)X.ar[X.A - j] : 0; z = (int)X.ar[X.A - 1 - j]; keep = (X.ar[s] & TOP) != 0; }
+        unsigned long long mask = __ballot(keep);
+        ex_sync<HBM>();                                             // the chunk's offsets are read before one of them is rewritten
+        while (mask) {
+            const int l = __ffsll((long long)mask) - 1;
+            mask &= mask - 1ull;
+            const int cs = __shfl(s, l), len = __shfl(z, l) - cs;
+            const uint32_t old = (uint32_t)(X.m + base + l);
+            for (int t0 = 0; t0 < len; t0 += EX_NT) {
+                const int t = t0 + lane;
+                LitT x = 0;
+                if (t < len) {
+                    x = (LitT)(X.ar[cs + t] & (LitT)~TOP);
+                    const int v = (int)(x >> 1);
+                    if (X.val[v] == 1u + (x & 1u) && X.rsn[v] == old) X.rsn[v] = (uint32_t)(X.m + kept);
+                }
+                ex_sync<HBM>();                                     // read by every lane before the (lower) target is written
+                if (t < len) X.ar[w + t] = x;
+                ex_sync<HBM>();
+            }
+            if (lane == 0) X.ar[X.A - 1 - kept] = (LitT)(w + len);
+            w += len; ++kept;
+        }
+        ex_sync<HBM>();
+    }
+    nl = kept; lits = w;
+}
+
+// The learning search of one instance by the calling wave: 1 / 0 as ex_search, -1 when the budget is spent or a learned clause does not
+// fit the arena even after a reduction.  *learned_out = clauses learned (also the deleted ones), *reductions_out = arena reductions.
+template <bool HBM, bool HINT, typename LitT, typename PtrT>
+__device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, bool check, int64_t *work_out, int *learned_out, int *reductions_out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int level = 0, tlen = 0, nl = 0, lits = 0, learned = 0, reductions = 0;     // nl live learned clauses holding lits literals: nl + lits arena words
+    int64_t work = 0;
+    int result = -1;
+    *learned_out = 0; *reductions_out = 0;
+    if constexpr (HINT) {
+        if (check) {
+            for (int v = lane; v < X.n; v += EX_NT) X.val[v] = (uint8_t)((X.pend[v] >> EX_HINT_SHIFT) & 3u);
+            ex_sync<HBM>();
+            int reads = 0, open = 0;
+            for (int c = lane; c < X.m; c += EX_NT) {
+                const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+                int sat = 0, k = a;
+                for (; k < z; ++k) {
+                    const uint32_t L = X.lit[k];
+                    if (X.val[L >> 1] == 1u + (L & 1u)) { sat = 1; ++k; break; }
+                }
+                reads += k - a;
+                open |= !sat;
+            }
+            work += ex_sum(reads);
+            if (__ballot(open) == 0ull) { *work_out = work; return 1; }
+            ex_sync<HBM>();
+            for (int v = lane; v < X.n; v += EX_NT) X.val[v] = 0;
+            ex_sync<HBM>();
+        }
+    }
+    for (;;) {
+        if (work >= budget) break;
+        const int nc = X.m + nl;
+        // ---- one unit-propagation pass: the lowest falsified clause, and per literal the lowest clause that asks for it
+        int reads = 0, unit = 0, wmin = EXL_INF, cmin = EXL_INF;
+        for (int c = lane; c < nc; c += EX_NT) {
+            int len;
+            const LitT *p = exl_span(X, c, len);
+            int nfree = 0, sat = 0, k = 0, distinct = 0;
+            uint32_t first = 0;
+            for (; k < len; ++k) {
+                const uint32_t L = p[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k;
+            if (sat) continue;
+            if (nfree == 0) cmin = c < cmin ? c : cmin;
+            else if (!distinct) { unit = 1; atomicMin(&X.req[first], (uint32_t)c); }
+            else wmin = nfree < wmin ? nfree : wmin;
+        }
+        work += ex_sum(reads);
+        int confl = ex_min(cmin);
+        const bool any_unit = __ballot(unit) != 0ull;
+        if (any_unit) {
+            ex_sync<HBM>();
+            if (confl != EXL_INF) {
+                // a falsified clause: the requests of the pass are dropped
+                for (int v = lane; v < X.n; v += EX_NT) { X.req[2 * v] = EXL_NONE; X.req[2 * v + 1] = EXL_NONE; }
+            } else {
+                // the lowest variable asked for in both polarities becomes true and its negative request the conflict; the other such
+                // variables stay unassigned
+                int vs = EXL_INF;
+                for (int v = lane; v < X.n; v += EX_NT)
+                    if (X.req[2 * v] != EXL_NONE && X.req[2 * v + 1] != EXL_NONE) vs = v < vs ? v : vs;
+                vs = ex_min(vs);
+                if (vs != EXL_INF) { confl = (int)X.req[2 * vs + 1]; ex_sync<HBM>(); }
+                for (int base = 0; base < X.n; base += EX_NT) {
+                    const int v = base + lane;
+                    const uint32_t r1 = v < X.n ? X.req[2 * v] : EXL_NONE, r0 = v < X.n ? X.req[2 * v + 1] : EXL_NONE;
+                    const bool p1 = r1 != EXL_NONE, p0 = r0 != EXL_NONE;
+                    const bool take = (p1 != p0) || (p1 && v == vs);
+                    const unsigned long long mask = __ballot(take);
+                    if (p1 || p0) { X.req[2 * v] = EXL_NONE; X.req[2 * v + 1] = EXL_NONE; }
+                    if (take) {
+                        X.val[v] = p1 ? 1 : 2; X.lev[v] = level; X.rsn[v] = p1 ? r1 : r0;
+                        X.trail[tlen + __popcll(mask & below)] = v;
+                    }
+                    tlen += __popcll(mask);
+                }
+            }
+            ex_sync<HBM>();
+        }
+        if (confl != EXL_INF) {
+            if (level == 0) { result = 0; break; }
+            // ---- first-UIP analysis: a clause's literals across the lanes, the next seen trail entry by a ballot over 64 slots
+            int open = 0, nout = 0, bl = 0, i = tlen - 1, uip = -1, c = confl;
+            bool bad = false;
+            for (;;) {
+                int len;
+                const LitT *p = exl_span(X, c, len);
+                work += len;
+                int mine = 0;
+                for (int k = lane; k < len; k += EX_NT) {
+                    const int v = (int)(p[k] >> 1);
+                    if (atomicOr(&X.pend[v], EXL_SEEN) & EXL_SEEN) continue;           // exactly one lane meets a variable first
+                    const int lv = X.lev[v];
+                    if (lv == level) ++mine;
+                    else if (lv > 0) { atomicOr(&X.pend[v], EXL_OUT); ++nout; bl = lv > bl ? lv : bl; }
+                }
+                open += ex_sum(mine);
+                ex_sync<HBM>();
+                int pos = -1;
+                while (i >= 0) {
+                    const int idx = i - lane;
+                    const unsigned long long mask = __ballot(idx >= 0 && (X.pend[X.trail[idx >= 0 ? idx : 0]] & EXL_SEEN) != 0u);
+                    if (mask) { pos = i - (__ffsll((long long)mask) - 1); break; }
+                    i -= EX_NT;
+                }
+                if (pos < 0) { bad = true; break; }                 // unreachable: a conflict clause has a literal of the current level
+                uip = X.trail[pos];
+                i = pos - 1;
+                if (--open == 0) break;
+                const uint32_t r = X.rsn[uip];
+                if (r == EXL_NONE) { bad = true; break; }           // unreachable: only the last variable met can be the decision
+                c = (int)r;
+            }
+            if (bad) break;
+            nout = ex_sum(nout);
+            bl = ex_max(bl);
+            const uint32_t ulit = ((uint32_t)uip << 1) | (X.val[uip] == 1 ? 1u : 0u);     // the negation of the UIP's literal
+            const int len = 1 + nout, from = X.mark[bl + 1];
+            ex_sync<HBM>();                                         // every lane has read the levels before they are undone
+            for (int t = from + lane; t < tlen; t += EX_NT) X.val[X.trail[t]] = 0;
+            tlen = from; level = bl;
+            ex_sync<HBM>();
+            if (lits + nl + len + 1 > X.A) {
+                exl_reduce<HBM>(X, tlen, nl, lits);
+                ++reductions;
+                if (lits + nl + len + 1 > X.A) break;               // does not fit: undecided
+            }
+            // the clause: the UIP's literal, then the marked variables ascending (all false now); the next pass finds it unit
+            if (lane == 0) X.ar[lits] = (LitT)ulit;
+            int w = lits + 1;
+            for (int base = 0; base < X.n; base += EX_NT) {
+                const int v = base + lane;
+                const uint32_t word = v < X.n ? X.pend[v] : 0u;
+                const bool o = (word & EXL_OUT) != 0u;
+                const unsigned long long mask = __ballot(o);
+                if (word & (EXL_SEEN | EXL_OUT)) X.pend[v] = word & ~(EXL_SEEN | EXL_OUT);
+                if (o) X.ar[w + __popcll(mask & below)] = (LitT)(((uint32_t)v << 1) | (X.val[v] == 1 ? 1u : 0u));
+                w += __popcll(mask);
+            }
+            if (lane == 0) X.ar[X.A - 1 - nl] = (LitT)w;
+            lits = w; ++nl; ++learned;
+            ex_sync<HBM>();
+            continue;
+        }
+        if (any_unit) continue;
+        wmin = ex_min(wmin);
+        if (wmin == EXL_INF) { result = 1; break; }
+        // ---- branching: as ex_search, over the learned clauses too
+        reads = 0;
+        for (int c = lane; c < nc; c += EX_NT) {
+            int len;
+            const LitT *p = exl_span(X, c, len);
+            int nfree = 0, sat = 0, k = 0;
+            for (; k < len; ++k) {
+                const uint32_t L = p[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) ++nfree;
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k;
+            if (sat || nfree != wmin) continue;
+            for (int j = 0; j < len; ++j) {
+                const uint32_t L = p[j];
+                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+            }
+            reads += len;
+        }
+        work += ex_sum(reads);
+        ex_sync<HBM>();
+        unsigned long long best = 0ull;
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+            if (p | q) {
+                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+                bool pos = p >= q;
+                if constexpr (HINT) {
+                    const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
+                    if (code) pos = code == 1u;
+                }
+                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                               (pos ? 1ull : 0ull);
+                best = key > best ? key : best;
+            }
+        }
+        best = ex_max64(best);
+        if (best == 0ull) break;            // unreachable, as in ex_search
+        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        ++level;
+        ex_sync<HBM>();
+        if (lane == 0) {
+            X.mark[level] = tlen; X.val[v] = (best & 1ull) ? 1 : 2; X.lev[v] = level; X.rsn[v] = EXL_NONE; X.trail[tlen] = v;
+        }
+        ++tlen;
+        ex_sync<HBM>();
+    }
+    *work_out = work;
+    *learned_out = learned;
+    *reductions_out = reductions;
+    return result;
+}
+
+template <bool HBM, bool HINT, typename LitT, typename PtrT>
+__device__ void ex_solve_learn(const ExlParams &xp, const Inst &I, ExlInst<LitT, PtrT> X, PtrT *cptr_fill)
+{
+    const int lane = (int)threadIdx.x;
+    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+    for (int k = lane; k < I.e; k += EX_NT) {
+        const int ed = I.f_edges[k];
+        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+    }
+    int none = !HINT || xp.hint == nullptr;
+    for (int v = lane; v < I.n; v += EX_NT) {
+        uint32_t code = 0u;
+        if constexpr (HINT) {
+            if (xp.hint) { const float h = xp.hint[I.v0 + v]; code = h != h ? 0u : (h > 0.5f ? 1u : 2u); }
+        }
+        none |= code == 0u;
+        X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        X.req[2 * v] = EXL_NONE; X.req[2 * v + 1] = EXL_NONE;
+    }
+    const bool check = HINT && __ballot(none) == 0ull;
+    ex_sync<HBM>();
+    int64_t work = 0;
+    int learned = 0, reductions = 0;
+    const int st = ex_search_learn<HBM, HINT>(X, xp.budget, check, &work, &learned, &reductions);
+    for (int v = lane; v < I.n; v += EX_NT) xp.model[I.v0 + v] = (st == 1 && X.val[v] == 1) ? 1.0f : 0.0f;
+    if (lane == 0) {
+        xp.status[I.b] = (int8_t)st;
+        if (xp.work) xp.work[I.b] = work;
+        if (xp.learned) xp.learned[I.b] = learned;
+        xp.reductions[I.b] = reductions;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+template <bool HINT>
+__global__ void __launch_bounds__(EX_NT) k_exact_learn(PView pv, ExlParams xp)
+{
+    extern __shared__ __align__(16) unsigned char exl_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        const int A = exl_arena(xp.arena, I.e);
+        if (i < xp.nbig) {
+            ExlInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr; X.ar = xp.h_arena + xp.h_aoff[I.b];
+            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.req = xp.h_req + 2 * (size_t)I.v0;
+            X.rsn = xp.h_rsn + I.v0; X.trail = xp.h_trail + I.v0; X.mark = xp.h_mark + I.v0 + I.b; X.lev = xp.h_lev + I.v0;
+            X.n = I.n; X.m = I.m; X.e = I.e; X.A = A;
+            ex_solve_learn<true, HINT, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
+        } else {
+            const ExlLds L = exl_lds_layout(I.n, I.m, I.e, A);
+            ExlInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(exl_slab + L.lit); X.cptr = (const uint16_t *)(exl_slab + L.cptr); X.ar = X.lit + I.e;
+            X.val = exl_slab + L.val; X.pend = (uint32_t *)(exl_slab + L.pend); X.cnt = (uint32_t *)(exl_slab + L.cnt);
+            X.req = (uint32_t *)(exl_slab + L.req); X.rsn = (uint32_t *)(exl_slab + L.rsn); X.trail = (int32_t *)(exl_slab + L.trail);
+            X.mark = (int32_t *)(exl_slab + L.mark); X.lev = (int32_t *)(exl_slab + L.lev);
+            X.n = I.n; X.m = I.m; X.e = I.e; X.A = A;
+            ex_solve_learn<false, HINT, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(exl_slab + L.cptr));
+        }
+    }
+}
+
+// Routing, instance order, working arrays and the HBM route's arenas: once per problem and arena size.
+// One block: order [B] | counter | aoff [B] | reductions [B] | (HBM route) lit [E] | pend [V] | cnt [2V] | req [2V] | rsn [V] | trail [V] | lev [V] |
+// mark [V+B] | arenas | val [V]
+int exl_prepare(pdp_problem *p, int64_t arena)
+{
+    if (p->exl_ready && p->exl_arena == arena) return PDP_OK;
+    if (p->exl_blob) { PDP_HIP_CHECK(hipDeviceSynchronize()); pdp_dev_free(p->exl_blob); p->exl_blob = nullptr; }
+    p->exl_ready = 0;
+    const size_t B = p->B;
+    std::vector<int32_t> v0(B + 1), f0(B + 1), e0(B + 1);
+    PDP_HIP_CHECK(hipMemcpy(v0.data(), p->inst_v0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(f0.data(), p->inst_f0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(e0.data(), p->inst_e0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> big, fit;
+    std::vector<int64_t> aoff(B, 0);
+    size_t lds = 0, words = 0;
+    for (size_t b = 0; b < B; ++b) {
+        const int n = v0[b + 1] - v0[b], m = f0[b + 1] - f0[b], e = e0[b + 1] - e0[b], A = exl_arena(arena, e);
+        if (exl_fits_lds(n, m, e, A)) { fit.push_back((int32_t)b); lds = std::max(lds, exl_lds_layout(n, m, e, A).bytes); }
+        else { big.push_back((int32_t)b); aoff[b] = (int64_t)words; words += (size_t)A; }
+    }
+    auto by_edges = [&](int32_t a, int32_t b) { const int ea = e0[a + 1] - e0[a], eb = e0[b + 1] - e0[b]; return ea != eb ? ea > eb : a < b; };
+    std::sort(big.begin(), big.end(), by_edges);
+    std::sort(fit.begin(), fit.end(), by_edges);
+    std::vector<int32_t> order(big);
+    order.insert(order.end(), fit.begin(), fit.end());
+    const size_t V = p->V, E = p->E;
+    const size_t head = ((B + 1) * 4 + 7) & ~(size_t)7;
+    size_t bytes = head + B * 12;
+    if (!big.empty()) bytes += E * 4 + V * 32 + (V + B) * 4 + words * 4 + V;
+    char *blk = nullptr;
+    { const int st_ = pdp_dev_alloc((void **)&blk, (bytes + 15) & ~(size_t)15); if (st_ != PDP_OK) return st_; }
+    p->exl_blob = blk;
+    PDP_HIP_CHECK(hipMemcpy(blk, order.data(), B * 4, hipMemcpyHostToDevice));
+    PDP_HIP_CHECK(hipMemcpy(blk + head, aoff.data(), B * 8, hipMemcpyHostToDevice));
+    p->exl_nbig = (int)big.size();
+    p->exl_lds_bytes = lds;
+    p->exl_words = words;
+    p->exl_arena = arena;
+    p->exl_ready = 1;
+    return PDP_OK;
+}
+
+template <bool HINT>
+int exl_launch(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work, int32_t *learned,
+               void *stream)
+{
+    { const int st_ = exl_prepare(p, arena); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t V = p->V, E = p->E, B = p->B;
+    const size_t head = ((B + 1) * 4 + 7) & ~(size_t)7;
+    ExlParams xp;
+    xp.order = (const int32_t *)p->exl_blob; xp.nbig = p->exl_nbig; xp.B = p->B; xp.next = (uint32_t *)(p->exl_blob + B * 4);
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.arena = arena;
+    xp.status = status; xp.model = model; xp.work = work; xp.learned = learned; xp.hint = hint;
+    xp.h_aoff = (const int64_t *)(p->exl_blob + head);
+    xp.reductions = (int32_t *)(p->exl_blob + head + B * 8);
+    xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_req = nullptr; xp.h_rsn = nullptr; xp.h_trail = nullptr; xp.h_lev = nullptr;
+    xp.h_mark = nullptr; xp.h_arena = nullptr; xp.h_val = nullptr;
+    if (p->exl_nbig) {
+        char *q = p->exl_blob + head + B * 12;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_pend = (uint32_t *)q;           q += V * 4;
+        xp.h_cnt = (uint32_t *)q;            q += V * 8;
+        xp.h_req = (uint32_t *)q;            q += V * 8;
+        xp.h_rsn = (uint32_t *)q;            q += V * 4;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_lev = (int32_t *)q;             q += V * 4;
+        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
+        xp.h_arena = (uint32_t *)q;          q += p->exl_words * 4;
+        xp.h_val = (uint8_t *)q;
+    }
+    const int lds = (int)p->exl_lds_bytes;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_learn<HINT>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu);
+    PDP_HIP_CHECK(hipMemsetAsync(xp.next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_learn<HINT>, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -422,4 +913,26 @@ extern "C" int pdp_exact_solve_hinted(pdp_problem *p, const float *hint, int64_t
         return PDP_ERR_UNSUPPORTED;
     }
     return ex_launch<true>(p, hint, budget, status, model, work, stream);
+}
+
+extern "C" int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work,
+                                     int32_t *learned, void *stream)
+{
+    PDP_REQUIRE(p && status && model, "NULL argument");
+    PDP_REQUIRE(arena >= 0 && arena <= EXL_MAX_ARENA, "pdp_exact_solve_learn: arena must be 0 (four words per literal) or 1 .. 2^30 words");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_solve_learn: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return hint ? exl_launch<true>(p, hint, budget, arena, status, model, work, learned, stream)
+                : exl_launch<false>(p, nullptr, budget, arena, status, model, work, learned, stream);
+}
+
+extern "C" int pdp_exact_learn_reductions(pdp_problem *p, int32_t *reductions, void *stream)
+{
+    PDP_REQUIRE(p && reductions, "NULL argument");
+    PDP_REQUIRE(p->exl_ready, "pdp_exact_learn_reductions: no pdp_exact_solve_learn call on this problem yet");
+    const size_t B = p->B, head = ((B + 1) * 4 + 7) & ~(size_t)7;
+    PDP_HIP_CHECK(hipMemcpyAsync(reductions, p->exl_blob + head + B * 8, B * 4, hipMemcpyDeviceToDevice, ST(stream)));
+    return PDP_OK;
 }

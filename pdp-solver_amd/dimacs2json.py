@@ -103,10 +103,10 @@ def json_line(path, label, propagate=False):
     return generator.format_json_line(var_num, clause_num, signed_vars, clause_ids, label=label, name=os.path.split(path)[1])
 
 
-def exact_labels(instances, budget=0):
+def exact_labels(instances, budget=0, learn=False):
     """Labels of compact instances ((var_num, clause_num, signed_vars, clause_ids) as written to the lines) from the complete GPU solver
     (pdp.exact), all instances in a few launches: 1.0 satisfiable, 0.0 unsatisfiable, -1 undecided within the budget (the converter's
-    "no label" value)."""
+    "no label" value).  ``learn``: the search with conflict clause learning (the same labels)."""
     import numpy as np
     from pdp import exact
     items = []
@@ -114,19 +114,19 @@ def exact_labels(instances, budget=0):
         sv, ci = np.asarray(signed_vars, dtype=np.int64), np.asarray(clause_ids, dtype=np.int64)
         graph_map = np.stack((np.abs(sv) - 1, ci - 1)).astype(np.int32).reshape(2, -1)
         items.append((int(var_num), int(clause_num), graph_map, np.sign(sv).astype(np.float32), -1.0, []))
-    status, _, _ = exact.solve_items(items, budget=budget)
+    status, _, _ = exact.solve_items(items, budget=budget, learn=learn)
     return [1.0 if s == 1 else (0.0 if s == 0 else -1) for s in status]
 
 
 def convert_directory(dimacs_dir, output_file, propagate=False, only_positive=False, label='name', budget=0):
     """label 'name': the reference's rule (the last digit of the file stem, else -1); 'exact': the complete solver's answer for the
-    instance the line holds (exact_labels).  Every other byte of a line is the same either way."""
+    instance the line holds (exact_labels), 'exact-learn': the same from the learning search.  Every other byte of a line is the same either way."""
     file_list = [os.path.join(dimacs_dir, f) for f in os.listdir(dimacs_dir) if os.path.isfile(os.path.join(dimacs_dir, f))]
-    if label == 'exact':
+    if label in ('exact', 'exact-learn'):
         paths = [p for p in file_list if os.path.splitext(p)[1].lower() in ('.dimacs', '.cnf')]
         instances = [compact_instance(p, propagate) for p in paths]
         with open(output_file, 'w') as f:
-            for path, inst, lab in zip(paths, instances, exact_labels(instances, budget) if instances else []):
+            for path, inst, lab in zip(paths, instances, exact_labels(instances, budget, learn=label == 'exact-learn') if instances else []):
                 if only_positive and lab == 0:
                     continue
                 f.write(generator.format_json_line(*inst, label=lab, name=os.path.split(path)[1]) + '\n')
@@ -158,9 +158,10 @@ def cli_parser():
     parser.add_argument('out_file', action='store', type=str)
     parser.add_argument('-s', '--simplify', help='Propagate binary constraints', required=False, action='store_true', default=False)
     parser.add_argument('-p', '--positive', help='Output only positive examples', required=False, action='store_true', default=False)
-    parser.add_argument('--label', choices=('name', 'exact'), default='name',
-                        help="name: the last digit of the file name (the reference's rule); exact: solve every instance on the GPU")
-    parser.add_argument('--budget', type=int, default=0, help="clause-literal reads per instance for --label exact (0: the library default)")
+    parser.add_argument('--label', choices=('name', 'exact', 'exact-learn'), default='name',
+                        help="name: the last digit of the file name (the reference's rule); exact: solve every instance on the GPU; "
+                             "exact-learn: the same with conflict clause learning")
+    parser.add_argument('--budget', type=int, default=0, help="clause-literal reads per instance for --label exact / exact-learn (0: the library default)")
     return parser
 
 

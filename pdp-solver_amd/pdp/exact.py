@@ -43,12 +43,16 @@ def _segments(items, max_edges):
     return runs
 
 
-def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
+def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0):
     """Solve loader items ((n, m, graph_map, edge_feature, label, misc) tuples: dataset.instance_from_clauses, dataset.random_ksat_items,
     dataset.parse_line, raw_item).  Returns numpy (status int8 [N] in {1, 0, -1}, models: a float32 0/1 array of n_i values per instance,
     work int64 [N]).  Instances are packed into problems of at most ``max_edges`` edges; nothing couples two instances.
     ``hints``: per instance an array of n_i phase hints (> 0.5 true first, other finite values false first, NaN none) or None (no hints for
-    that instance); the search is then pdp_exact_solve_hinted's (include/pdp_hip.h)."""
+    that instance); the search is then pdp_exact_solve_hinted's (include/pdp_hip.h).
+    ``learn``: the search with conflict clause learning (pdp_exact_solve_learn) and ``arena`` words per instance for its learned clauses
+    (0: four per literal); same answers, far fewer reads on structured instances."""
+    if arena and not learn:
+        raise ValueError("arena belongs to the learning search: pass learn=True")
     native.require_gpu()
     if hints is not None:
         if len(hints) != len(items):
@@ -81,7 +85,7 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
                 flat = [np.full(int(it[0]), np.nan, dtype=np.float32) if hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
                         for i, it in zip(seg, part)]
                 hint = torch.from_numpy(np.concatenate(flat)).to(device)
-            st, model, wk = prob.exact_solve(budget, hints=hint)
+            st, model, wk = prob.exact_solve(budget, hints=hint, learn=learn, arena=arena)
             st, model, wk = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
         del prob
         off = 0
@@ -97,12 +101,13 @@ def _label(s):
     return True if s == 1 else (False if s == 0 else None)
 
 
-def label_clause_lists(instances, budget=0, device=None, max_edges=MAX_EDGES):
+def label_clause_lists(instances, budget=0, device=None, max_edges=MAX_EDGES, learn=False, arena=0):
     """The batched labeller: [(n, clauses), ...] (clauses: lists of signed 1-based ints) -> [True / False / None, ...]."""
-    status, _, _ = solve_items([raw_item(n, clauses) for n, clauses in instances], budget=budget, device=device, max_edges=max_edges)
+    status, _, _ = solve_items([raw_item(n, clauses) for n, clauses in instances], budget=budget, device=device, max_edges=max_edges,
+                                learn=learn, arena=arena)
     return [_label(int(s)) for s in status]
 
 
-def is_sat(var_num, iclause_list, budget=0):
+def is_sat(var_num, iclause_list, budget=0, learn=False, arena=0):
     """The reference's labelling hook (generator.py:15-17) for one instance: True, False, or None when the budget ran out."""
-    return label_clause_lists([(var_num, iclause_list)], budget=budget)[0]
+    return label_clause_lists([(var_num, iclause_list)], budget=budget, learn=learn, arena=arena)[0]

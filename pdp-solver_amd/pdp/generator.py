@@ -173,15 +173,19 @@ def cli_parser():
     p.add_argument('--label', choices=('exact', 'none'), default='exact',
                    help="exact: label every candidate with the complete GPU solver (pdp.exact); none: the reference's stub labels (always False)")
     p.add_argument('--budget', type=int, default=0, help="clause-literal reads per instance for --label exact (0: the library default)")
+    p.add_argument('--learn', action='store_true', default=False,
+                   help="--label exact with conflict clause learning (pdp_exact_solve_learn): the same labels, far fewer reads on modular instances")
     return p
 
 
 def main(argv=None):
     args = cli_parser().parse_args(argv)
     labeller = None
+    if args.learn and args.label != 'exact':
+        cli_parser().error("--learn selects the search of --label exact")
     if args.label == 'exact':
         from pdp import exact
-        labeller = lambda instances: exact.label_clause_lists(instances, budget=args.budget)  # noqa: E731
+        labeller = lambda instances: exact.label_clause_lists(instances, budget=args.budget, learn=args.learn)  # noqa: E731
     make_generator(args.method, args).generate_dataset(args.size, args.out_dir, args.out_json, args.name, args.sat_only, labeller=labeller)
 
 

@@ -6,6 +6,7 @@ library is missing or no GPU is visible the calls raise (loudly), they never rer
 """
 
 import ctypes as C
+import numbers
 import os
 
 import torch
@@ -38,7 +39,7 @@ EXPORTED_SYMBOLS = [
     'pdp_train_linear', 'pdp_train_linear_backward', 'pdp_train_linear_s_supported', 'pdp_train_linear_s', 'pdp_train_linear_s_backward', 'pdp_train_row_sum', 'pdp_train_row_spread', 'pdp_train_gru', 'pdp_train_gru_fused', 'pdp_train_gru_backward', 'pdp_train_gru_backward_s',
     'pdp_sat_loss_grad', 'pdp_train_sp_adapted_backward',
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
-    'pdp_exact_solve', 'pdp_exact_solve_hinted',
+    'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
 ]
 
 
@@ -407,12 +408,19 @@ class Problem(object):
         return out
 
     # -- complete solver ---------------------------------------------------------------------------------------
-    def exact_solve(self, budget=0, hints=None):
+    def exact_solve(self, budget=0, hints=None, learn=False, arena=0, stats=False):
         """Label every instance with the batched DPLL solver (pdp_exact_solve): (status int8 [B]: 1 SAT, 0 UNSAT, -1 undecided within
         ``budget`` clause-literal reads per instance, 0 = the library default; model float [V]: a satisfying 0/1 assignment of every status-1
         instance, 0 elsewhere; work int64 [B]: the clause-literal reads of each search).  Asynchronous on the current stream.
         ``hints`` (float32, V elements, on the problem's device): phase hints, pdp_exact_solve_hinted -- > 0.5 true first, other finite values
-        false first, NaN no hint; an instance whose hints are all finite and satisfy it is answered by one pass over its clauses."""
+        false first, NaN no hint; an instance whose hints are all finite and satisfy it is answered by one pass over its clauses.
+        ``learn``: the search with conflict clause learning and backjumping (pdp_exact_solve_learn), with ``arena`` words per instance for
+        learned clauses (0: four per literal of the instance).  ``stats`` (learning search only): also return learned int32 [B], the clauses
+        each instance learned."""
+        if isinstance(arena, bool) or not isinstance(arena, numbers.Integral) or not 0 <= arena <= 1 << 30:
+            raise ValueError("arena must be an integer from 0 to 2^30 words, got %r" % (arena,))
+        if (arena or stats) and not learn:
+            raise ValueError("arena and stats belong to the learning search: pass learn=True")
         if hints is not None:
             if not torch.is_tensor(hints) or hints.dtype != torch.float32 or hints.numel() != self.V:
                 raise ValueError("hints must be a float32 tensor of %d elements (one per variable), got %s"
@@ -421,12 +429,23 @@ class Problem(object):
         status = torch.empty(self.B, dtype=torch.int8, device=self.device)
         model = torch.empty(self.V, dtype=torch.float32, device=self.device)
         work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        if learn:
+            learned = torch.empty(self.B, dtype=torch.int32, device=self.device)
+            check(lib().pdp_exact_solve_learn(self._h, ptr(hints, torch.float32, self.V, 'hints'), C.c_int64(int(budget)), C.c_int64(int(arena)),
+                                              ptr(status), ptr(model), ptr(work), ptr(learned), _stream()))
+            return (status, model, work, learned) if stats else (status, model, work)
         if hints is None:
             check(lib().pdp_exact_solve(self._h, C.c_int64(int(budget)), ptr(status), ptr(model), ptr(work), _stream()))
         else:
             check(lib().pdp_exact_solve_hinted(self._h, ptr(hints, torch.float32, self.V, 'hints'), C.c_int64(int(budget)), ptr(status), ptr(model),
                                                ptr(work), _stream()))
         return status, model, work
+
+    def exact_learn_reductions(self):
+        "int32 [B]: how often each instance's arena was reduced in the last exact_solve(learn=True) on this problem"
+        out = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        check(lib().pdp_exact_learn_reductions(self._h, ptr(out), _stream()))
+        return out
 
     # -- K14 ---------------------------------------------------------------------------------------------------
     def energy(self, assignment):

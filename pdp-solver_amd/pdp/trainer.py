@@ -155,7 +155,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         if handle is None or handle.R != 1 or handle.V != int(offs[-1]):
             handle = native.Problem(graph_map, batch_variable_map, batch_function_map, edge_feature, batch_size=len(rows))
         hint = prediction[0].detach().reshape(-1).to(torch.float32).contiguous()
-        status, solution, work = handle.exact_solve(int(self._config.get('complete_budget', 0) or 0), hints=hint)
+        status, solution, work = handle.exact_solve(int(self._config.get('complete_budget', 0) or 0), hints=hint,
+                                                    learn=bool(self._config.get('complete_learn')))
         status, work = status.cpu().numpy(), work.cpu().numpy()
         solution = solution.cpu().numpy().astype(int)
         for i, row in enumerate(rows):

@@ -7,7 +7,12 @@ Usage: python tools/exact_time.py [row ...]   (rows a b c d e; default all)
 Hinted rows (pdp_exact_solve_hinted; never part of the default): ``ha`` / ``hb`` = row (a) / (b) with the assignment of one p-d-p forward
 (T = 100, -w 100, philox) as phase hints: kernel time of the unhinted and the hinted solve on the same problem, total and median work over
 the satisfiable instances, the count PDP had solved, and the work sums over the unsatisfiable ones (they differ by the check-pass reads
-only).  ``wa`` = wall time of ``satyr.py`` on row (a)'s instances with and without ``--complete``."""
+only).  ``wa`` = wall time of ``satyr.py`` on row (a)'s instances with and without ``--complete``.
+
+Learning rows (pdp_exact_solve_learn; never part of the default): ``la`` .. ``ld`` = rows (a) .. (d) with conflict clause learning at the
+default arena, ``m100`` / ``m200`` = the reference's community-attachment family (ModularCNFGenerator(3, n, n, 0.8, 0.9, n/10, n/10, 3.8,
+4.2, 1), B = 2000) with both searches under a budget of 2^28 reads per instance.  A learning line adds the learned clauses per instance
+(median / max / total) and the arena reductions (instances with one, total)."""
 import io
 import json
 import logging
@@ -23,7 +28,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, 'pdp-solver_amd'))
 from pdp import native  # noqa: E402
-from pdp.cnf_generators import UniformCNFGenerator  # noqa: E402
+from pdp.cnf_generators import ModularCNFGenerator, UniformCNFGenerator  # noqa: E402
 from pdp.factorgraph import dataset  # noqa: E402
 
 
@@ -51,6 +56,22 @@ def gcnf_items(B):
         out.append((n, m, gm.astype(np.int32), ef.astype(np.float32), -1.0, ['gcnf_%d' % i]))
     return out
 
+
+def modular_items(B, n, alpha=3.8):
+    np.random.seed(0)
+    g = ModularCNFGenerator(3, n, n, 0.8, 0.9, n // 10, n // 10, alpha, alpha + 0.4, 1)
+    out = []
+    for i in range(B):
+        nn, m, gm, ef, _, _, _ = g.generate()
+        out.append((nn, m, gm.astype(np.int32), ef.astype(np.float32), -1.0, ['modular_%d' % i]))
+    return out
+
+
+MODULAR_BUDGET = 1 << 28
+MODULAR = {
+    'm100': ('modular ModularCNFGenerator(3,100,100,0.8,0.9,10,10,3.8,4.2,1), B=2000', lambda: modular_items(2000, 100)),
+    'm200': ('modular ModularCNFGenerator(3,200,200,0.8,0.9,20,20,3.8,4.2,1), B=2000', lambda: modular_items(2000, 200)),
+}
 
 ROWS = {
     'a': ('uniform 3-SAT n=100 m=426, B=5000', lambda: dataset.random_ksat_items(5000, 100, 3, m=426, seed=0)),
@@ -90,6 +111,50 @@ def run(key):
     if key == 'e':
         big = next(i for i, it in enumerate(items) if it[5] and it[5][0].startswith('planted'))
         print("    planted n=20000 instance: status %d  work %d" % (int(status[big]), int(work[big])), flush=True)
+
+
+def _line(tag, title, p, ms, status, work, extra=""):
+    B = len(status)
+    print("(%s) %s: E=%d  kernel %.2f ms  %.0f instances/s  SAT %d  UNSAT %d  undecided %d  work median %d  p99 %d  max %d  total %d  "
+          "%.3g literal reads/s%s"
+          % (tag, title, p.E, ms, B / (ms * 1e-3), int((status == 1).sum()), int((status == 0).sum()), int((status == -1).sum()),
+             int(np.median(work)), int(np.percentile(work, 99)), int(work.max()), int(work.sum()), float(work.sum()) / (ms * 1e-3), extra), flush=True)
+
+
+def _timed_learn(p, budget, learn):
+    "kernel ms (device events) of the second call on the problem, and its outputs on the host"
+    kw = dict(learn=True, stats=True) if learn else {}
+    p.exact_solve(budget, **kw)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    out = p.exact_solve(budget, **kw)
+    ev[1].record()
+    torch.cuda.synchronize()
+    return (ev[0].elapsed_time(ev[1]),) + tuple(t.cpu().numpy() for t in out)
+
+
+def run_learn(key):
+    "rows (a)-(d) with learning, the modular rows under one budget; the backtracking search runs on the same problem first (not on row c)"
+    modular = key in MODULAR
+    title, make = MODULAR[key] if modular else ROWS[key[1:]]
+    budget = MODULAR_BUDGET if modular else 0
+    items = make()
+    b = dataset.to_torch(dataset.collate_segment(items), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(items))
+    compare = key != 'lc'
+    if compare:
+        ms0, st0, _, wk0 = _timed_learn(p, budget, False)
+        _line(key + (', backtracking, budget 2^28' if modular else ', backtracking'), title, p, ms0, st0, wk0)
+    ms, st, _, wk, ln = _timed_learn(p, budget, True)
+    red = p.exact_learn_reductions().cpu().numpy()
+    _line(key + (', learning, budget 2^28' if modular else ', learning'), title, p, ms, st, wk,
+          "  learned median %d  max %d  total %d  arena reductions: %d instances, %d in all"
+          % (int(np.median(ln)), int(ln.max()), int(ln.sum()), int((red > 0).sum()), int(red.sum())))
+    if compare:
+        both = (st0 != -1) & (st != -1)
+        assert np.array_equal(st0[both], st[both]), "the two searches disagree"
+        print("    decided by both: %d  work there: backtracking %d, learning %d (ratio %.3f)"
+              % (int(both.sum()), int(wk0[both].sum()), int(wk[both].sum()), float(wk[both].sum()) / max(1.0, float(wk0[both].sum()))), flush=True)
 
 
 def _write_json(items, path):
@@ -171,4 +236,4 @@ def run_wall(key):
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
-        {'h': run_hinted, 'w': run_wall}.get(k[0], run)(k)
+        {'h': run_hinted, 'w': run_wall, 'l': run_learn, 'm': run_learn}.get(k[0], run)(k)
