@@ -7,7 +7,7 @@ conflict and a backjump.  It counts the same clause-literal reads, so the GPU re
 small instances (a propagation pass is a Python loop over every clause)."""
 import numpy as np
 
-from exact_model import NO_BUDGET, check_reads, hint_codes
+from exact_model import NO_BUDGET, check_reads, hint_codes, peak
 
 NO_ARENA = 1 << 40
 
@@ -21,10 +21,14 @@ def thrash(k):
     return 2 * k + 3, clauses
 
 
-def search(n, clauses, hints=None, budget=NO_BUDGET, arena=0):
+def search(n, clauses, hints=None, budget=NO_BUDGET, arena=0, *, stats=None):
     """(status 1 / 0 / -1, model float32 [n], work, learned, reductions) of the instance (n, clauses: lists of signed 1-based ints) under
     ``hints`` ([n] floats or None).  ``arena``: words for learned clauses (one of len literals takes len + 1), 0 = four per literal of
-    the instance."""
+    the instance.  ``stats``: a dict that receives the maxima over the run of ``trail`` (trail length at a conflict), ``span`` (trail
+    slots one analysis walks back), ``gap`` (slots one analysis skips between two variables it resolves on), ``confl_len`` (length of a
+    conflict clause or of a reason it is resolved with), ``lc`` (learned-clause length), ``pass_units`` (variables assigned by one pass),
+    and per reduction ``live`` (learned clauses before it), ``kept`` (after it), ``kept_idx`` (highest index before it, counted from the
+    first learned clause, of a kept one) and ``kept_len`` (longest kept clause); the results do not depend on it."""
     if budget <= 0:
         budget = 1 << 32
     clauses = [[int(l) for l in c if int(l) != 0] for c in clauses]
@@ -77,6 +81,7 @@ def search(n, clauses, hints=None, budget=NO_BUDGET, arena=0):
         if confl is None and req:
             asked = sorted({v for v, _ in req})
             both = [v for v in asked if (v, 1) in req and (v, 2) in req]
+            before = len(trail)
             for v in asked:
                 if both and v == both[0]:
                     val[v], rsn[v], confl = 1, req[(v, 1)], req[(v, 2)]
@@ -87,9 +92,11 @@ def search(n, clauses, hints=None, budget=NO_BUDGET, arena=0):
                     rsn[v] = req[(v, val[v])]
                 lev[v] = level
                 trail.append(v)
+            peak(stats, 'pass_units', len(trail) - before)
             if confl is None:
                 continue
         if confl is not None:
+            peak(stats, 'trail', len(trail))
             if level == 0:
                 return 0, zeros, work, learned, reductions
             # first-UIP analysis: resolve backwards along the trail until one literal of the current level is left
@@ -97,6 +104,7 @@ def search(n, clauses, hints=None, budget=NO_BUDGET, arena=0):
             c = cls[confl]
             while True:
                 work += len(c)
+                peak(stats, 'confl_len', len(c))
                 for v, p in c:
                     if v in seen:
                         continue
@@ -105,8 +113,10 @@ def search(n, clauses, hints=None, budget=NO_BUDGET, arena=0):
                         open_ += 1
                     elif lev[v] > 0:
                         out.append((v, p))
+                at = i
                 while i >= 0 and trail[i] not in seen:
                     i -= 1
+                peak(stats, 'gap', at - i)
                 assert i >= 0, "a conflict clause without a literal of the current level"
                 uip = trail[i]
                 i -= 1
@@ -115,6 +125,8 @@ def search(n, clauses, hints=None, budget=NO_BUDGET, arena=0):
                     break
                 c = cls[rsn[uip]]
             lc = [(uip, 3 - val[uip])] + sorted(out)
+            peak(stats, 'span', len(trail) - 1 - i)
+            peak(stats, 'lc', len(lc))
             bl = max([lev[v] for v, _ in out], default=0)
             for u in trail[mark[bl + 1]:]:
                 val[u] = 0
@@ -128,6 +140,10 @@ def search(n, clauses, hints=None, budget=NO_BUDGET, arena=0):
                     if ci < m0 or ci in reasons:
                         remap[ci] = len(kept)
                         kept.append(c2)
+                peak(stats, 'live', len(cls) - m0)
+                peak(stats, 'kept', len(kept) - m0)
+                peak(stats, 'kept_idx', max([ci - m0 for ci in remap if ci >= m0], default=0))
+                peak(stats, 'kept_len', max([len(c2) for c2 in kept[m0:]], default=0))
                 cls = kept
                 for v in trail:
                     if rsn[v] is not None:

@@ -29,8 +29,16 @@ def check_reads(clauses, bits):
     return reads, ok
 
 
-def search(n, clauses, hints=None, budget=NO_BUDGET):
-    "(status 1 / 0 / -1, model float32 [n], work) of the instance (n, clauses: lists of signed 1-based ints) under ``hints`` ([n] floats or None)"
+def peak(stats, key, value):
+    "stats[key] = the maximum seen so far (stats None: nothing is recorded)"
+    if stats is not None:
+        stats[key] = max(stats.get(key, 0), value)
+
+
+def search(n, clauses, hints=None, budget=NO_BUDGET, *, stats=None):
+    """(status 1 / 0 / -1, model float32 [n], work) of the instance (n, clauses: lists of signed 1-based ints) under ``hints`` ([n] floats or None).
+    ``stats``: a dict that receives the maxima over the run of ``trail`` (trail length at a conflict), ``pass_units`` (variables assigned by
+    one pass) and ``undone`` (trail entries cleared by one backtrack step); the results do not depend on it."""
     if budget <= 0:
         budget = 1 << 32
     clauses = [[int(l) for l in c if int(l) != 0] for c in clauses]
@@ -80,11 +88,14 @@ def search(n, clauses, hints=None, budget=NO_BUDGET):
             val[v] = 1 if pend[v] & 1 else 2
             conflict = conflict or pend[v] == 3
             trail.append(v)
+        peak(stats, 'pass_units', len(pend))
         if conflict:
+            peak(stats, 'trail', len(trail))
             resumed = False
             while level > 0:
                 v, second = dvar[level]
                 first = val[v]
+                peak(stats, 'undone', len(trail) - mark[level])
                 for u in trail[mark[level]:]:
                     val[u] = 0
                 del trail[mark[level]:]

@@ -338,3 +338,50 @@ def compose(core, big, place):
             clauses.append(c)
         clauses += cc2[j:]
     return n, clauses, core_ids
+
+
+# ---- instances wider than one wave for the complete solvers ------------------------------------------------------------------------
+def fan(n, seed, F=100):
+    """threshold 3-SAT (alpha 4.26, three distinct variables per clause) on variables 1 .. n behind a unit clause on variable a = n + 1
+    and F implications a -> a + i: one pass at level 0 assigns F variables, and every later trail is longer than F"""
+    rng = np.random.RandomState(seed)
+    a = n + 1
+    clauses = [[a]] + [[-a, a + i] for i in range(1, F + 1)]
+    for _ in range(int(round(4.26 * n))):
+        vs = rng.choice(n, size=3, replace=False) + 1
+        clauses.append([int(v) * int(s) for v, s in zip(vs, rng.choice([-1, 1], size=3))])
+    return n + 1 + F, clauses
+
+
+def wide(D):
+    """a_j = j, b_j = D + j, z = 2 D + 1, w = 2 D + 2: D binary clauses [a_j, b_j], then the four sign patterns of z and w behind all the
+    -a_j.  Satisfiable (some a_j false); the searches first make every a_j true and meet conflict, reason and learned clauses of D + 1
+    and D + 2 literals"""
+    z, w = 2 * D + 1, 2 * D + 2
+    no_a = [-j for j in range(1, D + 1)]
+    return 2 * D + 2, [[j, D + j] for j in range(1, D + 1)] + [no_a + [sz * z, sw * w] for sz in (1, -1) for sw in (1, -1)]
+
+
+def stride(inst, s):
+    "variable v becomes 1 + (v - 1) s: a monotone renumbering (the searches take the same steps) that spreads the ids in use over s times as many"
+    n, clauses = inst
+    return 1 + (n - 1) * s, [[(1 + (abs(l) - 1) * s) * (1 if l > 0 else -1) for l in c] for c in clauses]
+
+
+def wide_kept(D):
+    """wide(D) plus a second z / w gadget (z2 = 2 D + 3, w2 = 2 D + 4) behind -a_1 .. -a_{D-1} and -b_D, which opens only after the first
+    gadget has made a_D false by a learned clause of D literals.  At an arena of 3 D + 4 words the clause the second gadget learns does
+    not fit: the reduction keeps that D-literal reason, moves it to the front, and the next analysis resolves with it"""
+    n, clauses = wide(D)
+    z, w = n + 1, n + 2
+    rest = [-j for j in range(1, D)] + [-2 * D]
+    return n + 2, clauses + [rest + [sz * z, sw * w] for sz in (1, -1) for sw in (1, -1)]
+
+
+def far_uip(K):
+    """d = 1 decides true (K + 1 occurrences of each sign) and one pass assigns c = 2 and f_1 .. f_K = 3 .. K + 2 in this order; c implies
+    x and y, which contradict each other.  The analysis resolves on y and x and then walks back over the K entries f_K .. f_1 to reach c,
+    its first UIP; chronological backtracking undoes K + 4 entries in one step"""
+    x, y, g = K + 3, K + 4, K + 5
+    clauses = [[-1, 2]] + [[-1, 2 + i] for i in range(1, K + 1)] + [[1, g + i] for i in range(K + 1)]
+    return g + K, clauses + [[-2, x], [-2, y], [-x, -y]]
