@@ -24,8 +24,8 @@ extern "C" {
 
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
- * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn and pdp_exact_learn_reductions are additions that change no existing entry point or structure, so the
- * version stays 3. */
+ * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof and pdp_exact_check are
+ * additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -255,6 +255,43 @@ int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t budget, int
 /* reductions [B] (device) = how often each instance's arena was reduced in the last pdp_exact_solve_learn call on the problem, ordered
  * after it on `stream`; PDP_ERR_INVALID before the first such call.  A function of the same inputs as the other outputs. */
 int pdp_exact_learn_reductions(pdp_problem *p, int32_t *reductions, void *stream);
+
+/* pdp_exact_solve_learn with its lemma log: the evidence for a status 0.  The search is pdp_exact_solve_learn's -- status, model, work,
+ * learned and the reductions are that call's for the same inputs; logging reads nothing and decides nothing.  Every learned clause follows
+ * by unit propagation from the clauses before it, so the learned clauses in order, ending in the level-0 conflict, are a DRAT-style proof.
+ * proof_off [B+1] (device, ascending, >= 0) gives instance b the region proof[proof_off[b] .. proof_off[b+1]) of int32 words.  Whenever a
+ * learned clause is stored in the arena, the same literals in the same order (the negated UIP, then the other variables ascending) are
+ * appended to the region as one lemma: len, lit_0 .. lit_{len-1}, literal code (v << 1) | negative with the instance-local v.  A clause
+ * that does not fit the arena even after a reduction (status -1) is not logged; arena reductions log nothing (a forward check may keep
+ * deleted lemmas).  proof_len [B] = the words the instance's lemmas need, counted whether they were written or not.  A lemma is written
+ * only if it fits the region completely, and once one does not fit nothing more is written for that instance: the proof of b is complete
+ * iff proof_len[b] <= proof_off[b+1] - proof_off[b], and the words of the region past the stored lemmas are not touched.
+ * proof == NULL writes nothing (a sizing call; give regions of no words).  An instance answered by the check pass has proof_len 0.
+ * proof and proof_len are, like the other outputs, a function of the instance, its hints, the budget and the arena size alone. */
+int pdp_exact_solve_learn_proof(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work,
+                                int32_t *learned, const int64_t *proof_off, int32_t *proof, int64_t *proof_len, void *stream);
+
+/* The check of what a complete search answered, one wave per instance, independent of the searches (plain Python:
+ * tests/exact_proof_model.py).  verdict [B]: 1 the answer is proven, 0 it is refuted, -1 not judged; fail_at [B]; work [B] (may be NULL) =
+ * clause-literal reads, a clause or lemma being read up to and including its first true literal.
+ *   status 1: every clause is read under model (true: > 0.5).  Every clause has a true literal: verdict 1, fail_at -1; otherwise verdict 0
+ *     and fail_at = the lowest clause without one.  Every clause is read either way.
+ *   status 0: the first proof_len[b] words of the region are lemmas 0 .. L-1.  For i = 0 .. L-1 and then for the empty clause (i = L):
+ *     start from the empty assignment; falsify every literal of lemma i (work += len_i; a lemma with both polarities of a variable is
+ *     accepted at once); then passes to a fixed point.  Before each pass: work >= budget -> verdict -1, fail_at -1 (budget <= 0 means
+ *     PDP_EXACT_DEFAULT_BUDGET).  A pass reads the original clauses, then lemmas 0 .. i-1: a clause with no true and no unassigned literal
+ *     is a conflict, one with no true literal whose unassigned literals are all the same literal asks for that literal; the requests are
+ *     applied after the pass.  A conflict, or a variable asked for in both polarities: lemma i is accepted.  Neither a conflict nor a
+ *     request: verdict 0, fail_at i.  All of 0 .. L accepted: verdict 1, fail_at -1.
+ *     The proof is untrusted: before lemma i is used its length must be >= 0 and fit the proof_len[b] words, and every variable id must
+ *     be below n; otherwise verdict 0, fail_at i.  Nothing is read outside the region or the instance's arrays.
+ *   any other status, or proof_len[b] negative or larger than the region: verdict -1, fail_at -1, work 0, nothing is read.
+ * Between two budget checks lie at most one pass and one lemma's own literals: work < budget + e + W (W = the region's words).  Passes read
+ * a consistent assignment and every reduction is an OR or a sum, so verdict, fail_at and work are a function of the instance and its
+ * proof alone: the same in any batch, at any position and in both library builds.  proof may be NULL if every region is empty.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules; routing and working arrays are prepared once per problem. */
+int pdp_exact_check(pdp_problem *p, const int8_t *status, const float *model, const int64_t *proof_off, const int32_t *proof,
+                    const int64_t *proof_len, int64_t budget, int8_t *verdict, int32_t *fail_at, int64_t *work, void *stream);
 
 /* ---- persistent solve: the whole _forward_core loop in one launch ------------------------------------
  * replaces: PropagatorDecimatorSolverBase._forward_core (solver.py:355-386) for the classical

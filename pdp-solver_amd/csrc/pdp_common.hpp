@@ -145,6 +145,8 @@ struct pdp_problem {
     // learning complete solver (pdp_exact.hip::exl_prepare): the same for its own routing, with the HBM route's arenas (exl_words words);
     // rebuilt when the arena size of the call changes
     int exl_ready, exl_nbig; int64_t exl_arena; size_t exl_lds_bytes, exl_words; char *exl_blob;
+    // checker of the complete solver (pdp_exact.hip::exc_prepare): its own routing, order, counter and HBM working arrays, one block
+    int exc_ready, exc_nbig; size_t exc_lds_bytes; char *exc_blob;
     uint32_t *team_ws;          // barrier counters and reduction mailboxes of the workgroup teams (k_sp_solve<NT, true>)
     hipStream_t res_side_stream; hipEvent_t res_side_ev[2];   // the big instances' launches overlap the LDS-resident kernel on a stream of their own
     float *nws[4]; size_t nws_floats[4];             // neural workspaces (grow on demand)

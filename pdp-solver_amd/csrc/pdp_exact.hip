@@ -465,7 +465,14 @@ struct ExlParams {
     int32_t *h_mark;            // [V+B]
     uint32_t *h_arena;          // the HBM-routed instances' arenas
     const int64_t *h_aoff;      // [B] by instance id: where an HBM-routed instance's arena starts
+    // the lemma log, read by k_exact_learn<.., true> only; last, so the fields above keep their offsets
+    const int64_t *proof_off;   // [B+1] by instance id: its region is proof[proof_off[b] .. proof_off[b+1])
+    int32_t *proof;             // NULL: nothing is written, the words are only counted
+    int64_t *proof_len;         // [B] words the instance's lemmas need
 };
+
+// the region of one instance: base pointer (NULL: count only) and size in words
+struct ExlLog { int32_t *words; int64_t cap; };
 
 template <typename LitT, typename PtrT>
 struct ExlInst {
@@ -538,8 +545,11 @@ __device__ void exl_reduce(const ExlInst<LitT, PtrT> &X, int tlen, int &nl, int 
 
 // The learning search of one instance by the calling wave: 1 / 0 as ex_search, -1 when the budget is spent or a learned clause does not
 // fit the arena even after a reduction.  *learned_out = clauses learned (also the deleted ones), *reductions_out = arena reductions.
-template <bool HBM, bool HINT, typename LitT, typename PtrT>
-__device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, bool check, int64_t *work_out, int *learned_out, int *reductions_out)
+// PROOF: every clause that is stored in the arena is also appended to the instance's region G (len, then the literals in the arena's order,
+// as int32 words) while whole lemmas fit, and *plen_out = the words all of them need.  Logging reads nothing the search reads later.
+template <bool HBM, bool HINT, bool PROOF, typename LitT, typename PtrT>
+__device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, bool check, int64_t *work_out, int *learned_out, int *reductions_out,
+                               const ExlLog &G, int64_t *plen_out)
 {
     const int lane = (int)threadIdx.x;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -547,6 +557,9 @@ __device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, boo
     int64_t work = 0;
     int result = -1;
     *learned_out = 0; *reductions_out = 0;
+    [[maybe_unused]] int64_t plen = 0;  // PROOF: words of the lemmas so far
+    [[maybe_unused]] bool pfit = true;                   // PROOF: every lemma so far was written
+    if constexpr (PROOF) { *plen_out = 0; pfit = G.words != nullptr; }
     if constexpr (HINT) {
         if (check) {
             for (int v = lane; v < X.n; v += EX_NT) X.val[v] = (uint8_t)((X.pend[v] >> EX_HINT_SHIFT) & 3u);
@@ -673,6 +686,10 @@ __device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, boo
             }
             // the clause: the UIP's literal, then the marked variables ascending (all false now); the next pass finds it unit
             if (lane == 0) X.ar[lits] = (LitT)ulit;
+            if constexpr (PROOF) {
+                pfit = pfit && plen + len + 1 <= G.cap;
+                if (pfit && lane == 0) { G.words[plen] = len; G.words[plen + 1] = (int32_t)ulit; }
+            }
             int w = lits + 1;
             for (int base = 0; base < X.n; base += EX_NT) {
                 const int v = base + lane;
@@ -681,8 +698,12 @@ __device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, boo
                 const unsigned long long mask = __ballot(o);
                 if (word & (EXL_SEEN | EXL_OUT)) X.pend[v] = word & ~(EXL_SEEN | EXL_OUT);
                 if (o) X.ar[w + __popcll(mask & below)] = (LitT)(((uint32_t)v << 1) | (X.val[v] == 1 ? 1u : 0u));
+                if constexpr (PROOF) {
+                    if (o && pfit) G.words[plen + 1 + (int64_t)(w - lits + __popcll(mask & below))] = (int32_t)(((uint32_t)v << 1) | (X.val[v] == 1 ? 1u : 0u));
+                }
                 w += __popcll(mask);
             }
+            if constexpr (PROOF) plen += len + 1;
             if (lane == 0) X.ar[X.A - 1 - nl] = (LitT)w;
             lits = w; ++nl; ++learned;
             ex_sync<HBM>();
@@ -742,10 +763,11 @@ __device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, boo
     *work_out = work;
     *learned_out = learned;
     *reductions_out = reductions;
+    if constexpr (PROOF) *plen_out = plen;
     return result;
 }
 
-template <bool HBM, bool HINT, typename LitT, typename PtrT>
+template <bool HBM, bool HINT, bool PROOF, typename LitT, typename PtrT>
 __device__ void ex_solve_learn(const ExlParams &xp, const Inst &I, ExlInst<LitT, PtrT> X, PtrT *cptr_fill)
 {
     const int lane = (int)threadIdx.x;
@@ -768,18 +790,25 @@ __device__ void ex_solve_learn(const ExlParams &xp, const Inst &I, ExlInst<LitT,
     ex_sync<HBM>();
     int64_t work = 0;
     int learned = 0, reductions = 0;
-    const int st = ex_search_learn<HBM, HINT>(X, xp.budget, check, &work, &learned, &reductions);
+    ExlLog G{nullptr, 0};
+    [[maybe_unused]] int64_t plen = 0;
+    if constexpr (PROOF) {
+        const int64_t a = xp.proof_off[I.b], z = xp.proof_off[I.b + 1];
+        if (xp.proof && z > a) { G.words = xp.proof + a; G.cap = z - a; }
+    }
+    const int st = ex_search_learn<HBM, HINT, PROOF>(X, xp.budget, check, &work, &learned, &reductions, G, &plen);
     for (int v = lane; v < I.n; v += EX_NT) xp.model[I.v0 + v] = (st == 1 && X.val[v] == 1) ? 1.0f : 0.0f;
     if (lane == 0) {
         xp.status[I.b] = (int8_t)st;
         if (xp.work) xp.work[I.b] = work;
         if (xp.learned) xp.learned[I.b] = learned;
         xp.reductions[I.b] = reductions;
+        if constexpr (PROOF) xp.proof_len[I.b] = plen;
     }
     ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
 }
 
-template <bool HINT>
+template <bool HINT, bool PROOF>
 __global__ void __launch_bounds__(EX_NT) k_exact_learn(PView pv, ExlParams xp)
 {
     extern __shared__ __align__(16) unsigned char exl_slab[];
@@ -796,7 +825,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact_learn(PView pv, ExlParams xp)
             X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.req = xp.h_req + 2 * (size_t)I.v0;
             X.rsn = xp.h_rsn + I.v0; X.trail = xp.h_trail + I.v0; X.mark = xp.h_mark + I.v0 + I.b; X.lev = xp.h_lev + I.v0;
             X.n = I.n; X.m = I.m; X.e = I.e; X.A = A;
-            ex_solve_learn<true, HINT, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
+            ex_solve_learn<true, HINT, PROOF, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
         } else {
             const ExlLds L = exl_lds_layout(I.n, I.m, I.e, A);
             ExlInst<uint16_t, uint16_t> X;
@@ -805,7 +834,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact_learn(PView pv, ExlParams xp)
             X.req = (uint32_t *)(exl_slab + L.req); X.rsn = (uint32_t *)(exl_slab + L.rsn); X.trail = (int32_t *)(exl_slab + L.trail);
             X.mark = (int32_t *)(exl_slab + L.mark); X.lev = (int32_t *)(exl_slab + L.lev);
             X.n = I.n; X.m = I.m; X.e = I.e; X.A = A;
-            ex_solve_learn<false, HINT, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(exl_slab + L.cptr));
+            ex_solve_learn<false, HINT, PROOF, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(exl_slab + L.cptr));
         }
     }
 }
@@ -853,9 +882,9 @@ int exl_prepare(pdp_problem *p, int64_t arena)
     return PDP_OK;
 }
 
-template <bool HINT>
+template <bool HINT, bool PROOF>
 int exl_launch(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work, int32_t *learned,
-               void *stream)
+               const int64_t *proof_off, int32_t *proof, int64_t *proof_len, void *stream)
 {
     { const int st_ = exl_prepare(p, arena); if (st_ != PDP_OK) return st_; }
     const hipStream_t st = ST(stream);
@@ -866,6 +895,7 @@ int exl_launch(pdp_problem *p, const float *hint, int64_t budget, int64_t arena,
     xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
     xp.arena = arena;
     xp.status = status; xp.model = model; xp.work = work; xp.learned = learned; xp.hint = hint;
+    xp.proof_off = proof_off; xp.proof = proof; xp.proof_len = proof_len;
     xp.h_aoff = (const int64_t *)(p->exl_blob + head);
     xp.reductions = (int32_t *)(p->exl_blob + head + B * 8);
     xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_req = nullptr; xp.h_rsn = nullptr; xp.h_trail = nullptr; xp.h_lev = nullptr;
@@ -885,10 +915,302 @@ int exl_launch(pdp_problem *p, const float *hint, int64_t budget, int64_t arena,
     }
     const int lds = (int)p->exl_lds_bytes;
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_learn<HINT>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_learn<HINT, PROOF>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     const int64_t grid = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu);
     PDP_HIP_CHECK(hipMemsetAsync(xp.next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact_learn<HINT>, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    hipLaunchKernelGGL((k_exact_learn<HINT, PROOF>), dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    return PDP_OK;
+}
+
+// ---- pdp_exact_check: the forward check of what the searches answer ----------------------------------------------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_proof_model.py, part (ii)).  New code of its own: with the searches above it
+// shares the wave helpers (ex_sync, ex_sum, ex_min), the persistent grid and the instance order, nothing else.  State of one instance:
+//   lit [e], cptr [m+1]  the original clauses as above      val [n]  0 unassigned, 1 true, 2 false
+//   req [n]              polarity bits asked for by unit clauses in the current pass (bit 0 true, bit 1 false)
+// in a slab of LDS up to EX_LDS_LIMIT (u16 literals and offsets), else in HBM working arrays indexed by the problem's ids.  The lemmas are
+// never copied: the wave walks the instance's proof region word by word, one lemma at a time with its literals across the lanes.
+struct ExcLds { size_t req, lit, cptr, val, bytes; };
+
+__host__ __device__ inline ExcLds exc_lds_layout(int n, int m, int e)
+{
+    ExcLds L;
+    size_t o = 0;
+    L.req = o;  o += 4 * (size_t)n;
+    L.lit = o;  o += 2 * (size_t)e;
+    L.cptr = o; o += 2 * ((size_t)m + 1);
+    L.val = o;  o += (size_t)n;
+    L.bytes = (o + 15) & ~(size_t)15;
+    return L;
+}
+inline bool exc_fits_lds(int n, int m, int e) { return n < 32768 && e <= 65535 && exc_lds_layout(n, m, e).bytes <= EX_LDS_LIMIT; }
+
+struct ExcParams {
+    const int32_t *order;       // as ExParams: the nbig HBM-routed instances first
+    int nbig, B;
+    uint32_t *next;
+    int64_t budget;
+    const int8_t *status; const float *model;
+    const int64_t *proof_off; const int32_t *proof; const int64_t *proof_len;
+    int8_t *verdict; int32_t *fail_at; int64_t *work;
+    uint32_t *h_lit;            // [E]
+    uint32_t *h_req;            // [V]
+    uint8_t *h_val;             // [V]
+};
+
+template <typename LitT, typename PtrT>
+struct ExcInst {
+    LitT *lit; const PtrT *cptr; uint8_t *val; uint32_t *req;
+    int n, m, e;
+};
+
+// what one clause asks for under val: wave-uniform for a lemma, per lane for an original clause
+struct ExcPass { int reads, conflict, unit; };
+
+// One original clause by the calling lane, read up to and including its first true literal.
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ void exc_clause(const ExcInst<LitT, PtrT> &X, int c, ExcPass &P)
+{
+    const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+    int nfree = 0, sat = 0, k = a, distinct = 0;
+    uint32_t first = 0;
+    for (; k < z; ++k) {
+        const uint32_t L = X.lit[k];
+        const uint32_t x = X.val[L >> 1];
+        if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+        else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+    }
+    P.reads += k - a;
+    if (sat) return;
+    if (nfree == 0) P.conflict = 1;
+    else if (!distinct) { P.unit = 1; atomicOr(&X.req[first >> 1], 1u << (first & 1u)); }
+}
+
+// One lemma (len validated literals at w) by the whole wave, 64 literals at a time; every result is wave-uniform.
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ void exc_lemma(const ExcInst<LitT, PtrT> &X, const int32_t *w, int len, ExcPass &P)
+{
+    const int lane = (int)threadIdx.x;
+    int nfree = 0, distinct = 0;
+    uint32_t first = 0;
+    for (int base = 0; base < len; base += EX_NT) {
+        const int k = base + lane;
+        const uint32_t L = k < len ? (uint32_t)w[k] : 0u;
+        const uint32_t x = k < len ? (uint32_t)X.val[L >> 1] : 3u;
+        const unsigned long long tmask = __ballot(x == 1u + (L & 1u));
+        const int stop = tmask ? __ffsll((long long)tmask) - 1 : EX_NT;     // lanes below it hold the literals read before the true one
+        if (tmask) { P.reads += base + stop + 1; return; }
+        const unsigned long long fmask = __ballot(x == 0u);
+        if (fmask) {
+            if (nfree == 0) first = (uint32_t)__shfl((int)L, __ffsll((long long)fmask) - 1);
+            distinct |= __ballot(x == 0u && L != first) != 0ull;
+            nfree += __popcll(fmask);
+        }
+    }
+    P.reads += len;
+    if (nfree == 0) P.conflict = 1;
+    else if (!distinct) { P.unit = 1; if (lane == 0) atomicOr(&X.req[first >> 1], 1u << (first & 1u)); }
+}
+
+// The check of one instance by the calling wave: verdict 1 / 0 / -1, *fail_out and *work_out as the header states them.
+// `w`: the instance's region, of which the first W words are said to hold lemmas (0 <= W <= the region's size, checked by the caller).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int exc_check(const ExcInst<LitT, PtrT> &X, int status, const float *model, const int32_t *w, int64_t W, int64_t budget,
+                         int *fail_out, int64_t *work_out)
+{
+    const int lane = (int)threadIdx.x;
+    int64_t work = 0;
+    *fail_out = -1; *work_out = 0;
+    if (status == 1) {
+        // the model: every clause is read up to and including its first true literal
+        for (int v = lane; v < X.n; v += EX_NT) X.val[v] = model[v] > 0.5f ? 1 : 2;
+        ex_sync<HBM>();
+        int reads = 0, bad = EXL_INF;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int sat = 0, k = a;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                if (X.val[L >> 1] == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (!sat) bad = c < bad ? c : bad;
+        }
+        *work_out = (int64_t)ex_sum(reads);
+        bad = ex_min(bad);
+        if (bad == EXL_INF) return 1;
+        *fail_out = bad;
+        return 0;
+    }
+    // the proof: lemma i = 0 .. L - 1 at word `pos`, then the empty clause, each refuted by unit propagation from the original clauses
+    // and the lemmas before it
+    int64_t pos = 0;
+    for (int i = 0;; ++i) {
+        const bool last = pos >= W;
+        int len = 0;
+        const int32_t *mine = w + pos + 1;
+        if (!last) {
+            len = w[pos];
+            if (len < 0 || pos + 1 + (int64_t)len > W) { *fail_out = i; *work_out = work; return 0; }
+        }
+        for (int v = lane; v < X.n; v += EX_NT) X.val[v] = 0;
+        ex_sync<HBM>();
+        // falsify the lemma's literals: of two lanes that hold both polarities of a variable one finds the other's value afterwards
+        int bad = 0;
+        for (int k = lane; k < len; k += EX_NT) {
+            const uint32_t L = (uint32_t)mine[k];
+            if ((L >> 1) < (uint32_t)X.n) X.val[L >> 1] = (uint8_t)(2u - (L & 1u)); else bad = 1;
+        }
+        if (__ballot(bad) != 0ull) { *fail_out = i; *work_out = work; return 0; }
+        ex_sync<HBM>();
+        int taut = 0;
+        for (int k = lane; k < len; k += EX_NT) {
+            const uint32_t L = (uint32_t)mine[k];
+            taut |= X.val[L >> 1] != (uint8_t)(2u - (L & 1u));
+        }
+        work += len;
+        bool accepted = __ballot(taut) != 0ull;
+        while (!accepted) {
+            if (work >= budget) { *work_out = work; return -1; }
+            ExcPass P{0, 0, 0};
+            for (int c = lane; c < X.m; c += EX_NT) exc_clause(X, c, P);
+            work += ex_sum(P.reads);
+            ExcPass Q{0, 0, 0};
+            int64_t q = 0;
+            for (int j = 0; j < i; ++j) { const int lj = w[q]; exc_lemma(X, w + q + 1, lj, Q); q += 1 + lj; }
+            work += Q.reads;
+            const bool conflict = __ballot(P.conflict | Q.conflict) != 0ull;
+            const bool unit = __ballot(P.unit | Q.unit) != 0ull;
+            if (conflict) { accepted = true; break; }                // the requests of this pass are dropped when val is cleared ...
+            if (!unit) { *fail_out = i; *work_out = work; return 0; }
+            ex_sync<HBM>();
+            int both = 0;
+            for (int v = lane; v < X.n; v += EX_NT) {
+                const uint32_t bits = X.req[v];
+                if (bits) { X.req[v] = 0u; both |= bits == 3u; X.val[v] = (bits & 1u) ? 1 : 2; }
+            }
+            accepted = __ballot(both) != 0ull;
+            ex_sync<HBM>();
+        }
+        // ... and here: a pass that ended in a conflict may have left requests
+        ex_sync<HBM>();
+        for (int v = lane; v < X.n; v += EX_NT) X.req[v] = 0u;
+        if (last) { *work_out = work; return 1; }
+        pos += 1 + (int64_t)len;
+    }
+}
+
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void exc_run(const ExcParams &xp, const Inst &I, ExcInst<LitT, PtrT> X, PtrT *cptr_fill)
+{
+    const int lane = (int)threadIdx.x;
+    const int status = (int)xp.status[I.b];
+    const int64_t a = xp.proof_off[I.b], z = xp.proof_off[I.b + 1], W = xp.proof_len[I.b];
+    int verdict = -1, fail = -1;
+    int64_t work = 0;
+    // nothing is read for an undecided instance, an incomplete proof or a region that is none
+    if ((status == 1 || status == 0) && W >= 0 && a >= 0 && z >= a && W <= z - a && (xp.proof || W == 0)) {
+        if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+        for (int k = lane; k < I.e; k += EX_NT) {
+            const int ed = I.f_edges[k];
+            X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+        }
+        for (int v = lane; v < I.n; v += EX_NT) X.req[v] = 0u;
+        ex_sync<HBM>();
+        verdict = exc_check<HBM>(X, status, xp.model + I.v0, xp.proof ? xp.proof + a : nullptr, W, xp.budget, &fail, &work);
+    }
+    if (lane == 0) {
+        xp.verdict[I.b] = (int8_t)verdict;
+        xp.fail_at[I.b] = fail;
+        if (xp.work) xp.work[I.b] = work;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_check(PView pv, ExcParams xp)
+{
+    extern __shared__ __align__(16) unsigned char exc_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        if (i < xp.nbig) {
+            ExcInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr; X.val = xp.h_val + I.v0; X.req = xp.h_req + I.v0;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            exc_run<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
+        } else {
+            const ExcLds L = exc_lds_layout(I.n, I.m, I.e);
+            ExcInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(exc_slab + L.lit); X.cptr = (const uint16_t *)(exc_slab + L.cptr);
+            X.val = exc_slab + L.val; X.req = (uint32_t *)(exc_slab + L.req);
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            exc_run<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(exc_slab + L.cptr));
+        }
+    }
+}
+
+// Routing, instance order and the HBM route's working arrays of the checker: once per problem, like ex_prepare.
+// One block: order [B] | counter | (HBM route) lit [E] | req [V] | val [V]
+int exc_prepare(pdp_problem *p)
+{
+    if (p->exc_ready) return PDP_OK;
+    const size_t B = p->B;
+    std::vector<int32_t> v0(B + 1), f0(B + 1), e0(B + 1);
+    PDP_HIP_CHECK(hipMemcpy(v0.data(), p->inst_v0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(f0.data(), p->inst_f0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(e0.data(), p->inst_e0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> big, fit;
+    size_t lds = 0;
+    for (size_t b = 0; b < B; ++b) {
+        const int n = v0[b + 1] - v0[b], m = f0[b + 1] - f0[b], e = e0[b + 1] - e0[b];
+        if (exc_fits_lds(n, m, e)) { fit.push_back((int32_t)b); lds = std::max(lds, exc_lds_layout(n, m, e).bytes); }
+        else big.push_back((int32_t)b);
+    }
+    auto by_edges = [&](int32_t a, int32_t b) { const int ea = e0[a + 1] - e0[a], eb = e0[b + 1] - e0[b]; return ea != eb ? ea > eb : a < b; };
+    std::sort(big.begin(), big.end(), by_edges);
+    std::sort(fit.begin(), fit.end(), by_edges);
+    std::vector<int32_t> order(big);
+    order.insert(order.end(), fit.begin(), fit.end());
+    const size_t V = p->V, E = p->E;
+    size_t bytes = (B + 1) * 4;
+    if (!big.empty()) bytes += E * 4 + V * 4 + V;
+    char *blk = nullptr;
+    { const int st_ = pdp_dev_alloc((void **)&blk, (bytes + 15) & ~(size_t)15); if (st_ != PDP_OK) return st_; }
+    p->exc_blob = blk;
+    PDP_HIP_CHECK(hipMemcpy(blk, order.data(), B * 4, hipMemcpyHostToDevice));
+    p->exc_nbig = (int)big.size();
+    p->exc_lds_bytes = lds;
+    p->exc_ready = 1;
+    return PDP_OK;
+}
+
+int exc_launch(pdp_problem *p, const int8_t *status, const float *model, const int64_t *proof_off, const int32_t *proof, const int64_t *proof_len,
+               int64_t budget, int8_t *verdict, int32_t *fail_at, int64_t *work, void *stream)
+{
+    { const int st_ = exc_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t V = p->V, E = p->E, B = p->B;
+    ExcParams xp;
+    xp.order = (const int32_t *)p->exc_blob; xp.nbig = p->exc_nbig; xp.B = p->B; xp.next = (uint32_t *)(p->exc_blob + B * 4);
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.status = status; xp.model = model; xp.proof_off = proof_off; xp.proof = proof; xp.proof_len = proof_len;
+    xp.verdict = verdict; xp.fail_at = fail_at; xp.work = work;
+    xp.h_lit = nullptr; xp.h_req = nullptr; xp.h_val = nullptr;
+    if (p->exc_nbig) {
+        char *q = p->exc_blob + (B + 1) * 4;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_req = (uint32_t *)q;            q += V * 4;
+        xp.h_val = (uint8_t *)q;
+    }
+    const int lds = (int)p->exc_lds_bytes;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_check, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu);
+    PDP_HIP_CHECK(hipMemsetAsync(xp.next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_check, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
     return PDP_OK;
 }
@@ -924,8 +1246,32 @@ extern "C" int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t 
         pdp_set_error("pdp_exact_solve_learn: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
         return PDP_ERR_UNSUPPORTED;
     }
-    return hint ? exl_launch<true>(p, hint, budget, arena, status, model, work, learned, stream)
-                : exl_launch<false>(p, nullptr, budget, arena, status, model, work, learned, stream);
+    return hint ? exl_launch<true, false>(p, hint, budget, arena, status, model, work, learned, nullptr, nullptr, nullptr, stream)
+                : exl_launch<false, false>(p, nullptr, budget, arena, status, model, work, learned, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int pdp_exact_solve_learn_proof(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model,
+                                           int64_t *work, int32_t *learned, const int64_t *proof_off, int32_t *proof, int64_t *proof_len, void *stream)
+{
+    PDP_REQUIRE(p && status && model && proof_off && proof_len, "NULL argument");
+    PDP_REQUIRE(arena >= 0 && arena <= EXL_MAX_ARENA, "pdp_exact_solve_learn_proof: arena must be 0 (four words per literal) or 1 .. 2^30 words");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_solve_learn_proof: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return hint ? exl_launch<true, true>(p, hint, budget, arena, status, model, work, learned, proof_off, proof, proof_len, stream)
+                : exl_launch<false, true>(p, nullptr, budget, arena, status, model, work, learned, proof_off, proof, proof_len, stream);
+}
+
+extern "C" int pdp_exact_check(pdp_problem *p, const int8_t *status, const float *model, const int64_t *proof_off, const int32_t *proof,
+                               const int64_t *proof_len, int64_t budget, int8_t *verdict, int32_t *fail_at, int64_t *work, void *stream)
+{
+    PDP_REQUIRE(p && status && model && proof_off && proof_len && verdict && fail_at, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_check: a replicated problem (R = %d) is not supported; check the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exc_launch(p, status, model, proof_off, proof, proof_len, budget, verdict, fail_at, work, stream);
 }
 
 extern "C" int pdp_exact_learn_reductions(pdp_problem *p, int32_t *reductions, void *stream)

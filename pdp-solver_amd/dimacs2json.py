@@ -103,10 +103,12 @@ def json_line(path, label, propagate=False):
     return generator.format_json_line(var_num, clause_num, signed_vars, clause_ids, label=label, name=os.path.split(path)[1])
 
 
-def exact_labels(instances, budget=0, learn=False):
+def exact_labels(instances, budget=0, learn=False, certify=False):
     """Labels of compact instances ((var_num, clause_num, signed_vars, clause_ids) as written to the lines) from the complete GPU solver
     (pdp.exact), all instances in a few launches: 1.0 satisfiable, 0.0 unsatisfiable, -1 undecided within the budget (the converter's
-    "no label" value).  ``learn``: the search with conflict clause learning (the same labels)."""
+    "no label" value).  ``learn``: the search with conflict clause learning (the same labels).  ``certify``: (labels, proofs) from the
+    certified search (exact.solve_items): an answer that is not certified is labelled -1, and proofs holds the DRAT lines of every
+    unsatisfiable instance (None for the others)."""
     import numpy as np
     from pdp import exact
     items = []
@@ -114,19 +116,36 @@ def exact_labels(instances, budget=0, learn=False):
         sv, ci = np.asarray(signed_vars, dtype=np.int64), np.asarray(clause_ids, dtype=np.int64)
         graph_map = np.stack((np.abs(sv) - 1, ci - 1)).astype(np.int32).reshape(2, -1)
         items.append((int(var_num), int(clause_num), graph_map, np.sign(sv).astype(np.float32), -1.0, []))
+    if certify:
+        status, _, _, verdict, lemmas = exact.solve_items(items, budget=budget, certify=True, proofs=True)
+        labels = [(1.0 if s == 1 else 0.0) if s != -1 and v == 1 else -1 for s, v in zip(status, verdict)]
+        return labels, [exact.drat_lines(l) if lab == 0.0 else None for lab, l in zip(labels, lemmas)]
     status, _, _ = exact.solve_items(items, budget=budget, learn=learn)
     return [1.0 if s == 1 else (0.0 if s == 0 else -1) for s in status]
 
 
-def convert_directory(dimacs_dir, output_file, propagate=False, only_positive=False, label='name', budget=0):
+def convert_directory(dimacs_dir, output_file, propagate=False, only_positive=False, label='name', budget=0, proof_dir=None):
     """label 'name': the reference's rule (the last digit of the file stem, else -1); 'exact': the complete solver's answer for the
-    instance the line holds (exact_labels), 'exact-learn': the same from the learning search.  Every other byte of a line is the same either way."""
+    instance the line holds (exact_labels), 'exact-learn': the same from the learning search, 'exact-certified': the same with every answer
+    checked on the GPU (an answer that is not certified is labelled -1) and, with ``proof_dir``, one <file name>.drat per unsatisfiable
+    instance there.  Every other byte of a line is the same either way."""
     file_list = [os.path.join(dimacs_dir, f) for f in os.listdir(dimacs_dir) if os.path.isfile(os.path.join(dimacs_dir, f))]
-    if label in ('exact', 'exact-learn'):
+    if label in ('exact', 'exact-learn', 'exact-certified'):
         paths = [p for p in file_list if os.path.splitext(p)[1].lower() in ('.dimacs', '.cnf')]
         instances = [compact_instance(p, propagate) for p in paths]
+        labels = []
+        if instances and label == 'exact-certified':
+            labels, proofs = exact_labels(instances, budget, certify=True)
+            if proof_dir:
+                os.makedirs(proof_dir, exist_ok=True)
+                for path, lines in zip(paths, proofs):
+                    if lines is not None:
+                        with open(os.path.join(proof_dir, os.path.split(path)[1] + '.drat'), 'w') as g:
+                            g.write('\n'.join(lines) + '\n')
+        elif instances:
+            labels = exact_labels(instances, budget, learn=label == 'exact-learn')
         with open(output_file, 'w') as f:
-            for path, inst, lab in zip(paths, instances, exact_labels(instances, budget, learn=label == 'exact-learn') if instances else []):
+            for path, inst, lab in zip(paths, instances, labels):
                 if only_positive and lab == 0:
                     continue
                 f.write(generator.format_json_line(*inst, label=lab, name=os.path.split(path)[1]) + '\n')
@@ -158,13 +177,16 @@ def cli_parser():
     parser.add_argument('out_file', action='store', type=str)
     parser.add_argument('-s', '--simplify', help='Propagate binary constraints', required=False, action='store_true', default=False)
     parser.add_argument('-p', '--positive', help='Output only positive examples', required=False, action='store_true', default=False)
-    parser.add_argument('--label', choices=('name', 'exact', 'exact-learn'), default='name',
+    parser.add_argument('--label', choices=('name', 'exact', 'exact-learn', 'exact-certified'), default='name',
                         help="name: the last digit of the file name (the reference's rule); exact: solve every instance on the GPU; "
-                             "exact-learn: the same with conflict clause learning")
+                             "exact-learn: the same with conflict clause learning; exact-certified: the learning search with every answer checked "
+                             "on the GPU (pdp_exact_check), an answer that is not certified is labelled -1")
+    parser.add_argument('--proof-dir', dest='proof_dir', default=None,
+                        help="with --label exact-certified: write <file name>.drat (the learned clauses as DRAT text) per unsatisfiable instance here")
     parser.add_argument('--budget', type=int, default=0, help="clause-literal reads per instance for --label exact / exact-learn (0: the library default)")
     return parser
 
 
 if __name__ == '__main__':
     args = vars(cli_parser().parse_args())
-    convert_directory(args['in_dir'], args['out_file'], args['simplify'], args['positive'], args['label'], args['budget'])
+    convert_directory(args['in_dir'], args['out_file'], args['simplify'], args['positive'], args['label'], args['budget'], args['proof_dir'])

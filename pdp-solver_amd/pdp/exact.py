@@ -4,6 +4,9 @@ PDP is incomplete: it finds assignments but never proves an instance unsatisfiab
 of choice" (src/pdp/generator.py:15-17).  This module fills that hook: ``label_clause_lists`` labels many instances in a few launches,
 ``is_sat`` has the reference hook's signature, ``solve_items`` works on loader items.  A label is True (satisfiable), False
 (unsatisfiable) or None (undecided within the budget of clause-literal reads per instance; 0 = the library default, 2^32).
+With ``certify=True`` every answer is checked on the GPU before it becomes a label: a model against the clauses, an "unsatisfiable" by a
+forward check of the learning search's learned clauses as a proof (pdp_exact_solve_learn_proof, pdp_exact_check; DESIGN.md §9.3);
+``drat_lines`` writes such a proof for an external checker.
 """
 
 import numpy as np
@@ -43,14 +46,56 @@ def _segments(items, max_edges):
     return runs
 
 
-def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0):
+def proof_lemmas(words):
+    "the lemmas of a complete proof region (int32 words ``len, lit_0 .. lit_{len-1}`` per lemma) as lists of literal codes (v << 1) | negative"
+    w, out, pos = [int(x) for x in words], [], 0
+    while pos < len(w):
+        if w[pos] < 0 or pos + 1 + w[pos] > len(w):
+            raise ValueError("proof words: lemma %d does not fit the %d words given" % (len(out), len(w)))
+        out.append(w[pos + 1:pos + 1 + w[pos]])
+        pos += 1 + w[pos]
+    return out
+
+
+def drat_lines(lemmas):
+    """A proof (lemmas as lists of literal codes, proof_lemmas) as DRAT text for an external checker: one line per lemma, signed 1-based
+    literals terminated by 0, then the empty clause.  The searches never delete a clause from the proof, so there are no ``d`` lines."""
+    lines = [' '.join([str(-((L >> 1) + 1) if L & 1 else (L >> 1) + 1) for L in lemma] + ['0']) for lemma in lemmas]
+    return lines + ['0']
+
+
+def _certified(prob, budget, hint, arena, names, proof_off=None):
+    """exact_solve_proof and exact_check of one problem: numpy (status, model, work, verdict, proof_len, region sizes, lemma lists of the
+    unsatisfiable instances whose proof is complete, None elsewhere).  A verdict 0 raises: the solver answered what its own evidence refutes."""
+    st, model, wk, _, proof, off, plen = prob.exact_solve_proof(budget, hints=hint, arena=arena, proof_off=proof_off)
+    verdict, fail_at, _ = prob.exact_check(st, model, proof, off, plen)
+    st, model, wk, verdict, fail_at = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy(), verdict.cpu().numpy(), fail_at.cpu().numpy()
+    off, plen = off.cpu().numpy(), plen.cpu().numpy()
+    for j in np.nonzero(verdict == 0)[0]:
+        raise RuntimeError("the complete solver's answer for instance %s (status %d) fails its own check at %s %d: a solver bug, no label is "
+                           "written from it" % (names[j], st[j], 'clause' if st[j] == 1 else 'lemma', fail_at[j]))
+    words = None if proof is None else proof.cpu().numpy()
+    lemmas = [proof_lemmas(words[off[j]:off[j] + plen[j]]) if st[j] == 0 and verdict[j] == 1 and plen[j] else ([] if st[j] == 0 and verdict[j] == 1 else None)
+              for j in range(len(st))]
+    return st, model, wk, verdict, plen, off[1:] - off[:-1], lemmas
+
+
+def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0, certify=False, proofs=False):
     """Solve loader items ((n, m, graph_map, edge_feature, label, misc) tuples: dataset.instance_from_clauses, dataset.random_ksat_items,
     dataset.parse_line, raw_item).  Returns numpy (status int8 [N] in {1, 0, -1}, models: a float32 0/1 array of n_i values per instance,
     work int64 [N]).  Instances are packed into problems of at most ``max_edges`` edges; nothing couples two instances.
     ``hints``: per instance an array of n_i phase hints (> 0.5 true first, other finite values false first, NaN none) or None (no hints for
     that instance); the search is then pdp_exact_solve_hinted's (include/pdp_hip.h).
     ``learn``: the search with conflict clause learning (pdp_exact_solve_learn) and ``arena`` words per instance for its learned clauses
-    (0: four per literal); same answers, far fewer reads on structured instances."""
+    (0: four per literal); same answers, far fewer reads on structured instances.
+    ``certify``: the learning search with its lemma log (pdp_exact_solve_learn_proof), and every answer checked on the GPU (pdp_exact_check):
+    a model against the clauses, an "unsatisfiable" by a forward check of the learned clauses as a proof.  Also returns verdict int8 [N]:
+    1 checked, -1 not (undecided).  An instance whose proof did not fit its region is solved once more with a region of the size it
+    reported.  A refuted answer raises RuntimeError naming the instance.  ``proofs`` (with certify): also return, per instance, the lemmas
+    (lists of literal codes, see drat_lines) of a certified unsatisfiable instance and None for the others."""
+    learn = learn or certify
+    if proofs and not certify:
+        raise ValueError("proofs belong to the certified search: pass certify=True")
     if arena and not learn:
         raise ValueError("arena belongs to the learning search: pass learn=True")
     native.require_gpu()
@@ -65,6 +110,8 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
     status = np.zeros(N, dtype=np.int8)
     work = np.zeros(N, dtype=np.int64)
     models = [None] * N
+    verdict = np.full(N, -1, dtype=np.int8)
+    lemmas = [None] * N
     for seg in _segments(items, max_edges):
         part = [items[i] for i in seg]
         if sum(int(it[2].shape[1]) for it in part) == 0:
@@ -72,6 +119,7 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
             # clauses is satisfiable, one whose clauses are all empty is not
             for i, it in zip(seg, part):
                 status[i] = 1 if int(it[1]) == 0 else 0
+                verdict[i], lemmas[i] = 1, (None if status[i] else [])         # an empty clause is its own refutation
                 models[i] = np.zeros(int(it[0]), dtype=np.float32)
                 h = None if hints is None or hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
                 if status[i] == 1 and h is not None and not np.isnan(h).any():
@@ -85,8 +133,25 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
                 flat = [np.full(int(it[0]), np.nan, dtype=np.float32) if hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
                         for i, it in zip(seg, part)]
                 hint = torch.from_numpy(np.concatenate(flat)).to(device)
-            st, model, wk = prob.exact_solve(budget, hints=hint, learn=learn, arena=arena)
-            st, model, wk = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
+            if certify:
+                names = ['%d (%s)' % (i, ' '.join(str(x) for x in it[5])) if it[5] else str(i) for i, it in zip(seg, part)]
+                st, model, wk, vd, plen, size, lem = _certified(prob, budget, hint, arena, names)
+                again = [j for j in range(len(part)) if st[j] != -1 and plen[j] > size[j]]
+                if again:
+                    # the proof did not fit: the same search once more, in a batch of its own, with regions of exactly proof_len words
+                    b2 = dataset.to_torch(dataset.collate_segment([part[j] for j in again]), device)
+                    prob = native.Problem(b2['graph_map'], b2['batch_variable_map'], b2['batch_function_map'], b2['edge_feature'], batch_size=len(again))
+                    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+                    hint2 = None if hint is None else torch.cat([hint[voff[j]:voff[j + 1]] for j in again])
+                    off2 = torch.from_numpy(np.concatenate([[0], np.cumsum(plen[again])]).astype(np.int64)).to(device)
+                    r = _certified(prob, budget, hint2, arena, [names[j] for j in again], proof_off=off2)
+                    for k, j in enumerate(again):
+                        vd[j], lem[j] = r[3][k], r[6][k]
+                for j, i in enumerate(seg):
+                    verdict[i], lemmas[i] = vd[j], lem[j]
+            else:
+                st, model, wk = prob.exact_solve(budget, hints=hint, learn=learn, arena=arena)
+                st, model, wk = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
         del prob
         off = 0
         for j, (i, it) in enumerate(zip(seg, part)):
@@ -94,6 +159,8 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
             status[i], work[i] = st[j], wk[j]
             models[i] = model[off:off + n].copy()
             off += n
+    if certify:
+        return (status, models, work, verdict, lemmas) if proofs else (status, models, work, verdict)
     return status, models, work
 
 
@@ -101,13 +168,16 @@ def _label(s):
     return True if s == 1 else (False if s == 0 else None)
 
 
-def label_clause_lists(instances, budget=0, device=None, max_edges=MAX_EDGES, learn=False, arena=0):
-    """The batched labeller: [(n, clauses), ...] (clauses: lists of signed 1-based ints) -> [True / False / None, ...]."""
-    status, _, _ = solve_items([raw_item(n, clauses) for n, clauses in instances], budget=budget, device=device, max_edges=max_edges,
-                                learn=learn, arena=arena)
-    return [_label(int(s)) for s in status]
+def label_clause_lists(instances, budget=0, device=None, max_edges=MAX_EDGES, learn=False, arena=0, certify=False):
+    """The batched labeller: [(n, clauses), ...] (clauses: lists of signed 1-based ints) -> [True / False / None, ...].
+    ``certify``: only checked answers become labels (solve_items); an answer that is not certified is None."""
+    out = solve_items([raw_item(n, clauses) for n, clauses in instances], budget=budget, device=device, max_edges=max_edges,
+                      learn=learn, arena=arena, certify=certify)
+    if certify:
+        return [_label(int(s)) if v == 1 else None for s, v in zip(out[0], out[3])]
+    return [_label(int(s)) for s in out[0]]
 
 
-def is_sat(var_num, iclause_list, budget=0, learn=False, arena=0):
+def is_sat(var_num, iclause_list, budget=0, learn=False, arena=0, certify=False):
     """The reference's labelling hook (generator.py:15-17) for one instance: True, False, or None when the budget ran out."""
-    return label_clause_lists([(var_num, iclause_list)], budget=budget, learn=learn, arena=arena)[0]
+    return label_clause_lists([(var_num, iclause_list)], budget=budget, learn=learn, arena=arena, certify=certify)[0]

@@ -175,6 +175,9 @@ def cli_parser():
     p.add_argument('--budget', type=int, default=0, help="clause-literal reads per instance for --label exact (0: the library default)")
     p.add_argument('--learn', action='store_true', default=False,
                    help="--label exact with conflict clause learning (pdp_exact_solve_learn): the same labels, far fewer reads on modular instances")
+    p.add_argument('--certify', action='store_true', default=False,
+                   help="--label exact from the learning search with every answer checked on the GPU (pdp_exact_check): a label is written "
+                        "only from a model that satisfies the clauses or a proof of unsatisfiability that verifies")
     return p
 
 
@@ -183,9 +186,11 @@ def main(argv=None):
     labeller = None
     if args.learn and args.label != 'exact':
         cli_parser().error("--learn selects the search of --label exact")
+    if args.certify and args.label != 'exact':
+        cli_parser().error("--certify checks the answers of --label exact")
     if args.label == 'exact':
         from pdp import exact
-        labeller = lambda instances: exact.label_clause_lists(instances, budget=args.budget, learn=args.learn)  # noqa: E731
+        labeller = lambda instances: exact.label_clause_lists(instances, budget=args.budget, learn=args.learn, certify=args.certify)  # noqa: E731
     make_generator(args.method, args).generate_dataset(args.size, args.out_dir, args.out_json, args.name, args.sat_only, labeller=labeller)
 
 

@@ -22,6 +22,7 @@ if BUILD not in BUILDS:
 LIB_PATH = os.environ.get('PDP_HIP_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', BUILDS[BUILD])
 
 PDP_OK = 0
+PROOF_WORDS_PER_LITERAL = 8      # default proof region of an instance (Problem.exact_solve_proof), in words per literal: the smallest power of two that truncates no proof of tools/exact_time.py pa pm100 pm200; too few costs a retry, never an answer
 PDP_ERR_SPECULATION = 5
 RNG_STREAM, RNG_PHILOX = 0, 1
 MODEL_SP, MODEL_WALKSAT, MODEL_REINFORCE = 0, 1, 2
@@ -40,6 +41,7 @@ EXPORTED_SYMBOLS = [
     'pdp_sat_loss_grad', 'pdp_train_sp_adapted_backward',
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
+    'pdp_exact_solve_learn_proof', 'pdp_exact_check',
 ]
 
 
@@ -446,6 +448,82 @@ class Problem(object):
         out = torch.empty(self.B, dtype=torch.int32, device=self.device)
         check(lib().pdp_exact_learn_reductions(self._h, ptr(out), _stream()))
         return out
+
+    def instance_edges(self):
+        "int64 [B]: the literals (edges) of every instance"
+        gm, _, bfm, _ = self.export_graph()
+        return torch.bincount(bfm.long()[gm[1].long()], minlength=self.B)[:self.B]
+
+    def _proof_regions(self, proof_off, proof=None):
+        "proof_off as an int64 [B+1] tensor on the device, checked on the host (ascending from >= 0; ``proof`` holds the last offset)"
+        if not torch.is_tensor(proof_off) or proof_off.dtype != torch.int64 or proof_off.numel() != self.B + 1:
+            raise ValueError("proof_off must be an int64 tensor of %d elements (instances + 1), got %s"
+                             % (self.B + 1, '%s of %d' % (proof_off.dtype, proof_off.numel()) if torch.is_tensor(proof_off) else type(proof_off).__name__))
+        host = proof_off.detach().reshape(-1).cpu()
+        if int(host[0]) < 0 or bool((host[1:] < host[:-1]).any()):
+            raise ValueError("proof_off must ascend from an offset >= 0")
+        if proof is not None:
+            if not torch.is_tensor(proof) or proof.dtype != torch.int32 or proof.numel() < int(host[-1]):
+                raise ValueError("proof must be an int32 tensor of at least proof_off[-1] = %d words, got %s"
+                                 % (int(host[-1]), '%s of %d' % (proof.dtype, proof.numel()) if torch.is_tensor(proof) else type(proof).__name__))
+        return proof_off.reshape(-1).contiguous().to(self.device), host
+
+    def exact_solve_proof(self, budget=0, hints=None, arena=0, proof_off=None, proof=None):
+        """The learning search (exact_solve(learn=True)) with its lemma log (pdp_exact_solve_learn_proof): (status, model, work, learned,
+        proof int32, proof_off int64 [B+1], proof_len int64 [B]).  Every learned clause that is stored is appended to the instance's region
+        proof[proof_off[b] : proof_off[b+1]] as ``len, lit_0 .. lit_{len-1}`` (literal (v << 1) | negative, v local to the instance) while
+        whole lemmas fit; proof_len[b] is the number of words all of them need, so the proof of b is complete iff proof_len[b] <= its region.
+        ``proof_off`` None: regions of PROOF_WORDS_PER_LITERAL words per literal of the instance.  ``proof``: a buffer to write into (the
+        words outside the stored lemmas are not touched); None: a fresh zeroed one, or, with regions of no words at all, a sizing call that
+        writes nothing and returns proof None."""
+        if isinstance(arena, bool) or not isinstance(arena, numbers.Integral) or not 0 <= arena <= 1 << 30:
+            raise ValueError("arena must be an integer from 0 to 2^30 words, got %r" % (arena,))
+        if hints is not None:
+            if not torch.is_tensor(hints) or hints.dtype != torch.float32 or hints.numel() != self.V:
+                raise ValueError("hints must be a float32 tensor of %d elements (one per variable), got %s"
+                                 % (self.V, '%s of %d' % (hints.dtype, hints.numel()) if torch.is_tensor(hints) else type(hints).__name__))
+            hints = hints.reshape(-1).contiguous()
+        if proof_off is None:
+            e = self.instance_edges() if self.R == 1 else torch.zeros(self.B, dtype=torch.int64, device=self.device)   # R != 1: the library refuses
+            proof_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(e * PROOF_WORDS_PER_LITERAL, 0)])
+        proof_off, host = self._proof_regions(proof_off, proof)
+        if proof is None and int(host[-1]) > int(host[0]):
+            proof = torch.zeros(int(host[-1]), dtype=torch.int32, device=self.device)
+        elif proof is not None:
+            if not proof.is_cuda or not proof.is_contiguous():
+                raise ValueError("proof must be a contiguous tensor on the problem's device")
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        model = torch.empty(self.V, dtype=torch.float32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        learned = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        proof_len = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_solve_learn_proof(self._h, ptr(hints, torch.float32, self.V, 'hints'), C.c_int64(int(budget)), C.c_int64(int(arena)),
+                                                ptr(status), ptr(model), ptr(work), ptr(learned), ptr(proof_off), ptr(proof), ptr(proof_len),
+                                                _stream()))
+        return status, model, work, learned, proof, proof_off, proof_len
+
+    def exact_check(self, status, model, proof, proof_off, proof_len, budget=0):
+        """Check the answers of a complete search (pdp_exact_check): (verdict int8 [B], fail_at int32 [B], work int64 [B]).  A status-1
+        instance is checked against its model (verdict 0: fail_at = the lowest clause without a true literal); a status-0 instance against
+        its proof, lemma by lemma and then the empty clause, each by unit propagation from the clauses and the lemmas before it (verdict 0:
+        fail_at = the first lemma that does not follow, the number of lemmas for the empty clause).  Verdict -1: undecided status, incomplete
+        proof (proof_len[b] past the region) or ``budget`` clause-literal reads spent.  ``proof`` None: every region must be empty."""
+        for name, t, dt, k in (('status', status, torch.int8, self.B), ('model', model, torch.float32, self.V),
+                               ('proof_len', proof_len, torch.int64, self.B)):
+            if not torch.is_tensor(t) or t.dtype != dt or t.numel() != k:
+                raise ValueError("%s must be a %s tensor of %d elements, got %s"
+                                 % (name, dt, k, '%s of %d' % (t.dtype, t.numel()) if torch.is_tensor(t) else type(t).__name__))
+        proof_off, host = self._proof_regions(proof_off, proof)
+        if proof is None and int(host[-1]) > int(host[0]):
+            raise ValueError("proof is None but the regions hold %d words" % (int(host[-1]) - int(host[0])))
+        if proof is not None and (not proof.is_cuda or not proof.is_contiguous()):
+            raise ValueError("proof must be a contiguous tensor on the problem's device")
+        verdict = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        fail_at = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_check(self._h, ptr(status.reshape(-1).contiguous()), ptr(model.reshape(-1).contiguous()), ptr(proof_off), ptr(proof),
+                                    ptr(proof_len.reshape(-1).contiguous()), C.c_int64(int(budget)), ptr(verdict), ptr(fail_at), ptr(work), _stream()))
+        return verdict, fail_at, work
 
     # -- K14 ---------------------------------------------------------------------------------------------------
     def energy(self, assignment):

@@ -7,7 +7,9 @@ same ``-s`` seed; philox = on-device counters, fastest), ``--stepwise`` (disable
 (every instance on its own instead of the reference's batch-wide couplings), and ``--complete`` / ``--complete-budget N``: every instance
 is then decided by the batched exact search with the model's assignment as its phase hints (pdp_exact_solve_hinted), and a row gains
 "complete" (1 satisfiable, 0 unsatisfiable, -1 undecided within the budget), "pdp_solved" and "work"; ``--complete-learn`` gives that search
-conflict clause learning (pdp_exact_solve_learn).
+conflict clause learning (pdp_exact_solve_learn); ``--complete-certify`` (implies ``--complete-learn``) has every answer checked on the GPU -- a
+model against the clauses, an "unsatisfiable" by a forward check of the learned clauses as a proof (pdp_exact_check) -- and a row gains
+"certified" (1 checked, -1 undecided).
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -98,12 +100,19 @@ def main(argv=None):
                         type=int, default=0)
     parser.add_argument('--complete-learn', dest='complete_learn', help='With --complete: the exact search learns a clause from every conflict and backjumps '
                         '(pdp_exact_solve_learn); the same rows, far fewer reads on structured instances', action='store_true')
+    parser.add_argument('--complete-certify', dest='complete_certify', help='With --complete: the learning search logs its learned clauses as a proof and '
+                        'every answer is checked on the GPU (pdp_exact_check); implies --complete-learn; rows gain "certified" (1 checked, -1 undecided)',
+                        action='store_true')
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
     args = vars(parser.parse_args(argv))
     if args['complete_learn'] and not args['complete']:
         parser.error("--complete-learn selects the search of --complete: give --complete as well")
+    if args['complete_certify'] and not args['complete']:
+        parser.error("--complete-certify checks the answers of --complete: give --complete as well")
+    if args['complete_certify']:
+        args['complete_learn'] = True
 
     with open(args['model_config'], 'r') as f:
         model_config = yaml.safe_load(f)

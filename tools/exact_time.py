@@ -12,7 +12,12 @@ only).  ``wa`` = wall time of ``satyr.py`` on row (a)'s instances with and witho
 Learning rows (pdp_exact_solve_learn; never part of the default): ``la`` .. ``ld`` = rows (a) .. (d) with conflict clause learning at the
 default arena, ``m100`` / ``m200`` = the reference's community-attachment family (ModularCNFGenerator(3, n, n, 0.8, 0.9, n/10, n/10, 3.8,
 4.2, 1), B = 2000) with both searches under a budget of 2^28 reads per instance.  A learning line adds the learned clauses per instance
-(median / max / total) and the arena reductions (instances with one, total)."""
+(median / max / total) and the arena reductions (instances with one, total).
+
+Proof rows (pdp_exact_solve_learn_proof and pdp_exact_check; never part of the default): ``pa`` / ``pd`` / ``pm100`` / ``pm200`` = rows (a), (d),
+m100 and m200: kernel time of the learning search without and with the lemma log on the same problem, the check kernel on that call's
+outputs with its verdicts and reads, and the proof words per instance (median / p99 / max) with the largest number of words per literal
+of an instance and, per region factor k, the instances whose proof a region of k words per literal would truncate."""
 import io
 import json
 import logging
@@ -157,6 +162,47 @@ def run_learn(key):
               % (int(both.sum()), int(wk0[both].sum()), int(wk[both].sum()), float(wk[both].sum()) / max(1.0, float(wk0[both].sum()))), flush=True)
 
 
+def _event_ms(call):
+    "kernel ms (device events) of call(), and what it returns"
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ev[0].record()
+    out = call()
+    ev[1].record()
+    torch.cuda.synchronize()
+    return ev[0].elapsed_time(ev[1]), out
+
+
+def run_proof(key):
+    "the learning search without and with its lemma log, and the check of its answers, all on one problem (second calls are timed)"
+    modular = key[1:] in MODULAR
+    title, make = MODULAR[key[1:]] if modular else ROWS[key[1:]]
+    budget = MODULAR_BUDGET if modular else 0
+    items = make()
+    b = dataset.to_torch(dataset.collate_segment(items), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(items))
+    ms0, st0, _, wk0, _ = _timed_learn(p, budget, True)
+    p.exact_solve_proof(budget)
+    ms1, out = _event_ms(lambda: p.exact_solve_proof(budget))
+    st, model, wk, ln, proof, off, plen = out
+    assert np.array_equal(st.cpu().numpy(), st0) and np.array_equal(wk.cpu().numpy(), wk0), "logging changed the search"
+    p.exact_check(st, model, proof, off, plen)
+    ms2, (verdict, fail_at, cwk) = _event_ms(lambda: p.exact_check(st, model, proof, off, plen))
+    verdict, cwk, words = verdict.cpu().numpy(), cwk.cpu().numpy(), plen.cpu().numpy()
+    e = p.instance_edges().cpu().numpy()
+    unsat = st0 == 0
+    _line(key + ', learning', title, p, ms0, st0, wk0)
+    print("    with the lemma log (%d words per literal): kernel %.2f ms (%.3f of the search without)  proof words per instance: median %d  p99 %d  "
+          "max %d  total %d  most words per literal %.3f  truncated at k = 1 / 2 / 4 / 8 / 16: %s"
+          % (native.PROOF_WORDS_PER_LITERAL, ms1, ms1 / ms0, int(np.median(words)), int(np.percentile(words, 99)), int(words.max()), int(words.sum()),
+             float((words / np.maximum(e, 1)).max()), ' / '.join(str(int((words > k * e).sum())) for k in (1, 2, 4, 8, 16))), flush=True)
+    print("    check: kernel %.2f ms (%.3f of the search)  verdict 1 / 0 / -1: %d / %d / %d  reads total %d (%.3f of the search's)  over the %d "
+          "unsatisfiable: check %d, search %d (ratio %.3f)"
+          % (ms2, ms2 / ms0, int((verdict == 1).sum()), int((verdict == 0).sum()), int((verdict == -1).sum()), int(cwk.sum()),
+             float(cwk.sum()) / max(1.0, float(wk0.sum())), int(unsat.sum()), int(cwk[unsat].sum()), int(wk0[unsat].sum()),
+             float(cwk[unsat].sum()) / max(1.0, float(wk0[unsat].sum()))), flush=True)
+    assert not (verdict == 0).any(), "a solver answer failed its check"
+
+
 def _write_json(items, path):
     from pdp import generator
     with open(path, 'w') as f:
@@ -236,4 +282,4 @@ def run_wall(key):
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
-        {'h': run_hinted, 'w': run_wall, 'l': run_learn, 'm': run_learn}.get(k[0], run)(k)
+        {'h': run_hinted, 'w': run_wall, 'l': run_learn, 'm': run_learn, 'p': run_proof}.get(k[0], run)(k)
