@@ -24,8 +24,8 @@ extern "C" {
 
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
- * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof and pdp_exact_check are
- * additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check and
+ * pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -292,6 +292,14 @@ int pdp_exact_solve_learn_proof(pdp_problem *p, const float *hint, int64_t budge
  * R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules; routing and working arrays are prepared once per problem. */
 int pdp_exact_check(pdp_problem *p, const int8_t *status, const float *model, const int64_t *proof_off, const int32_t *proof,
                     const int64_t *proof_len, int64_t budget, int8_t *verdict, int32_t *fail_at, int64_t *work, void *stream);
+/* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
+ * pdp_exact_solve_learn_proof or pdp_exact_check issued without an error on the problem; 0 before the first, and a call that fails
+ * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
+ * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an
+ * integer v >= 1 and is ignored otherwise (unset, empty, 0, negative, not a number) -- a test switch that makes a wave run many
+ * instances one after the other on a small batch; no output of the entry points above depends on the grid.  Reads a host field the
+ * launches write: no synchronisation, no stream. */
+int pdp_exact_last_grid(const pdp_problem *p, int32_t *grid_host);
 
 /* ---- persistent solve: the whole _forward_core loop in one launch ------------------------------------
  * replaces: PropagatorDecimatorSolverBase._forward_core (solver.py:355-386) for the classical

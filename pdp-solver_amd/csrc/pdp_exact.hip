@@ -27,6 +27,7 @@
 // the decision reads anyway: no array is added to the slab, and the routing and ex_prepare's cached decision stay as they are.
 #include "pdp_common.hpp"
 #include <algorithm>
+#include <cstdlib>
 #include <vector>
 
 #define ST(s) ((hipStream_t)(s))
@@ -35,6 +36,19 @@ namespace {
 
 constexpr int EX_NT = 64;                       // one wave per instance
 constexpr size_t EX_LDS_LIMIT = 48 * 1024;      // per-instance slab: at least three instances per CU (160 KiB of LDS)
+
+// PDP_EXACT_GRID=<v>, read at every launch of the three persistent kernels: an integer v >= 1 lowers the workgroup count to min(grid, v);
+// any other value (unset, empty, 0, negative, not a number) leaves it.  Tests: many instances per wave, one after the other in one slab,
+// on small batches.  After a launch that succeeded the count is kept on the problem (ex_last_grid) for pdp_exact_last_grid.
+inline int64_t ex_grid(int64_t grid)
+{
+    if (const char *e = getenv("PDP_EXACT_GRID")) {
+        char *end = nullptr;
+        const long long v = strtoll(e, &end, 10);
+        if (end != e && *end == '\0' && v >= 1 && v < grid) grid = (int64_t)v;
+    }
+    return grid;
+}
 
 struct ExLds { size_t pend, cnt, trail, mark, dvar, lit, cptr, val, bytes; };
 
@@ -395,10 +409,11 @@ int ex_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status,
     if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact<HINT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact<HINT>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu);
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
     PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
     hipLaunchKernelGGL(k_exact<HINT>, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
     return PDP_OK;
 }
 
@@ -916,10 +931,11 @@ int exl_launch(pdp_problem *p, const float *hint, int64_t budget, int64_t arena,
     const int lds = (int)p->exl_lds_bytes;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_learn<HINT, PROOF>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu);
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
     PDP_HIP_CHECK(hipMemsetAsync(xp.next, 0, 4, st));
     hipLaunchKernelGGL((k_exact_learn<HINT, PROOF>), dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
     return PDP_OK;
 }
 
@@ -1208,10 +1224,11 @@ int exc_launch(pdp_problem *p, const int8_t *status, const float *model, const i
     const int lds = (int)p->exc_lds_bytes;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_check, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu);
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
     PDP_HIP_CHECK(hipMemsetAsync(xp.next, 0, 4, st));
     hipLaunchKernelGGL(k_exact_check, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
     return PDP_OK;
 }
 
@@ -1280,5 +1297,12 @@ extern "C" int pdp_exact_learn_reductions(pdp_problem *p, int32_t *reductions, v
     PDP_REQUIRE(p->exl_ready, "pdp_exact_learn_reductions: no pdp_exact_solve_learn call on this problem yet");
     const size_t B = p->B, head = ((B + 1) * 4 + 7) & ~(size_t)7;
     PDP_HIP_CHECK(hipMemcpyAsync(reductions, p->exl_blob + head + B * 8, B * 4, hipMemcpyDeviceToDevice, ST(stream)));
+    return PDP_OK;
+}
+
+extern "C" int pdp_exact_last_grid(const pdp_problem *p, int32_t *grid_host)
+{
+    PDP_REQUIRE(p && grid_host, "NULL argument");
+    *grid_host = p->ex_last_grid;
     return PDP_OK;
 }

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = [
     'pdp_sat_loss_grad', 'pdp_train_sp_adapted_backward',
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
-    'pdp_exact_solve_learn_proof', 'pdp_exact_check',
+    'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_last_grid',
 ]
 
 
@@ -524,6 +524,13 @@ class Problem(object):
         check(lib().pdp_exact_check(self._h, ptr(status.reshape(-1).contiguous()), ptr(model.reshape(-1).contiguous()), ptr(proof_off), ptr(proof),
                                     ptr(proof_len.reshape(-1).contiguous()), C.c_int64(int(budget)), ptr(verdict), ptr(fail_at), ptr(work), _stream()))
         return verdict, fail_at, work
+
+    def exact_last_grid(self):
+        """Workgroups of the last launch of exact_solve, exact_solve_proof or exact_check on this problem (pdp_exact_last_grid), 0 before the
+        first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
+        out = C.c_int32(-1)
+        check(lib().pdp_exact_last_grid(self._h, C.byref(out)))
+        return int(out.value)
 
     # -- K14 ---------------------------------------------------------------------------------------------------
     def energy(self, assignment):
