@@ -24,8 +24,8 @@ extern "C" {
 
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
- * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check and
- * pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
+ * pdp_exact_trim and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -292,8 +292,52 @@ int pdp_exact_solve_learn_proof(pdp_problem *p, const float *hint, int64_t budge
  * R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules; routing and working arrays are prepared once per problem. */
 int pdp_exact_check(pdp_problem *p, const int8_t *status, const float *model, const int64_t *proof_off, const int32_t *proof,
                     const int64_t *proof_len, int64_t budget, int8_t *verdict, int32_t *fail_at, int64_t *work, void *stream);
+
+/* The backward check of a proof of unsatisfiability, one wave per instance (plain Python: tests/exact_trim_model.py): which original clauses
+ * (the core) and which lemmas the refutation rests on.  proof, proof_off and proof_len are pdp_exact_check's.  Outputs: verdict [B],
+ * fail_at [B], work [B] (may be NULL) as there; core [F], one byte per clause in the problem's clause order; keep, one byte per proof word
+ * at the offsets of proof; n_core [B] and n_keep [B] (may be NULL), the core clauses and the kept lemmas of each instance.
+ *   Only status[b] == 0 is judged (a model needs no core).  Any other status, or proof_len[b] negative, larger than the region, or so
+ *   large that clauses + proof_len[b] >= 2^31: verdict -1, fail_at -1, work 0; nothing of the proof is read and keep is not touched.
+ *   core is written for every clause of every instance, 0 unless stated otherwise below.
+ *   Step 1.  The first proof_len[b] words are parsed into lemmas 0 .. L-1 and ALL of them are validated before one is used: a length must
+ *     be >= 0 and fit the proof_len[b] words, every variable id must be below n.  Lemma i the first malformed one: verdict 0, fail_at i,
+ *     work 0.  (pdp_exact_check meets a malformed lemma only when it arrives there, and has counted the reads up to it.)
+ *   Step 2.  The empty clause i = L is marked.  For i = L down to 0, lemma i is skipped unless it is marked; otherwise the assignment is
+ *     cleared, the literals of lemma i are falsified (work += len_i) and passes run to a fixed point.  Before each pass: work >= budget ->
+ *     verdict -1, fail_at -1 (budget <= 0 means PDP_EXACT_DEFAULT_BUDGET).  A pass reads the original clauses and then lemmas 0 .. i-1
+ *     in ascending index (lemma j has clause index m + j), each up to and including its first true literal, and records the lowest
+ *     falsified clause and, per requested literal, the lowest clause that asks for it.  A falsified clause: the antecedents start as
+ *     {that clause}.  Otherwise a variable asked for in both polarities: they start as {the positive request's clause, the negative
+ *     request's clause} of the lowest such variable, and nothing is assigned.  Otherwise no request: verdict 0, fail_at i.  Otherwise
+ *     every request is applied with its clause as the variable's reason, and the next pass runs.
+ *     The closure of a start set: every clause of it is marked, and for every literal of a marked clause the reason of its variable, if a
+ *     request of this lemma's check assigned it (the lemma's own falsified literals have none), until nothing new is marked.  Each clause
+ *     marked in a closure adds its length to work, once per lemma check.  A marked original clause sets its core byte, a marked lemma j
+ *     is marked for the backward loop.
+ *     (pdp_exact_check accepts a lemma with both polarities of a variable at once.  Here that rule has no counterpart: such a lemma is
+ *     never falsified and never asks for a literal, so nothing marks it and it is never checked.)
+ *   All marked lemmas refuted: verdict 1, fail_at -1, core as marked, keep = 1 on every word of a marked lemma (its length word and its
+ *     literals) and 0 on every other word among the first proof_len[b]; n_core and n_keep count them.  With verdict 0 or -1 the instance's
+ *     core bytes and its first proof_len[b] keep bytes are 0, n_core and n_keep are 0.  Words of a region past proof_len[b] are never touched.
+ * Between two budget checks lie at most one pass, one closure and one lemma's own literals: work < budget + 3 (e + W), W = the region's
+ * words.  Every quantity is a minimum, an OR or a sum over a consistent assignment and the closure is a set, so all seven outputs are a
+ * function of the instance and its proof alone: the same in any batch, at any position, at any grid and in both library builds.
+ * Consequences (unit propagation is monotone, and a check that needs fewer lemmas has fewer to refute):
+ *   T1  pdp_exact_check verdict 1 on a proof implies pdp_exact_trim verdict 1 on it.
+ *   T2  pdp_exact_trim verdict 0 implies pdp_exact_check verdict 0.
+ *   T3  with verdict 1, the clauses with core = 1 are unsatisfiable on their own;
+ *   T4  with verdict 1, the kept lemmas in order are a proof that pdp_exact_check accepts against those clauses alone.
+ * T3 and T4 hold for ANY input words -- genuine, mutated or forged: every kept lemma was refuted from core clauses and kept lemmas before
+ * it.  The backward check may accept a proof the forward check refutes, because a bad lemma nobody needs is never looked at; that is
+ * sound (T3), and it is why verdict 0 here is the weaker alarm.  proof and keep may both be NULL if every region is empty.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules; routing and working arrays are prepared once per problem. */
+int pdp_exact_trim(pdp_problem *p, const int8_t *status, const int64_t *proof_off, const int32_t *proof, const int64_t *proof_len,
+                   int64_t budget, int8_t *verdict, int32_t *fail_at, int64_t *work,
+                   int8_t *core, int8_t *keep, int32_t *n_core, int32_t *n_keep, void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof or pdp_exact_check issued without an error on the problem; 0 before the first, and a call that fails
+ * pdp_exact_solve_learn_proof, pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an
  * integer v >= 1 and is ignored otherwise (unset, empty, 0, negative, not a number) -- a test switch that makes a wave run many

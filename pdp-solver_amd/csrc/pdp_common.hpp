@@ -147,7 +147,9 @@ struct pdp_problem {
     int exl_ready, exl_nbig; int64_t exl_arena; size_t exl_lds_bytes, exl_words; char *exl_blob;
     // checker of the complete solver (pdp_exact.hip::exc_prepare): its own routing, order, counter and HBM working arrays, one block
     int exc_ready, exc_nbig; size_t exc_lds_bytes; char *exc_blob;
-    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_learn or k_exact_check on this problem (0: none yet)
+    // backward check of the complete solver's proofs (pdp_exact.hip::ext_prepare): the same, for its own routing
+    int ext_ready, ext_nbig; size_t ext_lds_bytes; char *ext_blob;
+    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_learn, k_exact_check or k_exact_trim on this problem (0: none yet)
     uint32_t *team_ws;          // barrier counters and reduction mailboxes of the workgroup teams (k_sp_solve<NT, true>)
     hipStream_t res_side_stream; hipEvent_t res_side_ev[2];   // the big instances' launches overlap the LDS-resident kernel on a stream of their own
     float *nws[4]; size_t nws_floats[4];             // neural workspaces (grow on demand)

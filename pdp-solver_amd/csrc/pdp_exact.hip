@@ -37,7 +37,7 @@ namespace {
 constexpr int EX_NT = 64;                       // one wave per instance
 constexpr size_t EX_LDS_LIMIT = 48 * 1024;      // per-instance slab: at least three instances per CU (160 KiB of LDS)
 
-// PDP_EXACT_GRID=<v>, read at every launch of the three persistent kernels: an integer v >= 1 lowers the workgroup count to min(grid, v);
+// PDP_EXACT_GRID=<v>, read at every launch of the four persistent kernels: an integer v >= 1 lowers the workgroup count to min(grid, v);
 // any other value (unset, empty, 0, negative, not a number) leaves it.  Tests: many instances per wave, one after the other in one slab,
 // on small batches.  After a launch that succeeded the count is kept on the problem (ex_last_grid) for pdp_exact_last_grid.
 inline int64_t ex_grid(int64_t grid)
@@ -1232,6 +1232,408 @@ int exc_launch(pdp_problem *p, const int8_t *status, const float *model, const i
     return PDP_OK;
 }
 
+// ---- pdp_exact_trim: the backward check of a proof, its core and its needed lemmas ---------------------------------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_trim_model.py).  A kernel of its own: with the code above it shares the wave
+// helpers (ex_sync, ex_sum, ex_min), the persistent grid, the instance order and the checker's way of streaming a lemma across the lanes.
+// State of one instance:
+//   lit [e], cptr [m+1]  the original clauses as above      val [n]   bits 0-1: 0 unassigned, 1 true, 2 false; EXT_SEEN: met by the closure
+//   req [2n]             per literal, the lowest clause that asks for it in the current pass (EXL_NONE between passes)
+//   rsn [n]              the clause whose request assigned the variable in the current lemma's check
+//   trail [n]            the variables the passes of the current lemma's check assigned, pass after pass
+//   bat [n+1]            trail length at the start of each pass that assigned something (a pass's variables are one batch)
+// in a slab of LDS up to EX_LDS_LIMIT (u16 literals and offsets), else in HBM working arrays indexed by the problem's ids.  A lemma is
+// named by where it starts: the lemma whose length word is word q of the region is clause m + q, so ascending clause numbers are ascending
+// lemma indices, a reason leads to its literals without a table, and the marks need no memory of their own: while an instance runs, core
+// holds the marked original clauses and keep[q] the mark of the lemma at word q; at the end keep is spread over the kept lemmas' literals.
+constexpr uint8_t EXT_SEEN = 4;
+
+struct ExtLds { size_t req, rsn, trail, bat, lit, cptr, val, bytes; };
+
+__host__ __device__ inline ExtLds ext_lds_layout(int n, int m, int e)
+{
+    ExtLds L;
+    size_t o = 0;
+    L.req = o;   o += 8 * (size_t)n;
+    L.rsn = o;   o += 4 * (size_t)n;
+    L.trail = o; o += 4 * (size_t)n;
+    L.bat = o;   o += 4 * ((size_t)n + 1);
+    L.lit = o;   o += 2 * (size_t)e;
+    L.cptr = o;  o += 2 * ((size_t)m + 1);
+    L.val = o;   o += (size_t)n;
+    L.bytes = (o + 15) & ~(size_t)15;
+    return L;
+}
+inline bool ext_fits_lds(int n, int m, int e) { return n < 32768 && e <= 65535 && ext_lds_layout(n, m, e).bytes <= EX_LDS_LIMIT; }
+
+struct ExtParams {
+    const int32_t *order;       // as ExParams: the nbig HBM-routed instances first
+    int nbig, B;
+    uint32_t *next;
+    int64_t budget;
+    const int8_t *status;
+    const int64_t *proof_off; const int32_t *proof; const int64_t *proof_len;
+    int8_t *verdict; int32_t *fail_at; int64_t *work;
+    int8_t *core, *keep; int32_t *n_core, *n_keep;
+    uint32_t *h_lit;            // [E]
+    uint32_t *h_req, *h_rsn;    // [2V], [V]
+    int32_t *h_trail;           // [V]
+    int32_t *h_bat;             // [V+B] (instance b at v0 + b: n+1 entries)
+    uint8_t *h_val;             // [V]
+};
+
+template <typename LitT, typename PtrT>
+struct ExtInst {
+    LitT *lit; const PtrT *cptr; uint8_t *val; uint32_t *req, *rsn; int32_t *trail, *bat;
+    const int32_t *w;           // the instance's proof region
+    int8_t *core, *keep;        // the instance's clauses / its region's words
+    int n, m, e;
+};
+
+// One original clause by the calling lane, read up to and including its first true literal.
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ void ext_clause(const ExtInst<LitT, PtrT> &X, int c, int &reads, int &cmin, int &unit)
+{
+    const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+    int nfree = 0, sat = 0, k = a, distinct = 0;
+    uint32_t first = 0;
+    for (; k < z; ++k) {
+        const uint32_t L = X.lit[k];
+        const uint32_t x = X.val[L >> 1] & 3u;
+        if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+        else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+    }
+    reads += k - a;
+    if (sat) return;
+    if (nfree == 0) cmin = c < cmin ? c : cmin;
+    else if (!distinct) { unit = 1; atomicMin(&X.req[first], (uint32_t)c); }
+}
+
+// One lemma (clause c: len validated literals at w) by the whole wave, 64 literals at a time; every result is wave-uniform.
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ void ext_lemma(const ExtInst<LitT, PtrT> &X, const int32_t *w, int len, int c, int &reads, int &cmin, int &unit)
+{
+    const int lane = (int)threadIdx.x;
+    int nfree = 0, distinct = 0;
+    uint32_t first = 0;
+    for (int base = 0; base < len; base += EX_NT) {
+        const int k = base + lane;
+        const uint32_t L = k < len ? (uint32_t)w[k] : 0u;
+        const uint32_t x = k < len ? (uint32_t)X.val[L >> 1] & 3u : 3u;
+        const unsigned long long tmask = __ballot(x == 1u + (L & 1u));
+        if (tmask) { reads += base + __ffsll((long long)tmask); return; }       // read up to and including the first true literal
+        const unsigned long long fmask = __ballot(x == 0u);
+        if (fmask) {
+            if (nfree == 0) first = (uint32_t)__shfl((int)L, __ffsll((long long)fmask) - 1);
+            distinct |= __ballot(x == 0u && L != first) != 0ull;
+            nfree += __popcll(fmask);
+        }
+    }
+    reads += len;
+    if (nfree == 0) cmin = c < cmin ? c : cmin;
+    else if (!distinct) { unit = 1; if (lane == 0) atomicMin(&X.req[first], (uint32_t)c); }
+}
+
+// Clause c enters the closure: its mark is set and the variables of its literals k0, k0 + step, ... become seen; returns its length.
+// The whole wave on one clause (k0 = lane, step = 64) or one lane on a clause of its own (0, 1).  Lanes that meet the same variable or
+// clause store the same byte.
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ int ext_visit(const ExtInst<LitT, PtrT> &X, uint32_t c, int k0, int step)
+{
+    int len;
+    if (c < (uint32_t)X.m) {
+        const int a = (int)X.cptr[c];
+        len = (int)X.cptr[c + 1] - a;
+        X.core[c] = 1;
+        for (int k = k0; k < len; k += step) {
+            const int v = (int)(X.lit[a + k] >> 1);
+            const uint8_t x = X.val[v];
+            if (!(x & EXT_SEEN)) X.val[v] = x | EXT_SEEN;
+        }
+    } else {
+        const int32_t q = (int32_t)(c - (uint32_t)X.m);
+        len = X.w[q];
+        X.keep[q] = 1;
+        for (int k = k0; k < len; k += step) {
+            const int v = (int)((uint32_t)X.w[q + 1 + k] >> 1);
+            const uint8_t x = X.val[v];
+            if (!(x & EXT_SEEN)) X.val[v] = x | EXT_SEEN;
+        }
+    }
+    return len;
+}
+
+// The check of one marked lemma (its length word at word `at`, len literals; the empty clause: at = the proof's words, len = 0) by unit
+// propagation from the original clauses and the lemmas before it, and the closure of what refuted it.  1: refuted, its antecedents are
+// marked; 0: the passes reached a fixed point without a conflict; -1: the budget is spent.  work: the reads so far, added to.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ext_refute(const ExtInst<LitT, PtrT> &X, int32_t at, int len, int64_t budget, int64_t &work)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int32_t *mine = X.w + at + 1;
+    for (int v = lane; v < X.n; v += EX_NT) X.val[v] = 0;
+    ex_sync<HBM>();
+    // a marked lemma was unit or falsified under some assignment, so it does not hold both polarities of a variable: no two lanes differ
+    for (int k = lane; k < len; k += EX_NT) {
+        const uint32_t L = (uint32_t)mine[k];
+        X.val[L >> 1] = (uint8_t)(2u - (L & 1u));
+    }
+    ex_sync<HBM>();
+    work += len;
+    int tlen = 0, nb = 0;
+    uint32_t s0 = EXL_NONE, s1 = EXL_NONE;                          // the clauses the closure starts from
+    for (;;) {
+        if (work >= budget) return -1;
+        // ---- one pass: the lowest falsified clause, and per literal the lowest clause that asks for it
+        int reads = 0, unit = 0, cmin = EXL_INF;
+        for (int c = lane; c < X.m; c += EX_NT) ext_clause(X, c, reads, cmin, unit);
+        work += ex_sum(reads);
+        int lreads = 0, lunit = 0, lmin = EXL_INF;
+        for (int32_t q = 0; q < at;) { const int lj = X.w[q]; ext_lemma(X, X.w + q + 1, lj, X.m + q, lreads, lmin, lunit); q += 1 + lj; }
+        work += lreads;
+        int confl = ex_min(cmin);
+        confl = lmin < confl ? lmin : confl;
+        const bool any_unit = __ballot(unit | lunit) != 0ull;
+        if (confl == EXL_INF && !any_unit) return 0;
+        ex_sync<HBM>();
+        if (confl != EXL_INF) s0 = (uint32_t)confl;
+        else {
+            // the lowest variable asked for in both polarities: its two requests refute the lemma, nothing is assigned
+            int vs = EXL_INF;
+            for (int v = lane; v < X.n; v += EX_NT)
+                if (X.req[2 * v] != EXL_NONE && X.req[2 * v + 1] != EXL_NONE) vs = v < vs ? v : vs;
+            vs = ex_min(vs);
+            if (vs != EXL_INF) { s0 = X.req[2 * vs]; s1 = X.req[2 * vs + 1]; ex_sync<HBM>(); }
+        }
+        if (s0 != EXL_NONE) {
+            // the requests of this pass are dropped
+            if (any_unit) for (int v = lane; v < X.n; v += EX_NT) { X.req[2 * v] = EXL_NONE; X.req[2 * v + 1] = EXL_NONE; }
+            break;
+        }
+        // every request is applied, with its clause as the variable's reason: one batch of the trail
+        if (lane == 0) X.bat[nb] = tlen;
+        ++nb;
+        for (int base = 0; base < X.n; base += EX_NT) {
+            const int v = base + lane;
+            const uint32_t r1 = v < X.n ? X.req[2 * v] : EXL_NONE, r0 = v < X.n ? X.req[2 * v + 1] : EXL_NONE;
+            const bool take = r1 != EXL_NONE || r0 != EXL_NONE;
+            const unsigned long long mask = __ballot(take);
+            if (take) {
+                X.req[2 * v] = EXL_NONE; X.req[2 * v + 1] = EXL_NONE;
+                X.val[v] = r1 != EXL_NONE ? 1 : 2; X.rsn[v] = r1 != EXL_NONE ? r1 : r0;
+                X.trail[tlen + __popcll(mask & below)] = v;
+            }
+            tlen += __popcll(mask);
+        }
+        ex_sync<HBM>();
+    }
+    // ---- the closure.  A reason's other literals were false before the pass that applied it, so a reason leads to variables of earlier
+    // batches (or of the lemma itself, which have no reason) only: one sweep over the batches, last to first, each lane on one variable
+    // (a lane walks its reason alone: a reason of hundreds of literals is a serial chain of loads by one lane; not measured on wide instances)
+    int add = ext_visit(X, s0, lane, EX_NT);
+    if (s1 != EXL_NONE) add += ext_visit(X, s1, lane, EX_NT);
+    work += add;
+    add = 0;
+    int hi = tlen;
+    for (int b = nb - 1; b >= 0; --b) {
+        ex_sync<HBM>();                                             // the seen bits the later batches set
+        const int lo = X.bat[b];
+        for (int t = lo + lane; t < hi; t += EX_NT) {
+            const int v = X.trail[t];
+            if (X.val[v] & EXT_SEEN) add += ext_visit(X, X.rsn[v], 0, 1);
+        }
+        hi = lo;
+    }
+    work += ex_sum(add);
+    return 1;
+}
+
+// The backward check of one instance by the calling wave: verdict 1 / 0 / -1 and the other outputs as the header states them.  W: the
+// words of the region X.w that are said to hold lemmas (0 <= W <= the region's size and m + W < 2^31, checked by the caller).  X.core is
+// all zero on entry.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ext_trim(const ExtInst<LitT, PtrT> &X, int32_t W, int64_t budget, int *fail_out, int64_t *work_out, int *ncore_out, int *nkeep_out)
+{
+    const int lane = (int)threadIdx.x;
+    *fail_out = -1; *work_out = 0; *ncore_out = 0; *nkeep_out = 0;
+    for (int32_t k = lane; k < W; k += EX_NT) X.keep[k] = 0;
+    // step 1: every lemma is validated before one is used
+    int nlem = 0, badlen = EXL_INF, badlit = EXL_INF;
+    for (int32_t q = 0; q < W;) {
+        const int len = X.w[q];
+        if (len < 0 || (int64_t)q + 1 + len > (int64_t)W) { badlen = nlem; break; }
+        for (int k = lane; k < len; k += EX_NT)
+            if (((uint32_t)X.w[q + 1 + k] >> 1) >= (uint32_t)X.n) badlit = nlem < badlit ? nlem : badlit;
+        ++nlem; q += 1 + len;
+    }
+    badlit = ex_min(badlit);
+    if (badlit != EXL_INF || badlen != EXL_INF) { *fail_out = badlit < badlen ? badlit : badlen; return 0; }
+    // step 2: from the empty clause backwards, the marked lemmas only
+    int64_t work = 0;
+    int32_t at = W;
+    int len = 0, verdict = 1;
+    for (;;) {
+        const int r = ext_refute<HBM>(X, at, len, budget, work);
+        if (r != 1) { verdict = r; break; }
+        ex_sync<HBM>();                                             // the marks of this closure
+        int32_t i = at - 1, found = -1;
+        while (i >= 0) {
+            const int32_t idx = i - lane;
+            const unsigned long long mask = __ballot(idx >= 0 && X.keep[idx >= 0 ? idx : 0] != 0);
+            if (mask) { found = i - (__ffsll((long long)mask) - 1); break; }
+            i -= EX_NT;
+        }
+        if (found < 0) break;
+        at = found; len = X.w[at];
+    }
+    *work_out = work;
+    ex_sync<HBM>();
+    if (verdict != 1) {
+        if (verdict == 0) { int i = 0; for (int32_t q = 0; q < at; q += 1 + X.w[q]) ++i; *fail_out = i; }
+        for (int c = lane; c < X.m; c += EX_NT) X.core[c] = 0;
+        for (int32_t k = lane; k < W; k += EX_NT) X.keep[k] = 0;
+        return verdict;
+    }
+    int ncore = 0, nkeep = 0;
+    for (int c = lane; c < X.m; c += EX_NT) ncore += X.core[c];
+    for (int32_t q = 0; q < W;) {
+        const int lq = X.w[q];
+        if (X.keep[q]) { ++nkeep; for (int k = lane; k < lq; k += EX_NT) X.keep[q + 1 + k] = 1; }
+        q += 1 + lq;
+    }
+    *ncore_out = ex_sum(ncore); *nkeep_out = nkeep;
+    return 1;
+}
+
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ext_run(const ExtParams &xp, const Inst &I, ExtInst<LitT, PtrT> X, PtrT *cptr_fill)
+{
+    const int lane = (int)threadIdx.x;
+    const int status = (int)xp.status[I.b];
+    const int64_t a = xp.proof_off[I.b], z = xp.proof_off[I.b + 1], W = xp.proof_len[I.b];
+    int verdict = -1, fail = -1, ncore = 0, nkeep = 0;
+    int64_t work = 0;
+    X.core = xp.core + I.f0;
+    for (int c = lane; c < I.m; c += EX_NT) X.core[c] = 0;
+    // nothing is read for an instance without the answer "unsatisfiable", an incomplete proof or a region that is none
+    if (status == 0 && W >= 0 && a >= 0 && z >= a && W <= z - a && W + (int64_t)I.m < (int64_t)EXL_INF && ((xp.proof && xp.keep) || W == 0)) {
+        if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+        for (int k = lane; k < I.e; k += EX_NT) {
+            const int ed = I.f_edges[k];
+            X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+        }
+        for (int v = lane; v < I.n; v += EX_NT) { X.req[2 * v] = EXL_NONE; X.req[2 * v + 1] = EXL_NONE; }
+        X.w = xp.proof ? xp.proof + a : nullptr;
+        X.keep = xp.keep ? xp.keep + a : nullptr;
+        ex_sync<HBM>();
+        verdict = ext_trim<HBM>(X, (int32_t)W, xp.budget, &fail, &work, &ncore, &nkeep);
+    }
+    if (lane == 0) {
+        xp.verdict[I.b] = (int8_t)verdict;
+        xp.fail_at[I.b] = fail;
+        if (xp.work) xp.work[I.b] = work;
+        if (xp.n_core) xp.n_core[I.b] = ncore;
+        if (xp.n_keep) xp.n_keep[I.b] = nkeep;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_trim(PView pv, ExtParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ext_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        if (i < xp.nbig) {
+            ExtInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr; X.val = xp.h_val + I.v0; X.req = xp.h_req + 2 * (size_t)I.v0; X.rsn = xp.h_rsn + I.v0;
+            X.trail = xp.h_trail + I.v0; X.bat = xp.h_bat + I.v0 + I.b;
+            X.w = nullptr; X.core = nullptr; X.keep = nullptr;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ext_run<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
+        } else {
+            const ExtLds L = ext_lds_layout(I.n, I.m, I.e);
+            ExtInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(ext_slab + L.lit); X.cptr = (const uint16_t *)(ext_slab + L.cptr);
+            X.val = ext_slab + L.val; X.req = (uint32_t *)(ext_slab + L.req); X.rsn = (uint32_t *)(ext_slab + L.rsn);
+            X.trail = (int32_t *)(ext_slab + L.trail); X.bat = (int32_t *)(ext_slab + L.bat);
+            X.w = nullptr; X.core = nullptr; X.keep = nullptr;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ext_run<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ext_slab + L.cptr));
+        }
+    }
+}
+
+// Routing, instance order and the HBM route's working arrays of the backward check: once per problem, like exc_prepare.
+// One block: order [B] | counter | (HBM route) lit [E] | req [2V] | rsn [V] | trail [V] | bat [V+B] | val [V]
+int ext_prepare(pdp_problem *p)
+{
+    if (p->ext_ready) return PDP_OK;
+    const size_t B = p->B;
+    std::vector<int32_t> v0(B + 1), f0(B + 1), e0(B + 1);
+    PDP_HIP_CHECK(hipMemcpy(v0.data(), p->inst_v0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(f0.data(), p->inst_f0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(e0.data(), p->inst_e0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> big, fit;
+    size_t lds = 0;
+    for (size_t b = 0; b < B; ++b) {
+        const int n = v0[b + 1] - v0[b], m = f0[b + 1] - f0[b], e = e0[b + 1] - e0[b];
+        if (ext_fits_lds(n, m, e)) { fit.push_back((int32_t)b); lds = std::max(lds, ext_lds_layout(n, m, e).bytes); }
+        else big.push_back((int32_t)b);
+    }
+    auto by_edges = [&](int32_t a, int32_t b) { const int ea = e0[a + 1] - e0[a], eb = e0[b + 1] - e0[b]; return ea != eb ? ea > eb : a < b; };
+    std::sort(big.begin(), big.end(), by_edges);
+    std::sort(fit.begin(), fit.end(), by_edges);
+    std::vector<int32_t> order(big);
+    order.insert(order.end(), fit.begin(), fit.end());
+    const size_t V = p->V, E = p->E;
+    size_t bytes = (B + 1) * 4;
+    if (!big.empty()) bytes += E * 4 + V * 16 + (V + B) * 4 + V;
+    char *blk = nullptr;
+    { const int st_ = pdp_dev_alloc((void **)&blk, (bytes + 15) & ~(size_t)15); if (st_ != PDP_OK) return st_; }
+    p->ext_blob = blk;
+    PDP_HIP_CHECK(hipMemcpy(blk, order.data(), B * 4, hipMemcpyHostToDevice));
+    p->ext_nbig = (int)big.size();
+    p->ext_lds_bytes = lds;
+    p->ext_ready = 1;
+    return PDP_OK;
+}
+
+int ext_launch(pdp_problem *p, const int8_t *status, const int64_t *proof_off, const int32_t *proof, const int64_t *proof_len, int64_t budget,
+               int8_t *verdict, int32_t *fail_at, int64_t *work, int8_t *core, int8_t *keep, int32_t *n_core, int32_t *n_keep, void *stream)
+{
+    { const int st_ = ext_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t V = p->V, E = p->E, B = p->B;
+    ExtParams xp;
+    xp.order = (const int32_t *)p->ext_blob; xp.nbig = p->ext_nbig; xp.B = p->B; xp.next = (uint32_t *)(p->ext_blob + B * 4);
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.status = status; xp.proof_off = proof_off; xp.proof = proof; xp.proof_len = proof_len;
+    xp.verdict = verdict; xp.fail_at = fail_at; xp.work = work; xp.core = core; xp.keep = keep; xp.n_core = n_core; xp.n_keep = n_keep;
+    xp.h_lit = nullptr; xp.h_req = nullptr; xp.h_rsn = nullptr; xp.h_trail = nullptr; xp.h_bat = nullptr; xp.h_val = nullptr;
+    if (p->ext_nbig) {
+        char *q = p->ext_blob + (B + 1) * 4;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_req = (uint32_t *)q;            q += V * 8;
+        xp.h_rsn = (uint32_t *)q;            q += V * 4;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_bat = (int32_t *)q;             q += (V + B) * 4;
+        xp.h_val = (uint8_t *)q;
+    }
+    const int lds = (int)p->ext_lds_bytes;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_trim, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
+    PDP_HIP_CHECK(hipMemsetAsync(xp.next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_trim, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -1289,6 +1691,19 @@ extern "C" int pdp_exact_check(pdp_problem *p, const int8_t *status, const float
         return PDP_ERR_UNSUPPORTED;
     }
     return exc_launch(p, status, model, proof_off, proof, proof_len, budget, verdict, fail_at, work, stream);
+}
+
+extern "C" int pdp_exact_trim(pdp_problem *p, const int8_t *status, const int64_t *proof_off, const int32_t *proof, const int64_t *proof_len,
+                              int64_t budget, int8_t *verdict, int32_t *fail_at, int64_t *work, int8_t *core, int8_t *keep, int32_t *n_core,
+                              int32_t *n_keep, void *stream)
+{
+    PDP_REQUIRE(p && status && proof_off && proof_len && verdict && fail_at && core, "NULL argument");
+    PDP_REQUIRE((proof == nullptr) == (keep == nullptr), "pdp_exact_trim: proof and keep are both given or both NULL");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_trim: a replicated problem (R = %d) is not supported; trim the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return ext_launch(p, status, proof_off, proof, proof_len, budget, verdict, fail_at, work, core, keep, n_core, n_keep, stream);
 }
 
 extern "C" int pdp_exact_learn_reductions(pdp_problem *p, int32_t *reductions, void *stream)

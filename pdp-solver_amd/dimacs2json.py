@@ -103,12 +103,13 @@ def json_line(path, label, propagate=False):
     return generator.format_json_line(var_num, clause_num, signed_vars, clause_ids, label=label, name=os.path.split(path)[1])
 
 
-def exact_labels(instances, budget=0, learn=False, certify=False):
+def exact_labels(instances, budget=0, learn=False, certify=False, cores=False):
     """Labels of compact instances ((var_num, clause_num, signed_vars, clause_ids) as written to the lines) from the complete GPU solver
     (pdp.exact), all instances in a few launches: 1.0 satisfiable, 0.0 unsatisfiable, -1 undecided within the budget (the converter's
     "no label" value).  ``learn``: the search with conflict clause learning (the same labels).  ``certify``: (labels, proofs) from the
     certified search (exact.solve_items): an answer that is not certified is labelled -1, and proofs holds the DRAT lines of every
-    unsatisfiable instance (None for the others)."""
+    unsatisfiable instance (None for the others).  ``cores`` (with certify): (labels, proofs, cores) from the backward check -- proofs holds
+    the lemmas the refutation needs only, cores the 0-based indices of the clauses it rests on (None for the others)."""
     import numpy as np
     from pdp import exact
     items = []
@@ -117,31 +118,51 @@ def exact_labels(instances, budget=0, learn=False, certify=False):
         graph_map = np.stack((np.abs(sv) - 1, ci - 1)).astype(np.int32).reshape(2, -1)
         items.append((int(var_num), int(clause_num), graph_map, np.sign(sv).astype(np.float32), -1.0, []))
     if certify:
-        status, _, _, verdict, lemmas = exact.solve_items(items, budget=budget, certify=True, proofs=True)
+        out = exact.solve_items(items, budget=budget, certify=True, proofs=True, cores=cores)
+        status, verdict, lemmas = out[0], out[3], out[4]
         labels = [(1.0 if s == 1 else 0.0) if s != -1 and v == 1 else -1 for s, v in zip(status, verdict)]
-        return labels, [exact.drat_lines(l) if lab == 0.0 else None for lab, l in zip(labels, lemmas)]
+        proofs = [exact.drat_lines(l) if lab == 0.0 else None for lab, l in zip(labels, lemmas)]
+        return (labels, proofs, [c if lab == 0.0 else None for lab, c in zip(labels, out[5])]) if cores else (labels, proofs)
     status, _, _ = exact.solve_items(items, budget=budget, learn=learn)
     return [1.0 if s == 1 else (0.0 if s == 0 else -1) for s in status]
 
 
-def convert_directory(dimacs_dir, output_file, propagate=False, only_positive=False, label='name', budget=0, proof_dir=None):
+def core_cnf_lines(instance, core):
+    """The core of a compact instance ((var_num, clause_num, signed_vars, clause_ids) as written to its line; core: 0-based clause indices)
+    as DIMACS text, with the variable numbers of that line -- the ones the lemmas of its .drat use."""
+    var_num, _, signed_vars, clause_ids = instance
+    rows = {}
+    for l, c in zip(signed_vars, clause_ids):
+        rows.setdefault(int(c) - 1, []).append(int(l))
+    return ['p cnf %d %d' % (int(var_num), len(core))] + [' '.join([str(l) for l in rows.get(int(c), [])] + ['0']) for c in core]
+
+
+def convert_directory(dimacs_dir, output_file, propagate=False, only_positive=False, label='name', budget=0, proof_dir=None, core=False):
     """label 'name': the reference's rule (the last digit of the file stem, else -1); 'exact': the complete solver's answer for the
     instance the line holds (exact_labels), 'exact-learn': the same from the learning search, 'exact-certified': the same with every answer
     checked on the GPU (an answer that is not certified is labelled -1) and, with ``proof_dir``, one <file name>.drat per unsatisfiable
-    instance there.  Every other byte of a line is the same either way."""
+    instance there.  ``core`` (with 'exact-certified' and ``proof_dir``): the unsatisfiable answers are certified by the backward check;
+    <file name>.drat holds only the lemmas the refutation needs and a new <file name>.core.cnf the clauses it rests on, in the variable
+    numbering of the instance's line, so that the .drat is a proof of the .core.cnf alone.  Every other byte of a line is the same either way."""
+    if core and (label != 'exact-certified' or not proof_dir):
+        raise ValueError("core needs label 'exact-certified' and a proof_dir to write to")
     file_list = [os.path.join(dimacs_dir, f) for f in os.listdir(dimacs_dir) if os.path.isfile(os.path.join(dimacs_dir, f))]
     if label in ('exact', 'exact-learn', 'exact-certified'):
         paths = [p for p in file_list if os.path.splitext(p)[1].lower() in ('.dimacs', '.cnf')]
         instances = [compact_instance(p, propagate) for p in paths]
         labels = []
         if instances and label == 'exact-certified':
-            labels, proofs = exact_labels(instances, budget, certify=True)
+            out = exact_labels(instances, budget, certify=True, cores=core)
+            labels, proofs, cores = out if core else out + (None,)
             if proof_dir:
                 os.makedirs(proof_dir, exist_ok=True)
-                for path, lines in zip(paths, proofs):
+                for k, (path, lines) in enumerate(zip(paths, proofs)):
                     if lines is not None:
                         with open(os.path.join(proof_dir, os.path.split(path)[1] + '.drat'), 'w') as g:
                             g.write('\n'.join(lines) + '\n')
+                        if core:
+                            with open(os.path.join(proof_dir, os.path.split(path)[1] + '.core.cnf'), 'w') as g:
+                                g.write('\n'.join(core_cnf_lines(instances[k], cores[k])) + '\n')
         elif instances:
             labels = exact_labels(instances, budget, learn=label == 'exact-learn')
         with open(output_file, 'w') as f:
@@ -183,10 +204,17 @@ def cli_parser():
                              "on the GPU (pdp_exact_check), an answer that is not certified is labelled -1")
     parser.add_argument('--proof-dir', dest='proof_dir', default=None,
                         help="with --label exact-certified: write <file name>.drat (the learned clauses as DRAT text) per unsatisfiable instance here")
+    parser.add_argument('--core', action='store_true', default=False,
+                        help="with --label exact-certified --proof-dir: certify the unsatisfiable answers by the backward check (pdp_exact_trim); "
+                             "<file name>.drat holds only the lemmas the refutation needs and <file name>.core.cnf the clauses it rests on, in the "
+                             "compact variable numbering of the written line (unused variable ids of the input file are dropped), which the .drat uses")
     parser.add_argument('--budget', type=int, default=0, help="clause-literal reads per instance for --label exact / exact-learn (0: the library default)")
     return parser
 
 
 if __name__ == '__main__':
-    args = vars(cli_parser().parse_args())
-    convert_directory(args['in_dir'], args['out_file'], args['simplify'], args['positive'], args['label'], args['budget'], args['proof_dir'])
+    parser = cli_parser()
+    args = vars(parser.parse_args())
+    if args['core'] and (args['label'] != 'exact-certified' or not args['proof_dir']):
+        parser.error("--core writes the core next to the proof: give --label exact-certified and --proof-dir as well")
+    convert_directory(args['in_dir'], args['out_file'], args['simplify'], args['positive'], args['label'], args['budget'], args['proof_dir'], args['core'])

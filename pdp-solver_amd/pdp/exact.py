@@ -6,7 +6,9 @@ of choice" (src/pdp/generator.py:15-17).  This module fills that hook: ``label_c
 (unsatisfiable) or None (undecided within the budget of clause-literal reads per instance; 0 = the library default, 2^32).
 With ``certify=True`` every answer is checked on the GPU before it becomes a label: a model against the clauses, an "unsatisfiable" by a
 forward check of the learning search's learned clauses as a proof (pdp_exact_solve_learn_proof, pdp_exact_check; DESIGN.md §9.3);
-``drat_lines`` writes such a proof for an external checker.
+``drat_lines`` writes such a proof for an external checker.  With ``cores=True`` the "unsatisfiable" answers are judged by the backward
+check instead (pdp_exact_trim), which also says why: the core, the original clauses the refutation rests on, and the
+lemmas it needs (``core_clauses``, ``trimmed``).
 """
 
 import numpy as np
@@ -64,23 +66,66 @@ def drat_lines(lemmas):
     return lines + ['0']
 
 
-def _certified(prob, budget, hint, arena, names, proof_off=None):
+def trimmed(proof, proof_off, proof_len, keep):
+    """The kept lemmas of Problem.exact_trim, compacted on the device: (words int32, offsets int64 [B+1]) -- instance b's kept lemmas, in
+    order, are words[offsets[b] : offsets[b+1]], a complete proof in the format of ``proof``.  Only keep's bytes among the first
+    proof_len[b] words of a region count, and a proof_len outside its region counts as none.  Nothing here knows a verdict: the kernel
+    does not write the region of an instance it does not judge, so such an instance gets no words from the zeroed keep that exact_trim
+    allocates, and whatever equals 1 there from a buffer the caller passed in -- mask by verdict then."""
+    off = proof_off.reshape(-1).long()
+    total = proof.numel()
+    size = off[1:] - off[:-1]
+    plen = torch.where((proof_len >= 0) & (proof_len <= size), proof_len, torch.zeros_like(proof_len))
+    edge = torch.zeros(total + 1, dtype=torch.int64, device=proof.device)
+    one = torch.ones_like(plen)
+    edge.index_add_(0, off[:-1], one)
+    edge.index_add_(0, off[:-1] + plen, -one)
+    mask = (torch.cumsum(edge, 0)[:total] > 0) & (keep.reshape(-1) == 1)
+    count = torch.cat([torch.zeros(1, dtype=torch.int64, device=proof.device), torch.cumsum(mask, 0)])
+    return proof.reshape(-1)[mask], count[off]
+
+
+def core_clauses(core, clauses_per_instance):
+    "per instance the 0-based indices, in its own clause order, of its clauses with core = 1 (core: Problem.exact_trim's, one byte per clause)"
+    core = core.cpu().numpy() if torch.is_tensor(core) else np.asarray(core)
+    ends = np.cumsum(np.asarray(clauses_per_instance, dtype=np.int64))
+    return [np.nonzero(part)[0] for part in np.split(core[:ends[-1]] if len(ends) else core[:0], ends[:-1])]
+
+
+def _certified(prob, budget, hint, arena, names, proof_off=None, counts=None):
     """exact_solve_proof and exact_check of one problem: numpy (status, model, work, verdict, proof_len, region sizes, lemma lists of the
-    unsatisfiable instances whose proof is complete, None elsewhere).  A verdict 0 raises: the solver answered what its own evidence refutes."""
+    unsatisfiable instances whose proof is complete, None elsewhere, core index arrays likewise).  A verdict 0 raises: the solver answered
+    what its own evidence refutes.  ``counts`` (the clauses of every instance): the unsatisfiable instances are judged by exact_trim
+    instead, the lemmas are the ones it keeps and the cores are filled in; None: no cores."""
     st, model, wk, _, proof, off, plen = prob.exact_solve_proof(budget, hints=hint, arena=arena, proof_off=proof_off)
-    verdict, fail_at, _ = prob.exact_check(st, model, proof, off, plen)
+    cores = [None] * prob.B
+    if counts is None:
+        verdict, fail_at, _ = prob.exact_check(st, model, proof, off, plen)
+    else:
+        # the models go through the forward check (it does not judge a status -1), the proofs through the backward one
+        unsat = st == 0
+        verdict, fail_at, _ = prob.exact_check(torch.where(unsat, torch.full_like(st, -1), st), model, proof, off, plen)
+        tv, tf, _, core, keep, _, _ = prob.exact_trim(st, proof, off, plen)
+        verdict, fail_at = torch.where(unsat, tv, verdict), torch.where(unsat, tf, fail_at)
+        if proof is not None:
+            proof, toff = trimmed(proof, off, plen, keep)
+            toff = toff.cpu().numpy()
     st, model, wk, verdict, fail_at = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy(), verdict.cpu().numpy(), fail_at.cpu().numpy()
     off, plen = off.cpu().numpy(), plen.cpu().numpy()
+    if counts is not None:
+        cores = [c if st[j] == 0 and verdict[j] == 1 else None for j, c in enumerate(core_clauses(core, counts))]
     for j in np.nonzero(verdict == 0)[0]:
         raise RuntimeError("the complete solver's answer for instance %s (status %d) fails its own check at %s %d: a solver bug, no label is "
                            "written from it" % (names[j], st[j], 'clause' if st[j] == 1 else 'lemma', fail_at[j]))
     words = None if proof is None else proof.cpu().numpy()
-    lemmas = [proof_lemmas(words[off[j]:off[j] + plen[j]]) if st[j] == 0 and verdict[j] == 1 and plen[j] else ([] if st[j] == 0 and verdict[j] == 1 else None)
+    # where the lemmas of instance j lie: its region's first proof_len words, or, trimmed, its own run of the compacted words
+    a, z = (off[:-1], off[:-1] + plen) if counts is None or proof is None else (toff[:-1], toff[1:])
+    lemmas = [proof_lemmas(words[a[j]:z[j]]) if st[j] == 0 and verdict[j] == 1 and z[j] > a[j] else ([] if st[j] == 0 and verdict[j] == 1 else None)
               for j in range(len(st))]
-    return st, model, wk, verdict, plen, off[1:] - off[:-1], lemmas
+    return st, model, wk, verdict, plen, off[1:] - off[:-1], lemmas, cores
 
 
-def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0, certify=False, proofs=False):
+def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0, certify=False, proofs=False, cores=False):
     """Solve loader items ((n, m, graph_map, edge_feature, label, misc) tuples: dataset.instance_from_clauses, dataset.random_ksat_items,
     dataset.parse_line, raw_item).  Returns numpy (status int8 [N] in {1, 0, -1}, models: a float32 0/1 array of n_i values per instance,
     work int64 [N]).  Instances are packed into problems of at most ``max_edges`` edges; nothing couples two instances.
@@ -92,10 +137,16 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
     a model against the clauses, an "unsatisfiable" by a forward check of the learned clauses as a proof.  Also returns verdict int8 [N]:
     1 checked, -1 not (undecided).  An instance whose proof did not fit its region is solved once more with a region of the size it
     reported.  A refuted answer raises RuntimeError naming the instance.  ``proofs`` (with certify): also return, per instance, the lemmas
-    (lists of literal codes, see drat_lines) of a certified unsatisfiable instance and None for the others."""
+    (lists of literal codes, see drat_lines) of a certified unsatisfiable instance and None for the others.
+    ``cores`` (with certify): an "unsatisfiable" is judged by the backward check (pdp_exact_trim) in place of the forward one -- models
+    still go through pdp_exact_check.  Returns (status, models, work, verdict, lemmas, cores): per certified unsatisfiable instance the
+    lemmas the refutation needs (a proof against the core alone) and the 0-based indices of its core clauses, an unsatisfiable subset of
+    the instance; None for the others."""
     learn = learn or certify
     if proofs and not certify:
         raise ValueError("proofs belong to the certified search: pass certify=True")
+    if cores and not certify:
+        raise ValueError("cores belong to the certified search: pass certify=True")
     if arena and not learn:
         raise ValueError("arena belongs to the learning search: pass learn=True")
     native.require_gpu()
@@ -112,6 +163,7 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
     models = [None] * N
     verdict = np.full(N, -1, dtype=np.int8)
     lemmas = [None] * N
+    core = [None] * N
     for seg in _segments(items, max_edges):
         part = [items[i] for i in seg]
         if sum(int(it[2].shape[1]) for it in part) == 0:
@@ -120,6 +172,7 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
             for i, it in zip(seg, part):
                 status[i] = 1 if int(it[1]) == 0 else 0
                 verdict[i], lemmas[i] = 1, (None if status[i] else [])         # an empty clause is its own refutation
+                core[i] = np.zeros(1, dtype=np.int64) if cores and not status[i] else None
                 models[i] = np.zeros(int(it[0]), dtype=np.float32)
                 h = None if hints is None or hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
                 if status[i] == 1 and h is not None and not np.isnan(h).any():
@@ -135,7 +188,8 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
                 hint = torch.from_numpy(np.concatenate(flat)).to(device)
             if certify:
                 names = ['%d (%s)' % (i, ' '.join(str(x) for x in it[5])) if it[5] else str(i) for i, it in zip(seg, part)]
-                st, model, wk, vd, plen, size, lem = _certified(prob, budget, hint, arena, names)
+                counts = [int(it[1]) for it in part] if cores else None
+                st, model, wk, vd, plen, size, lem, cor = _certified(prob, budget, hint, arena, names, counts=counts)
                 again = [j for j in range(len(part)) if st[j] != -1 and plen[j] > size[j]]
                 if again:
                     # the proof did not fit: the same search once more, in a batch of its own, with regions of exactly proof_len words
@@ -144,11 +198,12 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
                     voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
                     hint2 = None if hint is None else torch.cat([hint[voff[j]:voff[j + 1]] for j in again])
                     off2 = torch.from_numpy(np.concatenate([[0], np.cumsum(plen[again])]).astype(np.int64)).to(device)
-                    r = _certified(prob, budget, hint2, arena, [names[j] for j in again], proof_off=off2)
+                    r = _certified(prob, budget, hint2, arena, [names[j] for j in again], proof_off=off2,
+                                   counts=[counts[j] for j in again] if cores else None)
                     for k, j in enumerate(again):
-                        vd[j], lem[j] = r[3][k], r[6][k]
+                        vd[j], lem[j], cor[j] = r[3][k], r[6][k], r[7][k]
                 for j, i in enumerate(seg):
-                    verdict[i], lemmas[i] = vd[j], lem[j]
+                    verdict[i], lemmas[i], core[i] = vd[j], lem[j], cor[j]
             else:
                 st, model, wk = prob.exact_solve(budget, hints=hint, learn=learn, arena=arena)
                 st, model, wk = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
@@ -159,6 +214,8 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
             status[i], work[i] = st[j], wk[j]
             models[i] = model[off:off + n].copy()
             off += n
+    if cores:
+        return status, models, work, verdict, lemmas, core
     if certify:
         return (status, models, work, verdict, lemmas) if proofs else (status, models, work, verdict)
     return status, models, work

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = [
     'pdp_sat_loss_grad', 'pdp_train_sp_adapted_backward',
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
-    'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_last_grid',
+    'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid',
 ]
 
 
@@ -525,8 +525,43 @@ class Problem(object):
                                     ptr(proof_len.reshape(-1).contiguous()), C.c_int64(int(budget)), ptr(verdict), ptr(fail_at), ptr(work), _stream()))
         return verdict, fail_at, work
 
+    def exact_trim(self, status, proof, proof_off, proof_len, budget=0, keep=None):
+        """The backward check of the proofs of the status-0 instances (pdp_exact_trim): (verdict int8 [B], fail_at int32 [B], work int64 [B],
+        core int8 [F], keep int8 of proof's size, n_core int32 [B], n_keep int32 [B]).  From the empty clause backwards only the lemmas that
+        are needed are checked, each by unit propagation from the clauses and the lemmas before it.  Verdict 1: core[c] = 1 on the original
+        clauses the refutation rests on (they are unsatisfiable on their own) and keep = 1 on every word of a needed lemma (the kept lemmas
+        are a proof against the core alone; exact.trimmed compacts them).  Verdict 0: fail_at = the first malformed lemma, else the needed
+        lemma that does not follow; verdict -1: a status other than 0, an incomplete proof (proof_len[b] past the region) or ``budget``
+        clause-literal reads spent; core and keep are then 0.  keep is allocated at proof's size (``keep``: an int8 buffer of that size to
+        write into instead); its words past proof_len[b] in a region, and the regions of instances that are not judged, are not written:
+        0 in the buffer allocated here, whatever they held in a buffer that was passed in.  ``proof`` None: every region must be empty, keep is None."""
+        for name, t, dt, k in (('status', status, torch.int8, self.B), ('proof_len', proof_len, torch.int64, self.B)):
+            if not torch.is_tensor(t) or t.dtype != dt or t.numel() != k:
+                raise ValueError("%s must be a %s tensor of %d elements, got %s"
+                                 % (name, dt, k, '%s of %d' % (t.dtype, t.numel()) if torch.is_tensor(t) else type(t).__name__))
+        proof_off, host = self._proof_regions(proof_off, proof)
+        if proof is None and int(host[-1]) > int(host[0]):
+            raise ValueError("proof is None but the regions hold %d words" % (int(host[-1]) - int(host[0])))
+        if proof is not None and (not proof.is_cuda or not proof.is_contiguous()):
+            raise ValueError("proof must be a contiguous tensor on the problem's device")
+        verdict = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        fail_at = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        core = torch.empty(self.F, dtype=torch.int8, device=self.device)
+        if keep is not None and (proof is None or not torch.is_tensor(keep) or keep.dtype != torch.int8 or keep.numel() != proof.numel()
+                                 or not keep.is_cuda or not keep.is_contiguous()):
+            raise ValueError("keep must be a contiguous int8 tensor of proof's size on the problem's device")
+        if keep is None and proof is not None:
+            keep = torch.zeros(proof.numel(), dtype=torch.int8, device=self.device)
+        n_core = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        n_keep = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        check(lib().pdp_exact_trim(self._h, ptr(status.reshape(-1).contiguous().to(self.device)), ptr(proof_off), ptr(proof),
+                                   ptr(proof_len.reshape(-1).contiguous().to(self.device)), C.c_int64(int(budget)), ptr(verdict), ptr(fail_at),
+                                   ptr(work), ptr(core), ptr(keep), ptr(n_core), ptr(n_keep), _stream()))
+        return verdict, fail_at, work, core, keep, n_core, n_keep
+
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_proof or exact_check on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

@@ -144,7 +144,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         """The rows of ``_post_process_predictions`` completed by the exact search (satyr.py --complete): the prediction is the phase hint of
         pdp_exact_solve_hinted on the unreplicated instances of the forward.  Every row gains "complete" (1 satisfiable, 0 unsatisfiable, -1
         undecided within config['complete_budget'] clause-literal reads), "pdp_solved" (what "solved" is without the search) and "work" (the
-        reads of the search); with config['complete_certify'] also "certified" (1: the answer passed pdp_exact_check, -1: undecided).  A satisfiable row gets solved 1, unsat_clauses 0 and the search's model -- PDP's own assignment where PDP had
+        reads of the search); with config['complete_certify'] also "certified" (1: the answer passed pdp_exact_check, -1: undecided), and with config['complete_core'] an
+        unsatisfiable row also "core", the 0-based indices (in the instance's clause order) of the clauses its refutation rests on.  A satisfiable row gets solved 1, unsat_clauses 0 and the search's model -- PDP's own assignment where PDP had
         solved the instance, because the check pass accepts it; every other row keeps its five reference keys."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
@@ -162,10 +163,14 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             # logged once more into regions of the size the first run reported; a refuted answer raises
             from pdp import exact
             names = ['%d (%s)' % (i, row['ID']) for i, row in enumerate(rows)]
-            status, solution, work, certified, plen, size, _ = exact._certified(handle, budget, hint, 0, names)
+            # config['complete_core']: the unsatisfiable answers are judged by the backward check (pdp_exact_trim), which also names the core
+            counts = None
+            if self._config.get('complete_core'):
+                counts = torch.bincount(handle.export_graph()[2].long(), minlength=handle.B)[:handle.B].cpu().numpy()
+            status, solution, work, certified, plen, size, _, cores = exact._certified(handle, budget, hint, 0, names, counts=counts)
             if ((status != -1) & (plen > size)).any():
                 off = torch.from_numpy(np.concatenate([[0], np.cumsum(plen)]).astype(np.int64)).to(hint.device)
-                status, solution, work, certified, _, _, _ = exact._certified(handle, budget, hint, 0, names, proof_off=off)
+                status, solution, work, certified, _, _, _, cores = exact._certified(handle, budget, hint, 0, names, proof_off=off, counts=counts)
             solution = solution.astype(int)
         else:
             status, solution, work = handle.exact_solve(budget, hints=hint, learn=bool(self._config.get('complete_learn')))
@@ -175,6 +180,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             row['complete'], row['pdp_solved'], row['work'] = int(status[i]), row['solved'], int(work[i])
             if certified is not None:
                 row['certified'] = int(certified[i])
+                if cores[i] is not None:
+                    row['core'] = [int(c) for c in cores[i]]
             if status[i] == 1:
                 row['solved'], row['unsat_clauses'], row['solution'] = 1, 0, solution[offs[i]:offs[i + 1]].tolist()
         if hasattr(self, '_complete_stats'):

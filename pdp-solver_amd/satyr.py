@@ -9,7 +9,8 @@ is then decided by the batched exact search with the model's assignment as its p
 "complete" (1 satisfiable, 0 unsatisfiable, -1 undecided within the budget), "pdp_solved" and "work"; ``--complete-learn`` gives that search
 conflict clause learning (pdp_exact_solve_learn); ``--complete-certify`` (implies ``--complete-learn``) has every answer checked on the GPU -- a
 model against the clauses, an "unsatisfiable" by a forward check of the learned clauses as a proof (pdp_exact_check) -- and a row gains
-"certified" (1 checked, -1 undecided).
+"certified" (1 checked, -1 undecided); ``--complete-core`` (with ``--complete-certify``) judges an "unsatisfiable" by the backward check
+(pdp_exact_trim) and such a row gains "core", the 0-based indices of the clauses its refutation rests on.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -103,6 +104,9 @@ def main(argv=None):
     parser.add_argument('--complete-certify', dest='complete_certify', help='With --complete: the learning search logs its learned clauses as a proof and '
                         'every answer is checked on the GPU (pdp_exact_check); implies --complete-learn; rows gain "certified" (1 checked, -1 undecided)',
                         action='store_true')
+    parser.add_argument('--complete-core', dest='complete_core', help='With --complete --complete-certify: an "unsatisfiable" is certified by the backward '
+                        'check of its proof (pdp_exact_trim) and its row gains "core": the 0-based indices, in the instance\'s clause order, of an '
+                        'unsatisfiable subset of its clauses', action='store_true')
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -111,6 +115,8 @@ def main(argv=None):
         parser.error("--complete-learn selects the search of --complete: give --complete as well")
     if args['complete_certify'] and not args['complete']:
         parser.error("--complete-certify checks the answers of --complete: give --complete as well")
+    if args['complete_core'] and not args['complete_certify']:
+        parser.error("--complete-core names the core of a certified answer: give --complete-certify as well")
     if args['complete_certify']:
         args['complete_learn'] = True
 

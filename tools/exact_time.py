@@ -17,7 +17,12 @@ default arena, ``m100`` / ``m200`` = the reference's community-attachment family
 Proof rows (pdp_exact_solve_learn_proof and pdp_exact_check; never part of the default): ``pa`` / ``pd`` / ``pm100`` / ``pm200`` = rows (a), (d),
 m100 and m200: kernel time of the learning search without and with the lemma log on the same problem, the check kernel on that call's
 outputs with its verdicts and reads, and the proof words per instance (median / p99 / max) with the largest number of words per literal
-of an instance and, per region factor k, the instances whose proof a region of k words per literal would truncate."""
+of an instance and, per region factor k, the instances whose proof a region of k words per literal would truncate.
+
+Trim rows (pdp_exact_trim; never part of the default): ``ta`` / ``td`` / ``tm100`` / ``tm200`` = the problems and proofs of pa, pd, pm100 and pm200:
+the backward check next to the forward check of the same proofs on the same problem (the forward check once on every answer, once on the
+unsatisfiable ones alone; the kernels alternate, TRIM_REPEATS timed calls each, the median is reported), the core size over the clause count
+(median / p99 / max over the unsatisfiable instances), kept over logged lemmas and the reads of the two checks."""
 import io
 import json
 import logging
@@ -203,6 +208,48 @@ def run_proof(key):
     assert not (verdict == 0).any(), "a solver answer failed its check"
 
 
+TRIM_REPEATS = 5
+
+
+def run_trim(key):
+    "the backward check next to the forward check of the same proofs, all on one problem; the two kernels alternate"
+    modular = key[1:] in MODULAR
+    title, make = MODULAR[key[1:]] if modular else ROWS[key[1:]]
+    budget = MODULAR_BUDGET if modular else 0
+    items = make()
+    b = dataset.to_torch(dataset.collate_segment(items), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(items))
+    st, model, wk, ln, proof, off, plen = p.exact_solve_proof(budget)
+    proofs_only = torch.where(st == 0, st, torch.full_like(st, -1))
+    calls = {'check': lambda: p.exact_check(st, model, proof, off, plen), 'check-unsat': lambda: p.exact_check(proofs_only, model, proof, off, plen),
+             'trim': lambda: p.exact_trim(st, proof, off, plen)}
+    ms, out = {k: [] for k in calls}, {}
+    for k in calls:
+        calls[k]()                                                                   # the one-time routing preparation is not timed
+    for _ in range(TRIM_REPEATS):
+        for k in calls:
+            t, out[k] = _event_ms(calls[k])
+            ms[k].append(t)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    status, learned = st.cpu().numpy(), ln.cpu().numpy()
+    cv, cwk = out['check-unsat'][0].cpu().numpy(), out['check-unsat'][2].cpu().numpy()
+    tv, _, twk, core, keep, n_core, n_keep = [None if t is None else t.cpu().numpy() for t in out['trim']]
+    unsat = status == 0
+    assert np.array_equal(cv[unsat], out['check'][0].cpu().numpy()[unsat]) and not (cv == 0).any() and not (tv == 0).any(), "a solver answer failed its check"
+    assert np.array_equal(tv == 1, cv == 1), "the two checks judge different instances"
+    clauses = torch.bincount(p.export_graph()[2].long(), minlength=p.B)[:p.B].cpu().numpy()
+    frac = n_core[unsat] / np.maximum(clauses[unsat], 1)
+    print("(%s) %s: E=%d  UNSAT %d  forward check of every answer %.2f ms, of the proofs alone %.2f ms, backward check (trim) %.2f ms (%.3f of the "
+          "forward check of the proofs; %d alternated calls each, min / max: check %.2f / %.2f, trim %.2f / %.2f)"
+          % (key, title, p.E, int(unsat.sum()), med['check'], med['check-unsat'], med['trim'], med['trim'] / med['check-unsat'], TRIM_REPEATS,
+             min(ms['check-unsat']), max(ms['check-unsat']), min(ms['trim']), max(ms['trim'])), flush=True)
+    print("    core / clauses over the unsatisfiable: median %.3f  p99 %.3f  max %.3f (clauses: median %d, core: median %d)  lemmas kept / logged: %d / %d "
+          "(%.3f)  reads: trim %d, forward check %d (ratio %.3f)"
+          % (float(np.median(frac)), float(np.percentile(frac, 99)), float(frac.max()), int(np.median(clauses[unsat])), int(np.median(n_core[unsat])),
+             int(n_keep[unsat].sum()), int(learned[unsat].sum()), float(n_keep[unsat].sum()) / max(1.0, float(learned[unsat].sum())),
+             int(twk[unsat].sum()), int(cwk[unsat].sum()), float(twk[unsat].sum()) / max(1.0, float(cwk[unsat].sum()))), flush=True)
+
+
 def _write_json(items, path):
     from pdp import generator
     with open(path, 'w') as f:
@@ -282,4 +329,4 @@ def run_wall(key):
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
-        {'h': run_hinted, 'w': run_wall, 'l': run_learn, 'm': run_learn, 'p': run_proof}.get(k[0], run)(k)
+        {'h': run_hinted, 'w': run_wall, 'l': run_learn, 'm': run_learn, 'p': run_proof, 't': run_trim}.get(k[0], run)(k)
