@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -336,8 +336,48 @@ int pdp_exact_trim(pdp_problem *p, const int8_t *status, const int64_t *proof_of
                    int64_t budget, int8_t *verdict, int32_t *fail_at, int64_t *work,
                    int8_t *core, int8_t *keep, int32_t *n_core, int32_t *n_keep, void *stream);
 
+/* pdp_exact_solve_learn under assumptions: is the instance satisfiable with these literals held fixed, and if not, which of them are to
+ * blame (plain Python: tests/exact_assume_model.py).  assume [V] (may be NULL = all zero), one int8 per variable in the problem's variable
+ * order: > 0 the variable is assumed true, < 0 assumed false, 0 not assumed.  failed [V] (may be NULL): 1 on the variables of the failed
+ * set of a status-0 instance, 0 everywhere else.  The other arguments are pdp_exact_solve_learn's, and pdp_exact_learn_reductions reports
+ * this call's reductions as well.  The search of one instance is pdp_exact_solve_learn's, with these additions for an instance that has
+ * at least one assumed variable:
+ *   1. Effective code.  The hint code of an assumed variable is the assumption's polarity, whatever hint[v] says, and everything that reads
+ *      the code reads this one: the check pass runs iff no variable is left without a code, the assignment it tests agrees with every
+ *      assumption, and a check pass that accepts is a correct status 1.
+ *   2. The assumption level.  Level 1 belongs to the assumptions.  It is opened when a pass at level 0 ends with no conflict and no unit
+ *      request (the fixed point of level 0), before the "no open clause" test and before any branching scan: level = 1, mark[1] = the trail
+ *      length, and the assumed variables are visited in ascending index.  An unassigned one gets its assumed value at level 1 with no
+ *      reason and enters the trail (in ascending order); one that level 0 assigned to its assumed value is skipped; if level 0 assigned any
+ *      to the opposite value the instance ends with status 0 and failed = {the lowest such variable}.  Opening reads no clause literal, so
+ *      work does not move; the loop goes on with the next budget check and pass.  Search decisions therefore start at level 2.  A backjump
+ *      to level 0 (a learned clause with no literal above level 0) undoes level 1 like any other level, and the level is opened again at
+ *      the next fixed point of level 0.
+ *   3. Conflict at level 1: status 0, "unsatisfiable under the assumptions", after the final analysis.  It starts from the conflict clause
+ *      and walks the trail backwards like the first-UIP analysis, but down to mark[1] and without stopping at a UIP: a seen level-1
+ *      variable with a reason is resolved with it, a seen level-1 variable without a reason is an assumption and goes into failed, level-0
+ *      variables are dropped.  work grows by the length of the conflict clause and of every reason resolved with.  No clause is learned
+ *      from it and learned does not count it.  A conflict at level 0 stays status 0 with an empty failed: the formula is unsatisfiable on
+ *      its own.
+ *   4. First-UIP analysis at levels >= 2 is unchanged.  Level-1 literals are "a lower level above 0", so they enter the learned clause:
+ *      every learned clause follows from the formula alone, never from the assumptions (the certificate of a status 0 under assumptions
+ *      relies on that: the instance plus its failed assumptions as unit clauses goes through pdp_exact_solve_learn_proof as it stands).
+ *   5. The budget check, the arena rule and work < budget + 4 * (e + arena) are unchanged: the final analysis reads every live literal at
+ *      most once and takes the place of a first-UIP analysis in its iteration.  model of a status-1 instance satisfies every clause and
+ *      every assumption.  All six outputs are a function of the instance, its hints, its assumptions, the budget and the arena size alone.
+ *   6. An instance with no assumed variable (or assume == NULL) gets pdp_exact_solve_learn's five outputs exactly, and an all-zero failed.
+ * Consequences:
+ *   A1  item 6.
+ *   A2  a status-1 model agrees with the assumptions.
+ *   A3  failed is a subset of the assumed variables, and the instance plus the failed assumptions as unit clauses is unsatisfiable.
+ *   A4  a decided status equals the status of the instance with all assumptions appended as unit clauses.
+ *   A5  assuming every variable at the value of a model gives status 1 with that model from the check pass, and work = that pass's reads.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules; routing, working arrays and arenas are pdp_exact_solve_learn's, shared with it. */
+int pdp_exact_solve_learn_assume(pdp_problem *p, const float *hint, const int8_t *assume, int64_t budget, int64_t arena,
+                                 int8_t *status, float *model, int64_t *work, int32_t *learned, int8_t *failed, void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an
  * integer v >= 1 and is ignored otherwise (unset, empty, 0, negative, not a number) -- a test switch that makes a wave run many

@@ -429,6 +429,7 @@ int ex_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status,
 // the variable / clause it holds, and every reduction is a sum, a minimum or a maximum: the outputs do not depend on lane order.
 constexpr uint32_t EXL_NONE = 0xffffffffu;
 constexpr uint32_t EXL_SEEN = 4u, EXL_OUT = 8u;  // pend[v]: met by the analysis / goes into the learned clause (a level below the current one)
+constexpr uint32_t EXL_ASSUMED = 16u, EXL_FAILED = 32u;     // pend[v], ASSUME only: v is assumed (its hint code is the assumption) / is in the failed set
 constexpr int EXL_INF = 0x7fffffff;
 constexpr int64_t EXL_MAX_ARENA = (int64_t)1 << 30;
 
@@ -484,6 +485,9 @@ struct ExlParams {
     const int64_t *proof_off;   // [B+1] by instance id: its region is proof[proof_off[b] .. proof_off[b+1])
     int32_t *proof;             // NULL: nothing is written, the words are only counted
     int64_t *proof_len;         // [B] words the instance's lemmas need
+    // the assumptions, read by k_exact_learn<.., .., true> only; behind the proof fields, so every field above keeps its offset
+    const int8_t *assume;       // [V] > 0 assumed true, < 0 assumed false, 0 not assumed (NULL: none)
+    int8_t *failed;             // [V] 1 on the failed set of a status-0 instance, 0 elsewhere (NULL: not wanted)
 };
 
 // the region of one instance: base pointer (NULL: count only) and size in words
@@ -562,9 +566,12 @@ __device__ void exl_reduce(const ExlInst<LitT, PtrT> &X, int tlen, int &nl, int 
 // fit the arena even after a reduction.  *learned_out = clauses learned (also the deleted ones), *reductions_out = arena reductions.
 // PROOF: every clause that is stored in the arena is also appended to the instance's region G (len, then the literals in the arena's order,
 // as int32 words) while whole lemmas fit, and *plen_out = the words all of them need.  Logging reads nothing the search reads later.
-template <bool HBM, bool HINT, bool PROOF, typename LitT, typename PtrT>
-__device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, bool check, int64_t *work_out, int *learned_out, int *reductions_out,
-                               const ExlLog &G, int64_t *plen_out)
+// ASSUME: `assumed` (wave-uniform: the instance has an assumed variable, EXL_ASSUMED in pend[v], its polarity in the hint code) gives
+// level 1 to the assumptions: opened at every fixed point of level 0, and a conflict there ends the search with the final analysis, which
+// raises EXL_FAILED on the assumptions the conflict rests on.  Without `assumed` nothing below differs from ASSUME = false.
+template <bool HBM, bool HINT, bool PROOF, bool ASSUME, typename LitT, typename PtrT>
+__device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, bool check, [[maybe_unused]] bool assumed, int64_t *work_out,
+                               int *learned_out, int *reductions_out, const ExlLog &G, int64_t *plen_out)
 {
     const int lane = (int)threadIdx.x;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -653,6 +660,40 @@ __device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, boo
         }
         if (confl != EXL_INF) {
             if (level == 0) { result = 0; break; }
+            if constexpr (ASSUME) {
+                if (assumed && level == 1) {
+                    // ---- final analysis: unsatisfiable under the assumptions.  The walk of the first-UIP analysis down to mark[1]: a seen
+                    // variable with a reason is resolved with it, one without is an assumption of the failed set; nothing is learned
+                    const int from = X.mark[1];
+                    int i = tlen - 1, c = confl;
+                    for (;;) {
+                        int len;
+                        const LitT *p = exl_span(X, c, len);
+                        work += len;
+                        for (int k = lane; k < len; k += EX_NT) {
+                            const int v = (int)(p[k] >> 1);
+                            if (X.lev[v] == 1) atomicOr(&X.pend[v], EXL_SEEN);          // every literal is assigned; level 0 is dropped
+                        }
+                        ex_sync<HBM>();
+                        int next = -1;
+                        while (i >= from) {
+                            const int idx = i - lane;
+                            const unsigned long long mask = __ballot(idx >= from && (X.pend[X.trail[idx >= from ? idx : from]] & EXL_SEEN) != 0u);
+                            if (!mask) { i -= EX_NT; continue; }
+                            const int pos = i - (__ffsll((long long)mask) - 1);
+                            const int u = X.trail[pos];
+                            const uint32_t r = X.rsn[u];
+                            i = pos - 1;
+                            if (r != EXL_NONE) { next = (int)r; break; }
+                            if (lane == 0) atomicOr(&X.pend[u], EXL_FAILED);
+                        }
+                        if (next < 0) break;
+                        c = next;
+                    }
+                    result = 0;
+                    break;
+                }
+            }
             // ---- first-UIP analysis: a clause's literals across the lanes, the next seen trail entry by a ballot over 64 slots
             int open = 0, nout = 0, bl = 0, i = tlen - 1, uip = -1, c = confl;
             bool bad = false;
@@ -725,6 +766,38 @@ __device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, boo
             continue;
         }
         if (any_unit) continue;
+        if constexpr (ASSUME) {
+            if (assumed && level == 0) {
+                // ---- the fixed point of level 0: level 1 takes the assumptions, ascending, with ballot-prefix trail slots like a pass's units
+                level = 1;
+                ex_sync<HBM>();                                     // every lane has read the pass's val before it is written
+                if (lane == 0) X.mark[1] = tlen;
+                int opp = EXL_INF;
+                for (int base = 0; base < X.n; base += EX_NT) {
+                    const int v = base + lane;
+                    const uint32_t word = v < X.n ? X.pend[v] : 0u;
+                    const bool as = (word & EXL_ASSUMED) != 0u;
+                    const uint32_t want = (word >> EX_HINT_SHIFT) & 3u, x = as ? (uint32_t)X.val[v] : 0u;
+                    const bool take = as && x == 0u;
+                    if (as && x != 0u && x != want) opp = v < opp ? v : opp;
+                    const unsigned long long mask = __ballot(take);
+                    if (take) {
+                        X.val[v] = (uint8_t)want; X.lev[v] = 1; X.rsn[v] = EXL_NONE;
+                        X.trail[tlen + __popcll(mask & below)] = v;
+                    }
+                    tlen += __popcll(mask);
+                }
+                opp = ex_min(opp);
+                if (opp != EXL_INF) {
+                    // level 0 holds the opposite of an assumption: the lowest such variable is the failed set
+                    if (lane == 0) atomicOr(&X.pend[opp], EXL_FAILED);
+                    result = 0;
+                    break;
+                }
+                ex_sync<HBM>();
+                continue;
+            }
+        }
         wmin = ex_min(wmin);
         if (wmin == EXL_INF) { result = 1; break; }
         // ---- branching: as ex_search, over the learned clauses too
@@ -782,7 +855,7 @@ __device__ int ex_search_learn(const ExlInst<LitT, PtrT> &X, int64_t budget, boo
     return result;
 }
 
-template <bool HBM, bool HINT, bool PROOF, typename LitT, typename PtrT>
+template <bool HBM, bool HINT, bool PROOF, bool ASSUME, typename LitT, typename PtrT>
 __device__ void ex_solve_learn(const ExlParams &xp, const Inst &I, ExlInst<LitT, PtrT> X, PtrT *cptr_fill)
 {
     const int lane = (int)threadIdx.x;
@@ -791,17 +864,30 @@ __device__ void ex_solve_learn(const ExlParams &xp, const Inst &I, ExlInst<LitT,
         const int ed = I.f_edges[k];
         X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
     }
-    int none = !HINT || xp.hint == nullptr;
+    int none = !ASSUME && (!HINT || xp.hint == nullptr);
+    [[maybe_unused]] int any = 0;
     for (int v = lane; v < I.n; v += EX_NT) {
         uint32_t code = 0u;
         if constexpr (HINT) {
             if (xp.hint) { const float h = xp.hint[I.v0 + v]; code = h != h ? 0u : (h > 0.5f ? 1u : 2u); }
         }
+        uint32_t bits = 0u;
+        if constexpr (ASSUME) {
+            // the effective code of an assumed variable is the assumption's polarity, whatever its hint says
+            const int a = xp.assume ? (int)xp.assume[I.v0 + v] : 0;
+            if (a) { code = a > 0 ? 1u : 2u; bits = EXL_ASSUMED; any = 1; }
+        }
         none |= code == 0u;
-        X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        X.val[v] = 0; X.pend[v] = (code << EX_HINT_SHIFT) | bits; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
         X.req[2 * v] = EXL_NONE; X.req[2 * v + 1] = EXL_NONE;
     }
-    const bool check = HINT && __ballot(none) == 0ull;
+    bool check = HINT && __ballot(none) == 0ull;
+    bool assumed = false;
+    if constexpr (ASSUME) {
+        // with no hint array the check pass needs an assumption: an instance without one is pdp_exact_solve_learn's with hint == NULL
+        assumed = __ballot(any) != 0ull;
+        check = check && (xp.hint != nullptr || assumed);
+    }
     ex_sync<HBM>();
     int64_t work = 0;
     int learned = 0, reductions = 0;
@@ -811,8 +897,14 @@ __device__ void ex_solve_learn(const ExlParams &xp, const Inst &I, ExlInst<LitT,
         const int64_t a = xp.proof_off[I.b], z = xp.proof_off[I.b + 1];
         if (xp.proof && z > a) { G.words = xp.proof + a; G.cap = z - a; }
     }
-    const int st = ex_search_learn<HBM, HINT, PROOF>(X, xp.budget, check, &work, &learned, &reductions, G, &plen);
+    const int st = ex_search_learn<HBM, HINT, PROOF, ASSUME>(X, xp.budget, check, assumed, &work, &learned, &reductions, G, &plen);
     for (int v = lane; v < I.n; v += EX_NT) xp.model[I.v0 + v] = (st == 1 && X.val[v] == 1) ? 1.0f : 0.0f;
+    if constexpr (ASSUME) {
+        if (xp.failed) {
+            ex_sync<HBM>();                                         // the failed bits were raised by single lanes
+            for (int v = lane; v < I.n; v += EX_NT) xp.failed[I.v0 + v] = (st == 0 && (X.pend[v] & EXL_FAILED) != 0u) ? 1 : 0;
+        }
+    }
     if (lane == 0) {
         xp.status[I.b] = (int8_t)st;
         if (xp.work) xp.work[I.b] = work;
@@ -823,7 +915,7 @@ __device__ void ex_solve_learn(const ExlParams &xp, const Inst &I, ExlInst<LitT,
     ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
 }
 
-template <bool HINT, bool PROOF>
+template <bool HINT, bool PROOF, bool ASSUME>
 __global__ void __launch_bounds__(EX_NT) k_exact_learn(PView pv, ExlParams xp)
 {
     extern __shared__ __align__(16) unsigned char exl_slab[];
@@ -840,7 +932,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact_learn(PView pv, ExlParams xp)
             X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.req = xp.h_req + 2 * (size_t)I.v0;
             X.rsn = xp.h_rsn + I.v0; X.trail = xp.h_trail + I.v0; X.mark = xp.h_mark + I.v0 + I.b; X.lev = xp.h_lev + I.v0;
             X.n = I.n; X.m = I.m; X.e = I.e; X.A = A;
-            ex_solve_learn<true, HINT, PROOF, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
+            ex_solve_learn<true, HINT, PROOF, ASSUME, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
         } else {
             const ExlLds L = exl_lds_layout(I.n, I.m, I.e, A);
             ExlInst<uint16_t, uint16_t> X;
@@ -849,7 +941,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact_learn(PView pv, ExlParams xp)
             X.req = (uint32_t *)(exl_slab + L.req); X.rsn = (uint32_t *)(exl_slab + L.rsn); X.trail = (int32_t *)(exl_slab + L.trail);
             X.mark = (int32_t *)(exl_slab + L.mark); X.lev = (int32_t *)(exl_slab + L.lev);
             X.n = I.n; X.m = I.m; X.e = I.e; X.A = A;
-            ex_solve_learn<false, HINT, PROOF, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(exl_slab + L.cptr));
+            ex_solve_learn<false, HINT, PROOF, ASSUME, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(exl_slab + L.cptr));
         }
     }
 }
@@ -897,9 +989,9 @@ int exl_prepare(pdp_problem *p, int64_t arena)
     return PDP_OK;
 }
 
-template <bool HINT, bool PROOF>
+template <bool HINT, bool PROOF, bool ASSUME = false>
 int exl_launch(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work, int32_t *learned,
-               const int64_t *proof_off, int32_t *proof, int64_t *proof_len, void *stream)
+               const int64_t *proof_off, int32_t *proof, int64_t *proof_len, void *stream, const int8_t *assume = nullptr, int8_t *failed = nullptr)
 {
     { const int st_ = exl_prepare(p, arena); if (st_ != PDP_OK) return st_; }
     const hipStream_t st = ST(stream);
@@ -911,6 +1003,7 @@ int exl_launch(pdp_problem *p, const float *hint, int64_t budget, int64_t arena,
     xp.arena = arena;
     xp.status = status; xp.model = model; xp.work = work; xp.learned = learned; xp.hint = hint;
     xp.proof_off = proof_off; xp.proof = proof; xp.proof_len = proof_len;
+    xp.assume = assume; xp.failed = failed;
     xp.h_aoff = (const int64_t *)(p->exl_blob + head);
     xp.reductions = (int32_t *)(p->exl_blob + head + B * 8);
     xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_req = nullptr; xp.h_rsn = nullptr; xp.h_trail = nullptr; xp.h_lev = nullptr;
@@ -930,10 +1023,10 @@ int exl_launch(pdp_problem *p, const float *hint, int64_t budget, int64_t arena,
     }
     const int lds = (int)p->exl_lds_bytes;
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_learn<HINT, PROOF>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_learn<HINT, PROOF, ASSUME>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
     PDP_HIP_CHECK(hipMemsetAsync(xp.next, 0, 4, st));
-    hipLaunchKernelGGL((k_exact_learn<HINT, PROOF>), dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    hipLaunchKernelGGL((k_exact_learn<HINT, PROOF, ASSUME>), dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
     p->ex_last_grid = (int32_t)grid;
     return PDP_OK;
@@ -1667,6 +1760,19 @@ extern "C" int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t 
     }
     return hint ? exl_launch<true, false>(p, hint, budget, arena, status, model, work, learned, nullptr, nullptr, nullptr, stream)
                 : exl_launch<false, false>(p, nullptr, budget, arena, status, model, work, learned, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int pdp_exact_solve_learn_assume(pdp_problem *p, const float *hint, const int8_t *assume, int64_t budget, int64_t arena, int8_t *status,
+                                            float *model, int64_t *work, int32_t *learned, int8_t *failed, void *stream)
+{
+    PDP_REQUIRE(p && status && model, "NULL argument");
+    PDP_REQUIRE(arena >= 0 && arena <= EXL_MAX_ARENA, "pdp_exact_solve_learn_assume: arena must be 0 (four words per literal) or 1 .. 2^30 words");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_solve_learn_assume: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    // one instantiation: a NULL hint is "all NaN" there
+    return exl_launch<true, false, true>(p, hint, budget, arena, status, model, work, learned, nullptr, nullptr, nullptr, stream, assume, failed);
 }
 
 extern "C" int pdp_exact_solve_learn_proof(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model,

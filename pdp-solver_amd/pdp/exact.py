@@ -8,7 +8,9 @@ With ``certify=True`` every answer is checked on the GPU before it becomes a lab
 forward check of the learning search's learned clauses as a proof (pdp_exact_solve_learn_proof, pdp_exact_check; DESIGN.md §9.3);
 ``drat_lines`` writes such a proof for an external checker.  With ``cores=True`` the "unsatisfiable" answers are judged by the backward
 check instead (pdp_exact_trim), which also says why: the core, the original clauses the refutation rests on, and the
-lemmas it needs (``core_clauses``, ``trimmed``).
+lemmas it needs (``core_clauses``, ``trimmed``).  With ``assume=`` the question is "satisfiable with these literals held fixed, and if not,
+which of them are to blame" (pdp_exact_solve_learn_assume); ``backbone`` asks it once per variable of every satisfiable
+instance, in one batch: the literals that hold in every model.
 """
 
 import numpy as np
@@ -125,7 +127,94 @@ def _certified(prob, budget, hint, arena, names, proof_off=None, counts=None):
     return st, model, wk, verdict, plen, off[1:] - off[:-1], lemmas, cores
 
 
-def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0, certify=False, proofs=False, cores=False):
+def _problem(part, device):
+    b = dataset.to_torch(dataset.collate_segment(part), device)
+    return native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(part))
+
+
+def _certified_part(prob, part, names, budget, hint, arena, device, cores):
+    """_certified on the problem of ``part``; an instance whose proof did not fit its region is solved once more, in a batch of its own,
+    with a region of exactly the size it reported.  (status, model, work, verdict, lemmas, cores) in numpy / lists."""
+    counts = [int(it[1]) for it in part] if cores else None
+    st, model, wk, vd, plen, size, lem, cor = _certified(prob, budget, hint, arena, names, counts=counts)
+    again = [j for j in range(len(part)) if st[j] != -1 and plen[j] > size[j]]
+    if again:
+        prob = _problem([part[j] for j in again], device)
+        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+        hint2 = None if hint is None else torch.cat([hint[voff[j]:voff[j + 1]] for j in again])
+        off2 = torch.from_numpy(np.concatenate([[0], np.cumsum(plen[again])]).astype(np.int64)).to(device)
+        r = _certified(prob, budget, hint2, arena, [names[j] for j in again], proof_off=off2,
+                       counts=[counts[j] for j in again] if cores else None)
+        for k, j in enumerate(again):
+            vd[j], lem[j], cor[j] = r[3][k], r[6][k], r[7][k]
+    return st, model, wk, vd, lem, cor
+
+
+def with_units(item, literals):
+    "the loader item with one unit clause more per signed 1-based literal (after its own clauses; nothing else changes)"
+    n, m, gm, ef = int(item[0]), int(item[1]), np.asarray(item[2]), np.asarray(item[3])
+    lits = np.asarray(literals, dtype=np.int64).reshape(-1)
+    more = np.stack((np.abs(lits) - 1, m + np.arange(lits.size))).astype(gm.dtype).reshape(2, -1)
+    return (n, m + int(lits.size), np.concatenate([gm.reshape(2, -1), more], axis=1), np.concatenate([ef.reshape(-1), np.sign(lits).astype(ef.dtype)]),
+            item[4], item[5])
+
+
+def _assumed(prob, part, names, assume, budget, hint, arena, device, certify):
+    """exact_solve_assume of one problem: numpy (status, model, work, verdict, lemmas, failed index arrays).  ``certify``: a model is
+    checked by pdp_exact_check and against the assumptions; a status 0 by the refutation of the instance plus its failed assumptions as
+    unit clauses, found and checked by the certified learning search in a batch of its own -- the learned clauses of a search under
+    assumptions follow from the formula alone, so no new checker is needed.  A refuted answer raises RuntimeError."""
+    st_t, model_t, wk_t, failed_t = prob.exact_solve_assume(budget, hints=hint, assume=assume, arena=arena)
+    st, model, wk, fl = st_t.cpu().numpy(), model_t.cpu().numpy(), wk_t.cpu().numpy(), failed_t.cpu().numpy()
+    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+    failed = [np.nonzero(fl[voff[j]:voff[j + 1]])[0].astype(np.int64) if st[j] == 0 else None for j in range(len(part))]
+    verdict = np.full(len(part), -1, dtype=np.int8)
+    lemmas = [None] * len(part)
+    if not certify:
+        return st, model, wk, verdict, lemmas, failed
+    a = assume.cpu().numpy()
+    none = torch.zeros(len(part), dtype=torch.int64, device=device)
+    vd, fail_at, _ = prob.exact_check(torch.where(st_t == 1, st_t, torch.full_like(st_t, -1)), model_t, None,
+                                      torch.zeros(len(part) + 1, dtype=torch.int64, device=device), none)
+    vd, fail_at = vd.cpu().numpy(), fail_at.cpu().numpy()
+    for j in np.nonzero(st == 1)[0]:
+        if vd[j] != 1:
+            raise RuntimeError("the complete solver's answer for instance %s (status 1) fails its own check at clause %d: a solver bug, no label "
+                               "is written from it" % (names[j], fail_at[j]))
+        aj, mj = a[voff[j]:voff[j + 1]], model[voff[j]:voff[j + 1]]
+        bad = np.nonzero((aj != 0) & ((mj > 0.5) != (aj > 0)))[0]
+        if bad.size:
+            raise RuntimeError("the complete solver's model for instance %s disagrees with the assumption on variable %d: a solver bug, no "
+                               "label is written from it" % (names[j], bad[0] + 1))
+        verdict[j] = 1
+    unsat = [int(j) for j in np.nonzero(st == 0)[0]]
+    if unsat:
+        reduced = []
+        for j in unsat:
+            aj = a[voff[j]:voff[j + 1]]
+            if (aj[failed[j]] == 0).any():
+                raise RuntimeError("the failed set of instance %s names a variable that is not assumed: a solver bug" % names[j])
+            reduced.append(with_units(part[j], [(v + 1) if aj[v] > 0 else -(v + 1) for v in failed[j]]))
+        rnames = ['%s with its failed assumptions' % names[j] for j in unsat]
+        keep = [k for k, it in enumerate(reduced) if int(it[2].shape[1]) > 0]
+        for k in set(range(len(unsat))) - set(keep):
+            verdict[unsat[k]], lemmas[unsat[k]] = 1, []                # only empty clauses: an empty clause is its own refutation
+        if keep:
+            sub = [reduced[k] for k in keep]
+            r = _certified_part(_problem(sub, device), sub, [rnames[k] for k in keep], budget, None, arena, device, False)
+            for i, k in enumerate(keep):
+                j = unsat[k]
+                if r[0][i] == 1:
+                    raise RuntimeError("the complete solver's answer for instance %s (status 0 under assumptions) is refuted: the instance "
+                                       "with its failed assumptions as unit clauses is satisfiable; a solver bug, no label is written from it"
+                                       % names[j])
+                if r[0][i] == 0:
+                    verdict[j], lemmas[j] = r[3][i], r[4][i]
+    return st, model, wk, verdict, lemmas, failed
+
+
+def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0, certify=False, proofs=False, cores=False,
+                assume=None):
     """Solve loader items ((n, m, graph_map, edge_feature, label, misc) tuples: dataset.instance_from_clauses, dataset.random_ksat_items,
     dataset.parse_line, raw_item).  Returns numpy (status int8 [N] in {1, 0, -1}, models: a float32 0/1 array of n_i values per instance,
     work int64 [N]).  Instances are packed into problems of at most ``max_edges`` edges; nothing couples two instances.
@@ -141,8 +230,17 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
     ``cores`` (with certify): an "unsatisfiable" is judged by the backward check (pdp_exact_trim) in place of the forward one -- models
     still go through pdp_exact_check.  Returns (status, models, work, verdict, lemmas, cores): per certified unsatisfiable instance the
     lemmas the refutation needs (a proof against the core alone) and the 0-based indices of its core clauses, an unsatisfiable subset of
-    the instance; None for the others."""
-    learn = learn or certify
+    the instance; None for the others.
+    ``assume``: per instance an integer array of n_i values (> 0 the variable is held true, < 0 held false, 0 free) or None; the search is
+    then the learning one under assumptions (pdp_exact_solve_learn_assume), which ``assume`` implies.  A status 1 means "satisfiable with
+    these literals fixed" and its model agrees with them; the return value gains, as its last element, ``failed``: per status-0 instance
+    the int64 array of the 0-based assumed variables that are to blame (the instance plus those assumptions as unit clauses is
+    unsatisfiable; empty: it is unsatisfiable on its own), None for the others.  With ``certify`` a model is also checked against the
+    assumptions, and an "unsatisfiable" by the certified refutation of the instance plus its failed assumptions as unit clauses
+    (``proofs``: that refutation's lemmas).  ``cores`` under assumptions is not available."""
+    learn = learn or certify or assume is not None
+    if cores and assume is not None:
+        raise ValueError("cores under assumptions are not available: pass assume without cores")
     if proofs and not certify:
         raise ValueError("proofs belong to the certified search: pass certify=True")
     if cores and not certify:
@@ -156,8 +254,18 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
         for it, h in zip(items, hints):
             if h is not None and np.asarray(h).size != int(it[0]):
                 raise ValueError("hints: instance %r has %d variables, its hints %d values" % (it[5], int(it[0]), np.asarray(h).size))
+    if assume is not None:
+        if len(assume) != len(items):
+            raise ValueError("assume: one entry per instance (%d), got %d" % (len(items), len(assume)))
+        for it, a in zip(items, assume):
+            if a is not None and (np.asarray(a).size != int(it[0]) or np.asarray(a).dtype.kind not in 'iu'):
+                raise ValueError("assume: instance %r has %d variables, its assumptions are %d values of type %s"
+                                 % (it[5], int(it[0]), np.asarray(a).size, np.asarray(a).dtype))
+        if isinstance(arena, bool) or not isinstance(arena, (int, np.integer)) or not 0 <= arena <= 1 << 30:
+            raise ValueError("arena must be an integer from 0 to 2^30 words, got %r" % (arena,))
     device = torch.device('cuda:0') if device is None else torch.device(device)
     N = len(items)
+    failed = [None] * N
     status = np.zeros(N, dtype=np.int8)
     work = np.zeros(N, dtype=np.int64)
     models = [None] * N
@@ -177,31 +285,31 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
                 h = None if hints is None or hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
                 if status[i] == 1 and h is not None and not np.isnan(h).any():
                     models[i] = (h > 0.5).astype(np.float32)           # the check pass accepts a complete hint: no clause objects
+                if assume is not None:
+                    a = np.zeros(int(it[0]), dtype=np.int8) if assume[i] is None else np.sign(np.asarray(assume[i]).reshape(-1)).astype(np.int8)
+                    if status[i] == 1 and a.any():
+                        # the assumptions are the codes of their variables: the check pass if every variable has one, else level 1
+                        coded = h is not None and not (np.isnan(h) & (a == 0)).any()
+                        models[i] = np.where(a != 0, a > 0, (h > 0.5) if coded else False).astype(np.float32)
+                    failed[i] = None if status[i] else np.zeros(0, dtype=np.int64)
             continue
-        b = dataset.to_torch(dataset.collate_segment(part), device)
         with torch.cuda.device(device):
-            prob = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(part))
+            prob = _problem(part, device)
             hint = None
             if hints is not None:
                 flat = [np.full(int(it[0]), np.nan, dtype=np.float32) if hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
                         for i, it in zip(seg, part)]
                 hint = torch.from_numpy(np.concatenate(flat)).to(device)
-            if certify:
-                names = ['%d (%s)' % (i, ' '.join(str(x) for x in it[5])) if it[5] else str(i) for i, it in zip(seg, part)]
-                counts = [int(it[1]) for it in part] if cores else None
-                st, model, wk, vd, plen, size, lem, cor = _certified(prob, budget, hint, arena, names, counts=counts)
-                again = [j for j in range(len(part)) if st[j] != -1 and plen[j] > size[j]]
-                if again:
-                    # the proof did not fit: the same search once more, in a batch of its own, with regions of exactly proof_len words
-                    b2 = dataset.to_torch(dataset.collate_segment([part[j] for j in again]), device)
-                    prob = native.Problem(b2['graph_map'], b2['batch_variable_map'], b2['batch_function_map'], b2['edge_feature'], batch_size=len(again))
-                    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
-                    hint2 = None if hint is None else torch.cat([hint[voff[j]:voff[j + 1]] for j in again])
-                    off2 = torch.from_numpy(np.concatenate([[0], np.cumsum(plen[again])]).astype(np.int64)).to(device)
-                    r = _certified(prob, budget, hint2, arena, [names[j] for j in again], proof_off=off2,
-                                   counts=[counts[j] for j in again] if cores else None)
-                    for k, j in enumerate(again):
-                        vd[j], lem[j], cor[j] = r[3][k], r[6][k], r[7][k]
+            names = ['%d (%s)' % (i, ' '.join(str(x) for x in it[5])) if it[5] else str(i) for i, it in zip(seg, part)]
+            if assume is not None:
+                flat = [np.zeros(int(it[0]), dtype=np.int8) if assume[i] is None else np.sign(np.asarray(assume[i]).reshape(-1)).astype(np.int8)
+                        for i, it in zip(seg, part)]
+                st, model, wk, vd, lem, fl = _assumed(prob, part, names, torch.from_numpy(np.concatenate(flat)).to(device), budget, hint, arena,
+                                                      device, certify)
+                for j, i in enumerate(seg):
+                    verdict[i], lemmas[i], failed[i] = vd[j], lem[j], fl[j]
+            elif certify:
+                st, model, wk, vd, lem, cor = _certified_part(prob, part, names, budget, hint, arena, device, cores)
                 for j, i in enumerate(seg):
                     verdict[i], lemmas[i], core[i] = vd[j], lem[j], cor[j]
             else:
@@ -216,9 +324,54 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
             off += n
     if cores:
         return status, models, work, verdict, lemmas, core
+    tail = () if assume is None else (failed,)
     if certify:
-        return (status, models, work, verdict, lemmas) if proofs else (status, models, work, verdict)
-    return status, models, work
+        return ((status, models, work, verdict, lemmas) if proofs else (status, models, work, verdict)) + tail
+    return (status, models, work) + tail
+
+
+def backbone(items, budget=0, device=None, max_edges=MAX_EDGES, arena=0):
+    """The backbone of every satisfiable instance: (status int8 [N], backbones).  backbones[i] is an int8 array of n_i values -- +1 the
+    variable is true in every model, -1 false in every model, 0 free, 2 not decided within the budget -- and None when instance i is not
+    satisfiable or its own search was undecided.  With M the model of the base search, variable v is in the backbone iff the instance is
+    unsatisfiable under the single assumption v = not M[v].  One base solve_items(learn=True), then the n_i queries of every satisfiable
+    instance as one solve_items(assume=...) call: each query is the instance's own item with a one-hot assumption array, thousands of
+    small searches on the same clauses per launch."""
+    status, models, _ = solve_items(items, budget=budget, device=device, max_edges=max_edges, learn=True, arena=arena)
+    return status, backbone_of(items, status, models, budget=budget, device=device, max_edges=max_edges, arena=arena)
+
+
+def backbone_of(items, status, models, budget=0, device=None, max_edges=MAX_EDGES, arena=0):
+    """backbone()'s second result from answers already at hand: ``models[i]`` is a model of every instance with status[i] == 1 (any model
+    gives the same backbone: a forced variable has one value in all of them)."""
+    queries, assume, at = [], [], []
+    for i in np.nonzero(np.asarray(status) == 1)[0]:
+        for v in range(len(models[i])):
+            a = np.zeros(len(models[i]), dtype=np.int8)
+            a[v] = -1 if models[i][v] > 0.5 else 1
+            queries.append(items[i])
+            assume.append(a)
+            at.append((int(i), v))
+    out = [np.zeros(len(models[i]), dtype=np.int8) if status[i] == 1 else None for i in range(len(items))]
+    if queries:
+        answer = solve_items(queries, budget=budget, device=device, max_edges=max_edges, arena=arena, assume=assume)[0]
+        for (i, v), q in zip(at, answer):
+            out[i][v] = (1 if models[i][v] > 0.5 else -1) if q == 0 else (0 if q == 1 else 2)
+    return out
+
+
+def items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, batch_size):
+    """The loader items of a batch's tensors (the loader's instance-contiguous layout, unreplicated): per instance (n, m, graph_map with its
+    own 0-based ids, edge_feature, -1.0, [])."""
+    gm = graph_map.detach().cpu().numpy().astype(np.int64).reshape(2, -1)
+    ef = edge_feature.detach().cpu().numpy().reshape(-1).astype(np.float32)
+    bvm = batch_variable_map.detach().cpu().numpy().astype(np.int64).reshape(-1)
+    bfm = batch_function_map.detach().cpu().numpy().astype(np.int64).reshape(-1)
+    v0 = np.concatenate([[0], np.cumsum(np.bincount(bvm, minlength=batch_size)[:batch_size])])
+    f0 = np.concatenate([[0], np.cumsum(np.bincount(bfm, minlength=batch_size)[:batch_size])])
+    e0 = np.concatenate([[0], np.cumsum(np.bincount(bfm[gm[1]], minlength=batch_size)[:batch_size])])
+    return [(int(v0[i + 1] - v0[i]), int(f0[i + 1] - f0[i]),
+             (gm[:, e0[i]:e0[i + 1]] - np.array([[v0[i]], [f0[i]]])).astype(np.int32), ef[e0[i]:e0[i + 1]].copy(), -1.0, []) for i in range(batch_size)]
 
 
 def _label(s):

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = [
     'pdp_sat_loss_grad', 'pdp_train_sp_adapted_backward',
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
-    'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid',
+    'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid', 'pdp_exact_solve_learn_assume',
 ]
 
 
@@ -442,6 +442,37 @@ class Problem(object):
             check(lib().pdp_exact_solve_hinted(self._h, ptr(hints, torch.float32, self.V, 'hints'), C.c_int64(int(budget)), ptr(status), ptr(model),
                                                ptr(work), _stream()))
         return status, model, work
+
+    def exact_solve_assume(self, budget=0, hints=None, assume=None, arena=0, stats=False):
+        """The learning search under assumptions (pdp_exact_solve_learn_assume): (status, model, work, failed), plus learned with
+        ``stats``.  ``assume`` (int8, V elements, on the problem's device, or None): > 0 the variable is held true, < 0 held false, 0 free.
+        status 1: model satisfies every clause and every assumption.  status 0: unsatisfiable under the assumptions, and failed int8 [V]
+        is 1 on the assumed variables that are to blame (the instance plus those assumptions as unit clauses is unsatisfiable; none:
+        the instance is unsatisfiable on its own) and 0 everywhere else.  An instance without an assumed variable gets exactly
+        exact_solve(learn=True)'s outputs.  ``budget``, ``hints`` and ``arena`` as in exact_solve; exact_learn_reductions reports this
+        call as well.  Asynchronous on the current stream."""
+        if isinstance(arena, bool) or not isinstance(arena, numbers.Integral) or not 0 <= arena <= 1 << 30:
+            raise ValueError("arena must be an integer from 0 to 2^30 words, got %r" % (arena,))
+        if hints is not None:
+            if not torch.is_tensor(hints) or hints.dtype != torch.float32 or hints.numel() != self.V:
+                raise ValueError("hints must be a float32 tensor of %d elements (one per variable), got %s"
+                                 % (self.V, '%s of %d' % (hints.dtype, hints.numel()) if torch.is_tensor(hints) else type(hints).__name__))
+            hints = hints.reshape(-1).contiguous()
+        if assume is not None:
+            if not torch.is_tensor(assume) or assume.dtype != torch.int8 or assume.numel() != self.V or assume.device != self.device:
+                raise ValueError("assume must be an int8 tensor of %d elements (one per variable) on %s, got %s"
+                                 % (self.V, self.device, '%s of %d on %s' % (assume.dtype, assume.numel(), assume.device) if torch.is_tensor(assume)
+                                    else type(assume).__name__))
+            assume = assume.reshape(-1).contiguous()
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        model = torch.empty(self.V, dtype=torch.float32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        learned = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        failed = torch.empty(self.V, dtype=torch.int8, device=self.device)
+        check(lib().pdp_exact_solve_learn_assume(self._h, ptr(hints, torch.float32, self.V, 'hints'), ptr(assume, torch.int8, self.V, 'assume'),
+                                                 C.c_int64(int(budget)), C.c_int64(int(arena)), ptr(status), ptr(model), ptr(work), ptr(learned),
+                                                 ptr(failed), _stream()))
+        return (status, model, work, failed, learned) if stats else (status, model, work, failed)
 
     def exact_learn_reductions(self):
         "int32 [B]: how often each instance's arena was reduced in the last exact_solve(learn=True) on this problem"

@@ -146,7 +146,10 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         undecided within config['complete_budget'] clause-literal reads), "pdp_solved" (what "solved" is without the search) and "work" (the
         reads of the search); with config['complete_certify'] also "certified" (1: the answer passed pdp_exact_check, -1: undecided), and with config['complete_core'] an
         unsatisfiable row also "core", the 0-based indices (in the instance's clause order) of the clauses its refutation rests on.  A satisfiable row gets solved 1, unsat_clauses 0 and the search's model -- PDP's own assignment where PDP had
-        solved the instance, because the check pass accepts it; every other row keeps its five reference keys."""
+        solved the instance, because the check pass accepts it; every other row keeps its five reference keys.  With config['complete_backbone']
+        a satisfiable row also gains "backbone", the signed 1-based literals that hold in every model (ascending by variable; one query of
+        the search under assumptions per variable, all instances of the forward in one batch), and, when queries ran out of budget,
+        "backbone_unknown" with their count (those literals are left out)."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -184,6 +187,15 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                     row['core'] = [int(c) for c in cores[i]]
             if status[i] == 1:
                 row['solved'], row['unsat_clauses'], row['solution'] = 1, 0, solution[offs[i]:offs[i + 1]].tolist()
+        if self._config.get('complete_backbone'):
+            from pdp import exact
+            items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
+            models = [np.asarray(solution[offs[i]:offs[i + 1]], dtype=np.float32) for i in range(len(rows))]
+            for row, bb in zip(rows, exact.backbone_of(items, np.asarray(status), models, budget=budget, device=hint.device)):
+                if bb is not None:
+                    row['backbone'] = [int(v + 1) * int(bb[v]) for v in np.nonzero(np.abs(bb) == 1)[0]]
+                    if (bb == 2).any():
+                        row['backbone_unknown'] = int((bb == 2).sum())
         if hasattr(self, '_complete_stats'):
             for k, s in enumerate((1, 0, -1)):
                 self._complete_stats[k] += int((status == s).sum())

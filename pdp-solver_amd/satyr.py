@@ -10,7 +10,9 @@ is then decided by the batched exact search with the model's assignment as its p
 conflict clause learning (pdp_exact_solve_learn); ``--complete-certify`` (implies ``--complete-learn``) has every answer checked on the GPU -- a
 model against the clauses, an "unsatisfiable" by a forward check of the learned clauses as a proof (pdp_exact_check) -- and a row gains
 "certified" (1 checked, -1 undecided); ``--complete-core`` (with ``--complete-certify``) judges an "unsatisfiable" by the backward check
-(pdp_exact_trim) and such a row gains "core", the 0-based indices of the clauses its refutation rests on.
+(pdp_exact_trim) and such a row gains "core", the 0-based indices of the clauses its refutation rests on; ``--complete-backbone`` (with
+``--complete``) gives a satisfiable row "backbone", the signed 1-based literals that hold in every model of the instance (one query of
+the search under assumptions per variable, pdp_exact_solve_learn_assume), and "backbone_unknown" when queries ran out of budget.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -107,6 +109,10 @@ def main(argv=None):
     parser.add_argument('--complete-core', dest='complete_core', help='With --complete --complete-certify: an "unsatisfiable" is certified by the backward '
                         'check of its proof (pdp_exact_trim) and its row gains "core": the 0-based indices, in the instance\'s clause order, of an '
                         'unsatisfiable subset of its clauses', action='store_true')
+    parser.add_argument('--complete-backbone', dest='complete_backbone', help='With --complete: a satisfiable row gains "backbone", the signed 1-based '
+                        'literals that hold in every model of the instance, ascending by variable (pdp_exact_solve_learn_assume, one query per '
+                        'variable); literals whose query ran out of --complete-budget are left out and counted in "backbone_unknown"',
+                        action='store_true')
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -117,6 +123,8 @@ def main(argv=None):
         parser.error("--complete-certify checks the answers of --complete: give --complete as well")
     if args['complete_core'] and not args['complete_certify']:
         parser.error("--complete-core names the core of a certified answer: give --complete-certify as well")
+    if args['complete_backbone'] and not args['complete']:
+        parser.error("--complete-backbone names the backbone of an answer of --complete: give --complete as well")
     if args['complete_certify']:
         args['complete_learn'] = True
 

@@ -22,7 +22,13 @@ of an instance and, per region factor k, the instances whose proof a region of k
 Trim rows (pdp_exact_trim; never part of the default): ``ta`` / ``td`` / ``tm100`` / ``tm200`` = the problems and proofs of pa, pd, pm100 and pm200:
 the backward check next to the forward check of the same proofs on the same problem (the forward check once on every answer, once on the
 unsatisfiable ones alone; the kernels alternate, TRIM_REPEATS timed calls each, the median is reported), the core size over the clause count
-(median / p99 / max over the unsatisfiable instances), kept over logged lemmas and the reads of the two checks."""
+(median / p99 / max over the unsatisfiable instances), kept over logged lemmas and the reads of the two checks.
+
+Assumption rows (pdp_exact_solve_learn_assume; never part of the default): ``aa`` / ``am100`` = row (a) and m100 with nothing assumed through
+the kernel of the search under assumptions, next to pdp_exact_solve_learn on the same problem in the same process (the two kernels
+alternate, TRIM_REPEATS timed calls each, the median is reported; every output must be identical).  ``ab`` = exact.backbone of the first 200
+satisfiable instances of row (a): wall time, the kernel time of its queries (device events around every exact_solve_assume call, the
+one-time preparation of each problem included), queries per second, the backbone fraction and the queries left undecided."""
 import io
 import json
 import logging
@@ -250,6 +256,71 @@ def run_trim(key):
              int(twk[unsat].sum()), int(cwk[unsat].sum()), float(twk[unsat].sum()) / max(1.0, float(cwk[unsat].sum()))), flush=True)
 
 
+ASSUME_ROWS = ('aa', 'am100', 'ab')
+
+
+def run_assume(key):
+    if key == 'ab':
+        return run_backbone()
+    modular = key[1:] in MODULAR
+    title, make = MODULAR[key[1:]] if modular else ROWS[key[1:]]
+    budget = MODULAR_BUDGET if modular else 0
+    items = make()
+    b = dataset.to_torch(dataset.collate_segment(items), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(items))
+    zeros = torch.zeros(p.V, dtype=torch.int8, device=p.device)
+    calls = {'learn': lambda: p.exact_solve(budget, learn=True, stats=True), 'assume': lambda: p.exact_solve_assume(budget, assume=zeros, stats=True)}
+    ms, out, red = {k: [] for k in calls}, {}, {}
+    for k in calls:
+        calls[k]()                                                                   # the one-time routing preparation is not timed
+    for _ in range(TRIM_REPEATS):
+        for k in calls:
+            t, out[k] = _event_ms(calls[k])
+            ms[k].append(t)
+            red[k] = p.exact_learn_reductions().cpu().numpy()
+    st, model, wk, ln = [t.cpu().numpy() for t in out['learn']]
+    ast, amodel, awk, failed, aln = [t.cpu().numpy() for t in out['assume']]
+    assert np.array_equal(wk, awk), "work differs with nothing assumed"
+    assert np.array_equal(st, ast) and np.array_equal(model, amodel) and np.array_equal(ln, aln) and np.array_equal(red['learn'], red['assume']) \
+        and not failed.any(), "an output differs with nothing assumed"
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    _line(key + ', pdp_exact_solve_learn', title, p, med['learn'], st, wk)
+    print("    pdp_exact_solve_learn_assume with nothing assumed: kernel %.2f ms (%.3f of pdp_exact_solve_learn; %d alternated calls each, min / max: "
+          "learn %.2f / %.2f, assume %.2f / %.2f)  work identical: total %d"
+          % (med['assume'], med['assume'] / med['learn'], TRIM_REPEATS, min(ms['learn']), max(ms['learn']), min(ms['assume']), max(ms['assume']),
+             int(awk.sum())), flush=True)
+
+
+def run_backbone(count=200):
+    from pdp import exact
+    title, make = ROWS['a']
+    pool = make()[:3 * count]
+    status = exact.solve_items(pool, learn=True)[0]
+    items = [pool[i] for i in np.nonzero(status == 1)[0][:count]]
+    assert len(items) == count, "too few satisfiable instances among the first %d" % len(pool)
+    kernel, real = [], native.Problem.exact_solve_assume
+
+    def timed(self, *a, **kw):
+        t, out = _event_ms(lambda: real(self, *a, **kw))
+        kernel.append(t)
+        return out
+    native.Problem.exact_solve_assume = timed
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st, bbs = exact.backbone(items)
+        wall = time.perf_counter() - t0
+    finally:
+        native.Problem.exact_solve_assume = real
+    assert (st == 1).all()
+    bb = np.concatenate(bbs)
+    print("(ab) backbone of the first %d satisfiable instances of %s: %d queries in %d problems  wall %.2f s  query kernels %.2f ms  "
+          "%.0f queries/s of wall, %.0f queries/s of kernel  backbone fraction %.3f (per instance: median %.3f, min %.3f, max %.3f)  undecided queries %d"
+          % (count, title, bb.size, len(kernel), wall, sum(kernel), bb.size / wall, bb.size / (sum(kernel) * 1e-3), float((np.abs(bb) == 1).mean()),
+             float(np.median([(np.abs(x) == 1).mean() for x in bbs])), min((np.abs(x) == 1).mean() for x in bbs),
+             max((np.abs(x) == 1).mean() for x in bbs), int((bb == 2).sum())), flush=True)
+
+
 def _write_json(items, path):
     from pdp import generator
     with open(path, 'w') as f:
@@ -329,4 +400,4 @@ def run_wall(key):
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
-        {'h': run_hinted, 'w': run_wall, 'l': run_learn, 'm': run_learn, 'p': run_proof, 't': run_trim}.get(k[0], run)(k)
+        (run_assume if k in ASSUME_ROWS else {'h': run_hinted, 'w': run_wall, 'l': run_learn, 'm': run_learn, 'p': run_proof, 't': run_trim}.get(k[0], run))(k)
