@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -376,8 +376,37 @@ int pdp_exact_trim(pdp_problem *p, const int8_t *status, const int64_t *proof_of
 int pdp_exact_solve_learn_assume(pdp_problem *p, const float *hint, const int8_t *assume, int64_t budget, int64_t arena,
                                  int8_t *status, float *model, int64_t *work, int32_t *learned, int8_t *failed, void *stream);
 
+/* The fewest unsatisfied clauses of every instance, by depth-first branch and bound over pdp_exact_solve_hinted's passes (plain Python:
+ * tests/exact_min_unsat_model.py).  hint [V] (may be NULL) is the first incumbent: h > 0.5 true, every other value false, NaN
+ * included; NULL = all false.  Outputs per instance: status = 1, cost is the minimum number of unsatisfied clauses over all assignments,
+ * or -1, the budget ran out and cost is an upper bound (never 0); cost [B] = the clauses model leaves unsatisfied, in both cases; model [V]
+ * = a complete 0 / 1 assignment (never a placeholder); work [B] (may be NULL) = clause-literal reads; improvements [B] (may be NULL) = how
+ * often the incumbent was replaced.  The search of one instance is pdp_exact_solve_hinted's loop with these changes:
+ *   Incumbent.  A check pass over the thresholded hint always runs, before the first budget check: every clause is read up to and
+ *      including its first true literal (the whole clause if there is none), counted into work; ub = the clauses without a true literal,
+ *      model = that assignment.  ub == 0: done, status 1, cost 0.  Otherwise the search starts from the empty assignment.
+ *   A pass computes what pdp_exact_solve's computes, and cost = the clauses with no true and no unassigned literal (there: the conflict
+ *      flag), contra = the variables whose unit requests name both polarities, wmin = the minimum width over the clauses with no true and
+ *      at least one unassigned literal, where a unit (all unassigned literals the same literal) has width 1.
+ *   After the pass, in this order:
+ *      1. cost + contra >= ub: prune (of two contradicting units one is falsified, and different variables mean different clauses).
+ *      2. else cost == ub - 1 and there is a unit: every unit is forced; the pending set is assigned as in pdp_exact_solve, next pass.
+ *      3. else no open clause: a leaf with cost < ub.  ub = cost, improvements + 1, model = the current assignment with the unassigned
+ *         variables false; ub == 0 ends the search with status 1, otherwise prune.
+ *      4. else the unit requests are dropped and the search branches: pdp_exact_solve's rule over the clauses of width wmin (which may be
+ *         1 here), first polarity the incumbent hint's (without hints: false).
+ *   Prune is pdp_exact_solve's chronological backtracking; running out of levels ends the search with status 1 and cost = ub.
+ * The budget is checked before every pass (budget <= 0: PDP_EXACT_DEFAULT_BUDGET) and work < budget + 3 * (edges of the instance) holds.
+ * All five outputs are a function of the instance and its own hints: every reduction is an integer sum, an OR, a minimum or a maximum of
+ * unique keys.  M1: if the hint has no NaN and leaves at most one clause unsatisfied, work equals pdp_exact_solve_hinted's with the same
+ * hint, and cost is 0 where that search answers 1 and the hint's cost where it answers 0 (with ub = 1 every pass is in case 1 or 2).
+ * The bound is cost + contra and nothing stronger: k disjoint unsatisfiable blocks take about 8^k leaves.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules; routing and working arrays are pdp_exact_solve's, shared with it. */
+int pdp_exact_min_unsat(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, int32_t *cost, float *model,
+                        int64_t *work, int32_t *improvements, void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an
  * integer v >= 1 and is ignored otherwise (unset, empty, 0, negative, not a number) -- a test switch that makes a wave run many

@@ -203,6 +203,7 @@ __device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, bool check
         }
         if (any_conflict) {
             // chronological backtracking: undo levels until one whose second polarity is untried
+            // (ex_search_min below carries a copy of this block: a fix here belongs there too)
             bool resumed = false;
             while (level > 0) {
                 const uint32_t d = X.dvar[level];
@@ -255,6 +256,7 @@ __device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, bool check
             if (p | q) {
                 X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
                 // score, then the lower index, then the polarity (true when its occurrences are at least as many; the hint's if v has one)
+                // (ex_search_min below builds the same key, with the incumbent's polarity: a fix here belongs there too)
                 bool pos = p >= q;
                 if constexpr (HINT) {
                     const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
@@ -412,6 +414,286 @@ int ex_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status,
     const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
     PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
     hipLaunchKernelGGL(k_exact<HINT>, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
+    return PDP_OK;
+}
+
+// ---- pdp_exact_min_unsat: the fewest unsatisfied clauses by depth-first branch and bound over the same passes --------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_min_unsat_model.py).  Its own search, kernel and launch path: nothing above
+// is touched.  The state is ex_search's, array for array: the incumbent lives in the output model in HBM (written by the check pass,
+// rewritten on an improvement only) and the hint codes in bits 8-9 of pend[v], so the slab, the routing and the occupancy by LDS are
+// k_exact's.  A pass also counts the falsified clauses (cost, a wave sum) where ex_search raises a flag, and the pending words with both
+// unit bits (contra); cost + contra >= ub prunes, the units are assigned only where leaving one out would reach ub, and every other state
+// with an open clause branches, on a clause of width 1 too.
+struct ExmParams {
+    const int32_t *order;       // as ExParams
+    int nbig, B;
+    uint32_t *next;
+    int64_t budget;
+    int8_t *status; int32_t *cost; float *model; int64_t *work; int32_t *improvements;
+    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+    const float *hint;          // [V] the incumbents (NULL: all false)
+};
+
+// The optimising search of one instance by the calling wave.  pend[v] carries the code of the incumbent (1 true, 2 false: never 0), model
+// points at the instance's slice of the output.  Returns 1 (*cost_out is the minimum) or -1 (budget spent: an upper bound); model holds
+// an assignment that leaves exactly *cost_out clauses unsatisfied either way.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_min(const ExInst<LitT, PtrT> &X, int64_t budget, float *model, int64_t *work_out, int *cost_out, int *improved_out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    constexpr uint32_t UNIT = 3u;
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0, ub = 0, improved = 0;
+    int64_t work = 0;
+    int result = -1;
+    {
+        // the check pass: the incumbent's reads and its unsatisfied clauses; it always runs, before the first budget check
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
+            X.val[v] = (uint8_t)code;
+            model[v] = code == 1u ? 1.0f : 0.0f;
+        }
+        ex_sync<HBM>();
+        int reads = 0, open = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int sat = 0, k = a;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                if (X.val[L >> 1] == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            open += !sat;
+        }
+        work += ex_sum(reads);
+        ub = ex_sum(open);
+        if (ub == 0) { *work_out = work; *cost_out = 0; *improved_out = 0; return 1; }
+        ex_sync<HBM>();                                             // every lane has read val before it is cleared
+        for (int v = lane; v < X.n; v += EX_NT) X.val[v] = 0;
+        ex_sync<HBM>();
+    }
+    for (;;) {
+        if (work >= budget) break;
+        // ---- one pass: falsified clauses, unit requests, the minimum width of the open clauses (a unit has width 1)
+        int reads = 0, cost = 0, unit = 0, wmin = INF;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat) continue;
+            if (nfree == 0) { ++cost; continue; }
+            if (!distinct) { unit = 1; nfree = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
+            wmin = nfree < wmin ? nfree : wmin;
+        }
+        work += ex_sum(reads);
+        cost = ex_sum(cost);
+        wmin = ex_min(wmin);
+        const bool any_unit = __ballot(unit) != 0ull;
+        int contra = 0;
+        if (any_unit) {
+            ex_sync<HBM>();
+            for (int v = lane; v < X.n; v += EX_NT) contra += (X.pend[v] & UNIT) == UNIT;
+            contra = ex_sum(contra);
+        }
+        bool prune = cost + contra >= ub;
+        if (!prune && cost == ub - 1 && any_unit) {
+            // leaving any unit out reaches ub: the pending set is assigned as in ex_search (no variable is asked for twice: that was pruned)
+            for (int base = 0; base < X.n; base += EX_NT) {
+                const int v = base + lane;
+                const uint32_t word = v < X.n ? X.pend[v] : 0u;
+                const uint32_t bits = word & UNIT;
+                const unsigned long long mask = __ballot(bits != 0u);
+                if (bits) {
+                    X.pend[v] = word & ~UNIT;
+                    X.val[v] = (bits & 1u) ? 1 : 2;
+                    X.trail[tlen + __popcll(mask & below)] = v;
+                }
+                tlen += __popcll(mask);
+            }
+            ex_sync<HBM>();
+            continue;
+        }
+        if (any_unit) {
+            // every other path drops the unit requests
+            for (int v = lane; v < X.n; v += EX_NT) { const uint32_t word = X.pend[v]; if (word & UNIT) X.pend[v] = word & ~UNIT; }
+            ex_sync<HBM>();
+        }
+        if (!prune && wmin == INF) {
+            // a leaf below ub: the new incumbent, unassigned variables false
+            ub = cost;
+            ++improved;
+            for (int v = lane; v < X.n; v += EX_NT) model[v] = X.val[v] == 1 ? 1.0f : 0.0f;
+            if (ub == 0) { result = 1; break; }
+            prune = true;
+        }
+        if (prune) {
+            // chronological backtracking, a copy of ex_search's block (its device code must not move, so nothing is shared): keep the
+            // two in step; out of levels: ub is the minimum
+            bool resumed = false;
+            while (level > 0) {
+                const uint32_t d = X.dvar[level];
+                const int v = (int)(d & 0x7fffffffu);
+                const int from = X.mark[level];
+                const uint32_t first = X.val[v];
+                ex_sync<HBM>();                                     // every lane has read the level before it is undone
+                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
+                tlen = from;
+                if (!(d & 0x80000000u)) {
+                    ex_sync<HBM>();
+                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
+                    ++tlen;
+                    ex_sync<HBM>();
+                    resumed = true;
+                    break;
+                }
+                --level;
+            }
+            if (!resumed) { result = 1; break; }
+            continue;
+        }
+        // ---- branching: the unassigned variable with the most occurrences in the open clauses of width wmin (1: the units)
+        reads = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat || nfree == 0 || (distinct ? nfree : 1) != wmin) continue;
+            for (int j = a; j < z; ++j) {
+                const uint32_t L = X.lit[j];
+                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+            }
+            reads += z - a;
+        }
+        work += ex_sum(reads);
+        ex_sync<HBM>();
+        unsigned long long best = 0ull;
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+            if (p | q) {
+                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+                // ex_search's key (keep the two in step): score, then the lower index, then the polarity, here the incumbent's
+                const bool pos = ((X.pend[v] >> EX_HINT_SHIFT) & 3u) == 1u;
+                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                               (pos ? 1ull : 0ull);
+                best = key > best ? key : best;
+            }
+        }
+        best = ex_max64(best);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has an unassigned literal); never index with it
+        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        ++level;
+        ex_sync<HBM>();
+        if (lane == 0) { X.mark[level] = tlen; X.dvar[level] = (uint32_t)v; X.val[v] = (best & 1ull) ? 1 : 2; X.trail[tlen] = v; }
+        ++tlen;
+        ex_sync<HBM>();
+    }
+    *work_out = work; *cost_out = ub; *improved_out = improved;
+    return result;
+}
+
+// copy the instance's literals in clause order, clear the state (pend starts as the incumbent's codes), search, write the results
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_min(const ExmParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill)
+{
+    const int lane = (int)threadIdx.x;
+    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+    for (int k = lane; k < I.e; k += EX_NT) {
+        const int ed = I.f_edges[k];
+        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+    }
+    for (int v = lane; v < I.n; v += EX_NT) {
+        const uint32_t code = (xp.hint && xp.hint[I.v0 + v] > 0.5f) ? 1u : 2u;          // NaN compares false
+        X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+    }
+    ex_sync<HBM>();
+    int64_t work = 0;
+    int cost = 0, improved = 0;
+    const int st = ex_search_min<HBM>(X, xp.budget, xp.model + I.v0, &work, &cost, &improved);
+    if (lane == 0) {
+        xp.status[I.b] = (int8_t)st;
+        xp.cost[I.b] = cost;
+        if (xp.work) xp.work[I.b] = work;
+        if (xp.improvements) xp.improvements[I.b] = improved;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_min(PView pv, ExmParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        if (i < xp.nbig) {
+            ExInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
+            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
+            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve_min<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
+        } else {
+            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
+            ExInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
+            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
+            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve_min<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ex_slab + L.cptr));
+        }
+    }
+}
+
+// routing, order and working arrays are ex_prepare's, shared with pdp_exact_solve
+int exm_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, int32_t *cost, float *model, int64_t *work,
+               int32_t *improvements, void *stream)
+{
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    ExmParams xp;
+    xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.status = status; xp.cost = cost; xp.model = model; xp.work = work; xp.improvements = improvements; xp.hint = hint;
+    const size_t V = p->V, E = p->E, B = p->B;
+    if (p->ex_h_lit) {
+        char *q = (char *)p->ex_h_lit;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_pend = (uint32_t *)q;           q += V * 4;
+        xp.h_cnt = (uint32_t *)q;            q += V * 8;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
+        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
+        xp.h_val = (uint8_t *)q;
+    } else {
+        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
+        xp.h_val = nullptr;
+    }
+    const int lds = (int)p->ex_lds_bytes;
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_min, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_min, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
+    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_min, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
     p->ex_last_grid = (int32_t)grid;
     return PDP_OK;
@@ -1747,6 +2029,17 @@ extern "C" int pdp_exact_solve_hinted(pdp_problem *p, const float *hint, int64_t
         return PDP_ERR_UNSUPPORTED;
     }
     return ex_launch<true>(p, hint, budget, status, model, work, stream);
+}
+
+extern "C" int pdp_exact_min_unsat(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, int32_t *cost, float *model, int64_t *work,
+                                   int32_t *improvements, void *stream)
+{
+    PDP_REQUIRE(p && status && cost && model, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_min_unsat: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exm_launch(p, hint, budget, status, cost, model, work, improvements, stream);
 }
 
 extern "C" int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work,

@@ -10,7 +10,9 @@ forward check of the learning search's learned clauses as a proof (pdp_exact_sol
 check instead (pdp_exact_trim), which also says why: the core, the original clauses the refutation rests on, and the
 lemmas it needs (``core_clauses``, ``trimmed``).  With ``assume=`` the question is "satisfiable with these literals held fixed, and if not,
 which of them are to blame" (pdp_exact_solve_learn_assume); ``backbone`` asks it once per variable of every satisfiable
-instance, in one batch: the literals that hold in every model.
+instance, in one batch: the literals that hold in every model.  ``min_unsat`` optimises instead of deciding: the fewest clauses any
+assignment leaves unsatisfied, by branch and bound from a given assignment (pdp_exact_min_unsat) -- what an incomplete
+solver's ``unsat_clauses`` on an unsatisfiable instance is to be compared with.
 """
 
 import numpy as np
@@ -328,6 +330,50 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
     if certify:
         return ((status, models, work, verdict, lemmas) if proofs else (status, models, work, verdict)) + tail
     return (status, models, work) + tail
+
+
+def min_unsat(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
+    """The fewest unsatisfied clauses of loader items (as solve_items takes them) by branch and bound (pdp_exact_min_unsat).  Returns numpy
+    (status int8 [N]: 1 the cost is the minimum over all assignments, -1 the budget ran out and it is an upper bound; cost int32 [N];
+    models: per instance a float32 0/1 array of n_i values that leaves exactly cost clauses unsatisfied; work int64 [N]).
+    ``hints``: per instance an array of n_i values or None -- the assignment the search starts from as its incumbent (> 0.5 true, every
+    other value false, NaN included; None: all false), so cost never exceeds what that assignment leaves unsatisfied."""
+    native.require_gpu()
+    if hints is not None:
+        if len(hints) != len(items):
+            raise ValueError("hints: one entry per instance (%d), got %d" % (len(items), len(hints)))
+        for it, h in zip(items, hints):
+            if h is not None and np.asarray(h).size != int(it[0]):
+                raise ValueError("hints: instance %r has %d variables, its hints %d values" % (it[5], int(it[0]), np.asarray(h).size))
+    device = torch.device('cuda:0') if device is None else torch.device(device)
+    N = len(items)
+    status = np.ones(N, dtype=np.int8)
+    cost = np.zeros(N, dtype=np.int32)
+    work = np.zeros(N, dtype=np.int64)
+    models = [None] * N
+    for seg in _segments(items, max_edges):
+        part = [items[i] for i in seg]
+        flat = [np.zeros(int(it[0]), dtype=np.float32) if hints is None or hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
+                for i, it in zip(seg, part)]
+        if sum(int(it[2].shape[1]) for it in part) == 0:
+            # no literal anywhere (and no problem to build: the layout needs an edge): every assignment leaves exactly the empty clauses
+            # unsatisfied, the incumbent among them
+            for i, it, h in zip(seg, part, flat):
+                cost[i] = int(it[1])
+                models[i] = (h > 0.5).astype(np.float32)
+            continue
+        with torch.cuda.device(device):
+            prob = _problem(part, device)
+            st, co, model, wk = prob.exact_min_unsat(budget, hints=torch.from_numpy(np.concatenate(flat)).to(device))
+            st, co, model, wk = st.cpu().numpy(), co.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
+        del prob
+        off = 0
+        for j, (i, it) in enumerate(zip(seg, part)):
+            n = int(it[0])
+            status[i], cost[i], work[i] = st[j], co[j], wk[j]
+            models[i] = model[off:off + n].copy()
+            off += n
+    return status, cost, models, work
 
 
 def backbone(items, budget=0, device=None, max_edges=MAX_EDGES, arena=0):

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
     'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid', 'pdp_exact_solve_learn_assume',
+    'pdp_exact_min_unsat',
 ]
 
 
@@ -443,6 +444,26 @@ class Problem(object):
                                                ptr(work), _stream()))
         return status, model, work
 
+    def exact_min_unsat(self, budget=0, hints=None, stats=False):
+        """The fewest unsatisfied clauses of every instance by branch and bound (pdp_exact_min_unsat): (status int8 [B]: 1 the cost is the
+        minimum over all assignments, -1 the budget ran out and it is an upper bound; cost int32 [B]: the clauses the model leaves
+        unsatisfied; model float [V]: a complete 0/1 assignment; work int64 [B]), plus improvements int32 [B] with ``stats``: how often the
+        incumbent was replaced.  ``hints`` (float32, V elements, as in exact_solve): the first incumbent, > 0.5 true and every other value
+        false, NaN included; None: all false.  ``budget`` as in exact_solve.  Asynchronous on the current stream."""
+        if hints is not None:
+            if not torch.is_tensor(hints) or hints.dtype != torch.float32 or hints.numel() != self.V:
+                raise ValueError("hints must be a float32 tensor of %d elements (one per variable), got %s"
+                                 % (self.V, '%s of %d' % (hints.dtype, hints.numel()) if torch.is_tensor(hints) else type(hints).__name__))
+            hints = hints.reshape(-1).contiguous()
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        cost = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        model = torch.empty(self.V, dtype=torch.float32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        improvements = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        check(lib().pdp_exact_min_unsat(self._h, ptr(hints, torch.float32, self.V, 'hints'), C.c_int64(int(budget)), ptr(status), ptr(cost),
+                                        ptr(model), ptr(work), ptr(improvements), _stream()))
+        return (status, cost, model, work, improvements) if stats else (status, cost, model, work)
+
     def exact_solve_assume(self, budget=0, hints=None, assume=None, arena=0, stats=False):
         """The learning search under assumptions (pdp_exact_solve_learn_assume): (status, model, work, failed), plus learned with
         ``stats``.  ``assume`` (int8, V elements, on the problem's device, or None): > 0 the variable is held true, < 0 held false, 0 free.
@@ -592,7 +613,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_min_unsat, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

@@ -149,7 +149,10 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         solved the instance, because the check pass accepts it; every other row keeps its five reference keys.  With config['complete_backbone']
         a satisfiable row also gains "backbone", the signed 1-based literals that hold in every model (ascending by variable; one query of
         the search under assumptions per variable, all instances of the forward in one batch), and, when queries ran out of budget,
-        "backbone_unknown" with their count (those literals are left out)."""
+        "backbone_unknown" with their count (those literals are left out).  With config['complete_min_unsat'] every row whose "complete" is not 1
+        also gains "min_unsat" (the fewest unsatisfied clauses pdp_exact_min_unsat found from PDP's assignment, within the same budget),
+        "min_unsat_proved" (1: that is the minimum over all assignments, 0: an upper bound), "min_unsat_solution" and "min_unsat_work";
+        its five reference keys stay PDP's."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -196,6 +199,20 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                     row['backbone'] = [int(v + 1) * int(bb[v]) for v in np.nonzero(np.abs(bb) == 1)[0]]
                     if (bb == 2).any():
                         row['backbone_unknown'] = int((bb == 2).sum())
+        if self._config.get('complete_min_unsat'):
+            # the rows the search did not satisfy, once more, as one batch of their own: the fewest unsatisfied clauses from PDP's assignment
+            from pdp import exact
+            open_rows = [i for i in range(len(rows)) if status[i] != 1]
+            if open_rows:
+                items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
+                pred = hint.cpu().numpy()
+                st, cost, models, mwork = exact.min_unsat([items[i] for i in open_rows], budget=budget, device=hint.device,
+                                                          hints=[pred[offs[i]:offs[i + 1]] for i in open_rows])
+                for k, i in enumerate(open_rows):
+                    rows[i]['min_unsat'], rows[i]['min_unsat_proved'] = int(cost[k]), int(st[k] == 1)
+                    rows[i]['min_unsat_solution'], rows[i]['min_unsat_work'] = models[k].astype(int).tolist(), int(mwork[k])
+                if hasattr(self, '_min_unsat_stats'):
+                    self._min_unsat_stats[0] += int((st == 1).sum()); self._min_unsat_stats[1] += len(open_rows)
         if hasattr(self, '_complete_stats'):
             for k, s in enumerate((1, 0, -1)):
                 self._complete_stats[k] += int((status == s).sum())

@@ -12,7 +12,10 @@ model against the clauses, an "unsatisfiable" by a forward check of the learned 
 "certified" (1 checked, -1 undecided); ``--complete-core`` (with ``--complete-certify``) judges an "unsatisfiable" by the backward check
 (pdp_exact_trim) and such a row gains "core", the 0-based indices of the clauses its refutation rests on; ``--complete-backbone`` (with
 ``--complete``) gives a satisfiable row "backbone", the signed 1-based literals that hold in every model of the instance (one query of
-the search under assumptions per variable, pdp_exact_solve_learn_assume), and "backbone_unknown" when queries ran out of budget.
+the search under assumptions per variable, pdp_exact_solve_learn_assume), and "backbone_unknown" when queries ran out of budget;
+``--complete-min-unsat`` (with ``--complete``) gives every row that is not satisfiable "min_unsat", the fewest clauses any assignment leaves
+unsatisfied (pdp_exact_min_unsat, branch and bound from the model's assignment), "min_unsat_proved" (1 / 0: the budget ran out and it is
+an upper bound), "min_unsat_solution" and "min_unsat_work".
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -60,6 +63,7 @@ def run(config, logger, output):
     solver = SatFactorGraphTrainer(config=config, use_cuda=not config['cpu_mode'], logger=logger)
     solver._counter = 0
     solver._complete_stats = [0, 0, 0]                  # satisfiable, unsatisfiable, undecided (this rank's units)
+    solver._min_unsat_stats = [0, 0]                    # optima proved, rows asked (this rank's units)
     say("Starting the prediction phase...")
     sink, owned = _open_output(output)
     try:
@@ -70,7 +74,8 @@ def run(config, logger, output):
         if owned:
             sink.close()
     if complete:
-        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d" % tuple(solver._complete_stats))
+        proved = "; minimum unsatisfied clauses proved for %d of %d" % tuple(solver._min_unsat_stats) if config.get('complete_min_unsat') else ""
+        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s" % (tuple(solver._complete_stats) + (proved,)))
     return solver
 
 
@@ -113,6 +118,10 @@ def main(argv=None):
                         'literals that hold in every model of the instance, ascending by variable (pdp_exact_solve_learn_assume, one query per '
                         'variable); literals whose query ran out of --complete-budget are left out and counted in "backbone_unknown"',
                         action='store_true')
+    parser.add_argument('--complete-min-unsat', dest='complete_min_unsat', help='With --complete: every row that is not satisfiable gains "min_unsat", the '
+                        'fewest clauses any assignment leaves unsatisfied (pdp_exact_min_unsat, branch and bound from the model\'s assignment, '
+                        '--complete-budget reads), "min_unsat_proved" (0: the budget ran out, an upper bound), "min_unsat_solution" and "min_unsat_work"',
+                        action='store_true')
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -125,6 +134,8 @@ def main(argv=None):
         parser.error("--complete-core names the core of a certified answer: give --complete-certify as well")
     if args['complete_backbone'] and not args['complete']:
         parser.error("--complete-backbone names the backbone of an answer of --complete: give --complete as well")
+    if args['complete_min_unsat'] and not args['complete']:
+        parser.error("--complete-min-unsat bounds the rows --complete leaves unsatisfied: give --complete as well")
     if args['complete_certify']:
         args['complete_learn'] = True
 

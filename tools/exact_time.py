@@ -28,7 +28,14 @@ Assumption rows (pdp_exact_solve_learn_assume; never part of the default): ``aa`
 the kernel of the search under assumptions, next to pdp_exact_solve_learn on the same problem in the same process (the two kernels
 alternate, TRIM_REPEATS timed calls each, the median is reported; every output must be identical).  ``ab`` = exact.backbone of the first 200
 satisfiable instances of row (a): wall time, the kernel time of its queries (device events around every exact_solve_assume call, the
-one-time preparation of each problem included), queries per second, the backbone fraction and the queries left undecided."""
+one-time preparation of each problem included), queries per second, the backbone fraction and the queries left undecided.
+
+Minimum rows (pdp_exact_min_unsat; never part of the default): ``xa`` / ``xd`` = the instances of row (a) / (d) that pdp_exact_solve answers 0,
+``xm100`` = those of m100 that the learning search answers 0 (the backtracking one leaves some undecided), each as a batch of its own with
+its slice of one p-d-p forward's assignment (the forward of ``ha``) as the incumbent, at the default budget: kernel time, proved / not
+proved, the histogram of the cost, the histogram of PDP's unsat_clauses minus the cost, work median / p99 / max, the ratio to
+pdp_exact_solve's work on the same instances (xm100: under the budget of m100), and the wall time of ``satyr.py --complete`` on the row's
+instances without and with ``--complete-min-unsat``."""
 import io
 import json
 import logging
@@ -340,11 +347,9 @@ def _timed(p, hints):
     return ev[0].elapsed_time(ev[1]), st.cpu().numpy(), wk.cpu().numpy()
 
 
-def run_hinted(key):
-    "the prediction of one p-d-p forward (one segment: the batch is the loader batch) as the hints of the search on the same instances"
+def _pdp_forward(items):
+    "the p-d-p forwards over the items as one loader batch, per segment: (prediction float32 [V], graph_map, variable map, function map, edge feature)"
     from pdp.trainer import SatFactorGraphTrainer
-    title, make = ROWS[key[1:]]
-    items = make()
     cfg = dict(model_type='p-d-p', model_name='exact-time', verbose=False, local_search_iteration=100, epsilon=0.5, tolerance=0.02,
                t_max=100, pi=0.01, decimation_probability=0.5, rng='philox', random_seed=0, hidden_dim=3, test_batch_limit=40000000,
                batch_size=len(items), test_recurrence_num=100)
@@ -357,6 +362,14 @@ def run_hinted(key):
     with tempfile.TemporaryDirectory() as tmp:
         _write_json(items, os.path.join(tmp, 'in.json'))
         tr.predict(os.path.join(tmp, 'in.json'), io.StringIO(), import_path_base=None, post_processor=grab, batch_replication=1)
+    return grabbed
+
+
+def run_hinted(key):
+    "the prediction of one p-d-p forward (one segment: the batch is the loader batch) as the hints of the search on the same instances"
+    title, make = ROWS[key[1:]]
+    items = make()
+    grabbed = _pdp_forward(items)
     assert len(grabbed) == 1, "expected one forward, got %d" % len(grabbed)
     hint, gm, bvm, bfm, ef = grabbed[0]
     p = native.Problem(gm, bvm, bfm, ef, batch_size=len(items))
@@ -397,7 +410,71 @@ def run_wall(key):
           % (key, title, took['plain'], took['plain_solved'], took['complete'], took['complete_solved'], took['unsat'], took['undecided']), flush=True)
 
 
+def _hist(x):
+    return ' '.join('%d:%d' % (v, c) for v, c in enumerate(np.bincount(np.asarray(x, dtype=np.int64))) if c)
+
+
+def run_min_unsat(key):
+    "the unsatisfiable instances of a row as a batch of their own: pdp_exact_min_unsat from PDP's assignment, next to pdp_exact_solve"
+    from pdp import exact
+    modular = key[1:] in MODULAR
+    title, make = MODULAR[key[1:]] if modular else ROWS[key[1:]]
+    items = make()
+    pred = np.concatenate([g[0].cpu().numpy() for g in _pdp_forward(items)])    # the segments of the batch, in order
+    status = exact.solve_items(items, learn=modular)[0]
+    pick = np.nonzero(status == 0)[0]
+    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in items])])
+    assert pred.size == voff[-1], "the forward's variables are not the items'"
+    sub = [items[i] for i in pick]
+    b = dataset.to_torch(dataset.collate_segment(sub), torch.device('cuda:0'))
+    q = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(sub))
+    h = torch.from_numpy(np.concatenate([pred[voff[i]:voff[i + 1]] for i in pick])).to(q.device)
+    pdp_unsat = q.cnf_eval(h.contiguous())[1].cpu().numpy().reshape(-1).astype(np.int64)
+    budget = MODULAR_BUDGET if modular else 0
+    ms0, st0, _, wk0 = _timed_learn(q, budget, False)
+    # the one-time routing preparation is shared with pdp_exact_solve and done by the calls above
+    ms, out = _event_ms(lambda: q.exact_min_unsat(hints=h, stats=True))
+    st, cost, model, wk, imp = [t.cpu().numpy() for t in out]
+    again = q.cnf_eval(torch.from_numpy(model).to(q.device))[1].cpu().numpy().reshape(-1).astype(np.int64)
+    assert np.array_equal(again, cost), "a model does not attain its cost"
+    assert (cost >= 1).all() and (cost <= pdp_unsat).all(), "a cost outside [1, PDP's]"
+    proved = st == 1
+    print("(%s) the %d instances of %s that the %s search answers 0, incumbent = p-d-p forward T=100 -w 100 philox: E=%d  kernel %.2f ms  proved %d  "
+          "not proved %d (budget 2^32)  cost histogram %s  PDP's unsat_clauses minus the cost %s  improvements median %d max %d  "
+          "work median %d  p99 %d  max %d  total %d  %.3g literal reads/s"
+          % (key, len(sub), title, 'learning' if modular else 'deciding', q.E, ms, int(proved.sum()), int((~proved).sum()), _hist(cost),
+             _hist(pdp_unsat - cost), int(np.median(imp)), int(imp.max()), int(np.median(wk)), int(np.percentile(wk, 99)), int(wk.max()),
+             int(wk.sum()), float(wk.sum()) / (ms * 1e-3)), flush=True)
+    both = proved & (st0 == 0)
+    ratio = wk[both] / np.maximum(wk0[both], 1)
+    print("    pdp_exact_solve on the same batch%s: kernel %.2f ms  undecided %d  work total %d;  over the %d instances both finish: work ratio "
+          "min-unsat / deciding median %.2f  p99 %.2f  max %.2f  of the totals %.2f;  by proved cost: %s"
+          % (', budget 2^28' if modular else '', ms0, int((st0 == -1).sum()), int(wk0.sum()), int(both.sum()), float(np.median(ratio)),
+             float(np.percentile(ratio, 99)), float(ratio.max()), float(wk[both].sum()) / max(1.0, float(wk0[both].sum())),
+             '  '.join('cost %d: %d instances, median ratio %.2f' % (c, int((both & (cost == c)).sum()), float(np.median(ratio[cost[both] == c])))
+                       for c in sorted(set(cost[both].tolist())))), flush=True)
+    # the command line runs the same search at the same budget on (nearly) the same instances: its limit is the other runs' ten minutes
+    # plus four times the kernel just measured
+    satyr = os.path.join(REPO, 'pdp-solver_amd', 'satyr.py')
+    yaml = os.path.join(REPO, 'config', 'Predict', 'PDP-p-d-p-sp-pytorch.yaml')
+    with tempfile.TemporaryDirectory() as tmp:
+        _write_json(items, os.path.join(tmp, 'in.json'))
+        took = {}
+        for name, extra in (('complete', []), ('min', ['--complete-min-unsat'])):
+            path = os.path.join(tmp, name + '.jsonl')
+            t0 = time.perf_counter()
+            subprocess.check_call([sys.executable, satyr, yaml, os.path.join(tmp, 'in.json'), '100', '-z', str(len(items)), '-w', '100', '--rng', 'philox',
+                                   '-s', '0', '-o', path, '--complete'] + (['--complete-learn'] if modular else []) + extra,
+                                  stdout=subprocess.DEVNULL, timeout=600 + (4 * ms * 1e-3 if extra else 0))
+            took[name] = time.perf_counter() - t0
+        rows = [json.loads(l) for l in open(os.path.join(tmp, 'min.jsonl')) if l.strip()]
+        asked = [r for r in rows if r['complete'] != 1]
+    print("    satyr.py T=100 -w 100 philox --complete%s on the row's %d instances: wall %.2f s, with --complete-min-unsat %.2f s (%d rows asked, %d proved)"
+          % (' --complete-learn' if modular else '', len(items), took['complete'], took['min'], len(asked), sum(r['min_unsat_proved'] for r in asked)),
+          flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
-        (run_assume if k in ASSUME_ROWS else {'h': run_hinted, 'w': run_wall, 'l': run_learn, 'm': run_learn, 'p': run_proof, 't': run_trim}.get(k[0], run))(k)
+        (run_assume if k in ASSUME_ROWS else {'h': run_hinted, 'w': run_wall, 'x': run_min_unsat, 'l': run_learn, 'm': run_learn, 'p': run_proof, 't': run_trim}.get(k[0], run))(k)
