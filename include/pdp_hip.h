@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -405,8 +405,37 @@ int pdp_exact_solve_learn_assume(pdp_problem *p, const float *hint, const int8_t
 int pdp_exact_min_unsat(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, int32_t *cost, float *model,
                         int64_t *work, int32_t *improvements, void *stream);
 
+/* Exact model counts and per-variable counts of every instance: pdp_exact_solve's search (no hints) that does not stop at the first
+ * assignment under which no clause is open (plain Python, normative: tests/exact_count_model.py).  Outputs per instance:
+ * status = 1, the search is complete and count [B] is the number of models, or -1, the budget ran out and count covers the part of the
+ * tree visited so far (a lower bound), or -2, the instance has more than 1023 variables and is not searched (count, true_count, work and
+ * leaves are 0); never 0: an unsatisfiable instance is status 1 with count 0.  true_count [V] = the models among those counted in which
+ * the variable is true, 0 <= true_count <= count; work [B] (may be NULL) = clause-literal reads; leaves [B] (may be NULL) = the
+ * satisfying cubes met.  n counts every variable of the instance, also one in no clause.  All new arithmetic is IEEE double, in this order:
+ *   State.  count = 0.0, leaves = 0; T[v] = F[v] = 0.0; snap[level] per decision level, snap[0] = 0.0.
+ *   Opening a level.  snap[level] = count.
+ *   Leaf (a pass with no conflict, no unit and no open clause).  count = count + ldexp(1.0, n - trail length), leaves + 1, then continue
+ *      exactly as after a conflict.
+ *   Undoing a level (every level the backtracking pops, and the level whose decision is about to be flipped).  Before its trail entries
+ *      are cleared: d = count - snap[level]; for every u on the level's part of the trail, T[u] += d if u is true, else F[u] += d.  When
+ *      the decision is flipped to its second polarity, snap[level] = count again.
+ *   End (out of levels: status 1; the budget check fired before a pass: status -1).  Every open level is flushed by the same rule, the
+ *      newest first, level 0 (the variables fixed by the first propagation) with d = count; then
+ *      true_count[v] = T[v] + (count - T[v] - F[v]) * 0.5.
+ * Every addend is a non-negative integer and the partial sums are monotone: if count <= 2^53, then count, T, F and true_count are exact
+ * integers (count - T - F is even); above, they are the correctly rounded results of this operation order.  Up to n = 1023, 2^n and every
+ * partial sum are finite.  The passes, the branching rule (first polarity the one with at least as many occurrences), the budget check and
+ * work < budget + 3 * (edges of the instance) are pdp_exact_solve's.  All five outputs are a function of the instance and the budget alone:
+ * count and snap are uniform over the wave, T[u] and F[u] are updated by the one lane that holds u's trail slot, and there is no
+ * floating-point reduction across lanes.  Every satisfying cube is visited, with no component decomposition and no caching: an
+ * under-constrained instance ends at the budget with a lower bound.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream rules; routing and working arrays are pdp_exact_solve's, shared with it; the LDS slab is
+ * pdp_exact_solve's plus 24 n + 8 bytes of the kernel's own for snap, T and F (in HBM on the HBM route, T being true_count itself). */
+int pdp_exact_count(pdp_problem *p, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work, int64_t *leaves,
+                    void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an
  * integer v >= 1 and is ignored otherwise (unset, empty, 0, negative, not a number) -- a test switch that makes a wave run many

@@ -37,7 +37,7 @@ namespace {
 constexpr int EX_NT = 64;                       // one wave per instance
 constexpr size_t EX_LDS_LIMIT = 48 * 1024;      // per-instance slab: at least three instances per CU (160 KiB of LDS)
 
-// PDP_EXACT_GRID=<v>, read at every launch of the four persistent kernels: an integer v >= 1 lowers the workgroup count to min(grid, v);
+// PDP_EXACT_GRID=<v>, read at every launch of the persistent kernels: an integer v >= 1 lowers the workgroup count to min(grid, v);
 // any other value (unset, empty, 0, negative, not a number) leaves it.  Tests: many instances per wave, one after the other in one slab,
 // on small batches.  After a launch that succeeded the count is kept on the problem (ex_last_grid) for pdp_exact_last_grid.
 inline int64_t ex_grid(int64_t grid)
@@ -694,6 +694,344 @@ int exm_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status
     const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
     PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
     hipLaunchKernelGGL(k_exact_min, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
+    return PDP_OK;
+}
+
+// ---- pdp_exact_count: exact model counts and per-variable counts by the same passes, without stopping at the first model ---------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_count_model.py).  Its own search, kernel and launch path: nothing above is
+// touched.  The state is ex_search's, array for array, plus three arrays of doubles: snap [n+1], the count when a level was opened or its
+// decision flipped, and T [n] / F [n], the models counted under v = true / v = false while v was assigned.  On the LDS route they follow
+// ex_lds_layout's slab (24 n + 8 bytes of this kernel's own; an instance that is searched has n <= 1023, so the slab stays below 73 KiB
+// and ex_prepare's routing holds as it is); on the HBM route T is the instance's slice of the true_count output, F and snap are working
+// arrays on the handle.  count and snap are uniform over the wave; T[u] / F[u] are updated by the lane that holds u's trail slot, in
+// chunks of 64; a variable is on the trail once, so no two lanes meet, and a barrier lies between any two updates of one variable.
+constexpr int EXN_MAX_N = 1023;                 // 2^n and every partial sum are finite doubles up to here
+
+struct ExnLds { size_t snap, T, F, bytes; };
+
+// ex_lds_layout's slab (a multiple of 16 bytes), then the doubles
+__host__ __device__ inline ExnLds exn_lds_layout(int n, int m, int e)
+{
+    ExnLds L;
+    size_t o = ex_lds_layout(n, m, e).bytes;
+    L.snap = o; o += 8 * ((size_t)n + 1);
+    L.T = o;    o += 8 * (size_t)n;
+    L.F = o;    o += 8 * (size_t)n;
+    L.bytes = (o + 15) & ~(size_t)15;
+    return L;
+}
+
+struct ExnParams {
+    const int32_t *order;       // as ExParams
+    int nbig, B;
+    uint32_t *next;
+    int64_t budget;
+    int8_t *status; double *count; double *true_count; int64_t *work; int64_t *leaves;
+    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+    double *h_F;                // [V]   (HBM route; its T is true_count)
+    double *h_snap;             // [V+B] (instance b at v0 + b: n+1 entries)
+};
+
+struct ExnAcc { double *T, *F, *snap; };
+
+// The models counted since `level` was opened go to the variables on trail[from .. tlen): T[u] if u is true, F[u] if false.  d == 0 adds
+// nothing to a non-negative sum, bit for bit, so the loads and stores are skipped then (d is uniform over the wave).
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ void exn_credit(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int from, int tlen, double d)
+{
+    if (d == 0.0) return;
+    for (int i = from + (int)threadIdx.x; i < tlen; i += EX_NT) {
+        const int u = X.trail[i];
+        double *acc = X.val[u] == 1 ? A.T : A.F;
+        acc[u] = acc[u] + d;
+    }
+}
+
+// The counting search of one instance by the calling wave: ex_search<HBM, false> where a state without an open clause is a leaf that adds
+// 2^(unassigned variables) to the count and backtracks.  Returns 1 (complete) or -1 (budget spent); T and F hold every level's credit.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_count(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int64_t budget, int64_t *work_out, double *count_out,
+                               int64_t *leaves_out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0;
+    int64_t work = 0, leaves = 0;
+    double count = 0.0;
+    int result = -1;
+    for (;;) {
+        if (work >= budget) break;
+        // ---- one unit-propagation pass (ex_search's: keep the two in step)
+        int reads = 0, conflict = 0, unit = 0, wmin = INF;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat) continue;
+            if (nfree == 0) conflict = 1;
+            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
+            else wmin = nfree < wmin ? nfree : wmin;
+        }
+        work += ex_sum(reads);
+        bool any_conflict = __ballot(conflict) != 0ull;
+        const bool any_unit = __ballot(unit) != 0ull;
+        if (any_unit) {
+            // assign the pending set of the pass; a variable asked for both polarities is a conflict
+            ex_sync<HBM>();
+            int bad = 0;
+            for (int base = 0; base < X.n; base += EX_NT) {
+                const int v = base + lane;
+                const uint32_t bits = v < X.n ? X.pend[v] : 0u;
+                const unsigned long long mask = __ballot(bits != 0u);
+                if (bits) {
+                    X.pend[v] = 0u;
+                    X.val[v] = (bits & 1u) ? 1 : 2;
+                    bad |= bits == 3u;
+                    X.trail[tlen + __popcll(mask & below)] = v;
+                }
+                tlen += __popcll(mask);
+            }
+            any_conflict = any_conflict || __ballot(bad) != 0ull;
+            ex_sync<HBM>();
+        }
+        if (!any_conflict) {
+            if (any_unit) continue;
+            wmin = ex_min(wmin);
+            if (wmin == INF) {
+                // a leaf: every clause has a true literal and the unassigned variables are free; then as after a conflict
+                count = count + ldexp(1.0, X.n - tlen);
+                ++leaves;
+                any_conflict = true;
+            }
+        }
+        if (any_conflict) {
+            // chronological backtracking, ex_search's block with the credit of every undone level (keep the two in step)
+            bool resumed = false;
+            while (level > 0) {
+                const uint32_t d = X.dvar[level];
+                const int v = (int)(d & 0x7fffffffu);
+                const int from = X.mark[level];
+                const uint32_t first = X.val[v];
+                const double since = count - A.snap[level];
+                ex_sync<HBM>();                                     // every lane has read the level before it is undone
+                exn_credit(X, A, from, tlen, since);
+                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;      // the same lane as the credit
+                tlen = from;
+                if (!(d & 0x80000000u)) {
+                    ex_sync<HBM>();
+                    if (lane == 0) {
+                        X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v;
+                        A.snap[level] = count;                      // the level stays open: its first half is credited once
+                    }
+                    ++tlen;
+                    ex_sync<HBM>();
+                    resumed = true;
+                    break;
+                }
+                --level;
+            }
+            if (!resumed) { result = 1; break; }
+            continue;
+        }
+        // ---- branching: ex_search's, without hints (keep the two in step)
+        reads = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) ++nfree;
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat || nfree != wmin) continue;
+            for (int j = a; j < z; ++j) {
+                const uint32_t L = X.lit[j];
+                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+            }
+            reads += z - a;
+        }
+        work += ex_sum(reads);
+        ex_sync<HBM>();
+        unsigned long long best = 0ull;
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+            if (p | q) {
+                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                               (p >= q ? 1ull : 0ull);
+                best = key > best ? key : best;
+            }
+        }
+        best = ex_max64(best);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        ++level;
+        ex_sync<HBM>();
+        if (lane == 0) {
+            X.mark[level] = tlen; X.dvar[level] = (uint32_t)v; X.val[v] = (best & 1ull) ? 1 : 2; X.trail[tlen] = v;
+            A.snap[level] = count;
+        }
+        ++tlen;
+        ex_sync<HBM>();
+    }
+    // the end: every open level is flushed, the newest first; level 0 holds the variables of the first propagation (mark 0, snap 0.0).
+    // The levels' variables are disjoint and every path here has passed a barrier since the last write of mark, snap, trail and val.
+    for (; level >= 0; --level) {
+        const int from = level > 0 ? X.mark[level] : 0;
+        exn_credit(X, A, from, tlen, count - A.snap[level]);
+        tlen = from;
+    }
+    *work_out = work; *count_out = count; *leaves_out = leaves;
+    return result;
+}
+
+// copy the instance's literals in clause order, clear the state, search, write the results
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_count(const ExnParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExnAcc A, PtrT *cptr_fill)
+{
+    const int lane = (int)threadIdx.x;
+    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+    for (int k = lane; k < I.e; k += EX_NT) {
+        const int ed = I.f_edges[k];
+        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+    }
+    for (int v = lane; v < I.n; v += EX_NT) {
+        X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        A.T[v] = 0.0; A.F[v] = 0.0;
+    }
+    if (lane == 0) A.snap[0] = 0.0;
+    ex_sync<HBM>();
+    int64_t work = 0, leaves = 0;
+    double count = 0.0;
+    const int st = ex_search_count<HBM>(X, A, xp.budget, &work, &count, &leaves);
+    ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
+    for (int v = lane; v < I.n; v += EX_NT) {
+        const double t = A.T[v];
+        xp.true_count[I.v0 + v] = t + (count - t - A.F[v]) * 0.5;
+    }
+    if (lane == 0) {
+        xp.status[I.b] = (int8_t)st;
+        xp.count[I.b] = count;
+        if (xp.work) xp.work[I.b] = work;
+        if (xp.leaves) xp.leaves[I.b] = leaves;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_count(PView pv, ExnParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        if (I.n > EXN_MAX_N) {
+            // 2^n need not be a finite double: not searched.  This arm ends in the barrier every arm of the loop ends in, and falls
+            // through to the end of the loop body: the wave must be whole again before the shuffle that hands out the next instance
+            // (a `continue` after the lane-0 block let the compiler thread lane 0 alone to the atomic and the other lanes to the shuffle).
+            for (int v = (int)threadIdx.x; v < I.n; v += EX_NT) xp.true_count[I.v0 + v] = 0.0;
+            if (threadIdx.x == 0) {
+                xp.status[I.b] = (int8_t)-2;
+                xp.count[I.b] = 0.0;
+                if (xp.work) xp.work[I.b] = 0;
+                if (xp.leaves) xp.leaves[I.b] = 0;
+            }
+            ex_sync<false>();
+        } else if (i < xp.nbig) {
+            ExInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
+            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
+            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ExnAcc A;
+            A.T = xp.true_count + I.v0; A.F = xp.h_F + I.v0; A.snap = xp.h_snap + I.v0 + I.b;
+            ex_solve_count<true, uint32_t, int32_t>(xp, I, X, A, (int32_t *)nullptr);
+        } else {
+            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
+            const ExnLds N = exn_lds_layout(I.n, I.m, I.e);
+            ExInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
+            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
+            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ExnAcc A;
+            A.T = (double *)(ex_slab + N.T); A.F = (double *)(ex_slab + N.F); A.snap = (double *)(ex_slab + N.snap);
+            ex_solve_count<false, uint16_t, uint16_t>(xp, I, X, A, (uint16_t *)(ex_slab + L.cptr));
+        }
+    }
+}
+
+// ex_prepare's routing and order, plus what the count kernel needs of its own: the largest slab of its layout over the LDS-routed
+// instances it searches (n <= 1023), and F [V] | snap [V+B] for the HBM route.  Once per problem.
+int exn_prepare(pdp_problem *p)
+{
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    if (p->exn_ready) return PDP_OK;
+    const size_t B = p->B, V = p->V;
+    std::vector<int32_t> v0(B + 1), f0(B + 1), e0(B + 1);
+    PDP_HIP_CHECK(hipMemcpy(v0.data(), p->inst_v0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(f0.data(), p->inst_f0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(e0.data(), p->inst_e0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    size_t lds = 0;
+    for (size_t b = 0; b < B; ++b) {
+        const int n = v0[b + 1] - v0[b], m = f0[b + 1] - f0[b], e = e0[b + 1] - e0[b];
+        if (n <= EXN_MAX_N && ex_fits_lds(n, m, e)) lds = std::max(lds, exn_lds_layout(n, m, e).bytes);
+    }
+    p->exn_lds_bytes = lds;
+    p->exn_blob = nullptr;
+    if (p->ex_nbig > 0) {
+        const int st_ = pdp_dev_alloc((void **)&p->exn_blob, (V * 8 + (V + B) * 8 + 15) & ~(size_t)15);
+        if (st_ != PDP_OK) return st_;
+    }
+    p->exn_ready = 1;
+    return PDP_OK;
+}
+
+int exn_launch(pdp_problem *p, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work, int64_t *leaves, void *stream)
+{
+    { const int st_ = exn_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    ExnParams xp;
+    xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.status = status; xp.count = count; xp.true_count = true_count; xp.work = work; xp.leaves = leaves;
+    const size_t V = p->V, E = p->E, B = p->B;
+    if (p->ex_h_lit) {
+        char *q = (char *)p->ex_h_lit;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_pend = (uint32_t *)q;           q += V * 4;
+        xp.h_cnt = (uint32_t *)q;            q += V * 8;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
+        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
+        xp.h_val = (uint8_t *)q;
+        xp.h_F = (double *)p->exn_blob;
+        xp.h_snap = (double *)(p->exn_blob + V * 8);
+    } else {
+        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
+        xp.h_val = nullptr; xp.h_F = nullptr; xp.h_snap = nullptr;
+    }
+    const int lds = (int)p->exn_lds_bytes;
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_count, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_count, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
+    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_count, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
     p->ex_last_grid = (int32_t)grid;
     return PDP_OK;
@@ -2040,6 +2378,17 @@ extern "C" int pdp_exact_min_unsat(pdp_problem *p, const float *hint, int64_t bu
         return PDP_ERR_UNSUPPORTED;
     }
     return exm_launch(p, hint, budget, status, cost, model, work, improvements, stream);
+}
+
+extern "C" int pdp_exact_count(pdp_problem *p, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work, int64_t *leaves,
+                               void *stream)
+{
+    PDP_REQUIRE(p && status && count && true_count, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_count: a replicated problem (R = %d) is not supported; count on the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exn_launch(p, budget, status, count, true_count, work, leaves, stream);
 }
 
 extern "C" int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work,

@@ -12,7 +12,9 @@ lemmas it needs (``core_clauses``, ``trimmed``).  With ``assume=`` the question 
 which of them are to blame" (pdp_exact_solve_learn_assume); ``backbone`` asks it once per variable of every satisfiable
 instance, in one batch: the literals that hold in every model.  ``min_unsat`` optimises instead of deciding: the fewest clauses any
 assignment leaves unsatisfied, by branch and bound from a given assignment (pdp_exact_min_unsat) -- what an incomplete
-solver's ``unsat_clauses`` on an unsatisfiable instance is to be compared with.
+solver's ``unsat_clauses`` on an unsatisfiable instance is to be compared with.  ``count_models`` counts instead of deciding: the exact
+number of models of an instance and, per variable, the share of them in which it is true (pdp_exact_count) -- what PDP's
+soft prediction is to be compared with.
 """
 
 import numpy as np
@@ -22,6 +24,7 @@ from pdp import native
 from pdp.factorgraph import dataset
 
 MAX_EDGES = 1 << 24          # edges per problem handed to the library
+COUNT_MAX_N = 1023           # pdp_exact_count searches instances of up to this many variables (2^n is a finite double)
 
 
 def raw_item(n, clauses, label=-1.0, name=""):
@@ -374,6 +377,51 @@ def min_unsat(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
             models[i] = model[off:off + n].copy()
             off += n
     return status, cost, models, work
+
+
+def count_models(items, budget=0, device=None, max_edges=MAX_EDGES):
+    """Exact model counts of loader items (as solve_items takes them) by the counting search (pdp_exact_count).  Returns numpy (status int8
+    [N]: 1 count is the number of models, -1 the budget ran out and it is a lower bound, -2 the instance has more than 1023 variables and
+    was not searched; count float64 [N], over all n_i variables of an instance, unused ones included; marginals: per instance a float64
+    array of n_i values, the share of the counted models in which the variable is true, or None where count is 0; work int64 [N]).
+    count_is_exact says where count is an integer without rounding."""
+    native.require_gpu()
+    device = torch.device('cuda:0') if device is None else torch.device(device)
+    N = len(items)
+    status = np.ones(N, dtype=np.int8)
+    count = np.zeros(N, dtype=np.float64)
+    work = np.zeros(N, dtype=np.int64)
+    marginals = [None] * N
+    for seg in _segments(items, max_edges):
+        part = [items[i] for i in seg]
+        if sum(int(it[2].shape[1]) for it in part) == 0:
+            # no literal anywhere (and no problem to build: the layout needs an edge): without a clause every assignment is a model,
+            # with an (empty) clause none is
+            for i, it in zip(seg, part):
+                n = int(it[0])
+                if n > COUNT_MAX_N:
+                    status[i] = -2
+                elif int(it[1]) == 0:
+                    count[i] = np.ldexp(1.0, n)
+                    marginals[i] = np.full(n, 0.5, dtype=np.float64)
+            continue
+        with torch.cuda.device(device):
+            prob = _problem(part, device)
+            st, co, tc, wk = [t.cpu().numpy() for t in prob.exact_count(budget)]
+        del prob
+        off = 0
+        for j, (i, it) in enumerate(zip(seg, part)):
+            n = int(it[0])
+            status[i], count[i], work[i] = st[j], co[j], wk[j]
+            if co[j] > 0:
+                marginals[i] = tc[off:off + n] / co[j]
+            off += n
+    return status, count, marginals, work
+
+
+def count_is_exact(status, count):
+    "boolean array: the search was complete and count <= 2^53, so count and the per-variable counts are exact integers"
+    return (np.asarray(status) == 1) & (np.asarray(count, dtype=np.float64) <= 2.0 ** 53)
 
 
 def backbone(items, budget=0, device=None, max_edges=MAX_EDGES, arena=0):

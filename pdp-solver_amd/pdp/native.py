@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = [
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
     'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid', 'pdp_exact_solve_learn_assume',
-    'pdp_exact_min_unsat',
+    'pdp_exact_min_unsat', 'pdp_exact_count',
 ]
 
 
@@ -464,6 +464,24 @@ class Problem(object):
                                         ptr(model), ptr(work), ptr(improvements), _stream()))
         return (status, cost, model, work, improvements) if stats else (status, cost, model, work)
 
+    def exact_count(self, budget=0, stats=False):
+        """Exact model counts and per-variable counts of every instance (pdp_exact_count): (status int8 [B]: 1 the search is complete and
+        count is the number of models, -1 the budget ran out and count covers the part of the tree visited so far, a lower bound, -2 the
+        instance has more than 1023 variables and was not searched; count float64 [B]; true_count float64 [V]: the models among those
+        counted in which the variable is true; work int64 [B]), plus leaves int64 [B] with ``stats``: the satisfying cubes met.  An
+        unsatisfiable instance is status 1 with count 0.  While count <= 2^53 every value is an exact integer.  ``budget`` as in
+        exact_solve.  Asynchronous on the current stream."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads (0: the library default), got %r" % (budget,))
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        count = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        true_count = torch.empty(self.V, dtype=torch.float64, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        leaves = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_count(self._h, C.c_int64(int(budget)), ptr(status), ptr(count), ptr(true_count), ptr(work), ptr(leaves),
+                                    _stream()))
+        return (status, count, true_count, work, leaves) if stats else (status, count, true_count, work)
+
     def exact_solve_assume(self, budget=0, hints=None, assume=None, arena=0, stats=False):
         """The learning search under assumptions (pdp_exact_solve_learn_assume): (status, model, work, failed), plus learned with
         ``stats``.  ``assume`` (int8, V elements, on the problem's device, or None): > 0 the variable is held true, < 0 held false, 0 free.
@@ -613,7 +631,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_min_unsat, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_min_unsat, exact_count, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

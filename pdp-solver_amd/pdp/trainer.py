@@ -152,7 +152,11 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         "backbone_unknown" with their count (those literals are left out).  With config['complete_min_unsat'] every row whose "complete" is not 1
         also gains "min_unsat" (the fewest unsatisfied clauses pdp_exact_min_unsat found from PDP's assignment, within the same budget),
         "min_unsat_proved" (1: that is the minimum over all assignments, 0: an upper bound), "min_unsat_solution" and "min_unsat_work";
-        its five reference keys stay PDP's."""
+        its five reference keys stay PDP's.  With config['complete_count'] every row whose "complete" is 1 gains "model_count" (pdp_exact_count within
+        the same budget: an int while it is exact, a float above 2^53), "model_count_log2", "model_count_proved" (1: the number of models, 0: the budget
+        ran out, a lower bound), "marginals" (per variable, the share of the counted models in which it is true), "marginal_gap" (the mean
+        over the variables of |the soft prediction - marginal|) and "count_work"; marginals and marginal_gap are left out where nothing was
+        counted, and an instance of more than 1023 variables keeps its row as it is."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -213,6 +217,28 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                     rows[i]['min_unsat_solution'], rows[i]['min_unsat_work'] = models[k].astype(int).tolist(), int(mwork[k])
                 if hasattr(self, '_min_unsat_stats'):
                     self._min_unsat_stats[0] += int((st == 1).sum()); self._min_unsat_stats[1] += len(open_rows)
+        if self._config.get('complete_count'):
+            # the satisfiable rows, once more, as one batch of their own: how many models, and how far every variable is from being forced
+            from pdp import exact
+            sat_rows = [i for i in range(len(rows)) if status[i] == 1]
+            if sat_rows:
+                items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
+                pred = hint.cpu().numpy().astype(np.float64)
+                st, count, marginals, cwork = exact.count_models([items[i] for i in sat_rows], budget=budget, device=hint.device)
+                exact_int = exact.count_is_exact(st, count)
+                for k, i in enumerate(sat_rows):
+                    if st[k] == -2:
+                        continue                                        # more than 1023 variables: not counted, the row stays as it is
+                    row = rows[i]
+                    row['model_count'] = int(count[k]) if exact_int[k] else float(count[k])
+                    row['model_count_log2'] = float(np.log2(count[k])) if count[k] > 0 else None
+                    row['model_count_proved'] = int(st[k] == 1)
+                    if count[k] > 0:
+                        row['marginals'] = marginals[k].tolist()
+                        row['marginal_gap'] = float(np.mean(np.abs(pred[offs[i]:offs[i + 1]] - marginals[k])))
+                    row['count_work'] = int(cwork[k])
+                if hasattr(self, '_count_stats'):
+                    self._count_stats[0] += int((st == 1).sum()); self._count_stats[1] += len(sat_rows)
         if hasattr(self, '_complete_stats'):
             for k, s in enumerate((1, 0, -1)):
                 self._complete_stats[k] += int((status == s).sum())

@@ -15,7 +15,10 @@ model against the clauses, an "unsatisfiable" by a forward check of the learned 
 the search under assumptions per variable, pdp_exact_solve_learn_assume), and "backbone_unknown" when queries ran out of budget;
 ``--complete-min-unsat`` (with ``--complete``) gives every row that is not satisfiable "min_unsat", the fewest clauses any assignment leaves
 unsatisfied (pdp_exact_min_unsat, branch and bound from the model's assignment), "min_unsat_proved" (1 / 0: the budget ran out and it is
-an upper bound), "min_unsat_solution" and "min_unsat_work".
+an upper bound), "min_unsat_solution" and "min_unsat_work"; ``--complete-count`` (with ``--complete``) gives every satisfiable row "model_count",
+the exact number of its models (pdp_exact_count), "model_count_log2", "model_count_proved" (1 / 0: the budget ran out and it is a lower bound),
+"marginals" (per variable, the share of the models in which it is true), "marginal_gap" (the mean distance of the model's soft prediction
+from them) and "count_work".
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -64,6 +67,7 @@ def run(config, logger, output):
     solver._counter = 0
     solver._complete_stats = [0, 0, 0]                  # satisfiable, unsatisfiable, undecided (this rank's units)
     solver._min_unsat_stats = [0, 0]                    # optima proved, rows asked (this rank's units)
+    solver._count_stats = [0, 0]                        # counts completed, rows asked (this rank's units)
     say("Starting the prediction phase...")
     sink, owned = _open_output(output)
     try:
@@ -75,7 +79,8 @@ def run(config, logger, output):
             sink.close()
     if complete:
         proved = "; minimum unsatisfied clauses proved for %d of %d" % tuple(solver._min_unsat_stats) if config.get('complete_min_unsat') else ""
-        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s" % (tuple(solver._complete_stats) + (proved,)))
+        counted = "; models counted for %d of %d" % tuple(solver._count_stats) if config.get('complete_count') else ""
+        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s%s" % (tuple(solver._complete_stats) + (proved, counted)))
     return solver
 
 
@@ -122,6 +127,10 @@ def main(argv=None):
                         'fewest clauses any assignment leaves unsatisfied (pdp_exact_min_unsat, branch and bound from the model\'s assignment, '
                         '--complete-budget reads), "min_unsat_proved" (0: the budget ran out, an upper bound), "min_unsat_solution" and "min_unsat_work"',
                         action='store_true')
+    parser.add_argument('--complete-count', dest='complete_count', help='With --complete: every satisfiable row gains "model_count", the exact number of '
+                        'its models (pdp_exact_count, --complete-budget reads), "model_count_log2", "model_count_proved" (0: the budget ran out, a lower '
+                        'bound), "marginals" (the share of the models in which each variable is true), "marginal_gap" (the mean distance of the '
+                        'soft prediction from them) and "count_work"', action='store_true')
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -136,6 +145,8 @@ def main(argv=None):
         parser.error("--complete-backbone names the backbone of an answer of --complete: give --complete as well")
     if args['complete_min_unsat'] and not args['complete']:
         parser.error("--complete-min-unsat bounds the rows --complete leaves unsatisfied: give --complete as well")
+    if args['complete_count'] and not args['complete']:
+        parser.error("--complete-count counts the models of the rows --complete satisfies: give --complete as well")
     if args['complete_certify']:
         args['complete_learn'] = True
 

@@ -35,7 +35,13 @@ Minimum rows (pdp_exact_min_unsat; never part of the default): ``xa`` / ``xd`` =
 its slice of one p-d-p forward's assignment (the forward of ``ha``) as the incumbent, at the default budget: kernel time, proved / not
 proved, the histogram of the cost, the histogram of PDP's unsat_clauses minus the cost, work median / p99 / max, the ratio to
 pdp_exact_solve's work on the same instances (xm100: under the budget of m100), and the wall time of ``satyr.py --complete`` on the row's
-instances without and with ``--complete-min-unsat``."""
+instances without and with ``--complete-min-unsat``.
+
+Count rows (pdp_exact_count; never part of the default): ``ca`` / ``cd`` = the instances of row (a) / (d) that pdp_exact_solve answers 1, each as
+a batch of its own at the default budget: kernel time (one call, after a call with a budget of one read that does the one-time
+preparation), complete counts / lower bounds, leaves and work median / p99 / max, the ratio to pdp_exact_solve's work on the same batch,
+the distribution of log2(count), and the mean over the instances of marginal_gap, the mean distance of one p-d-p forward's prediction
+(the forward of ``ha``) from the exact marginals."""
 import io
 import json
 import logging
@@ -474,7 +480,56 @@ def run_min_unsat(key):
           flush=True)
 
 
+COUNT_ROWS = ('ca', 'cd')
+
+
+def _q(x):
+    return "median %.4g  p99 %.4g  max %.4g" % (float(np.median(x)), float(np.percentile(x, 99)), float(np.max(x)))
+
+
+def run_count(key):
+    "the satisfiable instances of a row as a batch of their own: pdp_exact_count next to pdp_exact_solve, and PDP's prediction against the marginals"
+    from pdp import exact
+    title, make = ROWS[key[1:]]
+    items = make()
+    pred = np.concatenate([g[0].cpu().numpy() for g in _pdp_forward(items)]).astype(np.float64)
+    status = exact.solve_items(items)[0]
+    pick = np.nonzero(status == 1)[0]
+    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in items])])
+    assert pred.size == voff[-1], "the forward's variables are not the items'"
+    sub = [items[i] for i in pick]
+    b = dataset.to_torch(dataset.collate_segment(sub), torch.device('cuda:0'))
+    q = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(sub))
+    ms0, st0, _, wk0 = _timed_learn(q, 0, False)
+    assert (st0 == 1).all(), "the batch of satisfiable instances is not satisfiable"
+    q.exact_count(1)                                                                 # the one-time preparation is not timed
+    ms, out = _event_ms(lambda: q.exact_count(stats=True))
+    st, count, tc, wk, leaves = [t.cpu().numpy() for t in out]
+    assert (count[st == 1] > 0).all() and (tc >= 0).all(), "a satisfiable instance without a model"
+    done, some = st == 1, count > 0
+    soff = np.concatenate([[0], np.cumsum([int(it[0]) for it in sub])])
+    gap = np.array([np.mean(np.abs(pred[voff[i]:voff[i + 1]] - tc[soff[k]:soff[k + 1]] / count[k])) if some[k] else np.nan for k, i in enumerate(pick)])
+    lg = np.log2(count[some])
+    ratio = wk[done] / np.maximum(wk0[done], 1)
+    print("(%s) the %d instances of %s that the deciding search answers 1: E=%d  kernel %.2f ms  complete counts %d  lower bounds %d (budget 2^32; "
+          "%d of them with nothing counted)  not searched %d  exact (count <= 2^53) %d  leaves %s  work %s  total %d  %.3g literal reads/s"
+          % (key, len(sub), title, q.E, ms, int(done.sum()), int((st == -1).sum()), int(((st == -1) & ~some).sum()), int((st == -2).sum()),
+             int(exact.count_is_exact(st, count).sum()), _q(leaves), _q(wk), int(wk.sum()), float(wk.sum()) / (ms * 1e-3)), flush=True)
+    print("    pdp_exact_solve on the same batch: kernel %.2f ms  work total %d;  over the %d complete counts: work ratio count / deciding %s  of the "
+          "totals %.2f" % (ms0, int(wk0.sum()), int(done.sum()), _q(ratio) if done.any() else "-",
+                           float(wk[done].sum()) / max(1.0, float(wk0[done].sum()))), flush=True)
+    print("    log2(count) over the %d instances with a count: min %.2f  %s;  by tens of bits: %s;  over the complete counts alone: %s"
+          % (int(some.sum()), float(lg.min()), _q(lg), '  '.join('%d-%d: %d' % (10 * v, 10 * v + 9, c) for v, c in enumerate(np.bincount((lg // 10).astype(np.int64))) if c),
+             _q(np.log2(count[done])) if done.any() else "-"), flush=True)
+    print("    marginal_gap (mean over the variables of |p-d-p forward T=100 -w 100 philox prediction - exact marginal|): mean %.4f over the %d "
+          "complete counts, %.4f over the %d lower bounds with a count;  share of backbone variables (marginal 0 or 1) over the complete counts %.3f"
+          % (float(np.nanmean(gap[done])) if done.any() else float('nan'), int(done.sum()),
+             float(np.nanmean(gap[~done & some])) if (~done & some).any() else float('nan'), int((~done & some).sum()),
+             float(np.mean(np.concatenate([(lambda m: (m == 0) | (m == 1))(tc[soff[k]:soff[k + 1]] / count[k]) for k in np.nonzero(done)[0]]))) if done.any() else float('nan')),
+          flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
-        (run_assume if k in ASSUME_ROWS else {'h': run_hinted, 'w': run_wall, 'x': run_min_unsat, 'l': run_learn, 'm': run_learn, 'p': run_proof, 't': run_trim}.get(k[0], run))(k)
+        (run_count if k in COUNT_ROWS else run_assume if k in ASSUME_ROWS else {'h': run_hinted, 'w': run_wall, 'x': run_min_unsat, 'l': run_learn, 'm': run_learn, 'p': run_proof, 't': run_trim}.get(k[0], run))(k)
