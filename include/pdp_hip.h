@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -434,8 +434,42 @@ int pdp_exact_min_unsat(pdp_problem *p, const float *hint, int64_t budget, int8_
 int pdp_exact_count(pdp_problem *p, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work, int64_t *leaves,
                     void *stream);
 
+/* pdp_exact_solve_hinted with the search of every instance spread over 2^depth[b] waves (plain Python, normative:
+ * tests/exact_split_model.py).  The deciding search is a deterministic depth-first tree; a cube is a prefix of it: cube
+ * `index` of the 2^depth cubes of an instance is that search, without its check pass, where the decision of every level L <= depth is
+ * pinned -- the polarity the search would try first if bit (index >> (depth - L)) & 1 is 0, else the other one -- and the level counts as
+ * already flipped, so backtracking pops through it and a cube whose subtree is exhausted answers 0.  A cube that meets a state without
+ * an open clause before `depth` levels exist answers 1 with that model.  The cubes partition the tree in the order the plain search walks
+ * it, so with a budget that no cube exhausts status and model are pdp_exact_solve_hinted's bit for bit, at every depth.
+ *   hint [V] (device; NULL: none) as pdp_exact_solve_hinted.  depth [B] (device int8; NULL: all 0) in 0 .. 16; at most 2^22 cubes per call;
+ *   either violated -> PDP_ERR_INVALID, the message names the instance.  An instance on the HBM route is searched at depth 0 (its working
+ *   arrays are per instance).  depth_used [B] (int8, may be NULL) = the depth each instance was searched at.
+ *   The check pass runs once per instance, in a kernel of its own before the cubes, under pdp_exact_solve_hinted's condition (no hint of
+ *   the instance is NaN); if it accepts: status 1, that model, work = its reads, first = -1, and the instance's cubes are not searched
+ *   (cube status -2, work 0).  Otherwise its reads count against the budget of EVERY cube of the instance: a cube checks
+ *   check reads + its own reads >= budget before every pass (budget <= 0: PDP_EXACT_DEFAULT_BUDGET), as the plain search does.
+ *   first [B] (int32, may be NULL) = the lowest cube that answers 1, or -1.  If it exists: status 1, model = that cube's, work = check reads
+ *   + the work of cubes 0 .. first.  Else status 0 if every cube answers 0, otherwise -1; model 0; work = check reads + the work of all
+ *   cubes.  depth 0 gives pdp_exact_solve_hinted's three outputs exactly (pdp_exact_solve's with hint NULL).
+ *   work < cubes * (budget + 3 * edges of the instance).
+ * One wave takes one cube at a time from one counter: instance order, within an instance ascending index.  A cube that answers 1 lowers
+ * best[b] to its index (one atomic minimum); at every budget check a cube whose index is ABOVE best[b] stops (cube status -2).  A cube
+ * never stops because of a higher cube and no wave waits for another, so cubes 0 .. first always run to their own end: status, model, work,
+ * first, depth_used and the records of cubes <= first are a function of the instance, its hints, its depth and the budget alone.  The
+ * records of cubes above first (which of them stopped, and after how many reads) depend on timing.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Routing and working arrays are pdp_exact_solve's, shared with it.  The call synchronises the stream once
+ * (the cube count sizes its records and its grid); the kernels that follow are asynchronous on it. */
+int pdp_exact_solve_split(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, float *model,
+                          int64_t *work, int32_t *first, int8_t *depth_used, void *stream);
+
+/* The per-cube records of the last pdp_exact_solve_split call on the problem that succeeded (PDP_ERR_INVALID before the first): cube_off
+ * [B+1] (int64; instance b owns cubes cube_off[b] .. cube_off[b+1]), cube_status [cubes] (1 / 0 / -1, -2 stopped early or not searched) and
+ * cube_work [cubes], cubes = cube_off[B] = the sum of 2^depth_used.  Device to device, asynchronous on the stream. */
+int pdp_exact_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int64_t *cube_work, void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split (its cube kernel:
+ * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an
  * integer v >= 1 and is ignored otherwise (unset, empty, 0, negative, not a number) -- a test switch that makes a wave run many

@@ -151,7 +151,11 @@ struct pdp_problem {
     int ext_ready, ext_nbig; size_t ext_lds_bytes; char *ext_blob;
     // counting complete solver (pdp_exact.hip::exn_prepare): ex_prepare's routing; the slab bytes of its own layout and the HBM route's F and snap
     int exn_ready; size_t exn_lds_bytes; char *exn_blob;
-    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_min, k_exact_count, k_exact_learn, k_exact_check or k_exact_trim on this problem (0: none yet)
+    // split complete solver (pdp_exact.hip::exs_launch): ex_prepare's routing; a fixed block (depth used, route, best, check reads, cube offsets)
+    // and the per-cube records of the last call (work, model rows, status), grown on demand; exs_total = the cubes of that call
+    // (0: no call yet, or the last one failed), exs_status_off = where their status bytes start in exs_cubes
+    char *exs_blob, *exs_cubes; size_t exs_cube_bytes, exs_status_off; int64_t exs_total;
+    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_min, k_exact_count, k_exact_learn, k_exact_check, k_exact_trim or k_exact_split on this problem (0: none yet)
     uint32_t *team_ws;          // barrier counters and reduction mailboxes of the workgroup teams (k_sp_solve<NT, true>)
     hipStream_t res_side_stream; hipEvent_t res_side_ev[2];   // the big instances' launches overlap the LDS-resident kernel on a stream of their own
     float *nws[4]; size_t nws_floats[4];             // neural workspaces (grow on demand)

@@ -25,6 +25,10 @@
 // tries the thresholded hint as a whole assignment before the search when no hint of the instance is NaN, and the first polarity of a
 // decision taken from the hint.  The hint code of a variable (0 none, 1 true, 2 false) lives in bits 8-9 of pend[v], next to the counters
 // the decision reads anyway: no array is added to the slab, and the routing and ex_prepare's cached decision stay as they are.
+//
+// pdp_exact_solve_split (further down) is the one entry point where two waves share an instance: the hinted search cut into 2^depth
+// cubes, prefixes of its own tree, one wave per cube; the only word the cubes of an instance share is best[b], lowered by an atomic
+// minimum and read at the budget checks, and no wave waits for another.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -2347,6 +2351,479 @@ int ext_launch(pdp_problem *p, const int8_t *status, const int64_t *proof_off, c
     return PDP_OK;
 }
 
+// ---- pdp_exact_solve_split: one instance's deciding search spread over 2^depth cubes, one wave per cube ------------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_split_model.py).  Its own search, kernels and launch path: nothing above is
+// touched.  A cube is ex_search<HBM, true> with the decisions of levels 1..depth pinned by the bits of the cube's index and recorded as
+// already flipped; a wave re-derives its prefix by running the ordinary search.  The state, the slab, the routing and the occupancy by LDS
+// are k_exact's.  Four launches on one stream: the setup (depth_used, route, cube_off), the check pass (once per instance: best[b] = -1
+// where it accepts, INT_MAX elsewhere), the cubes (one counter hands out cube ids: instance order, ascending index), the finish (first,
+// status, the work sum and the model of every instance from the per-cube records).
+// The only word two waves share is best[b]: a cube that answers 1 lowers it to its index (atomicMin), and a cube stops at a budget check
+// when a LOWER cube has answered 1.  No wave waits for another.  Cubes 0..first never stop, so everything the finish kernel reads is a
+// function of the instance, its hints, its depth and the budget alone.
+constexpr int EXS_MAX_DEPTH = 16;
+constexpr int64_t EXS_MAX_CUBES = (int64_t)1 << 22;
+constexpr int EXS_NONE = 0x7fffffff;            // best[b]: no cube has answered 1 (-1: the check pass accepted the hints)
+constexpr int EXS_SETUP_NT = 1024;
+
+struct ExsParams {
+    int B;
+    uint32_t total;             // cubes of the call
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;
+    const float *hint;          // [V] phase hints (NULL: none)
+    const int8_t *du;           // [B] depth used
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    const int64_t *chk;         // [B] reads of the rejected or accepted check pass (0: it did not run)
+    int32_t *best;              // [B]
+    int8_t *cube_status;        // [total] 1 / 0 / -1, -2 stopped early
+    int64_t *cube_work;         // [total]
+    uint32_t *rows;             // [total][words] bit-packed assignment of every cube that answered 1 (instances of depth > 0)
+    int words;
+    float *model;               // [V] written by the cube of a depth-0 instance, by the finish kernel elsewhere
+    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+};
+
+__device__ __forceinline__ int exs_best(const int32_t *best)
+{
+    return __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// depth_used, route and cube_off of the call, by one workgroup.  info[0] = the lowest instance whose depth is out of range, info[1] = the
+// lowest instance at which the running cube count passes 2^22 (EXS_NONE: none), info[2] = cubes, info[3] = the most variables of an
+// instance with depth_used > 0.
+__global__ void __launch_bounds__(EXS_SETUP_NT) k_exact_split_setup(PView pv, const int8_t *depth, const int32_t *order, int nbig, int8_t *du,
+                                                                    uint8_t *route, int64_t *cube_off, int8_t *depth_used, int64_t *info)
+{
+    __shared__ int64_t s[EXS_SETUP_NT];
+    __shared__ int bad, over, nmax;
+    const int t = (int)threadIdx.x, B = pv.B;
+    if (t == 0) { bad = EXS_NONE; over = EXS_NONE; nmax = 0; cube_off[0] = 0; }
+    __syncthreads();
+    for (int b = t; b < B; b += EXS_SETUP_NT) {
+        const int d = depth ? (int)depth[b] : 0;
+        const bool ok = d >= 0 && d <= EXS_MAX_DEPTH;
+        if (!ok) atomicMin(&bad, b);
+        du[b] = (int8_t)(ok ? d : 0);
+        route[b] = 0;
+    }
+    __syncthreads();
+    for (int i = t; i < nbig; i += EXS_SETUP_NT) { const int b = order[i]; du[b] = 0; route[b] = 1; }      // the HBM route: per-instance arrays
+    __syncthreads();
+    int64_t running = 0;
+    for (int base = 0; base < B; base += EXS_SETUP_NT) {
+        const int b = base + t;
+        const int d = b < B ? (int)du[b] : 0;
+        s[t] = b < B ? (int64_t)1 << d : 0;
+        __syncthreads();
+        for (int o = 1; o < EXS_SETUP_NT; o <<= 1) {
+            const int64_t x = t >= o ? s[t - o] : 0;
+            __syncthreads();
+            s[t] += x;
+            __syncthreads();
+        }
+        if (b < B) {
+            const int64_t end = running + s[t];
+            cube_off[b + 1] = end;
+            if (end > EXS_MAX_CUBES) atomicMin(&over, b);
+            if (d > 0) atomicMax(&nmax, pv.inst_v0[b + 1] - pv.inst_v0[b]);
+            if (depth_used) depth_used[b] = (int8_t)d;
+        }
+        running += s[EXS_SETUP_NT - 1];
+        __syncthreads();
+    }
+    if (t == 0) { info[0] = bad; info[1] = over; info[2] = running; info[3] = nmax; }
+}
+
+// The check pass of pdp_exact_solve_hinted, once per instance, straight from the problem's arrays: it runs when every variable of the
+// instance has a hint, reads every clause up to its first true literal under the thresholded hints, and accepts when every clause has one.
+__global__ void __launch_bounds__(EX_NT) k_exact_split_check(PView pv, const float *hint, int64_t *chk, int32_t *best)
+{
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const Inst I = load_inst(pv, b);
+        int none = hint == nullptr;
+        if (hint) for (int v = lane; v < I.n; v += EX_NT) { const float h = hint[I.v0 + v]; none |= h != h; }
+        const bool check = __ballot(none) == 0ull;
+        int reads = 0, open = 0;
+        if (check) {
+            for (int c = lane; c < I.m; c += EX_NT) {
+                const int a = I.f_ptr[c], z = I.f_ptr[c + 1];
+                int sat = 0, k = a;
+                for (; k < z; ++k) {
+                    const int ed = I.f_edges[k];
+                    if ((hint[I.v0 + I.e_var[ed]] > 0.5f) != (I.sgn[ed] < 0)) { sat = 1; ++k; break; }
+                }
+                reads += k - a;
+                open |= !sat;
+            }
+        }
+        reads = ex_sum(reads);
+        const bool accept = check && __ballot(open) == 0ull;
+        if (lane == 0) { chk[b] = reads; best[b] = accept ? -1 : EXS_NONE; }
+    }
+}
+
+// One cube of one instance by the calling wave: ex_search<HBM, true> without its check pass (keep the two in step), where a level
+// L <= depth takes the polarity bit (index >> (depth - L)) & 1 asks for (0: the search's first, 1: the other) and is recorded as already
+// flipped, so backtracking pops through it.  Returns 1 (val holds a model), 0 (the cube has none), -1 (budget spent) or -2 (stopped: a
+// lower cube has answered 1); *work_out = the cube's own reads.  `spent` (the check pass's reads) counts against the budget.  best[b] is
+// loaded by lane 0 one pass ahead of the budget check that reads it, so the load's latency lies behind a pass; an older value only stops
+// the cube a pass later.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_split(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t spent, int depth, int index, const int32_t *bestp, int seen,
+                               int64_t *work_out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    constexpr uint32_t UNIT = 3u;
+    int level = 0, tlen = 0;
+    int64_t work = 0;
+    int result = -1;
+    for (;;) {
+        if (spent + work >= budget) break;
+        seen = __shfl(seen, 0);
+        if (index > seen) { result = -2; break; }                   // wave-uniform; ends where the budget's break ends
+        if (lane == 0) seen = exs_best(bestp);
+        // ---- one unit-propagation pass
+        int reads = 0, conflict = 0, unit = 0, wmin = 0x7fffffff;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat) continue;
+            if (nfree == 0) conflict = 1;
+            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
+            else wmin = nfree < wmin ? nfree : wmin;
+        }
+        work += ex_sum(reads);
+        bool any_conflict = __ballot(conflict) != 0ull;
+        const bool any_unit = __ballot(unit) != 0ull;
+        if (any_unit) {
+            // assign the pending set of the pass; a variable asked for both polarities is a conflict
+            ex_sync<HBM>();
+            int bad = 0;
+            for (int base = 0; base < X.n; base += EX_NT) {
+                const int v = base + lane;
+                const uint32_t word = v < X.n ? X.pend[v] : 0u;
+                const uint32_t bits = word & UNIT;
+                const unsigned long long mask = __ballot(bits != 0u);
+                if (bits) {
+                    X.pend[v] = word & ~UNIT;
+                    X.val[v] = (bits & 1u) ? 1 : 2;
+                    bad |= bits == 3u;
+                    X.trail[tlen + __popcll(mask & below)] = v;
+                }
+                tlen += __popcll(mask);
+            }
+            any_conflict = any_conflict || __ballot(bad) != 0ull;
+            ex_sync<HBM>();
+        }
+        if (any_conflict) {
+            // chronological backtracking, a copy of ex_search's block: a pinned level carries the flipped bit from the start
+            bool resumed = false;
+            while (level > 0) {
+                const uint32_t d = X.dvar[level];
+                const int v = (int)(d & 0x7fffffffu);
+                const int from = X.mark[level];
+                const uint32_t first = X.val[v];
+                ex_sync<HBM>();                                     // every lane has read the level before it is undone
+                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
+                tlen = from;
+                if (!(d & 0x80000000u)) {
+                    ex_sync<HBM>();
+                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
+                    ++tlen;
+                    ex_sync<HBM>();
+                    resumed = true;
+                    break;
+                }
+                --level;
+            }
+            if (!resumed) { result = 0; break; }
+            continue;
+        }
+        if (any_unit) continue;
+        wmin = ex_min(wmin);
+        if (wmin == 0x7fffffff) { result = 1; break; }          // no open clause: every clause is satisfied
+        // ---- branching: ex_search's rule
+        reads = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) ++nfree;
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat || nfree != wmin) continue;
+            for (int j = a; j < z; ++j) {
+                const uint32_t L = X.lit[j];
+                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+            }
+            reads += z - a;
+        }
+        work += ex_sum(reads);
+        ex_sync<HBM>();
+        unsigned long long best = 0ull;
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+            if (p | q) {
+                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+                bool pos = p >= q;
+                const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
+                if (code) pos = code == 1u;
+                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                               (pos ? 1ull : 0ull);
+                best = key > best ? key : best;
+            }
+        }
+        best = ex_max64(best);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        ++level;
+        const bool pinned = level <= depth;
+        const bool other = pinned && ((index >> (depth - level)) & 1) != 0;
+        const bool pos = ((best & 1ull) != 0ull) != other;
+        ex_sync<HBM>();
+        if (lane == 0) {
+            X.mark[level] = tlen; X.dvar[level] = (uint32_t)v | (pinned ? 0x80000000u : 0u); X.val[v] = pos ? 1 : 2; X.trail[tlen] = v;
+        }
+        ++tlen;
+        ex_sync<HBM>();
+    }
+    *work_out = work;
+    return result;
+}
+
+// cube q = (instance I.b, index): unless a lower cube has answered already, copy the instance's literals in clause order, clear the state
+// (pend starts as the hint codes) and search; then the cube's record, and where it answers 1 the minimum on best[b] and its assignment: the
+// instance's slice of the model when the instance has this one cube, the cube's own row of bits otherwise.  Both arms end in the records
+// and the barrier below.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_split(const ExsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill, uint32_t q, int depth, int index)
+{
+    const int lane = (int)threadIdx.x;
+    int seen = 0;
+    if (lane == 0) seen = exs_best(xp.best + I.b);
+    seen = __shfl(seen, 0);
+    int st = -2;
+    int64_t work = 0;
+    if (index <= seen) {
+        if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+        for (int k = lane; k < I.e; k += EX_NT) {
+            const int ed = I.f_edges[k];
+            X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+        }
+        for (int v = lane; v < I.n; v += EX_NT) {
+            uint32_t code = 0u;
+            if (xp.hint) { const float h = xp.hint[I.v0 + v]; code = h != h ? 0u : (h > 0.5f ? 1u : 2u); }
+            X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        }
+        ex_sync<HBM>();
+        st = ex_search_split<HBM>(X, xp.budget, xp.chk[I.b], depth, index, xp.best + I.b, seen, &work);
+    }
+    if (depth == 0) {
+        for (int v = lane; v < I.n; v += EX_NT) xp.model[I.v0 + v] = (st == 1 && X.val[v] == 1) ? 1.0f : 0.0f;
+    } else if (st == 1) {
+        uint32_t *row = xp.rows + (size_t)q * (size_t)xp.words;
+        for (int base = 0; base < I.n; base += EX_NT) {
+            const int v = base + lane;
+            const unsigned long long mask = __ballot(v < I.n && X.val[v] == 1);
+            if (lane == 0) {
+                row[base >> 5] = (uint32_t)mask;
+                if (base + 32 < I.n) row[(base >> 5) + 1] = (uint32_t)(mask >> 32);
+            }
+        }
+    }
+    if (lane == 0) {
+        if (st == 1) atomicMin(xp.best + I.b, index);
+        xp.cube_status[q] = (int8_t)st;
+        xp.cube_work[q] = work;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_split(PView pv, ExsParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= xp.total) break;
+        int lo = 0, hi = xp.B;                                      // cube_off[lo] <= q < cube_off[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (xp.cube_off[mid] <= (int64_t)q) lo = mid; else hi = mid;
+        }
+        const Inst I = load_inst(pv, lo);
+        const int depth = (int)xp.du[lo], index = (int)((int64_t)q - xp.cube_off[lo]);
+        if (xp.route[lo]) {
+            ExInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
+            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
+            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve_split<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr, q, depth, index);
+        } else {
+            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
+            ExInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
+            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
+            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve_split<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ex_slab + L.cptr), q, depth, index);
+        }
+    }
+}
+
+__device__ __forceinline__ int64_t exs_sum64(int64_t x)
+{
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+// The instance's answer from its cubes' records, one wave per instance: first = best[b]; the work of cubes 0..first (all, when no cube
+// answered 1) plus the check pass's reads; status 1, or 0 when every cube answered 0, else -1; the model of cube `first` expanded from its
+// row (a depth-0 instance's single cube wrote its slice itself), the hints where the check pass accepted, 0 elsewhere.
+__global__ void __launch_bounds__(EX_NT) k_exact_split_finish(PView pv, ExsParams xp, int8_t *status, int64_t *work, int32_t *first)
+{
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        const int best = xp.best[b], depth = (int)xp.du[b];
+        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        int st;
+        int64_t w = xp.chk[b];
+        if (best == -1) {
+            st = 1;
+            for (int v = lane; v < n; v += EX_NT) xp.model[v0 + v] = xp.hint[v0 + v] > 0.5f ? 1.0f : 0.0f;
+        } else {
+            const bool found = best != EXS_NONE;
+            const int64_t last = found ? (int64_t)best : nc - 1;
+            int64_t sum = 0;
+            int open = 0;
+            for (int64_t j = lane; j <= last; j += EX_NT) { sum += xp.cube_work[c0 + j]; open |= xp.cube_status[c0 + j] != 0; }
+            w += exs_sum64(sum);
+            st = found ? 1 : (__ballot(open) != 0ull ? -1 : 0);
+            if (depth > 0) {
+                const uint32_t *row = xp.rows + (size_t)(c0 + last) * (size_t)xp.words;
+                for (int v = lane; v < n; v += EX_NT) xp.model[v0 + v] = (found && ((row[v >> 5] >> (v & 31)) & 1u)) ? 1.0f : 0.0f;
+            }
+        }
+        if (lane == 0) {
+            status[b] = (int8_t)st;
+            if (work) work[b] = w;
+            if (first) first[b] = (best == -1 || best == EXS_NONE) ? -1 : best;
+        }
+    }
+}
+
+// fixed block of the split call, once per problem, widest words first: chk [B] | cube_off [B+1] | info [4] | best [B] | du [B] | route [B]
+struct ExsFixed { int8_t *du; uint8_t *route; int32_t *best; int64_t *chk, *cube_off, *info; };
+
+inline ExsFixed exs_fixed(const pdp_problem *p)
+{
+    const size_t B = p->B;
+    ExsFixed F;
+    char *q = p->exs_blob;
+    F.chk = (int64_t *)q;       q += B * 8;
+    F.cube_off = (int64_t *)q;  q += (B + 1) * 8;
+    F.info = (int64_t *)q;      q += 4 * 8;
+    F.best = (int32_t *)q;      q += B * 4;
+    F.du = (int8_t *)q;         q += B;
+    F.route = (uint8_t *)q;
+    return F;
+}
+
+int exs_launch(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, float *model, int64_t *work, int32_t *first,
+               int8_t *depth_used, void *stream)
+{
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t V = p->V, E = p->E, B = p->B;
+    if (!p->exs_blob) {
+        const int st_ = pdp_dev_alloc((void **)&p->exs_blob, (B * 8 + (B + 1) * 8 + 32 + B * 4 + 2 * B + 15) & ~(size_t)15);
+        if (st_ != PDP_OK) return st_;
+    }
+    const ExsFixed F = exs_fixed(p);
+    p->exs_total = 0;                                                // no records to hand out until this call has launched its cubes
+    hipLaunchKernelGGL(k_exact_split_setup, dim3(1), dim3(EXS_SETUP_NT), 0, st, make_view(p), depth, p->ex_order, p->ex_nbig, F.du, F.route,
+                       F.cube_off, depth_used, F.info);
+    PDP_LAUNCH_CHECK();
+    int64_t info[4];
+    PDP_HIP_CHECK(hipMemcpyAsync(info, F.info, sizeof(info), hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));                        // the cube count sizes the records and the grid
+    if (info[0] != EXS_NONE) {
+        pdp_set_error("pdp_exact_solve_split: the depth of instance %lld is not in 0 .. %d", (long long)info[0], EXS_MAX_DEPTH);
+        return PDP_ERR_INVALID;
+    }
+    if (info[1] != EXS_NONE) {
+        pdp_set_error("pdp_exact_solve_split: more than 2^22 cubes in one call (reached at instance %lld); lower the depths or split the batch",
+                      (long long)info[1]);
+        return PDP_ERR_INVALID;
+    }
+    const size_t total = (size_t)info[2], words = ((size_t)info[3] + 31) / 32;
+    // per-cube records: work [total] | rows [total][words] | status [total]; grown on demand
+    const size_t need = (total * 8 + total * words * 4 + total + 15) & ~(size_t)15;
+    if (need > p->exs_cube_bytes) {
+        if (p->exs_cubes) { pdp_dev_free(p->exs_cubes); p->exs_cubes = nullptr; p->exs_cube_bytes = 0; }
+        const int st_ = pdp_dev_alloc((void **)&p->exs_cubes, need);
+        if (st_ != PDP_OK) return st_;
+        p->exs_cube_bytes = need;
+    }
+    ExsParams xp;
+    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.hint = hint; xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off; xp.chk = F.chk; xp.best = F.best;
+    xp.cube_work = (int64_t *)p->exs_cubes;
+    xp.rows = (uint32_t *)(p->exs_cubes + total * 8);
+    xp.cube_status = (int8_t *)(p->exs_cubes + total * 8 + total * words * 4);
+    xp.words = (int)words;
+    xp.model = model;
+    if (p->ex_h_lit) {
+        char *q = (char *)p->ex_h_lit;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_pend = (uint32_t *)q;           q += V * 4;
+        xp.h_cnt = (uint32_t *)q;            q += V * 8;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
+        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
+        xp.h_val = (uint8_t *)q;
+    } else {
+        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
+        xp.h_val = nullptr;
+    }
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_split_check, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), hint, F.chk, F.best);
+    PDP_LAUNCH_CHECK();
+    const int lds = (int)p->ex_lds_bytes;
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_split, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_split, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)total, (int64_t)pdp_device_cus() * per_cu));
+    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_split, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_exact_split_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp, status, work, first);
+    PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
+    p->exs_total = (int64_t)total;
+    p->exs_status_off = total * 8 + total * words * 4;
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -2452,6 +2929,29 @@ extern "C" int pdp_exact_trim(pdp_problem *p, const int8_t *status, const int64_
         return PDP_ERR_UNSUPPORTED;
     }
     return ext_launch(p, status, proof_off, proof, proof_len, budget, verdict, fail_at, work, core, keep, n_core, n_keep, stream);
+}
+
+extern "C" int pdp_exact_solve_split(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, float *model,
+                                     int64_t *work, int32_t *first, int8_t *depth_used, void *stream)
+{
+    PDP_REQUIRE(p && status && model, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_solve_split: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exs_launch(p, hint, depth, budget, status, model, work, first, depth_used, stream);
+}
+
+extern "C" int pdp_exact_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int64_t *cube_work, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && cube_status && cube_work, "NULL argument");
+    PDP_REQUIRE(p->exs_total > 0, "pdp_exact_split_cubes: no pdp_exact_solve_split call on this problem yet");
+    const size_t B = p->B, total = (size_t)p->exs_total;
+    const ExsFixed F = exs_fixed(p);
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exs_cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exs_cubes + p->exs_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
+    return PDP_OK;
 }
 
 extern "C" int pdp_exact_learn_reductions(pdp_problem *p, int32_t *reductions, void *stream)

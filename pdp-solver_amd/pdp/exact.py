@@ -14,7 +14,8 @@ instance, in one batch: the literals that hold in every model.  ``min_unsat`` op
 assignment leaves unsatisfied, by branch and bound from a given assignment (pdp_exact_min_unsat) -- what an incomplete
 solver's ``unsat_clauses`` on an unsatisfiable instance is to be compared with.  ``count_models`` counts instead of deciding: the exact
 number of models of an instance and, per variable, the share of them in which it is true (pdp_exact_count) -- what PDP's
-soft prediction is to be compared with.
+soft prediction is to be compared with.  With ``split=`` the deciding search of every instance is spread over 2^depth waves
+(pdp_exact_solve_split): same labels and models, for the one hard instance that would otherwise occupy one wave of the GPU.
 """
 
 import numpy as np
@@ -25,6 +26,12 @@ from pdp.factorgraph import dataset
 
 MAX_EDGES = 1 << 24          # edges per problem handed to the library
 COUNT_MAX_N = 1023           # pdp_exact_count searches instances of up to this many variables (2^n is a finite double)
+SPLIT_MAX_DEPTH = 16         # pdp_exact_solve_split: at most 2^16 cubes per instance
+SPLIT_WAVES_PER_SIMD = 4     # k_exact_split's occupancy by registers (resources); four SIMDs per CU
+# split='auto': the reads per instance of the plain first stage, and how many cubes the second stage makes per resident wave.  Chosen from
+# the sweep in profiles/exact_time.txt ("split='auto' constants", tools/exact_time.py sweep)
+AUTO_STAGE1_BUDGET = 1 << 18
+AUTO_CUBES_PER_WAVE = 16
 
 
 def raw_item(n, clauses, label=-1.0, name=""):
@@ -218,8 +225,53 @@ def _assumed(prob, part, names, assume, budget, hint, arena, device, certify):
     return st, model, wk, verdict, lemmas, failed
 
 
+def auto_depth(undecided, device):
+    """split='auto': the depth that gives ``undecided`` instances AUTO_CUBES_PER_WAVE cubes per resident wave of k_exact_split between them,
+    clamp(floor(log2(target / undecided)), 0, SPLIT_MAX_DEPTH)"""
+    waves = torch.cuda.get_device_properties(device).multi_processor_count * 4 * SPLIT_WAVES_PER_SIMD
+    target = AUTO_CUBES_PER_WAVE * waves
+    return max(0, min(SPLIT_MAX_DEPTH, (target // max(1, int(undecided))).bit_length() - 1))
+
+
+def _check_split(split):
+    if split is None or split == 'auto':
+        return split
+    if isinstance(split, bool) or not isinstance(split, (int, np.integer)) or not 0 <= split <= SPLIT_MAX_DEPTH:
+        raise ValueError("split must be None, 'auto' or a depth from 0 to %d, got %r" % (SPLIT_MAX_DEPTH, split))
+    return int(split)
+
+
+def split_solve(prob, part, budget, hint, split, device):
+    """The split search of one problem (``part``: its loader items, or a callable that returns them): numpy (status, model, work,
+    depth_used).  ``split`` an int: one pdp_exact_solve_split call at that depth.  'auto': a plain exact_solve with AUTO_STAGE1_BUDGET reads
+    per instance (``budget`` if that is smaller), then the undecided instances as one split call on a problem of their own at auto_depth;
+    work is the sum of the two stages."""
+    if split != 'auto':
+        st, model, wk, _, du = prob.exact_solve_split(budget, hints=hint, depth=split, stats=True)[:5]
+        return st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy(), du.cpu().numpy()
+    st, model, wk = prob.exact_solve(min(budget, AUTO_STAGE1_BUDGET) if budget > 0 else AUTO_STAGE1_BUDGET, hints=hint)
+    st, model, wk = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
+    du = np.zeros(len(st), dtype=np.int8)
+    again = [int(j) for j in np.nonzero(st == -1)[0]]
+    if again:
+        part = part() if callable(part) else part
+        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+        sub = _problem([part[j] for j in again], device)
+        hint2 = None if hint is None else torch.cat([hint[voff[j]:voff[j + 1]] for j in again])
+        r = [t.cpu().numpy() for t in sub.exact_solve_split(budget, hints=hint2, depth=auto_depth(len(again), device), stats=True)[:5]]
+        del sub
+        off = 0
+        for k, j in enumerate(again):
+            n = int(voff[j + 1] - voff[j])
+            st[j], du[j] = r[0][k], r[4][k]
+            wk[j] += r[2][k]
+            model[voff[j]:voff[j + 1]] = r[1][off:off + n]
+            off += n
+    return st, model, wk, du
+
+
 def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0, certify=False, proofs=False, cores=False,
-                assume=None):
+                assume=None, split=None):
     """Solve loader items ((n, m, graph_map, edge_feature, label, misc) tuples: dataset.instance_from_clauses, dataset.random_ksat_items,
     dataset.parse_line, raw_item).  Returns numpy (status int8 [N] in {1, 0, -1}, models: a float32 0/1 array of n_i values per instance,
     work int64 [N]).  Instances are packed into problems of at most ``max_edges`` edges; nothing couples two instances.
@@ -242,7 +294,13 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
     the int64 array of the 0-based assumed variables that are to blame (the instance plus those assumptions as unit clauses is
     unsatisfiable; empty: it is unsatisfiable on its own), None for the others.  With ``certify`` a model is also checked against the
     assumptions, and an "unsatisfiable" by the certified refutation of the instance plus its failed assumptions as unit clauses
-    (``proofs``: that refutation's lemmas).  ``cores`` under assumptions is not available."""
+    (``proofs``: that refutation's lemmas).  ``cores`` under assumptions is not available.
+    ``split``: the plain search (with ``hints`` if given) of every instance spread over 2^split waves (pdp_exact_solve_split; an int from 0
+    to 16), or 'auto': see split_solve.  Status and models are those of the call without ``split`` while no cube runs out of ``budget``,
+    which then applies to every cube; work is the sum over the cubes that count.  Not with ``learn``, ``certify`` or ``assume``."""
+    split = _check_split(split)
+    if split is not None and (learn or certify or assume is not None):
+        raise ValueError("split spreads the plain search: pass it without learn, certify and assume")
     learn = learn or certify or assume is not None
     if cores and assume is not None:
         raise ValueError("cores under assumptions are not available: pass assume without cores")
@@ -317,6 +375,8 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
                 st, model, wk, vd, lem, cor = _certified_part(prob, part, names, budget, hint, arena, device, cores)
                 for j, i in enumerate(seg):
                     verdict[i], lemmas[i], core[i] = vd[j], lem[j], cor[j]
+            elif split is not None:
+                st, model, wk, _ = split_solve(prob, part, budget, hint, split, device)
             else:
                 st, model, wk = prob.exact_solve(budget, hints=hint, learn=learn, arena=arena)
                 st, model, wk = st.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
@@ -472,16 +532,17 @@ def _label(s):
     return True if s == 1 else (False if s == 0 else None)
 
 
-def label_clause_lists(instances, budget=0, device=None, max_edges=MAX_EDGES, learn=False, arena=0, certify=False):
+def label_clause_lists(instances, budget=0, device=None, max_edges=MAX_EDGES, learn=False, arena=0, certify=False, split=None):
     """The batched labeller: [(n, clauses), ...] (clauses: lists of signed 1-based ints) -> [True / False / None, ...].
-    ``certify``: only checked answers become labels (solve_items); an answer that is not certified is None."""
+    ``certify``: only checked answers become labels (solve_items); an answer that is not certified is None.  ``split``: solve_items'."""
     out = solve_items([raw_item(n, clauses) for n, clauses in instances], budget=budget, device=device, max_edges=max_edges,
-                      learn=learn, arena=arena, certify=certify)
+                      learn=learn, arena=arena, certify=certify, split=split)
     if certify:
         return [_label(int(s)) if v == 1 else None for s, v in zip(out[0], out[3])]
     return [_label(int(s)) for s in out[0]]
 
 
-def is_sat(var_num, iclause_list, budget=0, learn=False, arena=0, certify=False):
-    """The reference's labelling hook (generator.py:15-17) for one instance: True, False, or None when the budget ran out."""
-    return label_clause_lists([(var_num, iclause_list)], budget=budget, learn=learn, arena=arena, certify=certify)[0]
+def is_sat(var_num, iclause_list, budget=0, learn=False, arena=0, certify=False, split=None):
+    """The reference's labelling hook (generator.py:15-17) for one instance: True, False, or None when the budget ran out.  ``split``
+    (an int depth or 'auto'): the one instance's search spread over the GPU (solve_items)."""
+    return label_clause_lists([(var_num, iclause_list)], budget=budget, learn=learn, arena=arena, certify=certify, split=split)[0]

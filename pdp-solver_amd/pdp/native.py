@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = [
     'pdp_coo_max', 'pdp_coo_argmax', 'pdp_coo_row_ptr', 'pdp_csr_matmul', 'pdp_csr_smooth_max',
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
     'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid', 'pdp_exact_solve_learn_assume',
-    'pdp_exact_min_unsat', 'pdp_exact_count',
+    'pdp_exact_min_unsat', 'pdp_exact_count', 'pdp_exact_solve_split', 'pdp_exact_split_cubes',
 ]
 
 
@@ -444,6 +444,46 @@ class Problem(object):
                                                ptr(work), _stream()))
         return status, model, work
 
+    def exact_solve_split(self, budget=0, hints=None, depth=None, stats=False):
+        """exact_solve(hints) with the search of instance b spread over 2^depth[b] waves (pdp_exact_solve_split): (status, model, work) as
+        exact_solve's -- status and model equal its bit for bit while no cube runs out of ``budget``, which applies to every cube; work is
+        the sum over the cubes that count.  ``depth``: an int, or an int8 tensor of B elements on the problem's device, values 0 .. 16, at
+        most 2^22 cubes per call; None: 0.  ``stats``: also first int32 [B] (the lowest cube with a model, -1: none, or the hints were
+        accepted as a whole), depth_used int8 [B] (0 for an instance on the HBM route), cube_off int64 [B+1], cube_status int8 [cubes]
+        (1 / 0 / -1, -2: stopped because a lower cube had answered) and cube_work int64 [cubes]; the records of cubes above first depend
+        on timing, nothing else does.  Synchronises the current stream once, then asynchronous on it (``stats`` synchronises again)."""
+        if hints is not None:
+            if not torch.is_tensor(hints) or hints.dtype != torch.float32 or hints.numel() != self.V:
+                raise ValueError("hints must be a float32 tensor of %d elements (one per variable), got %s"
+                                 % (self.V, '%s of %d' % (hints.dtype, hints.numel()) if torch.is_tensor(hints) else type(hints).__name__))
+            hints = hints.reshape(-1).contiguous()
+        if depth is None:
+            depth = 0
+        if torch.is_tensor(depth):
+            if depth.dtype != torch.int8 or depth.numel() != self.B or depth.device != self.device:
+                raise ValueError("depth must be an int or an int8 tensor of %d elements (one per instance) on %s, got %s of %d on %s"
+                                 % (self.B, self.device, depth.dtype, depth.numel(), depth.device))
+            depth = depth.reshape(-1).contiguous()
+        elif isinstance(depth, bool) or not isinstance(depth, numbers.Integral) or not -128 <= depth <= 127:
+            raise ValueError("depth must be an int or an int8 tensor of %d elements (one per instance), got %r" % (self.B, depth))
+        else:
+            depth = torch.full((self.B,), int(depth), dtype=torch.int8, device=self.device)
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        model = torch.empty(self.V, dtype=torch.float32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        first = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        depth_used = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        check(lib().pdp_exact_solve_split(self._h, ptr(hints, torch.float32, self.V, 'hints'), ptr(depth), C.c_int64(int(budget)), ptr(status),
+                                          ptr(model), ptr(work), ptr(first), ptr(depth_used), _stream()))
+        if not stats:
+            return status, model, work
+        cubes = int(torch.bitwise_left_shift(torch.ones_like(depth_used, dtype=torch.int64), depth_used.to(torch.int64)).sum().item())
+        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=self.device)
+        cube_status = torch.empty(cubes, dtype=torch.int8, device=self.device)
+        cube_work = torch.empty(cubes, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_split_cubes(self._h, ptr(cube_off), ptr(cube_status), ptr(cube_work), _stream()))
+        return status, model, work, first, depth_used, cube_off, cube_status, cube_work
+
     def exact_min_unsat(self, budget=0, hints=None, stats=False):
         """The fewest unsatisfied clauses of every instance by branch and bound (pdp_exact_min_unsat): (status int8 [B]: 1 the cost is the
         minimum over all assignments, -1 the budget ran out and it is an upper bound; cost int32 [B]: the clauses the model leaves
@@ -631,7 +671,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_min_unsat, exact_count, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split (its cube kernel), exact_min_unsat, exact_count, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

@@ -152,7 +152,9 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         "backbone_unknown" with their count (those literals are left out).  With config['complete_min_unsat'] every row whose "complete" is not 1
         also gains "min_unsat" (the fewest unsatisfied clauses pdp_exact_min_unsat found from PDP's assignment, within the same budget),
         "min_unsat_proved" (1: that is the minimum over all assignments, 0: an upper bound), "min_unsat_solution" and "min_unsat_work";
-        its five reference keys stay PDP's.  With config['complete_count'] every row whose "complete" is 1 gains "model_count" (pdp_exact_count within
+        its five reference keys stay PDP's.  With config['complete_split'] (a depth 0..16, or -1: exact.split_solve's 'auto') the same search runs
+        with every instance spread over 2^depth waves (pdp_exact_solve_split): "complete" and the solution are unchanged, "work" is the sum over
+        the cubes, and a row searched at a depth above 0 gains "split_depth" after "work".  With config['complete_count'] every row whose "complete" is 1 gains "model_count" (pdp_exact_count within
         the same budget: an int while it is exact, a float above 2^53), "model_count_log2", "model_count_proved" (1: the number of models, 0: the budget
         ran out, a lower bound), "marginals" (per variable, the share of the counted models in which it is true), "marginal_gap" (the mean
         over the variables of |the soft prediction - marginal|) and "count_work"; marginals and marginal_gap are left out where nothing was
@@ -167,7 +169,7 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             handle = native.Problem(graph_map, batch_variable_map, batch_function_map, edge_feature, batch_size=len(rows))
         hint = prediction[0].detach().reshape(-1).to(torch.float32).contiguous()
         budget = int(self._config.get('complete_budget', 0) or 0)
-        certified = None
+        certified = split_depth = None
         if self._config.get('complete_certify'):
             # the learning search with its lemma log, every answer checked (pdp_exact_check); a proof that did not fit its region is
             # logged once more into regions of the size the first run reported; a refuted answer raises
@@ -182,12 +184,22 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                 off = torch.from_numpy(np.concatenate([[0], np.cumsum(plen)]).astype(np.int64)).to(hint.device)
                 status, solution, work, certified, _, _, _, cores = exact._certified(handle, budget, hint, 0, names, proof_off=off, counts=counts)
             solution = solution.astype(int)
+        elif self._config.get('complete_split') is not None:
+            # config['complete_split']: the same search with every instance spread over 2^depth waves (pdp_exact_solve_split); -1: auto
+            from pdp import exact
+            split = int(self._config['complete_split'])
+            status, solution, work, split_depth = exact.split_solve(
+                handle, lambda: exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows)), budget, hint,
+                'auto' if split < 0 else split, hint.device)
+            solution = solution.astype(int)
         else:
             status, solution, work = handle.exact_solve(budget, hints=hint, learn=bool(self._config.get('complete_learn')))
             status, work = status.cpu().numpy(), work.cpu().numpy()
             solution = solution.cpu().numpy().astype(int)
         for i, row in enumerate(rows):
             row['complete'], row['pdp_solved'], row['work'] = int(status[i]), row['solved'], int(work[i])
+            if split_depth is not None and split_depth[i] > 0:
+                row['split_depth'] = int(split_depth[i])
             if certified is not None:
                 row['certified'] = int(certified[i])
                 if cores[i] is not None:

@@ -18,7 +18,10 @@ unsatisfied (pdp_exact_min_unsat, branch and bound from the model's assignment),
 an upper bound), "min_unsat_solution" and "min_unsat_work"; ``--complete-count`` (with ``--complete``) gives every satisfiable row "model_count",
 the exact number of its models (pdp_exact_count), "model_count_log2", "model_count_proved" (1 / 0: the budget ran out and it is a lower bound),
 "marginals" (per variable, the share of the models in which it is true), "marginal_gap" (the mean distance of the model's soft prediction
-from them) and "count_work".
+from them) and "count_work"; ``--complete-split N`` (with ``--complete``, not with ``--complete-learn`` or ``--complete-certify``) spreads the
+search of every instance over 2^N waves (pdp_exact_solve_split; -1: a plain first stage, then a depth chosen from the number of
+undecided instances): the same "complete" and solution, "work" summed over the cubes, and "split_depth" on the rows searched at a depth
+above 0.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -131,6 +134,10 @@ def main(argv=None):
                         'its models (pdp_exact_count, --complete-budget reads), "model_count_log2", "model_count_proved" (0: the budget ran out, a lower '
                         'bound), "marginals" (the share of the models in which each variable is true), "marginal_gap" (the mean distance of the '
                         'soft prediction from them) and "count_work"', action='store_true')
+    parser.add_argument('--complete-split', dest='complete_split', help='With --complete: spread the exact search of every instance over 2^N waves '
+                        '(pdp_exact_solve_split), N from 0 to 16, or -1: a plain first stage, then the undecided instances at a depth that fills the GPU; '
+                        'the same "complete" and solution, "work" summed over the cubes, "split_depth" on the rows searched at a depth above 0; '
+                        'not with --complete-learn or --complete-certify', type=int, default=None)
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -147,6 +154,13 @@ def main(argv=None):
         parser.error("--complete-min-unsat bounds the rows --complete leaves unsatisfied: give --complete as well")
     if args['complete_count'] and not args['complete']:
         parser.error("--complete-count counts the models of the rows --complete satisfies: give --complete as well")
+    if args['complete_split'] is not None:
+        if not args['complete']:
+            parser.error("--complete-split spreads the search of --complete: give --complete as well")
+        if args['complete_learn'] or args['complete_certify']:
+            parser.error("--complete-split spreads the plain search: give it without --complete-learn and --complete-certify")
+        if not -1 <= args['complete_split'] <= 16:
+            parser.error("--complete-split takes a depth from 0 to 16, or -1 for a depth chosen from the undecided instances")
     if args['complete_certify']:
         args['complete_learn'] = True
 

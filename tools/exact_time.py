@@ -41,7 +41,14 @@ Count rows (pdp_exact_count; never part of the default): ``ca`` / ``cd`` = the i
 a batch of its own at the default budget: kernel time (one call, after a call with a budget of one read that does the one-time
 preparation), complete counts / lower bounds, leaves and work median / p99 / max, the ratio to pdp_exact_solve's work on the same batch,
 the distribution of log2(count), and the mean over the instances of marginal_gap, the mean distance of one p-d-p forward's prediction
-(the forward of ``ha``) from the exact marginals."""
+(the forward of ``ha``) from the exact marginals.
+
+Split rows (pdp_exact_solve_split; never part of the default): ``sa`` / ``sb`` / ``sc`` = the first 1 / 8 / 64 instances of row (c) (uniform 3-SAT
+n=200 m=852), ``sb150`` = the first 8 of row (b) (n=150 m=639): kernel time of pdp_exact_solve, of the split call at depths 4 / 8 / 12 and of
+exact.split_solve(..., 'auto') on the same problem, each after an untimed call with a budget of one read that does the one-time
+preparation; per depth the cubes run, the cubes stopped early, the sum of reads against the plain search's and the largest counted cube's share of
+its instance's plain search.  ``sweep`` = on ``sb`` and ``sc``, split='auto' over its two constants (AUTO_STAGE1_BUDGET, AUTO_CUBES_PER_WAVE).
+PDP_SPLIT_ONLY=plain / split:<depth> times that one call alone (a fresh process per measurement of an alternating comparison)."""
 import io
 import json
 import logging
@@ -529,7 +536,76 @@ def run_count(key):
           flush=True)
 
 
+SPLIT_ROWS = {
+    'sa': ('uniform 3-SAT n=200 m=852, B=1', lambda: dataset.random_ksat_items(1, 200, 3, m=852, seed=0)),
+    'sb': ('uniform 3-SAT n=200 m=852, B=8', lambda: dataset.random_ksat_items(8, 200, 3, m=852, seed=0)),
+    'sc': ('uniform 3-SAT n=200 m=852, B=64', lambda: dataset.random_ksat_items(64, 200, 3, m=852, seed=0)),
+    'sb150': ('uniform 3-SAT n=150 m=639, B=8', lambda: dataset.random_ksat_items(8, 150, 3, m=639, seed=0)),
+}
+SPLIT_DEPTHS = (4, 8, 12)
+
+
+def _split_problem(key, split=True):
+    title, make = SPLIT_ROWS[key]
+    items = make()
+    b = dataset.to_torch(dataset.collate_segment(items), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(items))
+    p.exact_solve(1)                                                                 # the one-time preparation is not timed
+    if split:
+        p.exact_solve_split(1, depth=1)
+    torch.cuda.synchronize()
+    return title, items, p
+
+
+def run_split(key):
+    from pdp import exact
+    only = os.environ.get('PDP_SPLIT_ONLY')
+    title, items, p = _split_problem(key, split=only != 'plain')
+    if only:
+        call = (lambda: p.exact_solve()) if only == 'plain' else (lambda: p.exact_solve_split(depth=int(only.split(':')[1])))
+        ms, out = _event_ms(call)
+        st = out[0].cpu().numpy()
+        print("(%s, %s alone) %s: kernel %.2f ms  SAT %d  UNSAT %d  undecided %d  work total %d"
+              % (key, only, title, ms, int((st == 1).sum()), int((st == 0).sum()), int((st == -1).sum()), int(out[2].sum().item())), flush=True)
+        return
+    ms0, out = _event_ms(lambda: p.exact_solve())
+    st0, model0, wk0 = [t.cpu().numpy() for t in out]
+    _line(key + ', pdp_exact_solve', title, p, ms0, st0, wk0)
+    for depth in SPLIT_DEPTHS:
+        ms, out = _event_ms(lambda: p.exact_solve_split(depth=depth, stats=True))
+        st, model, wk, first, du, off, cst, cwk = [t.cpu().numpy() for t in out]
+        assert np.array_equal(st, st0) and np.array_equal(model, model0), "the split search answers differently"
+        counted = np.concatenate([cwk[off[j]:(off[j] + first[j] + 1 if first[j] >= 0 else off[j + 1])] for j in range(len(st))])
+        # the largest cube among those that count (0 .. first, or all), against its own instance's plain search
+        share = max(float(cwk[off[j]:(off[j] + first[j] + 1 if first[j] >= 0 else off[j + 1])].max()) / max(1.0, float(wk0[j])) for j in range(len(st)))
+        print("    split depth %2d: kernel %.2f ms (%.3f of pdp_exact_solve)  cubes %d  run to their end %d  stopped early %d  reads: counted %d "
+              "(%.3f of the plain search's), of all cubes %d (%.3f)  largest counted cube's share of its instance's plain search %.4f  grid %d"
+              % (depth, ms, ms / ms0, cst.size, int((cst != -2).sum()), int((cst == -2).sum()), int(counted.sum()), float(wk.sum()) / float(wk0.sum()),
+                 int(cwk.sum()), float(cwk.sum()) / float(wk0.sum()), share, p.exact_last_grid()), flush=True)
+    ms, out = _event_ms(lambda: exact.split_solve(p, items, 0, None, 'auto', p.device))
+    assert np.array_equal(out[0], st0) and np.array_equal(out[1], model0), "split='auto' answers differently"
+    print("    split auto (stage 1 budget %d, %d cubes per wave): wall incl. set-up of the second stage %.2f ms (%.3f of pdp_exact_solve)  "
+          "depths %s  reads %d (%.3f)" % (exact.AUTO_STAGE1_BUDGET, exact.AUTO_CUBES_PER_WAVE, ms, ms / ms0,
+                                           sorted(set(out[3].tolist())), int(out[2].sum()), float(out[2].sum()) / float(wk0.sum())), flush=True)
+
+
+def run_split_sweep():
+    from pdp import exact
+    for key in ('sb', 'sc'):
+        title, items, p = _split_problem(key)
+        for stage1 in (1 << 14, 1 << 18, 1 << 22, 1 << 26):
+            for per_wave in (1, 4, 16, 64):
+                exact.AUTO_STAGE1_BUDGET, exact.AUTO_CUBES_PER_WAVE = stage1, per_wave
+                ms, out = _event_ms(lambda: exact.split_solve(p, items, 0, None, 'auto', p.device))
+                print("(sweep %s) %s: stage 1 budget 2^%d  cubes per wave %d: %.2f ms  depths %s  undecided after stage 1 %d  reads %d"
+                      % (key, title, stage1.bit_length() - 1, per_wave, ms, sorted(set(out[3].tolist())), int((out[3] > 0).sum()),
+                         int(out[2].sum())), flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
+        if k in SPLIT_ROWS or k == 'sweep':
+            run_split(k) if k in SPLIT_ROWS else run_split_sweep()
+            continue
         (run_count if k in COUNT_ROWS else run_assume if k in ASSUME_ROWS else {'h': run_hinted, 'w': run_wall, 'x': run_min_unsat, 'l': run_learn, 'm': run_learn, 'p': run_proof, 't': run_trim}.get(k[0], run))(k)
