@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -467,8 +467,41 @@ int pdp_exact_solve_split(pdp_problem *p, const float *hint, const int8_t *depth
  * cube_work [cubes], cubes = cube_off[B] = the sum of 2^depth_used.  Device to device, asynchronous on the stream. */
 int pdp_exact_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int64_t *cube_work, void *stream);
 
+/* pdp_exact_count with the search of every instance spread over 2^depth[b] waves (plain Python, normative:
+ * tests/exact_count_split_model.py).  Cube `index` of the 2^depth cubes of an instance is pdp_exact_count's search with the
+ * decision of every level L <= depth pinned as in pdp_exact_solve_split (bit (index >> (depth - L)) & 1: 0 the polarity the search tries
+ * first, 1 the other; the level counts as already flipped).  The cubes partition the tree, so their counts add.  A leaf met with fewer
+ * than `depth` levels open (L < depth) is reached by every cube that shares those levels' bits; it is credited to exactly one of them,
+ * the cube with index & ((1 << (depth - L)) - 1) == 0, and the others add nothing to count or leaves; either way the cube backtracks as
+ * after a conflict, which ends it (every open level is pinned).  The end flush and true_count_c[v] = T[v] + (count_c - T[v] - F[v]) * 0.5
+ * are pdp_exact_count's, per cube.  The budget is per cube: own reads >= budget before every pass (budget <= 0: PDP_EXACT_DEFAULT_BUDGET).
+ *   The instance's outputs are sums over its cubes in ASCENDING index: count = count + count_c and true_count[v] = true_count[v] +
+ *   true_count_c[v], sequentially in double; work and leaves are integer sums; status 1 if every cube's is 1, else -1 (count is then a
+ *   lower bound).  While count <= 2^53 every per-cube value is an exact integer and count, true_count and leaves equal pdp_exact_count's
+ *   bit for bit at every depth; above, they are the correctly rounded results of this order.  depth 0 gives pdp_exact_count's five
+ *   outputs exactly.  work >= pdp_exact_count's (prefixes are replayed) and work < cubes * (budget + 3 * edges of the instance).
+ *   depth [B] (device int8; NULL: all 0) in 0 .. 16; at most 2^22 cubes per call; the per-cube rows below at most 2^31 bytes; any of them
+ *   violated -> PDP_ERR_INVALID, the message names the instance (for the two sizes: the one at which the running total passes the cap).
+ *   An instance on the HBM route and an instance of more than 1023 variables (status -2, one record -2 / 0 / 0 / 0) have one cube;
+ *   depth_used [B] (int8, may be NULL) = the depth each instance was searched at.  work and leaves may be NULL.
+ * One wave takes one cube at a time from one counter and runs it to its own end; no word is shared between two cubes and no wave waits
+ * for another.  A cube of an instance with depth_used > 0 leaves its record and, unless its count is 0.0, its row of true_count_c in
+ * [cubes][n_max] doubles on the handle (n_max over those instances); a second kernel sums records and rows per instance in cube order,
+ * one lane per variable.  No double goes through an atomic or a reduction across lanes or waves: every output and every record is a
+ * function of the instance, the depth and the budget alone.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Routing, slab and working arrays are pdp_exact_count's, shared with it.  The call synchronises the stream
+ * once (the cube count sizes its records and its grid); the kernels that follow are asynchronous on it. */
+int pdp_exact_count_split(pdp_problem *p, const int8_t *depth, int64_t budget, int8_t *status, double *count, double *true_count,
+                          int64_t *work, int64_t *leaves, int8_t *depth_used, void *stream);
+
+/* The per-cube records of the last pdp_exact_count_split call on the problem that succeeded (PDP_ERR_INVALID before the first): cube_off
+ * [B+1] (int64), cube_status [cubes] (1 / -1, -2: more than 1023 variables), cube_count [cubes] (double), cube_work and cube_leaves [cubes],
+ * cubes = cube_off[B] = the sum of 2^depth_used.  Device to device, asynchronous on the stream. */
+int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, double *cube_count, int64_t *cube_work,
+                                int64_t *cube_leaves, void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split (its cube kernel:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split and pdp_exact_count_split (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

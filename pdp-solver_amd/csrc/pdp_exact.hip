@@ -28,7 +28,8 @@
 //
 // pdp_exact_solve_split (further down) is the one entry point where two waves share an instance: the hinted search cut into 2^depth
 // cubes, prefixes of its own tree, one wave per cube; the only word the cubes of an instance share is best[b], lowered by an atomic
-// minimum and read at the budget checks, and no wave waits for another.
+// minimum and read at the budget checks, and no wave waits for another.  pdp_exact_count_split (at the end) cuts the counting search the
+// same way; its cubes share nothing at all, and a second kernel adds their counts up in cube order.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -2824,6 +2825,499 @@ int exs_launch(pdp_problem *p, const float *hint, const int8_t *depth, int64_t b
     return PDP_OK;
 }
 
+// ---- pdp_exact_count_split: one instance's model count spread over 2^depth cubes, one wave per cube ------------------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_count_split_model.py).  Its own search, kernels and launch path: nothing above
+// is touched.  A cube is ex_search_count with the decisions of levels 1..depth pinned as in ex_search_split, and a leaf met with fewer than
+// `depth` levels open credited to the one cube whose remaining index bits are 0.  Every cube runs to its own end: no word is shared between
+// two waves, there is no check pass and no early stop.  The state, the slab (exn_lds_layout), the routing and the HBM arrays are
+// k_exact_count's.  Three launches on one stream: the setup (depth_used, cube_off, the caps), the cubes (one counter hands out cube ids;
+// every cube leaves a record, and where its instance has more than one cube and its count is not 0.0, its row of n per-variable counts),
+// the finish (per instance of depth > 0: the records and rows summed in ascending cube order).  An instance at depth 0 has one cube, which
+// writes the instance's outputs itself exactly as k_exact_count does.  No double goes through an atomic or a reduction across lanes: the
+// sums are sequential in cube order, so every output is a function of the instance, the depth and the budget alone.
+constexpr int64_t EXNS_MAX_ROW_BYTES = (int64_t)1 << 31;
+
+struct ExnsParams {
+    int B;
+    uint32_t total;             // cubes of the call
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;             // per cube
+    const int8_t *du;           // [B] depth used
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    int8_t *cube_status;        // [total] 1 / -1, -2: n > 1023
+    double *cube_count;         // [total]
+    int64_t *cube_work;         // [total]
+    int64_t *cube_leaves;       // [total]
+    double *rows;               // [total][n_max] true_count of every cube of an instance with depth_used > 0 whose count is not 0.0
+    int n_max;
+    int8_t *status; double *count; double *true_count; int64_t *work; int64_t *leaves;      // the instance's outputs
+    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+    double *h_F, *h_snap;       // as ExnParams
+};
+
+// k_exact_split_setup's job for the count: depth_used (0 on the HBM route and for n > 1023), route and cube_off, by one workgroup.
+// info[0] = the lowest instance whose depth is out of range, info[1] = the lowest instance at which the running cube count passes 2^22,
+// info[4] = the lowest instance at which the running size of the rows, cube_off[b + 1] * n_max * 8 bytes, passes 2^31 (EXS_NONE: none),
+// info[2] = cubes, info[3] = n_max, the most variables of an instance with depth_used > 0.
+__global__ void __launch_bounds__(EXS_SETUP_NT) k_exact_count_split_setup(PView pv, const int8_t *depth, const int32_t *order, int nbig, int8_t *du,
+                                                                          uint8_t *route, int64_t *cube_off, int8_t *depth_used, int64_t *info)
+{
+    __shared__ int64_t s[EXS_SETUP_NT];
+    __shared__ int bad, over, wide, nmax;
+    const int t = (int)threadIdx.x, B = pv.B;
+    if (t == 0) { bad = EXS_NONE; over = EXS_NONE; wide = EXS_NONE; nmax = 0; cube_off[0] = 0; }
+    __syncthreads();
+    for (int b = t; b < B; b += EXS_SETUP_NT) {
+        const int d = depth ? (int)depth[b] : 0;
+        const bool ok = d >= 0 && d <= EXS_MAX_DEPTH;
+        if (!ok) atomicMin(&bad, b);
+        du[b] = (int8_t)(ok && pv.inst_v0[b + 1] - pv.inst_v0[b] <= EXN_MAX_N ? d : 0);
+        route[b] = 0;
+    }
+    __syncthreads();
+    for (int i = t; i < nbig; i += EXS_SETUP_NT) { const int b = order[i]; du[b] = 0; route[b] = 1; }      // the HBM route: per-instance arrays
+    __syncthreads();
+    int64_t running = 0;
+    for (int base = 0; base < B; base += EXS_SETUP_NT) {
+        const int b = base + t;
+        const int d = b < B ? (int)du[b] : 0;
+        s[t] = b < B ? (int64_t)1 << d : 0;
+        __syncthreads();
+        for (int o = 1; o < EXS_SETUP_NT; o <<= 1) {
+            const int64_t x = t >= o ? s[t - o] : 0;
+            __syncthreads();
+            s[t] += x;
+            __syncthreads();
+        }
+        if (b < B) {
+            const int64_t end = running + s[t];
+            cube_off[b + 1] = end;
+            if (end > EXS_MAX_CUBES) atomicMin(&over, b);
+            if (d > 0) atomicMax(&nmax, pv.inst_v0[b + 1] - pv.inst_v0[b]);
+            if (depth_used) depth_used[b] = (int8_t)d;
+        }
+        running += s[EXS_SETUP_NT - 1];
+        __syncthreads();
+    }
+    // cube_off[b + 1] <= 2^22 * B and n_max <= 1023: the product stays far inside int64
+    for (int b = t; b < B; b += EXS_SETUP_NT)
+        if (cube_off[b + 1] * (int64_t)nmax * 8 > EXNS_MAX_ROW_BYTES) atomicMin(&wide, b);
+    __syncthreads();
+    if (t == 0) { info[0] = bad; info[1] = over; info[2] = running; info[3] = nmax; info[4] = wide; }
+}
+
+// One cube of one instance by the calling wave: ex_search_count (keep the two in step) where a level L <= depth takes the polarity that bit
+// (index >> (depth - L)) & 1 asks for (0: the search's first, 1: the other) and is recorded as already flipped, and where a leaf met with
+// level < depth levels open counts only if index's low depth - level bits are 0.  Returns 1 (complete) or -1 (the cube's budget is spent).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_count_split(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int64_t budget, int depth, int index, int64_t *work_out,
+                                     double *count_out, int64_t *leaves_out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0;
+    int64_t work = 0, leaves = 0;
+    double count = 0.0;
+    int result = -1;
+    for (;;) {
+        if (work >= budget) break;
+        // ---- one unit-propagation pass
+        int reads = 0, conflict = 0, unit = 0, wmin = INF;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat) continue;
+            if (nfree == 0) conflict = 1;
+            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
+            else wmin = nfree < wmin ? nfree : wmin;
+        }
+        work += ex_sum(reads);
+        bool any_conflict = __ballot(conflict) != 0ull;
+        const bool any_unit = __ballot(unit) != 0ull;
+        if (any_unit) {
+            // assign the pending set of the pass; a variable asked for both polarities is a conflict
+            ex_sync<HBM>();
+            int bad = 0;
+            for (int base = 0; base < X.n; base += EX_NT) {
+                const int v = base + lane;
+                const uint32_t bits = v < X.n ? X.pend[v] : 0u;
+                const unsigned long long mask = __ballot(bits != 0u);
+                if (bits) {
+                    X.pend[v] = 0u;
+                    X.val[v] = (bits & 1u) ? 1 : 2;
+                    bad |= bits == 3u;
+                    X.trail[tlen + __popcll(mask & below)] = v;
+                }
+                tlen += __popcll(mask);
+            }
+            any_conflict = any_conflict || __ballot(bad) != 0ull;
+            ex_sync<HBM>();
+        }
+        if (!any_conflict) {
+            if (any_unit) continue;
+            wmin = ex_min(wmin);
+            if (wmin == INF) {
+                // a leaf.  Inside the prefix every cube with these levels' bits arrives here: the one whose remaining bits are 0 takes it.
+                // Either way the search goes on as after a conflict (every open level is pinned then, so that ends the cube)
+                const int rest = depth - level;
+                if (rest <= 0 || (index & ((1 << rest) - 1)) == 0) {
+                    count = count + ldexp(1.0, X.n - tlen);
+                    ++leaves;
+                }
+                any_conflict = true;
+            }
+        }
+        if (any_conflict) {
+            // chronological backtracking with the credit of every undone level: a pinned level carries the flipped bit from the start
+            bool resumed = false;
+            while (level > 0) {
+                const uint32_t d = X.dvar[level];
+                const int v = (int)(d & 0x7fffffffu);
+                const int from = X.mark[level];
+                const uint32_t first = X.val[v];
+                const double since = count - A.snap[level];
+                ex_sync<HBM>();                                     // every lane has read the level before it is undone
+                exn_credit(X, A, from, tlen, since);
+                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;      // the same lane as the credit
+                tlen = from;
+                if (!(d & 0x80000000u)) {
+                    ex_sync<HBM>();
+                    if (lane == 0) {
+                        X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v;
+                        A.snap[level] = count;                      // the level stays open: its first half is credited once
+                    }
+                    ++tlen;
+                    ex_sync<HBM>();
+                    resumed = true;
+                    break;
+                }
+                --level;
+            }
+            if (!resumed) { result = 1; break; }
+            continue;
+        }
+        // ---- branching: ex_search_count's rule, then the cube's bit on a pinned level
+        reads = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) ++nfree;
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat || nfree != wmin) continue;
+            for (int j = a; j < z; ++j) {
+                const uint32_t L = X.lit[j];
+                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+            }
+            reads += z - a;
+        }
+        work += ex_sum(reads);
+        ex_sync<HBM>();
+        unsigned long long best = 0ull;
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+            if (p | q) {
+                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                               (p >= q ? 1ull : 0ull);
+                best = key > best ? key : best;
+            }
+        }
+        best = ex_max64(best);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        ++level;
+        const bool pinned = level <= depth;
+        const bool other = pinned && ((index >> (depth - level)) & 1) != 0;
+        const bool pos = ((best & 1ull) != 0ull) != other;
+        ex_sync<HBM>();
+        if (lane == 0) {
+            X.mark[level] = tlen; X.dvar[level] = (uint32_t)v | (pinned ? 0x80000000u : 0u); X.val[v] = pos ? 1 : 2; X.trail[tlen] = v;
+            A.snap[level] = count;
+        }
+        ++tlen;
+        ex_sync<HBM>();
+    }
+    // the end: every open level is flushed, the newest first, as in ex_search_count
+    for (; level >= 0; --level) {
+        const int from = level > 0 ? X.mark[level] : 0;
+        exn_credit(X, A, from, tlen, count - A.snap[level]);
+        tlen = from;
+    }
+    *work_out = work; *count_out = count; *leaves_out = leaves;
+    return result;
+}
+
+// cube q = (instance I.b, index): copy the instance's literals in clause order, clear the state, search; then the cube's record, and its
+// per-variable counts: the instance's slice of true_count and the instance's other outputs when this is its one cube (depth 0), the cube's
+// own row otherwise, skipped when the count is 0.0 (every entry is then +0.0, and the finish kernel skips the row as well).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_count_split(const ExnsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExnAcc A, PtrT *cptr_fill, uint32_t q,
+                                     int depth, int index)
+{
+    const int lane = (int)threadIdx.x;
+    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+    for (int k = lane; k < I.e; k += EX_NT) {
+        const int ed = I.f_edges[k];
+        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+    }
+    for (int v = lane; v < I.n; v += EX_NT) {
+        X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        A.T[v] = 0.0; A.F[v] = 0.0;
+    }
+    if (lane == 0) A.snap[0] = 0.0;
+    ex_sync<HBM>();
+    int64_t work = 0, leaves = 0;
+    double count = 0.0;
+    const int st = ex_search_count_split<HBM>(X, A, xp.budget, depth, index, &work, &count, &leaves);
+    ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
+    if (depth == 0 || count != 0.0) {
+        double *out = depth == 0 ? xp.true_count + I.v0 : xp.rows + (size_t)q * (size_t)xp.n_max;
+        for (int v = lane; v < I.n; v += EX_NT) {
+            const double t = A.T[v];
+            out[v] = t + (count - t - A.F[v]) * 0.5;
+        }
+    }
+    if (lane == 0) {
+        xp.cube_status[q] = (int8_t)st;
+        xp.cube_count[q] = count;
+        xp.cube_work[q] = work;
+        xp.cube_leaves[q] = leaves;
+        if (depth == 0) {
+            xp.status[I.b] = (int8_t)st;
+            xp.count[I.b] = count;
+            if (xp.work) xp.work[I.b] = work;
+            if (xp.leaves) xp.leaves[I.b] = leaves;
+        }
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_count_split(PView pv, ExnsParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= xp.total) break;
+        int lo = 0, hi = xp.B;                                      // cube_off[lo] <= q < cube_off[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (xp.cube_off[mid] <= (int64_t)q) lo = mid; else hi = mid;
+        }
+        const Inst I = load_inst(pv, lo);
+        const int depth = (int)xp.du[lo], index = (int)((int64_t)q - xp.cube_off[lo]);
+        // every arm ends in the barrier every arm ends in and falls through to the end of the loop body (see k_exact_count)
+        if (I.n > EXN_MAX_N) {
+            for (int v = (int)threadIdx.x; v < I.n; v += EX_NT) xp.true_count[I.v0 + v] = 0.0;
+            if (threadIdx.x == 0) {
+                xp.cube_status[q] = (int8_t)-2; xp.cube_count[q] = 0.0; xp.cube_work[q] = 0; xp.cube_leaves[q] = 0;
+                xp.status[I.b] = (int8_t)-2;
+                xp.count[I.b] = 0.0;
+                if (xp.work) xp.work[I.b] = 0;
+                if (xp.leaves) xp.leaves[I.b] = 0;
+            }
+            ex_sync<false>();
+        } else if (xp.route[lo]) {
+            ExInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
+            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
+            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ExnAcc A;
+            A.T = xp.true_count + I.v0; A.F = xp.h_F + I.v0; A.snap = xp.h_snap + I.v0 + I.b;
+            ex_solve_count_split<true, uint32_t, int32_t>(xp, I, X, A, (int32_t *)nullptr, q, 0, 0);
+        } else {
+            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
+            const ExnLds N = exn_lds_layout(I.n, I.m, I.e);
+            ExInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
+            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
+            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ExnAcc A;
+            A.T = (double *)(ex_slab + N.T); A.F = (double *)(ex_slab + N.F); A.snap = (double *)(ex_slab + N.snap);
+            ex_solve_count_split<false, uint16_t, uint16_t>(xp, I, X, A, (uint16_t *)(ex_slab + L.cptr), q, depth, index);
+        }
+    }
+}
+
+// The outputs of every instance with depth_used > 0 from its cubes' records and rows, one wave per instance.  The doubles are summed
+// sequentially in ascending cube order: the counts of 64 cubes at a time are staged in LDS and every lane adds them up in the same order
+// (the same uniform value in every lane, no exchange between lanes); true_count[v] by the lane that holds v, over the rows of the cubes
+// whose count is not 0.0, eight rows in flight at a time.  work and leaves are integer sums, status is 1 when every cube's is.
+constexpr int EXNS_ROWS_IN_FLIGHT = 8;
+
+__global__ void __launch_bounds__(EX_NT) k_exact_count_split_finish(PView pv, ExnsParams xp)
+{
+    __shared__ double s_count[EX_NT];
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        if (xp.du[b] == 0) continue;                                // wave-uniform, before any barrier of the body
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        double count = 0.0;
+        int64_t w = 0, lv = 0;
+        int open = 0;
+        for (int64_t base = 0; base < nc; base += EX_NT) {
+            const int64_t j = base + lane;
+            const bool in = j < nc;
+            s_count[lane] = in ? xp.cube_count[c0 + j] : 0.0;
+            if (in) { w += xp.cube_work[c0 + j]; lv += xp.cube_leaves[c0 + j]; open |= xp.cube_status[c0 + j] != 1; }
+            __syncthreads();
+            const int lim = (int)(nc - base < EX_NT ? nc - base : EX_NT);
+            for (int t = 0; t < lim; ++t) count = count + s_count[t];
+            __syncthreads();
+        }
+        w = exs_sum64(w);
+        lv = exs_sum64(lv);
+        const bool any_open = __ballot(open) != 0ull;
+        for (int vb = 0; vb < n; vb += EX_NT) {
+            const int v = vb + lane;
+            double acc = 0.0;
+            for (int64_t base = 0; base < nc; base += EX_NT) {
+                const int64_t j = base + lane;
+                s_count[lane] = j < nc ? xp.cube_count[c0 + j] : 0.0;
+                __syncthreads();
+                const int lim = (int)(nc - base < EX_NT ? nc - base : EX_NT);
+                for (int t = 0; t < lim; t += EXNS_ROWS_IN_FLIGHT) {
+                    double r[EXNS_ROWS_IN_FLIGHT];
+#pragma unroll
+                    for (int u = 0; u < EXNS_ROWS_IN_FLIGHT; ++u) {
+                        const bool take = t + u < lim && s_count[t + u] != 0.0 && v < n;
+                        r[u] = take ? xp.rows[(size_t)(c0 + base + t + u) * (size_t)xp.n_max + (size_t)v] : 0.0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < EXNS_ROWS_IN_FLIGHT; ++u)
+                        if (t + u < lim && s_count[t + u] != 0.0) acc = acc + r[u];
+                }
+                __syncthreads();
+            }
+            if (v < n) xp.true_count[v0 + v] = acc;
+        }
+        if (lane == 0) {
+            xp.status[b] = (int8_t)(any_open ? -1 : 1);
+            xp.count[b] = count;
+            if (xp.work) xp.work[b] = w;
+            if (xp.leaves) xp.leaves[b] = lv;
+        }
+    }
+}
+
+// fixed block of the split count, once per problem, widest words first: cube_off [B+1] | info [5] | du [B] | route [B]
+struct ExnsFixed { int8_t *du; uint8_t *route; int64_t *cube_off, *info; };
+
+inline ExnsFixed exns_fixed(const pdp_problem *p)
+{
+    const size_t B = p->B;
+    ExnsFixed F;
+    char *q = p->exns_blob;
+    F.cube_off = (int64_t *)q;  q += (B + 1) * 8;
+    F.info = (int64_t *)q;      q += 5 * 8;
+    F.du = (int8_t *)q;         q += B;
+    F.route = (uint8_t *)q;
+    return F;
+}
+
+int exns_launch(pdp_problem *p, const int8_t *depth, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work,
+                int64_t *leaves, int8_t *depth_used, void *stream)
+{
+    { const int st_ = exn_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t V = p->V, E = p->E, B = p->B;
+    if (!p->exns_blob) {
+        const int st_ = pdp_dev_alloc((void **)&p->exns_blob, ((B + 1) * 8 + 40 + 2 * B + 15) & ~(size_t)15);
+        if (st_ != PDP_OK) return st_;
+    }
+    const ExnsFixed F = exns_fixed(p);
+    p->exns_total = 0;                                               // no records to hand out until this call has launched its cubes
+    hipLaunchKernelGGL(k_exact_count_split_setup, dim3(1), dim3(EXS_SETUP_NT), 0, st, make_view(p), depth, p->ex_order, p->ex_nbig, F.du, F.route,
+                       F.cube_off, depth_used, F.info);
+    PDP_LAUNCH_CHECK();
+    int64_t info[5];
+    PDP_HIP_CHECK(hipMemcpyAsync(info, F.info, sizeof(info), hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));                        // the cube count sizes the records and the grid
+    if (info[0] != EXS_NONE) {
+        pdp_set_error("pdp_exact_count_split: the depth of instance %lld is not in 0 .. %d", (long long)info[0], EXS_MAX_DEPTH);
+        return PDP_ERR_INVALID;
+    }
+    if (info[1] != EXS_NONE) {
+        pdp_set_error("pdp_exact_count_split: more than 2^22 cubes in one call (reached at instance %lld); lower the depths or split the batch",
+                      (long long)info[1]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[4] != EXS_NONE) {
+        pdp_set_error("pdp_exact_count_split: the per-cube rows (cubes x %lld variables x 8 bytes) pass 2^31 bytes at instance %lld; lower the "
+                      "depths or split the batch", (long long)info[3], (long long)info[4]);
+        return PDP_ERR_INVALID;
+    }
+    const size_t total = (size_t)info[2], nmax = (size_t)info[3];
+    // per-cube records: count [total] | work [total] | leaves [total] | rows [total][n_max] | status [total]; grown on demand
+    const size_t need = (total * 24 + total * nmax * 8 + total + 15) & ~(size_t)15;
+    if (need > p->exns_cube_bytes) {
+        if (p->exns_cubes) { pdp_dev_free(p->exns_cubes); p->exns_cubes = nullptr; p->exns_cube_bytes = 0; }
+        const int st_ = pdp_dev_alloc((void **)&p->exns_cubes, need);
+        if (st_ != PDP_OK) return st_;
+        p->exns_cube_bytes = need;
+    }
+    ExnsParams xp;
+    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off;
+    xp.cube_count = (double *)p->exns_cubes;
+    xp.cube_work = (int64_t *)(p->exns_cubes + total * 8);
+    xp.cube_leaves = (int64_t *)(p->exns_cubes + total * 16);
+    xp.rows = (double *)(p->exns_cubes + total * 24);
+    xp.cube_status = (int8_t *)(p->exns_cubes + total * 24 + total * nmax * 8);
+    xp.n_max = (int)nmax;
+    xp.status = status; xp.count = count; xp.true_count = true_count; xp.work = work; xp.leaves = leaves;
+    if (p->ex_h_lit) {
+        char *q = (char *)p->ex_h_lit;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_pend = (uint32_t *)q;           q += V * 4;
+        xp.h_cnt = (uint32_t *)q;            q += V * 8;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
+        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
+        xp.h_val = (uint8_t *)q;
+        xp.h_F = (double *)p->exn_blob;
+        xp.h_snap = (double *)(p->exn_blob + V * 8);
+    } else {
+        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
+        xp.h_val = nullptr; xp.h_F = nullptr; xp.h_snap = nullptr;
+    }
+    const int lds = (int)p->exn_lds_bytes;
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_count_split, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_count_split, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)total, (int64_t)pdp_device_cus() * per_cu));
+    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_count_split, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_count_split_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
+    p->exns_total = (int64_t)total;
+    p->exns_status_off = total * 24 + total * nmax * 8;
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -2951,6 +3445,32 @@ extern "C" int pdp_exact_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *
     PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
     PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exs_cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
     PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exs_cubes + p->exs_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
+    return PDP_OK;
+}
+
+extern "C" int pdp_exact_count_split(pdp_problem *p, const int8_t *depth, int64_t budget, int8_t *status, double *count, double *true_count,
+                                     int64_t *work, int64_t *leaves, int8_t *depth_used, void *stream)
+{
+    PDP_REQUIRE(p && status && count && true_count, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_count_split: a replicated problem (R = %d) is not supported; count on the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exns_launch(p, depth, budget, status, count, true_count, work, leaves, depth_used, stream);
+}
+
+extern "C" int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, double *cube_count, int64_t *cube_work,
+                                           int64_t *cube_leaves, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && cube_status && cube_count && cube_work && cube_leaves, "NULL argument");
+    PDP_REQUIRE(p->exns_total > 0, "pdp_exact_count_split_cubes: no pdp_exact_count_split call on this problem yet");
+    const size_t B = p->B, total = (size_t)p->exns_total;
+    const ExnsFixed F = exns_fixed(p);
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_count, p->exns_cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exns_cubes + total * 8, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, p->exns_cubes + total * 16, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exns_cubes + p->exns_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
     return PDP_OK;
 }
 

@@ -16,6 +16,8 @@ solver's ``unsat_clauses`` on an unsatisfiable instance is to be compared with. 
 number of models of an instance and, per variable, the share of them in which it is true (pdp_exact_count) -- what PDP's
 soft prediction is to be compared with.  With ``split=`` the deciding search of every instance is spread over 2^depth waves
 (pdp_exact_solve_split): same labels and models, for the one hard instance that would otherwise occupy one wave of the GPU.
+``count_models(split=)`` does the same for the count (pdp_exact_count_split): cube counts add, so the tail of a batch and a
+single instance get the whole GPU, with the same counts and marginals.
 """
 
 import numpy as np
@@ -32,6 +34,9 @@ SPLIT_WAVES_PER_SIMD = 4     # k_exact_split's occupancy by registers (DESIGN.md
 # the sweep in profiles/exact_time.txt ("split='auto' constants", tools/exact_time.py sweep)
 AUTO_STAGE1_BUDGET = 1 << 18
 AUTO_CUBES_PER_WAVE = 16
+# count_models(split='auto'): the reads per instance of the plain first count.  Chosen from the sweep in profiles/exact_time.txt
+# (tools/exact_time.py cssweep)
+AUTO_COUNT_STAGE1_BUDGET = 1 << 26
 
 
 def raw_item(n, clauses, label=-1.0, name=""):
@@ -439,18 +444,51 @@ def min_unsat(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
     return status, cost, models, work
 
 
-def count_models(items, budget=0, device=None, max_edges=MAX_EDGES):
+def count_split(prob, part, budget, split, device):
+    """The split count of one problem (``part``: its loader items, or a callable that returns them): numpy (status, count, true_count,
+    work, depth_used).  ``split`` an int: one pdp_exact_count_split call at that depth.  'auto': a plain exact_count with
+    AUTO_COUNT_STAGE1_BUDGET reads per instance (``budget`` if that is smaller), then the instances that ran out are counted again from the
+    start -- a partial count cannot be resumed, so the first stage's is discarded -- as one split call on a problem of their own at
+    auto_depth, with ``budget`` per cube; work is the sum of the two stages."""
+    if split != 'auto':
+        st, co, tc, wk, _, du = prob.exact_count_split(budget, depth=split, stats=True)[:6]
+        return st.cpu().numpy(), co.cpu().numpy(), tc.cpu().numpy(), wk.cpu().numpy(), du.cpu().numpy()
+    st, co, tc, wk = [t.cpu().numpy() for t in prob.exact_count(min(budget, AUTO_COUNT_STAGE1_BUDGET) if budget > 0 else AUTO_COUNT_STAGE1_BUDGET)]
+    du = np.zeros(len(st), dtype=np.int8)
+    again = [int(j) for j in np.nonzero(st == -1)[0]]
+    if again:
+        part = part() if callable(part) else part
+        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+        sub = _problem([part[j] for j in again], device)
+        r = [t.cpu().numpy() for t in sub.exact_count_split(budget, depth=auto_depth(len(again), device), stats=True)[:6]]
+        del sub
+        off = 0
+        for k, j in enumerate(again):
+            n = int(voff[j + 1] - voff[j])
+            st[j], co[j], du[j] = r[0][k], r[1][k], r[5][k]
+            wk[j] += r[3][k]
+            tc[voff[j]:voff[j + 1]] = r[2][off:off + n]
+            off += n
+    return st, co, tc, wk, du
+
+
+def count_models(items, budget=0, device=None, max_edges=MAX_EDGES, split=None, depths=False):
     """Exact model counts of loader items (as solve_items takes them) by the counting search (pdp_exact_count).  Returns numpy (status int8
     [N]: 1 count is the number of models, -1 the budget ran out and it is a lower bound, -2 the instance has more than 1023 variables and
     was not searched; count float64 [N], over all n_i variables of an instance, unused ones included; marginals: per instance a float64
     array of n_i values, the share of the counted models in which the variable is true, or None where count is 0; work int64 [N]).
-    count_is_exact says where count is an integer without rounding."""
+    count_is_exact says where count is an integer without rounding.
+    ``split``: the count of every instance spread over 2^split waves (pdp_exact_count_split; an int from 0 to 16), or 'auto': see
+    count_split.  Status, count and marginals are those of the call without ``split`` while count <= 2^53 and no cube runs out of
+    ``budget``, which then applies to every cube; work is the sum over the cubes.  ``depths``: also return depth_used int8 [N]."""
+    split = _check_split(split)
     native.require_gpu()
     device = torch.device('cuda:0') if device is None else torch.device(device)
     N = len(items)
     status = np.ones(N, dtype=np.int8)
     count = np.zeros(N, dtype=np.float64)
     work = np.zeros(N, dtype=np.int64)
+    used = np.zeros(N, dtype=np.int8)
     marginals = [None] * N
     for seg in _segments(items, max_edges):
         part = [items[i] for i in seg]
@@ -467,16 +505,20 @@ def count_models(items, budget=0, device=None, max_edges=MAX_EDGES):
             continue
         with torch.cuda.device(device):
             prob = _problem(part, device)
-            st, co, tc, wk = [t.cpu().numpy() for t in prob.exact_count(budget)]
+            if split is None:
+                st, co, tc, wk = [t.cpu().numpy() for t in prob.exact_count(budget)]
+                du = np.zeros(len(part), dtype=np.int8)
+            else:
+                st, co, tc, wk, du = count_split(prob, part, budget, split, device)
         del prob
         off = 0
         for j, (i, it) in enumerate(zip(seg, part)):
             n = int(it[0])
-            status[i], count[i], work[i] = st[j], co[j], wk[j]
+            status[i], count[i], work[i], used[i] = st[j], co[j], wk[j], du[j]
             if co[j] > 0:
                 marginals[i] = tc[off:off + n] / co[j]
             off += n
-    return status, count, marginals, work
+    return (status, count, marginals, work, used) if depths else (status, count, marginals, work)
 
 
 def count_is_exact(status, count):

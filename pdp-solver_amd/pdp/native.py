@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
     'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid', 'pdp_exact_solve_learn_assume',
     'pdp_exact_min_unsat', 'pdp_exact_count', 'pdp_exact_solve_split', 'pdp_exact_split_cubes',
+    'pdp_exact_count_split', 'pdp_exact_count_split_cubes',
 ]
 
 
@@ -522,6 +523,47 @@ class Problem(object):
                                     _stream()))
         return (status, count, true_count, work, leaves) if stats else (status, count, true_count, work)
 
+    def exact_count_split(self, budget=0, depth=None, stats=False):
+        """exact_count with the search of instance b spread over 2^depth[b] waves (pdp_exact_count_split): (status, count, true_count, work)
+        as exact_count's -- count and true_count equal its bit for bit while count <= 2^53 and no cube runs out of ``budget``, which applies
+        to every cube; work is the sum over the cubes.  ``depth``: an int, or an int8 tensor of B elements on the problem's device, values
+        0 .. 16, at most 2^22 cubes and 2^31 bytes of per-cube rows per call; None: 0.  ``stats``: also leaves int64 [B], depth_used int8
+        [B] (0 for an instance on the HBM route or of more than 1023 variables), cube_off int64 [B+1], cube_status int8 [cubes], cube_count
+        float64 [cubes], cube_work and cube_leaves int64 [cubes].  Everything is a function of the instances, the depths and the budget.
+        Synchronises the current stream once, then asynchronous on it (``stats`` synchronises again)."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads (0: the library default), got %r" % (budget,))
+        if depth is None:
+            depth = 0
+        if torch.is_tensor(depth):
+            if depth.dtype != torch.int8 or depth.numel() != self.B or depth.device != self.device:
+                raise ValueError("depth must be an int or an int8 tensor of %d elements (one per instance) on %s, got %s of %d on %s"
+                                 % (self.B, self.device, depth.dtype, depth.numel(), depth.device))
+            depth = depth.reshape(-1).contiguous()
+        elif isinstance(depth, bool) or not isinstance(depth, numbers.Integral) or not -128 <= depth <= 127:
+            raise ValueError("depth must be an int or an int8 tensor of %d elements (one per instance), got %r" % (self.B, depth))
+        else:
+            depth = torch.full((self.B,), int(depth), dtype=torch.int8, device=self.device)
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        count = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        true_count = torch.empty(self.V, dtype=torch.float64, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        leaves = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        depth_used = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        check(lib().pdp_exact_count_split(self._h, ptr(depth), C.c_int64(int(budget)), ptr(status), ptr(count), ptr(true_count), ptr(work),
+                                          ptr(leaves), ptr(depth_used), _stream()))
+        if not stats:
+            return status, count, true_count, work
+        cubes = int(torch.bitwise_left_shift(torch.ones_like(depth_used, dtype=torch.int64), depth_used.to(torch.int64)).sum().item())
+        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=self.device)
+        cube_status = torch.empty(cubes, dtype=torch.int8, device=self.device)
+        cube_count = torch.empty(cubes, dtype=torch.float64, device=self.device)
+        cube_work = torch.empty(cubes, dtype=torch.int64, device=self.device)
+        cube_leaves = torch.empty(cubes, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_count_split_cubes(self._h, ptr(cube_off), ptr(cube_status), ptr(cube_count), ptr(cube_work), ptr(cube_leaves),
+                                                _stream()))
+        return status, count, true_count, work, leaves, depth_used, cube_off, cube_status, cube_count, cube_work, cube_leaves
+
     def exact_solve_assume(self, budget=0, hints=None, assume=None, arena=0, stats=False):
         """The learning search under assumptions (pdp_exact_solve_learn_assume): (status, model, work, failed), plus learned with
         ``stats``.  ``assume`` (int8, V elements, on the problem's device, or None): > 0 the variable is held true, < 0 held false, 0 free.
@@ -671,7 +713,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split (its cube kernel), exact_min_unsat, exact_count, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split and exact_count_split (their cube kernels), exact_min_unsat, exact_count, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

@@ -2,7 +2,8 @@
 
 The inference side of ``SatFactorGraphTrainer``: ``_build_graph`` (model_type -> solver class,
 trainer.py:48-99), ``_check_recurrence_termination`` (:150-162), ``_post_process_predictions`` (:125-148; ``_post_process_complete``: the same rows
-decided by the hinted exact search, satyr.py --complete) and the test-mode
+decided by the hinted exact search, satyr.py --complete; with --complete-count the satisfiable rows' models counted, and with
+--complete-count-split that count spread over 2^depth waves per row, pdp_exact_count_split) and the test-mode
 metrics ``_compute_evaluation_metrics`` (:108-123: accuracy / recall errors of the clause check and the energy loss), and the training
 loss ``_compute_loss`` (:100-106) used by ``FactorGraphTrainerBase._train_batch``.
 """
@@ -158,7 +159,10 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         the same budget: an int while it is exact, a float above 2^53), "model_count_log2", "model_count_proved" (1: the number of models, 0: the budget
         ran out, a lower bound), "marginals" (per variable, the share of the counted models in which it is true), "marginal_gap" (the mean
         over the variables of |the soft prediction - marginal|) and "count_work"; marginals and marginal_gap are left out where nothing was
-        counted, and an instance of more than 1023 variables keeps its row as it is."""
+        counted, and an instance of more than 1023 variables keeps its row as it is.  With config['complete_count_split'] (a depth 0..16, or
+        -1: exact.count_split's 'auto') that count runs with every instance spread over 2^depth waves (pdp_exact_count_split): the same
+        counts and marginals while no budget runs out, "count_work" is the sum over the cubes, and a row counted at a depth above 0 gains
+        "count_split_depth" after "count_work"."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -236,7 +240,11 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             if sat_rows:
                 items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
                 pred = hint.cpu().numpy().astype(np.float64)
-                st, count, marginals, cwork = exact.count_models([items[i] for i in sat_rows], budget=budget, device=hint.device)
+                # config['complete_count_split']: the count of every row spread over 2^depth waves (pdp_exact_count_split); -1: auto
+                csplit = self._config.get('complete_count_split')
+                csplit = None if csplit is None else ('auto' if int(csplit) < 0 else int(csplit))
+                st, count, marginals, cwork, cdepth = exact.count_models([items[i] for i in sat_rows], budget=budget, device=hint.device,
+                                                                         split=csplit, depths=True)
                 exact_int = exact.count_is_exact(st, count)
                 for k, i in enumerate(sat_rows):
                     if st[k] == -2:
@@ -249,6 +257,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                         row['marginals'] = marginals[k].tolist()
                         row['marginal_gap'] = float(np.mean(np.abs(pred[offs[i]:offs[i + 1]] - marginals[k])))
                     row['count_work'] = int(cwork[k])
+                    if cdepth[k] > 0:
+                        row['count_split_depth'] = int(cdepth[k])
                 if hasattr(self, '_count_stats'):
                     self._count_stats[0] += int((st == 1).sum()); self._count_stats[1] += len(sat_rows)
         if hasattr(self, '_complete_stats'):

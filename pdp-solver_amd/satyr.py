@@ -21,7 +21,9 @@ the exact number of its models (pdp_exact_count), "model_count_log2", "model_cou
 from them) and "count_work"; ``--complete-split N`` (with ``--complete``, not with ``--complete-learn`` or ``--complete-certify``) spreads the
 search of every instance over 2^N waves (pdp_exact_solve_split; -1: a plain first stage, then a depth chosen from the number of
 undecided instances): the same "complete" and solution, "work" summed over the cubes, and "split_depth" on the rows searched at a depth
-above 0.
+above 0; ``--complete-count-split N`` (with ``--complete-count``) does the same for the count (pdp_exact_count_split; -1: a plain first count,
+then the instances that ran out once more at a depth chosen from their number): the same counts and marginals, "count_work" summed over
+the cubes, and "count_split_depth" on the rows counted at a depth above 0.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -138,6 +140,10 @@ def main(argv=None):
                         '(pdp_exact_solve_split), N from 0 to 16, or -1: a plain first stage, then the undecided instances at a depth that fills the GPU; '
                         'the same "complete" and solution, "work" summed over the cubes, "split_depth" on the rows searched at a depth above 0; '
                         'not with --complete-learn or --complete-certify', type=int, default=None)
+    parser.add_argument('--complete-count-split', dest='complete_count_split', help='With --complete --complete-count: spread the count of every '
+                        'satisfiable row over 2^N waves (pdp_exact_count_split), N from 0 to 16, or -1: a plain first count, then the rows that ran '
+                        'out of its reads once more at a depth that fills the GPU; the same counts and marginals, "count_work" summed over the cubes, '
+                        '"count_split_depth" on the rows counted at a depth above 0', type=int, default=None)
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -161,6 +167,11 @@ def main(argv=None):
             parser.error("--complete-split spreads the plain search: give it without --complete-learn and --complete-certify")
         if not -1 <= args['complete_split'] <= 16:
             parser.error("--complete-split takes a depth from 0 to 16, or -1 for a depth chosen from the undecided instances")
+    if args['complete_count_split'] is not None:
+        if not args['complete_count']:
+            parser.error("--complete-count-split spreads the count of --complete-count: give --complete-count as well")
+        if not -1 <= args['complete_count_split'] <= 16:
+            parser.error("--complete-count-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows that ran out")
     if args['complete_certify']:
         args['complete_learn'] = True
 

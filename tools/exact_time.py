@@ -48,7 +48,17 @@ n=200 m=852), ``sb150`` = the first 8 of row (b) (n=150 m=639): kernel time of p
 exact.split_solve(..., 'auto') on the same problem, each after an untimed call with a budget of one read that does the one-time
 preparation; per depth the cubes run, the cubes stopped early, the sum of reads against the plain search's and the largest counted cube's share of
 its instance's plain search.  ``sweep`` = on ``sb`` and ``sc``, split='auto' over its two constants (AUTO_STAGE1_BUDGET, AUTO_CUBES_PER_WAVE).
-PDP_SPLIT_ONLY=plain / split:<depth> times that one call alone (a fresh process per measurement of an alternating comparison)."""
+PDP_SPLIT_ONLY=plain / split:<depth> times that one call alone (a fresh process per measurement of an alternating comparison).
+
+Split count rows (pdp_exact_count_split; never part of the default): ``csa`` / ``csb`` = the 1 / 8 instances of row ``ca`` with the largest plain
+count_work as a batch of their own: kernel time of pdp_exact_count and of the split call at depths 4 / 8 / 12 on the same problem (each
+after an untimed call with a budget of one read), the reads against the plain count's, the largest cube's share of its instance's plain
+work, the cubes without a model; equal counts, leaves and true_counts asserted.  ``csauto`` = row ``ca`` whole: host wall time around
+exact.count_models(split='auto') and, untimed, the plain count_models next to it with status, counts and marginals asserted equal;
+PDP_COUNT_ONLY=plain times the plain count_models alone (a fresh process per measurement of the alternating comparison).  ``cssweep`` =
+count_models(split='auto') on row ``ca`` over AUTO_COUNT_STAGE1_BUDGET = 2^20 / 2^22 / 2^24 / 2^26.  ``csd`` = row ``cd`` with split='auto' and a
+budget of PDP_CSD_BUDGET reads per stage-1 instance and per cube (default and cap 2^28), one timed call: how many instances end with a
+complete count, next to the plain count under the same budget per instance."""
 import io
 import json
 import logging
@@ -602,9 +612,99 @@ def run_split_sweep():
                          int(out[2].sum())), flush=True)
 
 
+COUNT_SPLIT_ROWS = ('csa', 'csb', 'csauto', 'cssweep', 'csd')
+CSD_MAX_BUDGET = 1 << 28
+
+
+def _satisfiable_of(key):
+    "the instances of row ``key`` that the deciding search answers 1 (the batch of row c<key>), and the row's title"
+    from pdp import exact
+    title, make = ROWS[key]
+    items = make()
+    status = exact.solve_items(items)[0]
+    return title, [items[i] for i in np.nonzero(status == 1)[0]]
+
+
+def _wall(call):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = call()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def _same_counts(a, b, what):
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), what + ": status or count differs"
+    assert all((x is None) == (y is None) and (x is None or np.array_equal(x, y)) for x, y in zip(a[2], b[2])), what + ": marginals differ"
+
+
+def run_count_split(key):
+    from pdp import exact
+    if key == 'csd':
+        budget = min(CSD_MAX_BUDGET, int(os.environ.get('PDP_CSD_BUDGET', CSD_MAX_BUDGET)))
+        title, sub = _satisfiable_of('d')
+        exact.count_models(sub[:8], budget=1, split=1)
+        ms0, plain = _wall(lambda: exact.count_models(sub, budget=budget))
+        ms, got = _wall(lambda: exact.count_models(sub, budget=budget, split='auto', depths=True))
+        both = (plain[0] == 1) & (got[0] == 1)
+        assert np.array_equal(plain[1][both], got[1][both]) and (got[1][plain[0] == 1] >= plain[1][plain[0] == 1]).all(), "a complete count differs"
+        print("(csd) the %d instances of %s that the deciding search answers 1, budget %d reads per instance / per cube: plain count_models wall %.0f ms, "
+              "complete counts %d, lower bounds %d;  split='auto' (stage 1 budget %d) wall %.0f ms, complete counts %d, lower bounds %d, of the plain "
+              "lower bounds %d become complete;  depths %s  reads %d (plain %d)"
+              % (len(sub), title, budget, ms0, int((plain[0] == 1).sum()), int((plain[0] == -1).sum()), min(budget, exact.AUTO_COUNT_STAGE1_BUDGET), ms,
+                 int((got[0] == 1).sum()), int((got[0] == -1).sum()), int(((plain[0] == -1) & (got[0] == 1)).sum()),
+                 sorted(set(got[4].tolist())), int(got[3].sum()), int(plain[3].sum())), flush=True)
+        return
+    title, sub = _satisfiable_of('a')
+    if key in ('csauto', 'cssweep'):
+        exact.count_models(sub[:8], budget=1, split=1)                               # the context, the library and both kernels are loaded
+        if os.environ.get('PDP_COUNT_ONLY') == 'plain':
+            ms, out = _wall(lambda: exact.count_models(sub))
+            print("(csauto, plain alone) the %d satisfiable instances of %s: count_models wall %.1f ms  complete %d  reads %d"
+                  % (len(sub), title, ms, int((out[0] == 1).sum()), int(out[3].sum())), flush=True)
+            return
+        plain = None
+        for stage1 in ((1 << 20, 1 << 22, 1 << 24, 1 << 26) if key == 'cssweep' else (exact.AUTO_COUNT_STAGE1_BUDGET,)):
+            exact.AUTO_COUNT_STAGE1_BUDGET = stage1
+            ms, out = _wall(lambda: exact.count_models(sub, split='auto', depths=True))
+            if plain is None:
+                plain = exact.count_models(sub)
+            _same_counts(out, plain, "split='auto'")
+            print("(%s) the %d satisfiable instances of %s: count_models(split='auto') stage 1 budget 2^%d: wall %.1f ms  counted again %d at depth %s  "
+                  "reads %d (plain %d);  status, counts and marginals equal to the plain count_models on all %d"
+                  % (key, len(sub), title, stage1.bit_length() - 1, ms, int((out[4] > 0).sum()), sorted(set(out[4][out[4] > 0].tolist())),
+                     int(out[3].sum()), int(plain[3].sum()), len(sub)), flush=True)
+        return
+    work = exact.count_models(sub)[3]
+    top = np.argsort(-work, kind='stable')[:1 if key == 'csa' else 8]
+    part = [sub[i] for i in top]
+    b = dataset.to_torch(dataset.collate_segment(part), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(part))
+    p.exact_count(1)                                                                 # the one-time preparation is not timed
+    p.exact_count_split(1, depth=1)
+    torch.cuda.synchronize()
+    ms0, out = _event_ms(lambda: p.exact_count(stats=True))
+    st0, co0, tc0, wk0, lv0 = [t.cpu().numpy() for t in out]
+    print("(%s) the %d instances of row ca (%s, satisfiable) with the largest count_work: pdp_exact_count kernel %.2f ms  complete %d  work %s  "
+          "total %d  leaves total %d  log2(count) max %.1f" % (key, len(part), title, ms0, int((st0 == 1).sum()), _q(wk0), int(wk0.sum()), int(lv0.sum()),
+                                                              float(np.log2(co0.max()))), flush=True)
+    for depth in SPLIT_DEPTHS:
+        ms, out = _event_ms(lambda: p.exact_count_split(depth=depth, stats=True))
+        st, co, tc, wk, lv, du, off, cst, cco, cwk, clv = [t.cpu().numpy() for t in out]
+        assert np.array_equal(st, st0) and np.array_equal(co, co0) and np.array_equal(tc, tc0) and np.array_equal(lv, lv0), "the split count differs"
+        share = max(float(cwk[off[j]:off[j + 1]].max()) / max(1.0, float(wk0[j])) for j in range(len(st)))
+        print("    split depth %2d: kernel %.2f ms (%.3f of pdp_exact_count)  cubes %d  without a model %d  reads %d (%.3f of the plain count's)  "
+              "largest cube's share of its instance's plain work %.4f  grid %d;  count, true_count and leaves equal"
+              % (depth, ms, ms / ms0, cst.size, int((cco == 0).sum()), int(wk.sum()), float(wk.sum()) / float(wk0.sum()), share, p.exact_last_grid()),
+              flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
+        if k in COUNT_SPLIT_ROWS:
+            run_count_split(k)
+            continue
         if k in SPLIT_ROWS or k == 'sweep':
             run_split(k) if k in SPLIT_ROWS else run_split_sweep()
             continue
