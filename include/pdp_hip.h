@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -500,8 +500,38 @@ int pdp_exact_count_split(pdp_problem *p, const int8_t *depth, int64_t budget, i
 int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, double *cube_count, int64_t *cube_work,
                                 int64_t *cube_leaves, void *stream);
 
+/* The models of given ranks in pdp_exact_count's own order (plain Python, normative: tests/exact_rank_model.py).  The
+ * counting search meets its leaves in a fixed depth-first order and a leaf with f unassigned variables stands for 2^f models, so "count
+ * before the leaf + offset inside it" numbers every model of an instance exactly once.  Instance b asks for K_b = rank_off[b+1] -
+ * rank_off[b] ranks, ranks[rank_off[b] ..), non-decreasing (duplicates allowed), each in 0 .. 2^53 - 1.  The search is pdp_exact_count's
+ * -- passes, branching rule, backtracking, the budget check before every pass (budget <= 0: PDP_EXACT_DEFAULT_BUDGET), work < budget +
+ * 3 * (edges of the instance), the leaf rule count = count + ldexp(1.0, n - trail length) -- without T, F, snap and the crediting, and
+ * with a cursor over the instance's ranks:
+ *   Leaf.  before = count, then the leaf rule.  While a rank is open and rank < count: o = rank - before in integers (both are below
+ *      2^53: exact); an assigned variable takes its value, the j-th unassigned variable in ascending index (j from 0) takes bit j of o,
+ *      bits from 53 up are 0; found = 1; the cursor moves on.  If no rank is open any more the search ends here, status 1, before any
+ *      backtracking.  Emitting a model costs no work: work counts clause-literal reads only.
+ *   End.  Out of levels: status 1, every open rank gets found = 0 ("there is no such model").  Budget: status -1, every open rank gets
+ *      found = -1.  count_seen [B] = count at the end: the instance's model count if a rank >= that count was asked and status is 1,
+ *      else the count up to and including the leaf of the last rank.
+ *   Before any search.  More than 1023 variables: status -2, found = -1 for every rank, count_seen, work and leaves 0.  K_b = 0: status 1,
+ *      count_seen 0.0, work and leaves 0.
+ * found [rank_off[B]] (int8) and models (uint8, 0 / 1): instance b's rows start at byte sum over b' < b of K_b' * n_b', row j of them at
+ * + j * n_b, one byte per variable of the instance (n counts every variable, also one in no clause); the row of a rank with found != 1 is
+ * zero.  work and leaves [B] may be NULL; found and models may be NULL if rank_off[B] = 0.
+ * Consequences: ranks 0 .. count - 1 enumerate the models of a complete count, each once; a call with a rank >= the instance's count has
+ * pdp_exact_count's work, leaves and count, every other call at most those; the model of a rank is a function of the instance and the
+ * rank alone -- it does not depend on the other ranks asked for, and under a smaller budget a rank is answered with the same model or
+ * with found = -1.  count and before are uniform over the wave, one lane writes one byte of a row, and nothing goes through an atomic.
+ * rank_off [B+1] and ranks are device int64.  PDP_ERR_INVALID, the message names the instance: rank_off[0] != 0, a decreasing rank_off,
+ * a rank below 0 or >= 2^53, decreasing ranks inside an instance, more than 2^31 bytes of models (the instance at which the running
+ * total passes the cap).  R != 1 -> PDP_ERR_UNSUPPORTED.  Routing, slab and working arrays are pdp_exact_solve's, shared with it.  The call
+ * synchronises the stream once (it validates the ranks and sizes the rows); what follows is asynchronous on it. */
+int pdp_exact_models_at(pdp_problem *p, const int64_t *rank_off, const int64_t *ranks, int64_t budget, int8_t *status, double *count_seen,
+                        int8_t *found, uint8_t *models, int64_t *work, int64_t *leaves, void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split and pdp_exact_count_split (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_models_at, pdp_exact_solve_split and pdp_exact_count_split (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

@@ -29,7 +29,8 @@
 // pdp_exact_solve_split (further down) is the one entry point where two waves share an instance: the hinted search cut into 2^depth
 // cubes, prefixes of its own tree, one wave per cube; the only word the cubes of an instance share is best[b], lowered by an atomic
 // minimum and read at the budget checks, and no wave waits for another.  pdp_exact_count_split (at the end) cuts the counting search the
-// same way; its cubes share nothing at all, and a second kernel adds their counts up in cube order.
+// same way; its cubes share nothing at all, and a second kernel adds their counts up in cube order.  pdp_exact_models_at (last) walks
+// the counting search's leaves with a cursor over given ranks and writes the models of those ranks, one wave per instance again.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -3318,6 +3319,403 @@ int exns_launch(pdp_problem *p, const int8_t *depth, int64_t budget, int8_t *sta
     return PDP_OK;
 }
 
+// ---- pdp_exact_models_at: the models of given ranks in the counting search's own order -------------------------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_rank_model.py).  Its own search, kernel and launch path:
+// nothing above is touched.  The state is ex_search's, array for array, in ex_lds_layout's slab (no doubles per variable: count and
+// before are uniform over the wave, and nothing is credited).  The ranks of an instance are non-decreasing, so one cursor walks them while
+// the search walks its leaves: a leaf that raises count from `before` to `count` answers every rank below count that is still open.  The
+// cursor and the ranks are read from HBM by the whole wave at once (one address); a model goes out as one row of bytes, one lane per
+// variable in chunks of 64, the index of a variable among the unassigned ones from a ballot prefix carried from chunk to chunk.
+constexpr int64_t EXR_MAX_RANK = (int64_t)1 << 53;          // ranks lie below: every rank, and every count one is compared with, is an exact double
+constexpr int64_t EXR_MAX_MODEL_BYTES = (int64_t)1 << 31;
+constexpr int64_t EXR_NONE = 0x7fffffff;
+constexpr int EXR_SETUP_NT = 1024;
+constexpr int EXR_INFO = 6;
+
+struct ExrParams {
+    const int32_t *order;       // as ExParams
+    int nbig, B;
+    uint32_t *next;
+    int64_t budget;
+    const int64_t *rank_off;    // [B+1]
+    const int64_t *ranks;       // [rank_off[B]]
+    const int64_t *model_off;   // [B+1] first byte of every instance's rows in models
+    int8_t *status; double *count_seen; int8_t *found; uint8_t *models; int64_t *work; int64_t *leaves;
+    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+};
+
+// rank_off and the sizes, by one workgroup: model_off [B+1] = the running sum of K_b * n_b bytes; info[0] = 1 if rank_off[0] != 0,
+// info[1] = the lowest instance whose rank_off decreases, info[2] = the lowest instance at which model_off passes 2^31 bytes
+// (EXR_NONE: none), info[3] = model_off[B]; info[4] and info[5] are reset for k_exact_models_ranks.  A term K_b * n_b above the cap is
+// entered as cap + 1, so the sum cannot leave int64.
+__global__ void __launch_bounds__(EXR_SETUP_NT) k_exact_models_setup(PView pv, const int64_t *rank_off, int64_t *model_off, int64_t *info)
+{
+    __shared__ int64_t s[EXR_SETUP_NT];
+    __shared__ int dec, over;
+    const int t = (int)threadIdx.x, B = pv.B;
+    if (t == 0) { dec = (int)EXR_NONE; over = (int)EXR_NONE; model_off[0] = 0; }
+    __syncthreads();
+    for (int b = t; b < B; b += EXR_SETUP_NT)
+        if (rank_off[b + 1] < rank_off[b]) atomicMin(&dec, b);
+    __syncthreads();
+    int64_t running = 0;
+    for (int base = 0; base < B; base += EXR_SETUP_NT) {
+        const int b = base + t;
+        int64_t term = 0;
+        if (b < B) {
+            const int64_t K = rank_off[b + 1] - rank_off[b], n = pv.inst_v0[b + 1] - pv.inst_v0[b];
+            term = K <= 0 || n <= 0 ? 0 : (K > EXR_MAX_MODEL_BYTES / n ? EXR_MAX_MODEL_BYTES + 1 : K * n);
+        }
+        s[t] = term;
+        __syncthreads();
+        for (int o = 1; o < EXR_SETUP_NT; o <<= 1) {
+            const int64_t x = t >= o ? s[t - o] : 0;
+            __syncthreads();
+            s[t] += x;
+            __syncthreads();
+        }
+        if (b < B) {
+            const int64_t end = running + s[t];
+            model_off[b + 1] = end;
+            if (end > EXR_MAX_MODEL_BYTES) atomicMin(&over, b);
+        }
+        running += s[EXR_SETUP_NT - 1];
+        __syncthreads();
+    }
+    if (t == 0) {
+        info[0] = rank_off[0] != 0; info[1] = dec; info[2] = over; info[3] = running; info[4] = EXR_NONE; info[5] = EXR_NONE;
+    }
+}
+
+// The ranks themselves, one wave per instance at a time, after k_exact_models_setup on the same stream: nothing is read unless rank_off
+// is sound (then every index below rank_off[B] is the caller's).  info[4] = the lowest instance with a rank outside 0 .. 2^53 - 1,
+// info[5] = the lowest instance whose ranks decrease.
+__global__ void __launch_bounds__(EX_NT) k_exact_models_ranks(int B, const int64_t *rank_off, const int64_t *ranks, int64_t *info)
+{
+    if (info[0] != 0 || info[1] != EXR_NONE) return;
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < B; b += (int)gridDim.x) {
+        const int64_t a = rank_off[b], z = rank_off[b + 1];
+        int range = 0, unsorted = 0;
+        for (int64_t i = a + lane; i < z; i += EX_NT) {
+            const int64_t r = ranks[i];
+            range |= r < 0 || r >= EXR_MAX_RANK;
+            unsorted |= i > a && ranks[i - 1] > r;
+        }
+        const bool any_range = __ballot(range) != 0ull, any_unsorted = __ballot(unsorted) != 0ull;
+        if (lane == 0 && any_range) atomicMin((unsigned long long *)&info[4], (unsigned long long)b);
+        if (lane == 0 && any_unsorted) atomicMin((unsigned long long *)&info[5], (unsigned long long)b);
+    }
+}
+
+// One model: row[v] = the value of an assigned variable, bit j of `o` for the j-th unassigned one in ascending index (0 from bit 53 up).
+// val is at rest (a barrier lies behind its last store) and every lane runs every chunk, so the ballots are whole.
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ void exr_emit(const ExInst<LitT, PtrT> &X, uint64_t o, uint8_t *row)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int carry = 0;
+    for (int base = 0; base < X.n; base += EX_NT) {
+        const int v = base + lane;
+        const uint32_t x = v < X.n ? X.val[v] : 1u;
+        const unsigned long long mask = __ballot(x == 0u);
+        if (v < X.n) {
+            const int j = carry + __popcll(mask & below);
+            const uint32_t bit = x == 0u ? (j < 53 ? (uint32_t)((o >> j) & 1ull) : 0u) : (x == 1u ? 1u : 0u);
+            row[v] = (uint8_t)bit;
+        }
+        carry += __popcll(mask);
+    }
+}
+
+// The search of one instance by the calling wave: ex_search_count without the crediting, with the cursor `cur` over ranks[0 .. K), K >= 1.
+// Returns 1 (the last rank is answered, or the tree is exhausted: the open ranks get found 0) or -1 (budget spent: the open ranks get
+// found -1).  rows: K rows of n bytes, zero on entry; only answered ranks are written.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_rank(const ExInst<LitT, PtrT> &X, int64_t budget, const int64_t *ranks, int64_t K, int8_t *found, uint8_t *rows,
+                              int64_t *work_out, double *count_out, int64_t *leaves_out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0;
+    int64_t work = 0, leaves = 0, cur = 0;
+    double count = 0.0;
+    int result = -1;
+    for (;;) {
+        if (work >= budget) break;
+        // ---- one unit-propagation pass (ex_search's: keep the two in step)
+        int reads = 0, conflict = 0, unit = 0, wmin = INF;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat) continue;
+            if (nfree == 0) conflict = 1;
+            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
+            else wmin = nfree < wmin ? nfree : wmin;
+        }
+        work += ex_sum(reads);
+        bool any_conflict = __ballot(conflict) != 0ull;
+        const bool any_unit = __ballot(unit) != 0ull;
+        if (any_unit) {
+            // assign the pending set of the pass; a variable asked for both polarities is a conflict
+            ex_sync<HBM>();
+            int bad = 0;
+            for (int base = 0; base < X.n; base += EX_NT) {
+                const int v = base + lane;
+                const uint32_t bits = v < X.n ? X.pend[v] : 0u;
+                const unsigned long long mask = __ballot(bits != 0u);
+                if (bits) {
+                    X.pend[v] = 0u;
+                    X.val[v] = (bits & 1u) ? 1 : 2;
+                    bad |= bits == 3u;
+                    X.trail[tlen + __popcll(mask & below)] = v;
+                }
+                tlen += __popcll(mask);
+            }
+            any_conflict = any_conflict || __ballot(bad) != 0ull;
+            ex_sync<HBM>();
+        }
+        if (!any_conflict) {
+            if (any_unit) continue;
+            wmin = ex_min(wmin);
+            if (wmin == INF) {
+                // a leaf: its models are the ranks before .. count - 1; every open rank below count is answered here
+                const double before = count;
+                count = count + ldexp(1.0, X.n - tlen);
+                ++leaves;
+                while (cur < K) {
+                    const int64_t r = ranks[cur];
+                    if (!((double)r < count)) break;
+                    // before <= r < 2^53 (every rank below `before` was answered at an earlier leaf): the difference is exact
+                    exr_emit(X, (uint64_t)(r - (int64_t)before), rows + (size_t)cur * (size_t)X.n);
+                    if (lane == 0) found[cur] = 1;
+                    ++cur;
+                }
+                if (cur == K) { result = 1; break; }
+                any_conflict = true;
+            }
+        }
+        if (any_conflict) {
+            // chronological backtracking, ex_search's block (keep the two in step)
+            bool resumed = false;
+            while (level > 0) {
+                const uint32_t d = X.dvar[level];
+                const int v = (int)(d & 0x7fffffffu);
+                const int from = X.mark[level];
+                const uint32_t first = X.val[v];
+                ex_sync<HBM>();                                     // every lane has read the level before it is undone
+                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
+                tlen = from;
+                if (!(d & 0x80000000u)) {
+                    ex_sync<HBM>();
+                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
+                    ++tlen;
+                    ex_sync<HBM>();
+                    resumed = true;
+                    break;
+                }
+                --level;
+            }
+            if (!resumed) { result = 1; break; }
+            continue;
+        }
+        // ---- branching: ex_search's, without hints (keep the two in step)
+        reads = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) ++nfree;
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat || nfree != wmin) continue;
+            for (int j = a; j < z; ++j) {
+                const uint32_t L = X.lit[j];
+                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+            }
+            reads += z - a;
+        }
+        work += ex_sum(reads);
+        ex_sync<HBM>();
+        unsigned long long best = 0ull;
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+            if (p | q) {
+                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                               (p >= q ? 1ull : 0ull);
+                best = key > best ? key : best;
+            }
+        }
+        best = ex_max64(best);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        ++level;
+        ex_sync<HBM>();
+        if (lane == 0) { X.mark[level] = tlen; X.dvar[level] = (uint32_t)v; X.val[v] = (best & 1ull) ? 1 : 2; X.trail[tlen] = v; }
+        ++tlen;
+        ex_sync<HBM>();
+    }
+    // the ranks the search did not reach: no such model (the tree is exhausted), or not known (the budget is spent)
+    for (int64_t i = cur + lane; i < K; i += EX_NT) found[i] = (int8_t)(result == 1 ? 0 : -1);
+    *work_out = work; *count_out = count; *leaves_out = leaves;
+    return result;
+}
+
+// copy the instance's literals in clause order, clear the state, search, write the results
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_rank(const ExrParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill, int64_t r0, int64_t K)
+{
+    const int lane = (int)threadIdx.x;
+    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+    for (int k = lane; k < I.e; k += EX_NT) {
+        const int ed = I.f_edges[k];
+        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+    }
+    for (int v = lane; v < I.n; v += EX_NT) { X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u; }
+    ex_sync<HBM>();
+    int64_t work = 0, leaves = 0;
+    double count = 0.0;
+    const int st = ex_search_rank<HBM>(X, xp.budget, xp.ranks + r0, K, xp.found + r0, xp.models + xp.model_off[I.b], &work, &count, &leaves);
+    if (lane == 0) {
+        xp.status[I.b] = (int8_t)st;
+        xp.count_seen[I.b] = count;
+        if (xp.work) xp.work[I.b] = work;
+        if (xp.leaves) xp.leaves[I.b] = leaves;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_models(PView pv, ExrParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        const int64_t r0 = xp.rank_off[I.b], K = xp.rank_off[I.b + 1] - r0;
+        // Every arm ends in the barrier the others end in and falls through to the end of the loop body (k_exact_count's note: the wave
+        // must be whole again before the shuffle that hands out the next instance).
+        if (I.n > EXN_MAX_N || K == 0) {
+            // more than 1023 variables: not searched, every rank unknown; no ranks: nothing to search for
+            const bool wide = I.n > EXN_MAX_N;
+            for (int64_t j = (int64_t)threadIdx.x; j < K; j += EX_NT) xp.found[r0 + j] = (int8_t)-1;
+            if (threadIdx.x == 0) {
+                xp.status[I.b] = (int8_t)(wide ? -2 : 1);
+                xp.count_seen[I.b] = 0.0;
+                if (xp.work) xp.work[I.b] = 0;
+                if (xp.leaves) xp.leaves[I.b] = 0;
+            }
+            ex_sync<false>();
+        } else if (i < xp.nbig) {
+            ExInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
+            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
+            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve_rank<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr, r0, K);
+        } else {
+            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
+            ExInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
+            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
+            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve_rank<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ex_slab + L.cptr), r0, K);
+        }
+    }
+}
+
+int exr_launch(pdp_problem *p, const int64_t *rank_off, const int64_t *ranks, int64_t budget, int8_t *status, double *count_seen, int8_t *found,
+               uint8_t *models, int64_t *work, int64_t *leaves, void *stream)
+{
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t V = p->V, E = p->E, B = p->B;
+    // model_off [B+1] | info [EXR_INFO], once per problem
+    if (!p->exr_blob) {
+        const int st_ = pdp_dev_alloc((void **)&p->exr_blob, ((B + 1 + EXR_INFO) * 8 + 15) & ~(size_t)15);
+        if (st_ != PDP_OK) return st_;
+    }
+    int64_t *model_off = (int64_t *)p->exr_blob, *dinfo = model_off + B + 1;
+    hipLaunchKernelGGL(k_exact_models_setup, dim3(1), dim3(EXR_SETUP_NT), 0, st, make_view(p), rank_off, model_off, dinfo);
+    PDP_LAUNCH_CHECK();
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_models_ranks, dim3((unsigned)flat), dim3(EX_NT), 0, st, (int)B, rank_off, ranks, dinfo);
+    PDP_LAUNCH_CHECK();
+    int64_t info[EXR_INFO];
+    PDP_HIP_CHECK(hipMemcpyAsync(info, dinfo, sizeof(info), hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));                        // the ranks are validated and the rows sized before anything is written
+    if (info[0] != 0) {
+        pdp_set_error("pdp_exact_models_at: rank_off does not start at 0 (instance 0)");
+        return PDP_ERR_INVALID;
+    }
+    if (info[1] != EXR_NONE) {
+        pdp_set_error("pdp_exact_models_at: rank_off decreases at instance %lld", (long long)info[1]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[4] != EXR_NONE) {
+        pdp_set_error("pdp_exact_models_at: a rank of instance %lld is not in 0 .. 2^53 - 1", (long long)info[4]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[5] != EXR_NONE) {
+        pdp_set_error("pdp_exact_models_at: the ranks of instance %lld decrease; sort them per instance", (long long)info[5]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[2] != EXR_NONE) {
+        pdp_set_error("pdp_exact_models_at: the models (ranks x variables bytes) pass 2^31 bytes at instance %lld; ask for fewer ranks or split "
+                      "the batch", (long long)info[2]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[3] > 0) {
+        PDP_REQUIRE(found && models, "pdp_exact_models_at: found and models are NULL but ranks are given");
+        PDP_HIP_CHECK(hipMemsetAsync(models, 0, (size_t)info[3], st));     // rows of ranks that are not answered stay zero
+    }
+    ExrParams xp;
+    xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.rank_off = rank_off; xp.ranks = ranks; xp.model_off = model_off;
+    xp.status = status; xp.count_seen = count_seen; xp.found = found; xp.models = models; xp.work = work; xp.leaves = leaves;
+    if (p->ex_h_lit) {
+        char *q = (char *)p->ex_h_lit;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_pend = (uint32_t *)q;           q += V * 4;
+        xp.h_cnt = (uint32_t *)q;            q += V * 8;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
+        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
+        xp.h_val = (uint8_t *)q;
+    } else {
+        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
+        xp.h_val = nullptr;
+    }
+    const int lds = (int)p->ex_lds_bytes;
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_models, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_models, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
+    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_models, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -3472,6 +3870,17 @@ extern "C" int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, in
     PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, p->exns_cubes + total * 16, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
     PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exns_cubes + p->exns_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
     return PDP_OK;
+}
+
+extern "C" int pdp_exact_models_at(pdp_problem *p, const int64_t *rank_off, const int64_t *ranks, int64_t budget, int8_t *status, double *count_seen,
+                                   int8_t *found, uint8_t *models, int64_t *work, int64_t *leaves, void *stream)
+{
+    PDP_REQUIRE(p && rank_off && status && count_seen, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_models_at: a replicated problem (R = %d) is not supported; ask on the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exr_launch(p, rank_off, ranks, budget, status, count_seen, found, models, work, leaves, stream);
 }
 
 extern "C" int pdp_exact_learn_reductions(pdp_problem *p, int32_t *reductions, void *stream)

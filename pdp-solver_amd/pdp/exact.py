@@ -17,7 +17,11 @@ number of models of an instance and, per variable, the share of them in which it
 soft prediction is to be compared with.  With ``split=`` the deciding search of every instance is spread over 2^depth waves
 (pdp_exact_solve_split): same labels and models, for the one hard instance that would otherwise occupy one wave of the GPU.
 ``count_models(split=)`` does the same for the count (pdp_exact_count_split): cube counts add, so the tail of a batch and a
-single instance get the whole GPU, with the same counts and marginals.
+single instance get the whole GPU, with the same counts and marginals.  ``models_at`` turns the count into the models themselves: the
+counting search meets its satisfying cubes in a fixed order, so "count before the cube + offset inside it" numbers every model once, and
+a rank becomes a model by walking that order with a cursor (pdp_exact_models_at) -- ``enumerate_models`` lists the first
+models of an instance, ``sample_models`` draws uniformly from all of them (uniform ranks below the exact count): what PDP's own solution
+is to be compared with, and a supervised target the marginals alone do not give.
 """
 
 import numpy as np
@@ -28,7 +32,8 @@ from pdp.factorgraph import dataset
 
 MAX_EDGES = 1 << 24          # edges per problem handed to the library
 COUNT_MAX_N = 1023           # pdp_exact_count searches instances of up to this many variables (2^n is a finite double)
-SPLIT_MAX_DEPTH = 16         # pdp_exact_solve_split: at most 2^16 cubes per instance
+MAX_RANK = 1 << 53           # pdp_exact_models_at: ranks lie below (every rank and every count it is compared with is an exact double)
+SPLIT_MAX_DEPTH = 16        # pdp_exact_solve_split: at most 2^16 cubes per instance
 SPLIT_WAVES_PER_SIMD = 4     # k_exact_split's occupancy by registers (resources); four SIMDs per CU
 # split='auto': the reads per instance of the plain first stage, and how many cubes the second stage makes per resident wave.  Chosen from
 # the sweep in profiles/exact_time.txt ("split='auto' constants", tools/exact_time.py sweep)
@@ -524,6 +529,105 @@ def count_models(items, budget=0, device=None, max_edges=MAX_EDGES, split=None, 
 def count_is_exact(status, count):
     "boolean array: the search was complete and count <= 2^53, so count and the per-variable counts are exact integers"
     return (np.asarray(status) == 1) & (np.asarray(count, dtype=np.float64) <= 2.0 ** 53)
+
+
+def models_at(items, ranks, budget=0, device=None, max_edges=MAX_EDGES):
+    """The models of given ranks in the counting search's own order (pdp_exact_models_at): rank r of an instance is its
+    r-th model, r from 0, in the order count_models meets them, so ranks 0 .. count - 1 are all its models, each once, and the model of
+    a rank depends on the instance and the rank alone.  ``ranks``: per instance an integer array in any order, each in 0 .. 2^53 - 1
+    (None or empty: none).  Returns (status int8 [N]: 1 every rank of the instance is answered, -1 the budget ran out first, -2 more than
+    1023 variables; count_seen float64 [N]: the count when the search ended, the model count if a rank >= it was asked; found: per
+    instance an int8 array, 1 the row is that rank's model, 0 there is no such model, -1 not known; models: per instance a uint8 array
+    [k_i, n_i], rows in the order of ``ranks``, zero where found != 1; work int64 [N])."""
+    native.require_gpu()
+    if len(ranks) != len(items):
+        raise ValueError("ranks: one entry per instance (%d), got %d" % (len(items), len(ranks)))
+    asked = []
+    for it, r in zip(items, ranks):
+        r = np.zeros(0, dtype=np.int64) if r is None else np.asarray(r)
+        if r.size and (r.dtype.kind not in 'iu' or int(r.min()) < 0 or int(r.max()) >= MAX_RANK):
+            raise ValueError("ranks: instance %r needs integers in 0 .. 2^53 - 1" % (it[5],))
+        asked.append(r.astype(np.int64).reshape(-1))
+    device = torch.device('cuda:0') if device is None else torch.device(device)
+    N = len(items)
+    status = np.ones(N, dtype=np.int8)
+    seen = np.zeros(N, dtype=np.float64)
+    work = np.zeros(N, dtype=np.int64)
+    found, models = [None] * N, [None] * N
+    for seg in _segments(items, max_edges):
+        part = [items[i] for i in seg]
+        if sum(int(it[2].shape[1]) for it in part) == 0:
+            # no literal anywhere (and no problem to build: the layout needs an edge): without a clause the search has one leaf with every
+            # variable free, so rank r < 2^n is the binary digits of r; with an (empty) clause there is no model
+            for i, it in zip(seg, part):
+                n, r = int(it[0]), asked[i]
+                found[i] = np.zeros(r.size, dtype=np.int8)
+                models[i] = np.zeros((r.size, n), dtype=np.uint8)
+                if n > COUNT_MAX_N:
+                    status[i] = -2
+                    found[i][:] = -1
+                elif r.size and int(it[1]) == 0:
+                    seen[i] = np.ldexp(1.0, n)
+                    found[i][:] = r < seen[i]
+                    bits = (r[:, None] >> np.minimum(np.arange(n), 63)[None, :]) & 1
+                    models[i][:] = np.where(found[i][:, None] == 1, bits, 0)
+            continue
+        order = [np.argsort(asked[i], kind='stable') for i in seg]
+        off = np.concatenate([[0], np.cumsum([asked[i].size for i in seg])]).astype(np.int64)
+        flat = np.concatenate([asked[i][o] for i, o in zip(seg, order)]) if off[-1] else np.zeros(0, dtype=np.int64)
+        with torch.cuda.device(device):
+            prob = _problem(part, device)
+            st, cs, fo, mo, wk = [t.cpu().numpy() for t in prob.exact_models_at(torch.from_numpy(flat).to(device),
+                                                                                torch.from_numpy(off).to(device), budget)]
+        del prob
+        at = 0
+        for j, (i, it, o) in enumerate(zip(seg, part, order)):
+            n, k = int(it[0]), asked[i].size
+            status[i], seen[i], work[i] = st[j], cs[j], wk[j]
+            found[i] = np.empty(k, dtype=np.int8)
+            found[i][o] = fo[off[j]:off[j + 1]]
+            models[i] = np.empty((k, n), dtype=np.uint8)
+            models[i][o] = mo[at:at + k * n].reshape(k, n)
+            at += k * n
+    return status, seen, found, models, work
+
+
+def enumerate_models(items, limit, budget=0, device=None, max_edges=MAX_EDGES):
+    """The first ``limit`` models of every instance in the counting search's order (models_at with ranks 0 .. limit - 1): (models: per
+    instance a uint8 array [min(count, limit), n_i]; complete: boolean array, True where those are all the models of the instance --
+    the search ran to its end within ``limit`` models and the budget)."""
+    limit = int(limit)
+    if limit < 0:
+        raise ValueError("limit must be >= 0, got %d" % limit)
+    # one rank more than asked for tells "exactly limit models" from "more"
+    status, _, found, models, _ = models_at(items, [np.arange(limit + 1, dtype=np.int64)] * len(items), budget, device, max_edges)
+    out = [m[:limit][f[:limit] == 1] for f, m in zip(found, models)]
+    complete = np.array([st == 1 and f[limit] == 0 for st, f in zip(status, found)], dtype=bool)
+    return out, complete
+
+
+def sample_ranks(count, k, seed, index):
+    "the k ranks sample_models draws for the instance at position ``index`` of its items: uniform on 0 .. count - 1, a function of (seed, index, count, k)"
+    return np.random.Generator(np.random.Philox(key=[int(seed), int(index)])).integers(0, int(count), size=int(k))
+
+
+def sample_models(items, k, seed=0, budget=0, counts=None, device=None, max_edges=MAX_EDGES):
+    """k models of every instance drawn uniformly, with replacement, from ALL its models: uniform ranks below the exact count, then
+    models_at.  ``counts``: an earlier count_models result for the same items (its first two entries, status and count, are read);
+    None: count_models(items, budget) is run here.  Returns (samples, ranks): per instance a uint8 array [k, n_i] in draw order and the
+    int64 ranks drawn -- or None for both where no uniform sample exists: the count is a lower bound or above 2^53 (count_is_exact is
+    False), the instance has no model, or models_at ran out of budget on one of the ranks.  Instance i draws from
+    np.random.Philox(key=[seed, i]), i its index in ``items``, so its sample does not depend on the other instances or the batch cut."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1, got %d" % k)
+    if counts is None:
+        counts = count_models(items, budget, device, max_edges)
+    exact = count_is_exact(counts[0], counts[1]) & (np.asarray(counts[1]) > 0)
+    ranks = [sample_ranks(counts[1][i], k, seed, i) if exact[i] else None for i in range(len(items))]
+    _, _, found, models, _ = models_at(items, ranks, budget, device, max_edges)
+    good = [r is not None and bool((f == 1).all()) for r, f in zip(ranks, found)]
+    return [m if g else None for m, g in zip(models, good)], [r if g else None for r, g in zip(ranks, good)]
 
 
 def backbone(items, budget=0, device=None, max_edges=MAX_EDGES, arena=0):

@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_solve', 'pdp_exact_solve_hinted', 'pdp_exact_solve_learn', 'pdp_exact_learn_reductions',
     'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid', 'pdp_exact_solve_learn_assume',
     'pdp_exact_min_unsat', 'pdp_exact_count', 'pdp_exact_solve_split', 'pdp_exact_split_cubes',
-    'pdp_exact_count_split', 'pdp_exact_count_split_cubes',
+    'pdp_exact_count_split', 'pdp_exact_count_split_cubes', 'pdp_exact_models_at',
 ]
 
 
@@ -564,6 +564,44 @@ class Problem(object):
                                                 _stream()))
         return status, count, true_count, work, leaves, depth_used, cube_off, cube_status, cube_count, cube_work, cube_leaves
 
+    def exact_models_at(self, ranks, rank_off, budget=0, stats=False):
+        """The models of given ranks in exact_count's own order (pdp_exact_models_at): (status int8 [B]: 1 every rank of the instance is
+        answered, -1 the budget ran out first, -2 more than 1023 variables, not searched; count_seen float64 [B]: the count when the search
+        ended -- the model count if a rank >= it was asked; found int8 [K]: 1 the row is the model of that rank, 0 the instance has no
+        model of that rank, -1 not known (budget, or status -2); models uint8 [sum K_b * n_b]: instance b's K_b rows of n_b bytes one after
+        the other, instances in order, zero rows where found != 1; work int64 [B]), plus leaves int64 [B] with ``stats``.  ``rank_off``:
+        int64 [B+1] on the problem's device, instance b asks for ranks[rank_off[b]:rank_off[b+1]]; ``ranks``: int64 [rank_off[B]] on the
+        problem's device, non-decreasing inside an instance, each in 0 .. 2^53 - 1.  The model of a rank is a function of the instance
+        and the rank alone.  ``budget`` as in exact_solve.  Synchronises the current stream, then asynchronous on it."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads (0: the library default), got %r" % (budget,))
+        for name, t in (('rank_off', rank_off), ('ranks', ranks)):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.device != self.device:
+                raise ValueError("%s must be an int64 tensor on %s, got %s" % (name, self.device, '%s on %s' % (t.dtype, t.device)
+                                                                                if torch.is_tensor(t) else type(t).__name__))
+        if rank_off.numel() != self.B + 1:
+            raise ValueError("rank_off must have %d elements (one per instance and the end), got %d" % (self.B + 1, rank_off.numel()))
+        rank_off, ranks = rank_off.reshape(-1).contiguous(), ranks.reshape(-1).contiguous()
+        off = rank_off.cpu()
+        K = int(off[-1])
+        if ranks.numel() != K:
+            raise ValueError("ranks must have rank_off[%d] = %d elements, got %d" % (self.B, K, ranks.numel()))
+        nbytes = 0
+        if K > 0 and self.R == 1 and int(off[0]) == 0 and bool((off[1:] >= off[:-1]).all()):
+            # the rows' size; an unsound rank_off or a replicated problem goes to the library, which refuses before it writes anything
+            if getattr(self, '_inst_n', None) is None:
+                self._inst_n = torch.bincount(self.export_graph()[1].to(torch.int64), minlength=self.B).cpu()
+            nbytes = int(((off[1:] - off[:-1]) * self._inst_n).sum())
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        count_seen = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        found = torch.empty(K, dtype=torch.int8, device=self.device)
+        models = torch.empty(min(nbytes, 1 << 31), dtype=torch.uint8, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        leaves = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_models_at(self._h, ptr(rank_off), ptr(ranks), C.c_int64(int(budget)), ptr(status), ptr(count_seen), ptr(found),
+                                        ptr(models), ptr(work), ptr(leaves), _stream()))
+        return (status, count_seen, found, models, work, leaves) if stats else (status, count_seen, found, models, work)
+
     def exact_solve_assume(self, budget=0, hints=None, assume=None, arena=0, stats=False):
         """The learning search under assumptions (pdp_exact_solve_learn_assume): (status, model, work, failed), plus learned with
         ``stats``.  ``assume`` (int8, V elements, on the problem's device, or None): > 0 the variable is held true, < 0 held false, 0 free.
@@ -713,7 +751,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split and exact_count_split (their cube kernels), exact_min_unsat, exact_count, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split and exact_count_split (their cube kernels), exact_min_unsat, exact_count, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

@@ -3,7 +3,8 @@
 The inference side of ``SatFactorGraphTrainer``: ``_build_graph`` (model_type -> solver class,
 trainer.py:48-99), ``_check_recurrence_termination`` (:150-162), ``_post_process_predictions`` (:125-148; ``_post_process_complete``: the same rows
 decided by the hinted exact search, satyr.py --complete; with --complete-count the satisfiable rows' models counted, and with
---complete-count-split that count spread over 2^depth waves per row, pdp_exact_count_split) and the test-mode
+--complete-count-split that count spread over 2^depth waves per row, pdp_exact_count_split, with --complete-sample K uniform samples of
+those models, pdp_exact_models_at) and the test-mode
 metrics ``_compute_evaluation_metrics`` (:108-123: accuracy / recall errors of the clause check and the energy loss), and the training
 loss ``_compute_loss`` (:100-106) used by ``FactorGraphTrainerBase._train_batch``.
 """
@@ -162,7 +163,10 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         counted, and an instance of more than 1023 variables keeps its row as it is.  With config['complete_count_split'] (a depth 0..16, or
         -1: exact.count_split's 'auto') that count runs with every instance spread over 2^depth waves (pdp_exact_count_split): the same
         counts and marginals while no budget runs out, "count_work" is the sum over the cubes, and a row counted at a depth above 0 gains
-        "count_split_depth" after "count_work"."""
+        "count_split_depth" after "count_work".  With config['complete_sample'] (K >= 1, with complete_count) every row whose count is proved and
+        exact (at most 2^53, above 0) gains "samples", K models in the format of "solution" drawn uniformly with replacement from ALL its
+        models (exact.sample_models: uniform ranks below the count, then pdp_exact_models_at; the seed is config['random_seed'], the stream
+        that of the row's position among the forward's satisfiable rows), and "sample_ranks", the ranks drawn; every other row is unchanged."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -261,6 +265,17 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                         row['count_split_depth'] = int(cdepth[k])
                 if hasattr(self, '_count_stats'):
                     self._count_stats[0] += int((st == 1).sum()); self._count_stats[1] += len(sat_rows)
+                if self._config.get('complete_sample'):
+                    # config['complete_sample']: K models of every row with an exact count, drawn uniformly from all of them (exact.sample_models)
+                    samples, sranks = exact.sample_models([items[i] for i in sat_rows], int(self._config['complete_sample']),
+                                                          seed=int(self._config.get('random_seed', 0) or 0), budget=budget, counts=(st, count),
+                                                          device=hint.device)
+                    for k, i in enumerate(sat_rows):
+                        if samples[k] is not None:
+                            rows[i]['samples'] = samples[k].astype(int).tolist()
+                            rows[i]['sample_ranks'] = [int(r) for r in sranks[k]]
+                    if hasattr(self, '_sample_stats'):
+                        self._sample_stats[0] += sum(s is not None for s in samples); self._sample_stats[1] += len(sat_rows)
         if hasattr(self, '_complete_stats'):
             for k, s in enumerate((1, 0, -1)):
                 self._complete_stats[k] += int((status == s).sum())

@@ -23,7 +23,9 @@ search of every instance over 2^N waves (pdp_exact_solve_split; -1: a plain firs
 undecided instances): the same "complete" and solution, "work" summed over the cubes, and "split_depth" on the rows searched at a depth
 above 0; ``--complete-count-split N`` (with ``--complete-count``) does the same for the count (pdp_exact_count_split; -1: a plain first count,
 then the instances that ran out once more at a depth chosen from their number): the same counts and marginals, "count_work" summed over
-the cubes, and "count_split_depth" on the rows counted at a depth above 0.
+the cubes, and "count_split_depth" on the rows counted at a depth above 0; ``--complete-sample K`` (with ``--complete-count``) gives every row
+whose count is proved and exact "samples", K models in the format of "solution" drawn uniformly from all its models (pdp_exact_models_at at
+uniform ranks below the count, seeded by ``-s``), and "sample_ranks", the ranks drawn; every other row is unchanged.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -73,6 +75,7 @@ def run(config, logger, output):
     solver._complete_stats = [0, 0, 0]                  # satisfiable, unsatisfiable, undecided (this rank's units)
     solver._min_unsat_stats = [0, 0]                    # optima proved, rows asked (this rank's units)
     solver._count_stats = [0, 0]                        # counts completed, rows asked (this rank's units)
+    solver._sample_stats = [0, 0]                       # rows sampled, rows asked (this rank's units)
     say("Starting the prediction phase...")
     sink, owned = _open_output(output)
     try:
@@ -85,7 +88,8 @@ def run(config, logger, output):
     if complete:
         proved = "; minimum unsatisfied clauses proved for %d of %d" % tuple(solver._min_unsat_stats) if config.get('complete_min_unsat') else ""
         counted = "; models counted for %d of %d" % tuple(solver._count_stats) if config.get('complete_count') else ""
-        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s%s" % (tuple(solver._complete_stats) + (proved, counted)))
+        sampled = "; sampled %d of %d" % tuple(solver._sample_stats) if config.get('complete_sample') else ""
+        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s%s%s" % (tuple(solver._complete_stats) + (proved, counted, sampled)))
     return solver
 
 
@@ -144,6 +148,10 @@ def main(argv=None):
                         'satisfiable row over 2^N waves (pdp_exact_count_split), N from 0 to 16, or -1: a plain first count, then the rows that ran '
                         'out of its reads once more at a depth that fills the GPU; the same counts and marginals, "count_work" summed over the cubes, '
                         '"count_split_depth" on the rows counted at a depth above 0', type=int, default=None)
+    parser.add_argument('--complete-sample', dest='complete_sample', help='With --complete --complete-count: every row whose count is proved and '
+                        'exact (at most 2^53) gains "samples", K models in the format of "solution" drawn uniformly, with replacement, from all its '
+                        'models (pdp_exact_models_at at uniform ranks below the count; the seed is -s), and "sample_ranks", the ranks drawn',
+                        type=int, default=None, metavar='K')
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -172,6 +180,11 @@ def main(argv=None):
             parser.error("--complete-count-split spreads the count of --complete-count: give --complete-count as well")
         if not -1 <= args['complete_count_split'] <= 16:
             parser.error("--complete-count-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows that ran out")
+    if args['complete_sample'] is not None:
+        if not args['complete_count']:
+            parser.error("--complete-sample draws from the models --complete-count counts: give --complete-count as well")
+        if args['complete_sample'] < 1:
+            parser.error("--complete-sample takes the number of models to draw per row, at least 1")
     if args['complete_certify']:
         args['complete_learn'] = True
 

@@ -58,7 +58,13 @@ exact.count_models(split='auto') and, untimed, the plain count_models next to it
 PDP_COUNT_ONLY=plain times the plain count_models alone (a fresh process per measurement of the alternating comparison).  ``cssweep`` =
 count_models(split='auto') on row ``ca`` over AUTO_COUNT_STAGE1_BUDGET = 2^20 / 2^22 / 2^24 / 2^26.  ``csd`` = row ``cd`` with split='auto' and a
 budget of PDP_CSD_BUDGET reads per stage-1 instance and per cube (default and cap 2^28), one timed call: how many instances end with a
-complete count, next to the plain count under the same budget per instance."""
+complete count, next to the plain count under the same budget per instance.
+
+Rank rows (pdp_exact_models_at; never part of the default): ``ra`` = the batch of row ``ca`` in one process: pdp_exact_count, then
+pdp_exact_models_at with one and with 1 000 uniformly drawn ranks per instance (exact.sample_ranks, sorted), one timed call each after a
+call with a budget of one read that does the one-time preparation: kernel time (the call's validation kernels and its one synchronisation
+included), total work against the count's, leaves, and the bytes of models written; every rank answered and the first row of every
+instance checked by pdp_cnf_eval."""
 import io
 import json
 import logging
@@ -699,9 +705,48 @@ def run_count_split(key):
               flush=True)
 
 
+RANK_ROWS = ('ra',)
+RANK_MANY = 1000
+
+
+def run_rank(key):
+    "row ca's batch: pdp_exact_count, then pdp_exact_models_at with one and with RANK_MANY uniformly drawn ranks per instance, one timed call each"
+    from pdp import exact
+    title, sub = _satisfiable_of(key[1:])
+    dev = torch.device('cuda:0')
+    b = dataset.to_torch(dataset.collate_segment(sub), dev)
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(sub))
+    one = torch.arange(len(sub) + 1, dtype=torch.int64, device=dev)
+    p.exact_count(1)                                                                 # the one-time preparation is not timed
+    p.exact_models_at(torch.zeros(len(sub), dtype=torch.int64, device=dev), one, 1)
+    torch.cuda.synchronize()
+    ms0, out = _event_ms(lambda: p.exact_count(stats=True))
+    st0, co0, tc0, wk0, lv0 = [t.cpu().numpy() for t in out]
+    assert exact.count_is_exact(st0, co0).all() and (co0 > 0).all(), "row %s needs complete, exact, positive counts" % key
+    n = np.array([int(it[0]) for it in sub], dtype=np.int64)
+    print("(%s) the %d instances of %s that the deciding search answers 1: E=%d  pdp_exact_count kernel %.2f ms  work total %d  leaves total %d"
+          % (key, len(sub), title, p.E, ms0, int(wk0.sum()), int(lv0.sum())), flush=True)
+    for k in (1, RANK_MANY):
+        ranks = np.stack([np.sort(exact.sample_ranks(co0[i], k, 0, i)) for i in range(len(sub))])
+        flat, off = torch.from_numpy(ranks.reshape(-1)).to(dev), one * k
+        ms, out = _event_ms(lambda: p.exact_models_at(flat, off, stats=True))
+        st, seen, found, models, wk, lv = [t.cpu().numpy() for t in out]
+        assert (st == 1).all() and (found == 1).all() and (wk <= wk0).all() and (lv <= lv0).all() and (seen <= co0).all(), "a rank below the count is not answered"
+        rows = np.split(models, np.cumsum(k * n)[:-1])
+        unsat = p.cnf_eval(torch.from_numpy(np.concatenate([r.reshape(k, -1)[0] for r in rows]).astype(np.float32)).to(dev))[1]
+        assert int(unsat.sum().item()) == 0, "the first sampled row of an instance is not a model"
+        print("    pdp_exact_models_at, %d uniform rank%s per instance: kernel %.2f ms (%.3f of pdp_exact_count, validation and its synchronisation "
+              "included)  work total %d (%.3f of the count's)  leaves total %d  models written %d bytes  grid %d"
+              % (k, '' if k == 1 else 's', ms, ms / ms0, int(wk.sum()), float(wk.sum()) / float(wk0.sum()), int(lv.sum()), models.size, p.exact_last_grid()),
+              flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
+        if k in RANK_ROWS:
+            run_rank(k)
+            continue
         if k in COUNT_SPLIT_ROWS:
             run_count_split(k)
             continue
