@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -530,8 +530,55 @@ int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_
 int pdp_exact_models_at(pdp_problem *p, const int64_t *rank_off, const int64_t *ranks, int64_t budget, int8_t *status, double *count_seen,
                         int8_t *found, uint8_t *models, int64_t *work, int64_t *leaves, void *stream);
 
+/* pdp_exact_min_unsat with the search of every instance spread over 2^depth[b] waves that share one word, the best cost found so far
+ * (plain Python, normative: tests/exact_min_unsat_split_model.py).  Same passes, same bound, same branching rule as
+ * pdp_exact_min_unsat; same cubes as pdp_exact_solve_split: cube `index` of the 2^depth cubes of an instance is that search where the
+ * decision of every level L <= depth is pinned -- the incumbent hint's polarity if bit (index >> (depth - L)) & 1 is 0, else the other
+ * one -- and the level counts as already flipped, so backtracking pops through it and ends the cube.
+ *   Check pass.  Once per instance, in a kernel of its own before the cubes; it always runs: the thresholded hint goes to model, its reads
+ *      to chk, the clauses it leaves unsatisfied to ub0, and the shared word starts as ub[b] = ub0.  ub0 == 0: status 1, cost 0,
+ *      first = -1, no cube is searched (cube status 1, work 0).
+ *   Two bounds.  live is the cube's view of ub[b]: its own accepted cost at once, the other cubes' at the next re-read.  Every pass
+ *      prunes on cost + contra >= live, at every level.  Case 2 of pdp_exact_min_unsat (all units are forced when cost == rule - 1) uses
+ *      rule = ub0 while level < depth and rule = live once level >= depth.  The decisions of levels 1 .. depth are therefore taken in
+ *      states that depend on the instance and its hint alone: all cubes agree on the prefix tree whatever the timing, and partition it.
+ *      Forcing under ub0 is sound because live <= ub0; not forcing merely leaves a unit to a pinned decision.
+ *   A prefix that ends early.  A prune while level < depth ends the cube (every open level is pinned).  A leaf met while level < depth
+ *      belongs to the one cube with index & ((1 << (depth - level)) - 1) == 0; every other cube that reaches it ends there with nothing
+ *      credited.
+ *   Improvement.  A leaf (not pruned, no open clause) does one device-scope atomicMin(&ub[b], cost) and is accepted iff the old value
+ *      was above cost.  On acceptance the cube writes its assignment (unassigned variables false) to its own row, records the cost as
+ *      its cube_cost and one improvement more, and goes on with live = cost; otherwise live = the old value.  Either way it prunes.
+ *   Budget.  Per cube: chk[b] + own reads >= budget before every pass (budget <= 0: PDP_EXACT_DEFAULT_BUDGET), so
+ *      work < chk + cubes * (budget + 3 * edges of the instance).  At the same point the cube takes the minimum of live and the value of
+ *      ub[b] it loaded at the previous check (a relaxed device-scope load by one lane, issued one pass ahead of its use; the first one
+ *      before the cube copies the instance), ends as exhausted when live == 0, and only then tests the budget.  No wave waits for another.
+ *   Finish (one wave per instance, sums in int64 and cube order).  cost = ub[b].  first [B] (int32, may be NULL) = the lowest cube whose
+ *      cube_cost == cost, -1 if none: the thresholded hint stays in model; else model = that cube's row.  status 1 if every cube ended
+ *      exhausted, else -1.  work = chk + the cubes' work.  improvements = the cubes' accepted improvements.
+ * Promised.  At depth 0: pdp_exact_min_unsat's five outputs bit for bit under every budget.  At any depth with a budget that no cube
+ * exhausts: status 1, cost = the minimum (pdp_exact_min_unsat's wherever that is proved), model leaves exactly cost clauses unsatisfied,
+ * cube_cost[first] == cost, depth_used as requested (0 for an instance on the HBM route).  At any budget: cost is an upper bound that model
+ * attains, cost <= ub0, and the work bound.  With one wave (PDP_EXACT_GRID=1) the cubes run in ascending order, each to its end, and every
+ * output and record is the model's sequential().  NOT promised with more than one wave, because they depend on which cube lowers ub[b]
+ * first: which minimiser model is, first, work, improvements, the cube records, and the status of a cube that ends near its budget.
+ *   hint [V] (device; NULL: all false) as pdp_exact_min_unsat.  depth [B] (device int8; NULL: all 0) in 0 .. 16; at most 2^22 cubes per
+ *   call; either violated -> PDP_ERR_INVALID, the message names the instance.  depth_used [B] (int8, may be NULL).  work, improvements
+ *   and first may be NULL.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Routing and working arrays are pdp_exact_solve's, shared with it.  The call synchronises the stream once
+ * (the cube count sizes its records and its grid); the kernels that follow are asynchronous on it. */
+int pdp_exact_min_unsat_split(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, int32_t *cost,
+                              float *model, int64_t *work, int32_t *improvements, int32_t *first, int8_t *depth_used, void *stream);
+
+/* The per-cube records of the last pdp_exact_min_unsat_split call on the problem that succeeded (PDP_ERR_INVALID before the first and
+ * after a refused one): cube_off [B+1] (int64), cube_status [cubes] (1 exhausted / -1 budget spent), cube_cost [cubes] (int32: the cube's
+ * last accepted cost, -1: it accepted none), cube_work [cubes] (int64) and cube_improvements [cubes] (int32), cubes = cube_off[B] = the
+ * sum of 2^depth_used.  Device to device, asynchronous on the stream. */
+int pdp_exact_min_unsat_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int32_t *cube_cost, int64_t *cube_work,
+                                    int32_t *cube_improvements, void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_models_at, pdp_exact_solve_split and pdp_exact_count_split (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split and pdp_exact_min_unsat_split (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

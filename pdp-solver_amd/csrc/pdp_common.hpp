@@ -158,10 +158,14 @@ struct pdp_problem {
     // split counting solver (pdp_exact.hip::exns_launch): exn_prepare's routing and slab; a fixed block (cube offsets, depth used, route) and the
     // per-cube records of the last call (count, work, leaves, true_count rows, status), grown on demand; exns_total and exns_status_off as above
     char *exns_blob, *exns_cubes; size_t exns_cube_bytes, exns_status_off; int64_t exns_total;
+    // split optimising solver (pdp_exact.hip::exms_launch): ex_prepare's routing; a fixed block (check reads, cube offsets, the shared best
+    // costs, depth used, route) and the per-cube records of the last call (work, cost, improvements, model rows, status), grown on demand;
+    // exms_total and exms_status_off as above, exms_words = the words of one model row
+    char *exms_blob, *exms_cubes; size_t exms_cube_bytes, exms_status_off, exms_words; int64_t exms_total;
     // k-th models of the counting search (pdp_exact.hip::exr_launch): ex_prepare's routing and slab; the rows' byte offsets [B+1] and the
     // validation words of the last call, one block allocated on first use
     char *exr_blob;
-    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_min, k_exact_count, k_exact_learn, k_exact_check, k_exact_trim, k_exact_split, k_exact_count_split or k_exact_models on this problem (0: none yet)
+    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_min, k_exact_count, k_exact_learn, k_exact_check, k_exact_trim, k_exact_split, k_exact_count_split, k_exact_min_split or k_exact_models on this problem (0: none yet)
     uint32_t *team_ws;          // barrier counters and reduction mailboxes of the workgroup teams (k_sp_solve<NT, true>)
     hipStream_t res_side_stream; hipEvent_t res_side_ev[2];   // the big instances' launches overlap the LDS-resident kernel on a stream of their own
     float *nws[4]; size_t nws_floats[4];             // neural workspaces (grow on demand)

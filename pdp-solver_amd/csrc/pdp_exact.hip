@@ -31,6 +31,7 @@
 // minimum and read at the budget checks, and no wave waits for another.  pdp_exact_count_split (at the end) cuts the counting search the
 // same way; its cubes share nothing at all, and a second kernel adds their counts up in cube order.  pdp_exact_models_at (last) walks
 // the counting search's leaves with a cursor over given ranks and writes the models of those ranks, one wave per instance again.
+// pdp_exact_min_unsat_split (after it) cuts the branch and bound into cubes that share ub[b], the best cost any of them has found.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -3716,6 +3717,457 @@ int exr_launch(pdp_problem *p, const int64_t *rank_off, const int64_t *ranks, in
     return PDP_OK;
 }
 
+// ---- pdp_exact_min_unsat_split: one instance's branch and bound spread over 2^depth cubes, one wave per cube ----------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_min_unsat_split_model.py).  Its own search, kernels and launch path: nothing
+// above is touched (k_exact_split_setup is launched as it is).  A cube is ex_search_min with the decisions of levels 1..depth pinned as in
+// ex_search_split.  The state, the slab, the routing and the occupancy by LDS are k_exact's.  Four launches on one stream: the setup
+// (depth_used, route, cube_off), the check pass (once per instance: the thresholded hint into model, its reads into chk[b], its
+// unsatisfied clauses into ub0[b] and ub[b]), the cubes (one counter hands out cube ids: instance order, ascending index), the finish.
+// The only word two waves share is ub[b], the best cost any cube of instance b has found: lowered by one atomicMin per improvement, read
+// by lane 0 at the budget checks with a relaxed agent-scope load, one pass ahead of its use.  No wave waits for another.  `live` is the
+// cube's view of it and prunes at every level; forcing the units uses ub0 while level < depth and live from then on, so the decisions of
+// the pinned levels are taken in states that depend on the instance and its hint alone and the cubes partition one prefix tree whatever
+// the timing.  Every condition below is uniform over the wave, and both arms of ex_solve_min_split end in its one barrier.
+constexpr int EXMS_NO_COST = -1;                // cube_cost: the cube accepted no improvement
+
+struct ExmsParams {
+    int B;
+    uint32_t total;             // cubes of the call
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;
+    const float *hint;          // [V] the incumbents (NULL: all false)
+    const int8_t *du;           // [B] depth used
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    const int64_t *chk;         // [B] reads of the check pass
+    const int32_t *ub0;         // [B] the clauses the thresholded hint leaves unsatisfied
+    int32_t *ub;                // [B] the shared best cost
+    int8_t *cube_status;        // [total] 1 exhausted / -1 budget spent
+    int64_t *cube_work;         // [total]
+    int32_t *cube_cost;         // [total] the cube's last accepted cost (EXMS_NO_COST: none)
+    int32_t *cube_imp;          // [total] improvements the cube had accepted
+    uint32_t *rows;             // [total][words] bit-packed assignment of the cube's last accepted cost (instances of depth > 0)
+    int words;
+    float *model;               // [V] written by the check pass; by the cube of a depth-0 instance, by the finish kernel elsewhere
+    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+};
+
+__device__ __forceinline__ int exms_load(const int32_t *ub)
+{
+    return __hip_atomic_load(ub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The check pass of pdp_exact_min_unsat, once per instance, straight from the problem's arrays: the thresholded hint is the first
+// incumbent; every clause is read up to its first true literal.
+__global__ void __launch_bounds__(EX_NT) k_exact_min_split_check(PView pv, const float *hint, int64_t *chk, int32_t *ub0, int32_t *ub, float *model)
+{
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const Inst I = load_inst(pv, b);
+        for (int v = lane; v < I.n; v += EX_NT) model[I.v0 + v] = (hint && hint[I.v0 + v] > 0.5f) ? 1.0f : 0.0f;        // NaN compares false
+        int reads = 0, open = 0;
+        for (int c = lane; c < I.m; c += EX_NT) {
+            const int a = I.f_ptr[c], z = I.f_ptr[c + 1];
+            int sat = 0, k = a;
+            for (; k < z; ++k) {
+                const int ed = I.f_edges[k];
+                const bool t = hint && hint[I.v0 + I.e_var[ed]] > 0.5f;
+                if (t != (I.sgn[ed] < 0)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            open += !sat;
+        }
+        reads = ex_sum(reads);
+        open = ex_sum(open);
+        if (lane == 0) { chk[b] = reads; ub0[b] = open; ub[b] = open; }
+    }
+}
+
+// One cube of one instance by the calling wave: ex_search_min without its check pass (keep the two in step), where a level L <= depth
+// takes the polarity bit (index >> (depth - L)) & 1 asks for (0: the incumbent's, 1: the other) and is recorded as already flipped.
+// `live` comes in as the value of *ubp loaded before the instance was copied (not 0).  An accepted improvement writes the assignment to
+// `model` (the instance's slice of the output: depth 0) or bit-packed to `row` (depth > 0).  Returns 1 (the cube is exhausted, or some
+// cube has reached cost 0) or -1 (budget spent); `spent` (the check pass's reads) counts against the budget.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_min_split(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t spent, int depth, int index, int32_t *ubp, int ub0, int live,
+                                   float *model, uint32_t *row, int64_t *work_out, int *cost_out, int *improved_out)
+{
+    const int lane = (int)threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    constexpr uint32_t UNIT = 3u;
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0, improved = 0, accepted = EXMS_NO_COST, seen = live;
+    int64_t work = 0;
+    int result = -1;
+    for (;;) {
+        seen = __shfl(seen, 0);
+        live = seen < live ? seen : live;
+        if (live == 0) { result = 1; break; }                       // some cube has satisfied every clause
+        if (spent + work >= budget) break;
+        if (lane == 0) seen = exms_load(ubp);                       // used at the next check: its latency lies behind the pass
+        // ---- one pass: falsified clauses, unit requests, the minimum width of the open clauses (a unit has width 1)
+        int reads = 0, cost = 0, unit = 0, wmin = INF;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat) continue;
+            if (nfree == 0) { ++cost; continue; }
+            if (!distinct) { unit = 1; nfree = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
+            wmin = nfree < wmin ? nfree : wmin;
+        }
+        work += ex_sum(reads);
+        cost = ex_sum(cost);
+        wmin = ex_min(wmin);
+        const bool any_unit = __ballot(unit) != 0ull;
+        int contra = 0;
+        if (any_unit) {
+            ex_sync<HBM>();
+            for (int v = lane; v < X.n; v += EX_NT) contra += (X.pend[v] & UNIT) == UNIT;
+            contra = ex_sum(contra);
+        }
+        const int rule = level < depth ? ub0 : live;
+        bool prune = cost + contra >= live;
+        if (!prune && cost == rule - 1 && any_unit) {
+            // leaving any unit out reaches rule >= live: the pending set is assigned (no variable is asked for twice: that was pruned)
+            for (int base = 0; base < X.n; base += EX_NT) {
+                const int v = base + lane;
+                const uint32_t word = v < X.n ? X.pend[v] : 0u;
+                const uint32_t bits = word & UNIT;
+                const unsigned long long mask = __ballot(bits != 0u);
+                if (bits) {
+                    X.pend[v] = word & ~UNIT;
+                    X.val[v] = (bits & 1u) ? 1 : 2;
+                    X.trail[tlen + __popcll(mask & below)] = v;
+                }
+                tlen += __popcll(mask);
+            }
+            ex_sync<HBM>();
+            continue;
+        }
+        if (any_unit) {
+            // every other path drops the unit requests
+            for (int v = lane; v < X.n; v += EX_NT) { const uint32_t word = X.pend[v]; if (word & UNIT) X.pend[v] = word & ~UNIT; }
+            ex_sync<HBM>();
+        }
+        if (!prune && wmin == INF) {
+            // a leaf below live.  Inside the prefix every cube with these levels' bits arrives here: the one whose remaining bits are 0
+            // takes it, the others end (every open level is pinned) with nothing credited
+            if (level >= depth || (index & ((1 << (depth - level)) - 1)) == 0) {
+                int old = 0;
+                if (lane == 0) old = atomicMin(ubp, cost);
+                old = __shfl(old, 0);
+                if (old > cost) {
+                    // accepted: the assignment of this cost, unassigned variables false
+                    if (model) {
+                        for (int v = lane; v < X.n; v += EX_NT) model[v] = X.val[v] == 1 ? 1.0f : 0.0f;
+                    } else {
+                        for (int base = 0; base < X.n; base += EX_NT) {
+                            const int v = base + lane;
+                            const unsigned long long mask = __ballot(v < X.n && X.val[v] == 1);
+                            if (lane == 0) {
+                                row[base >> 5] = (uint32_t)mask;
+                                if (base + 32 < X.n) row[(base >> 5) + 1] = (uint32_t)(mask >> 32);
+                            }
+                        }
+                    }
+                    accepted = cost;
+                    ++improved;
+                    live = cost;
+                } else {
+                    live = old;                                     // another cube was there first
+                }
+            }
+            prune = true;
+        }
+        if (prune) {
+            // chronological backtracking, a copy of ex_search_min's block: a pinned level carries the flipped bit from the start; out of
+            // levels: the cube is exhausted
+            bool resumed = false;
+            while (level > 0) {
+                const uint32_t d = X.dvar[level];
+                const int v = (int)(d & 0x7fffffffu);
+                const int from = X.mark[level];
+                const uint32_t first = X.val[v];
+                ex_sync<HBM>();                                     // every lane has read the level before it is undone
+                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
+                tlen = from;
+                if (!(d & 0x80000000u)) {
+                    ex_sync<HBM>();
+                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
+                    ++tlen;
+                    ex_sync<HBM>();
+                    resumed = true;
+                    break;
+                }
+                --level;
+            }
+            if (!resumed) { result = 1; break; }
+            continue;
+        }
+        // ---- branching: ex_search_min's rule
+        reads = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int nfree = 0, sat = 0, k = a, distinct = 0;
+            uint32_t first = 0;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                const uint32_t x = X.val[L >> 1];
+                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            if (sat || nfree == 0 || (distinct ? nfree : 1) != wmin) continue;
+            for (int j = a; j < z; ++j) {
+                const uint32_t L = X.lit[j];
+                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+            }
+            reads += z - a;
+        }
+        work += ex_sum(reads);
+        ex_sync<HBM>();
+        unsigned long long best = 0ull;
+        for (int v = lane; v < X.n; v += EX_NT) {
+            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+            if (p | q) {
+                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+                const bool pos = ((X.pend[v] >> EX_HINT_SHIFT) & 3u) == 1u;
+                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                               (pos ? 1ull : 0ull);
+                best = key > best ? key : best;
+            }
+        }
+        best = ex_max64(best);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has an unassigned literal); never index with it
+        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        ++level;
+        const bool pinned = level <= depth;
+        const bool other = pinned && ((index >> (depth - level)) & 1) != 0;
+        const bool pos = ((best & 1ull) != 0ull) != other;
+        ex_sync<HBM>();
+        if (lane == 0) {
+            X.mark[level] = tlen; X.dvar[level] = (uint32_t)v | (pinned ? 0x80000000u : 0u); X.val[v] = pos ? 1 : 2; X.trail[tlen] = v;
+        }
+        ++tlen;
+        ex_sync<HBM>();
+    }
+    *work_out = work; *cost_out = accepted; *improved_out = improved;
+    return result;
+}
+
+// cube q = (instance I.b, index): load ub[b]; unless it is 0 already, copy the instance's literals in clause order, clear the state (pend
+// starts as the incumbent's codes) and search; then the cube's record.  Both arms end in the record and the barrier below.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_min_split(const ExmsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill, uint32_t q, int depth, int index)
+{
+    const int lane = (int)threadIdx.x;
+    int live = 0;
+    if (lane == 0) live = exms_load(xp.ub + I.b);
+    live = __shfl(live, 0);
+    int st = 1, cost = EXMS_NO_COST, improved = 0;
+    int64_t work = 0;
+    if (live != 0) {
+        if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
+        for (int k = lane; k < I.e; k += EX_NT) {
+            const int ed = I.f_edges[k];
+            X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+        }
+        for (int v = lane; v < I.n; v += EX_NT) {
+            const uint32_t code = (xp.hint && xp.hint[I.v0 + v] > 0.5f) ? 1u : 2u;          // NaN compares false
+            X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        }
+        ex_sync<HBM>();
+        st = ex_search_min_split<HBM>(X, xp.budget, xp.chk[I.b], depth, index, xp.ub + I.b, xp.ub0[I.b], live,
+                                      depth == 0 ? xp.model + I.v0 : (float *)nullptr, xp.rows + (size_t)q * (size_t)xp.words, &work, &cost,
+                                      &improved);
+    }
+    if (lane == 0) {
+        xp.cube_status[q] = (int8_t)st;
+        xp.cube_work[q] = work;
+        xp.cube_cost[q] = cost;
+        xp.cube_imp[q] = improved;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_min_split(PView pv, ExmsParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= xp.total) break;
+        int lo = 0, hi = xp.B;                                      // cube_off[lo] <= q < cube_off[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (xp.cube_off[mid] <= (int64_t)q) lo = mid; else hi = mid;
+        }
+        const Inst I = load_inst(pv, lo);
+        const int depth = (int)xp.du[lo], index = (int)((int64_t)q - xp.cube_off[lo]);
+        if (xp.route[lo]) {
+            ExInst<uint32_t, int32_t> X;
+            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
+            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
+            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve_min_split<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr, q, depth, index);
+        } else {
+            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
+            ExInst<uint16_t, uint16_t> X;
+            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
+            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
+            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
+            X.n = I.n; X.m = I.m; X.e = I.e;
+            ex_solve_min_split<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ex_slab + L.cptr), q, depth, index);
+        }
+    }
+}
+
+// The instance's answer from its cubes' records, one wave per instance: cost = ub[b]; first = the lowest cube whose last accepted cost
+// is that (-1: none, the thresholded hint stays in model); the model of cube `first` expanded from its row (a depth-0 instance's single
+// cube wrote its slice itself); status 1 when every cube is exhausted, else -1; work and improvements summed in int64.
+__global__ void __launch_bounds__(EX_NT) k_exact_min_split_finish(PView pv, ExmsParams xp, int8_t *status, int32_t *cost, int64_t *work,
+                                                                  int32_t *improvements, int32_t *first)
+{
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        const int best = xp.ub[b], depth = (int)xp.du[b];
+        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        int64_t sum = 0, imp = 0;
+        int open = 0, at = EXS_NONE;
+        for (int64_t j = lane; j < nc; j += EX_NT) {
+            sum += xp.cube_work[c0 + j];
+            imp += xp.cube_imp[c0 + j];
+            open |= xp.cube_status[c0 + j] != 1;
+            if (at == EXS_NONE && xp.cube_cost[c0 + j] == best) at = (int)j;
+        }
+        sum = exs_sum64(sum);
+        imp = exs_sum64(imp);
+        at = ex_min(at);
+        const bool all_done = __ballot(open) == 0ull;
+        if (depth > 0 && at != EXS_NONE) {
+            const uint32_t *row = xp.rows + (size_t)(c0 + at) * (size_t)xp.words;
+            for (int v = lane; v < n; v += EX_NT) xp.model[v0 + v] = ((row[v >> 5] >> (v & 31)) & 1u) ? 1.0f : 0.0f;
+        }
+        if (lane == 0) {
+            status[b] = (int8_t)(all_done ? 1 : -1);
+            cost[b] = best;
+            if (work) work[b] = xp.chk[b] + sum;
+            if (improvements) improvements[b] = (int32_t)imp;
+            if (first) first[b] = at == EXS_NONE ? -1 : at;
+        }
+    }
+}
+
+// fixed block of the call, once per problem, widest words first: chk [B] | cube_off [B+1] | info [4] | ub [B] | ub0 [B] | du [B] | route [B]
+struct ExmsFixed { int8_t *du; uint8_t *route; int32_t *ub, *ub0; int64_t *chk, *cube_off, *info; };
+
+inline ExmsFixed exms_fixed(const pdp_problem *p)
+{
+    const size_t B = p->B;
+    ExmsFixed F;
+    char *q = p->exms_blob;
+    F.chk = (int64_t *)q;       q += B * 8;
+    F.cube_off = (int64_t *)q;  q += (B + 1) * 8;
+    F.info = (int64_t *)q;      q += 4 * 8;
+    F.ub = (int32_t *)q;        q += B * 4;
+    F.ub0 = (int32_t *)q;       q += B * 4;
+    F.du = (int8_t *)q;         q += B;
+    F.route = (uint8_t *)q;
+    return F;
+}
+
+int exms_launch(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, int32_t *cost, float *model, int64_t *work,
+                int32_t *improvements, int32_t *first, int8_t *depth_used, void *stream)
+{
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t V = p->V, E = p->E, B = p->B;
+    if (!p->exms_blob) {
+        const int st_ = pdp_dev_alloc((void **)&p->exms_blob, (B * 8 + (B + 1) * 8 + 32 + 2 * B * 4 + 2 * B + 15) & ~(size_t)15);
+        if (st_ != PDP_OK) return st_;
+    }
+    const ExmsFixed F = exms_fixed(p);
+    p->exms_total = 0;                                               // no records to hand out until this call has launched its cubes
+    hipLaunchKernelGGL(k_exact_split_setup, dim3(1), dim3(EXS_SETUP_NT), 0, st, make_view(p), depth, p->ex_order, p->ex_nbig, F.du, F.route,
+                       F.cube_off, depth_used, F.info);
+    PDP_LAUNCH_CHECK();
+    int64_t info[4];
+    PDP_HIP_CHECK(hipMemcpyAsync(info, F.info, sizeof(info), hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));                        // the cube count sizes the records and the grid
+    if (info[0] != EXS_NONE) {
+        pdp_set_error("pdp_exact_min_unsat_split: the depth of instance %lld is not in 0 .. %d", (long long)info[0], EXS_MAX_DEPTH);
+        return PDP_ERR_INVALID;
+    }
+    if (info[1] != EXS_NONE) {
+        pdp_set_error("pdp_exact_min_unsat_split: more than 2^22 cubes in one call (reached at instance %lld); lower the depths or split the "
+                      "batch", (long long)info[1]);
+        return PDP_ERR_INVALID;
+    }
+    const size_t total = (size_t)info[2], words = ((size_t)info[3] + 31) / 32;
+    // per-cube records: work [total] | cost [total] | improvements [total] | rows [total][words] | status [total]; grown on demand
+    const size_t need = (total * 16 + total * words * 4 + total + 15) & ~(size_t)15;
+    if (need > p->exms_cube_bytes) {
+        if (p->exms_cubes) { pdp_dev_free(p->exms_cubes); p->exms_cubes = nullptr; p->exms_cube_bytes = 0; }
+        const int st_ = pdp_dev_alloc((void **)&p->exms_cubes, need);
+        if (st_ != PDP_OK) return st_;
+        p->exms_cube_bytes = need;
+    }
+    ExmsParams xp;
+    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.hint = hint; xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off; xp.chk = F.chk; xp.ub0 = F.ub0; xp.ub = F.ub;
+    xp.cube_work = (int64_t *)p->exms_cubes;
+    xp.cube_cost = (int32_t *)(p->exms_cubes + total * 8);
+    xp.cube_imp = (int32_t *)(p->exms_cubes + total * 12);
+    xp.rows = (uint32_t *)(p->exms_cubes + total * 16);
+    xp.cube_status = (int8_t *)(p->exms_cubes + total * 16 + total * words * 4);
+    xp.words = (int)words;
+    xp.model = model;
+    if (p->ex_h_lit) {
+        char *q = (char *)p->ex_h_lit;
+        xp.h_lit = (uint32_t *)q;            q += E * 4;
+        xp.h_pend = (uint32_t *)q;           q += V * 4;
+        xp.h_cnt = (uint32_t *)q;            q += V * 8;
+        xp.h_trail = (int32_t *)q;           q += V * 4;
+        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
+        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
+        xp.h_val = (uint8_t *)q;
+    } else {
+        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
+        xp.h_val = nullptr;
+    }
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_min_split_check, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), hint, F.chk, F.ub0, F.ub, model);
+    PDP_LAUNCH_CHECK();
+    const int lds = (int)p->ex_lds_bytes;
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_min_split, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_min_split, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)total, (int64_t)pdp_device_cus() * per_cu));
+    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
+    hipLaunchKernelGGL(k_exact_min_split, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_exact_min_split_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp, status, cost, work, improvements,
+                       first);
+    PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
+    p->exms_total = (int64_t)total;
+    p->exms_status_off = total * 16 + total * words * 4;
+    p->exms_words = words;
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -3869,6 +4321,32 @@ extern "C" int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, in
     PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exns_cubes + total * 8, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
     PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, p->exns_cubes + total * 16, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
     PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exns_cubes + p->exns_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
+    return PDP_OK;
+}
+
+extern "C" int pdp_exact_min_unsat_split(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, int32_t *cost,
+                                         float *model, int64_t *work, int32_t *improvements, int32_t *first, int8_t *depth_used, void *stream)
+{
+    PDP_REQUIRE(p && status && cost && model, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_min_unsat_split: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exms_launch(p, hint, depth, budget, status, cost, model, work, improvements, first, depth_used, stream);
+}
+
+extern "C" int pdp_exact_min_unsat_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int32_t *cube_cost, int64_t *cube_work,
+                                               int32_t *cube_improvements, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && cube_status && cube_cost && cube_work && cube_improvements, "NULL argument");
+    PDP_REQUIRE(p->exms_total > 0, "pdp_exact_min_unsat_split_cubes: no pdp_exact_min_unsat_split call on this problem yet");
+    const size_t B = p->B, total = (size_t)p->exms_total;
+    const ExmsFixed F = exms_fixed(p);
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exms_cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_cost, p->exms_cubes + total * 8, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_improvements, p->exms_cubes + total * 12, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exms_cubes + p->exms_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
     return PDP_OK;
 }
 

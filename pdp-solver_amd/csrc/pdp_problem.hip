@@ -351,6 +351,8 @@ extern "C" int pdp_problem_destroy(pdp_problem *p)
     if (p->exs_cubes) pdp_dev_free(p->exs_cubes);
     if (p->exns_blob) pdp_dev_free(p->exns_blob);
     if (p->exns_cubes) pdp_dev_free(p->exns_cubes);
+    if (p->exms_blob) pdp_dev_free(p->exms_blob);
+    if (p->exms_cubes) pdp_dev_free(p->exms_cubes);
     if (p->exr_blob) pdp_dev_free(p->exr_blob);
     if (p->ws_side_stream) { (void)hipStreamDestroy(p->ws_side_stream); for (int i = 0; i < 2; ++i) (void)hipEventDestroy(p->ws_side_ev[i]); }
     if (p->res_side_stream) { (void)hipStreamDestroy(p->res_side_stream); for (int i = 0; i < 2; ++i) (void)hipEventDestroy(p->res_side_ev[i]); }

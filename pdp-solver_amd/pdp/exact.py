@@ -17,8 +17,10 @@ number of models of an instance and, per variable, the share of them in which it
 soft prediction is to be compared with.  With ``split=`` the deciding search of every instance is spread over 2^depth waves
 (pdp_exact_solve_split): same labels and models, for the one hard instance that would otherwise occupy one wave of the GPU.
 ``count_models(split=)`` does the same for the count (pdp_exact_count_split): cube counts add, so the tail of a batch and a
-single instance get the whole GPU, with the same counts and marginals.  ``models_at`` turns the count into the models themselves: the
-counting search meets its satisfying cubes in a fixed order, so "count before the cube + offset inside it" numbers every model once, and
+single instance get the whole GPU, with the same counts and marginals.  ``min_unsat(split=)`` spreads the branch and bound
+(pdp_exact_min_unsat_split): the cubes of an instance share the best cost found, so one cube's incumbent prunes all the
+others; a proved cost is the same minimum, which minimiser comes back depends on the timing of the cubes.  ``models_at`` turns the
+count into the models themselves: the counting search meets its satisfying cubes in a fixed order, so "count before the cube + offset inside it" numbers every model once, and
 a rank becomes a model by walking that order with a cursor (pdp_exact_models_at) -- ``enumerate_models`` lists the first
 models of an instance, ``sample_models`` draws uniformly from all of them (uniform ranks below the exact count): what PDP's own solution
 is to be compared with, and a supervised target the marginals alone do not give.
@@ -42,6 +44,9 @@ AUTO_CUBES_PER_WAVE = 16
 # count_models(split='auto'): the reads per instance of the plain first count.  Chosen from the sweep in profiles/exact_time.txt
 # (tools/exact_time.py cssweep)
 AUTO_COUNT_STAGE1_BUDGET = 1 << 26
+# min_unsat(split='auto'): the reads per instance of the plain first branch and bound.  Chosen from the sweep in profiles/exact_time.txt
+# (tools/exact_time.py xsweep)
+AUTO_MIN_STAGE1_BUDGET = 1 << 26
 
 
 def raw_item(n, clauses, label=-1.0, name=""):
@@ -405,12 +410,47 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
     return (status, models, work) + tail
 
 
-def min_unsat(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
+def min_unsat_split(prob, part, budget, hint, split, device):
+    """The split branch and bound of one problem (``part``: its loader items, or a callable that returns them; ``hint``: a float32 tensor
+    of V values): numpy (status, cost, model, work, depth_used).  ``split`` an int: one pdp_exact_min_unsat_split call at that depth.
+    'auto': a plain exact_min_unsat with AUTO_MIN_STAGE1_BUDGET reads per instance (``budget`` if that is smaller), then the instances
+    whose optimum is not proved go through one split call on a problem of their own at auto_depth, with ``budget`` per cube.  The models
+    of the first stage are the hints of that call -- an incumbent carries over, so the second stage starts from the first stage's cost;
+    work is the sum of the two stages."""
+    if split != 'auto':
+        st, co, model, wk, _, _, du = prob.exact_min_unsat_split(budget, hints=hint, depth=split, stats=True)[:7]
+        return st.cpu().numpy(), co.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy(), du.cpu().numpy()
+    st, co, model, wk = prob.exact_min_unsat(min(budget, AUTO_MIN_STAGE1_BUDGET) if budget > 0 else AUTO_MIN_STAGE1_BUDGET, hints=hint)
+    st, co, model, wk = st.cpu().numpy(), co.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
+    du = np.zeros(len(st), dtype=np.int8)
+    again = [int(j) for j in np.nonzero(st == -1)[0]]
+    if again:
+        part = part() if callable(part) else part
+        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+        sub = _problem([part[j] for j in again], device)
+        hint2 = torch.from_numpy(np.concatenate([model[voff[j]:voff[j + 1]] for j in again])).to(device)
+        r = [t.cpu().numpy() for t in sub.exact_min_unsat_split(budget, hints=hint2, depth=auto_depth(len(again), device), stats=True)[:7]]
+        del sub
+        off = 0
+        for k, j in enumerate(again):
+            n = int(voff[j + 1] - voff[j])
+            st[j], co[j], du[j] = r[0][k], r[1][k], r[6][k]
+            wk[j] += r[3][k]
+            model[voff[j]:voff[j + 1]] = r[2][off:off + n]
+            off += n
+    return st, co, model, wk, du
+
+
+def min_unsat(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, split=None, depths=False):
     """The fewest unsatisfied clauses of loader items (as solve_items takes them) by branch and bound (pdp_exact_min_unsat).  Returns numpy
     (status int8 [N]: 1 the cost is the minimum over all assignments, -1 the budget ran out and it is an upper bound; cost int32 [N];
     models: per instance a float32 0/1 array of n_i values that leaves exactly cost clauses unsatisfied; work int64 [N]).
     ``hints``: per instance an array of n_i values or None -- the assignment the search starts from as its incumbent (> 0.5 true, every
-    other value false, NaN included; None: all false), so cost never exceeds what that assignment leaves unsatisfied."""
+    other value false, NaN included; None: all false), so cost never exceeds what that assignment leaves unsatisfied.
+    ``split``: the search of every instance spread over 2^split waves that share the best cost found (pdp_exact_min_unsat_split; an int
+    from 0 to 16), or 'auto': see min_unsat_split.  ``budget`` then applies to every cube.  A proved cost is the same minimum; which
+    minimiser the model is and work depend on the timing of the cubes.  ``depths``: also return depth_used int8 [N]."""
+    split = _check_split(split)
     native.require_gpu()
     if hints is not None:
         if len(hints) != len(items):
@@ -423,6 +463,7 @@ def min_unsat(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
     status = np.ones(N, dtype=np.int8)
     cost = np.zeros(N, dtype=np.int32)
     work = np.zeros(N, dtype=np.int64)
+    used = np.zeros(N, dtype=np.int8)
     models = [None] * N
     for seg in _segments(items, max_edges):
         part = [items[i] for i in seg]
@@ -437,16 +478,21 @@ def min_unsat(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None):
             continue
         with torch.cuda.device(device):
             prob = _problem(part, device)
-            st, co, model, wk = prob.exact_min_unsat(budget, hints=torch.from_numpy(np.concatenate(flat)).to(device))
-            st, co, model, wk = st.cpu().numpy(), co.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
+            hint = torch.from_numpy(np.concatenate(flat)).to(device)
+            if split is None:
+                st, co, model, wk = prob.exact_min_unsat(budget, hints=hint)
+                st, co, model, wk = st.cpu().numpy(), co.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy()
+                du = np.zeros(len(part), dtype=np.int8)
+            else:
+                st, co, model, wk, du = min_unsat_split(prob, part, budget, hint, split, device)
         del prob
         off = 0
         for j, (i, it) in enumerate(zip(seg, part)):
             n = int(it[0])
-            status[i], cost[i], work[i] = st[j], co[j], wk[j]
+            status[i], cost[i], work[i], used[i] = st[j], co[j], wk[j], du[j]
             models[i] = model[off:off + n].copy()
             off += n
-    return status, cost, models, work
+    return (status, cost, models, work, used) if depths else (status, cost, models, work)
 
 
 def count_split(prob, part, budget, split, device):

@@ -154,7 +154,10 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         "backbone_unknown" with their count (those literals are left out).  With config['complete_min_unsat'] every row whose "complete" is not 1
         also gains "min_unsat" (the fewest unsatisfied clauses pdp_exact_min_unsat found from PDP's assignment, within the same budget),
         "min_unsat_proved" (1: that is the minimum over all assignments, 0: an upper bound), "min_unsat_solution" and "min_unsat_work";
-        its five reference keys stay PDP's.  With config['complete_split'] (a depth 0..16, or -1: exact.split_solve's 'auto') the same search runs
+        its five reference keys stay PDP's.  With config['complete_min_unsat_split'] (a depth 0..16, or -1: exact.min_unsat_split's 'auto') that
+        search runs with every row spread over 2^depth waves that share the best cost found (pdp_exact_min_unsat_split): "min_unsat" and
+        "min_unsat_proved" mean the same, which minimiser "min_unsat_solution" is and "min_unsat_work" depend on the timing of the cubes, and a
+        row searched at a depth above 0 gains "min_unsat_split_depth" after "min_unsat_work".  With config['complete_split'] (a depth 0..16, or -1: exact.split_solve's 'auto') the same search runs
         with every instance spread over 2^depth waves (pdp_exact_solve_split): "complete" and the solution are unchanged, "work" is the sum over
         the cubes, and a row searched at a depth above 0 gains "split_depth" after "work".  With config['complete_count'] every row whose "complete" is 1 gains "model_count" (pdp_exact_count within
         the same budget: an int while it is exact, a float above 2^53), "model_count_log2", "model_count_proved" (1: the number of models, 0: the budget
@@ -230,11 +233,16 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             if open_rows:
                 items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
                 pred = hint.cpu().numpy()
-                st, cost, models, mwork = exact.min_unsat([items[i] for i in open_rows], budget=budget, device=hint.device,
-                                                          hints=[pred[offs[i]:offs[i + 1]] for i in open_rows])
+                # config['complete_min_unsat_split']: every row spread over 2^depth waves (pdp_exact_min_unsat_split); -1: auto
+                msplit = self._config.get('complete_min_unsat_split')
+                msplit = None if msplit is None else ('auto' if int(msplit) < 0 else int(msplit))
+                st, cost, models, mwork, mdepth = exact.min_unsat([items[i] for i in open_rows], budget=budget, device=hint.device,
+                                                                  hints=[pred[offs[i]:offs[i + 1]] for i in open_rows], split=msplit, depths=True)
                 for k, i in enumerate(open_rows):
                     rows[i]['min_unsat'], rows[i]['min_unsat_proved'] = int(cost[k]), int(st[k] == 1)
                     rows[i]['min_unsat_solution'], rows[i]['min_unsat_work'] = models[k].astype(int).tolist(), int(mwork[k])
+                    if mdepth[k] > 0:
+                        rows[i]['min_unsat_split_depth'] = int(mdepth[k])
                 if hasattr(self, '_min_unsat_stats'):
                     self._min_unsat_stats[0] += int((st == 1).sum()); self._min_unsat_stats[1] += len(open_rows)
         if self._config.get('complete_count'):

@@ -23,7 +23,10 @@ search of every instance over 2^N waves (pdp_exact_solve_split; -1: a plain firs
 undecided instances): the same "complete" and solution, "work" summed over the cubes, and "split_depth" on the rows searched at a depth
 above 0; ``--complete-count-split N`` (with ``--complete-count``) does the same for the count (pdp_exact_count_split; -1: a plain first count,
 then the instances that ran out once more at a depth chosen from their number): the same counts and marginals, "count_work" summed over
-the cubes, and "count_split_depth" on the rows counted at a depth above 0; ``--complete-sample K`` (with ``--complete-count``) gives every row
+the cubes, and "count_split_depth" on the rows counted at a depth above 0; ``--complete-min-unsat-split N`` (with ``--complete-min-unsat``)
+spreads that branch and bound over 2^N waves per row that share the best cost found (pdp_exact_min_unsat_split; -1: a plain first stage,
+then the rows left unproved once more from the cost reached): "min_unsat" and "min_unsat_proved" mean the same, "min_unsat_work" is summed
+over the cubes, and "min_unsat_split_depth" appears on the rows searched at a depth above 0; ``--complete-sample K`` (with ``--complete-count``) gives every row
 whose count is proved and exact "samples", K models in the format of "solution" drawn uniformly from all its models (pdp_exact_models_at at
 uniform ranks below the count, seeded by ``-s``), and "sample_ranks", the ranks drawn; every other row is unchanged.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
@@ -148,6 +151,11 @@ def main(argv=None):
                         'satisfiable row over 2^N waves (pdp_exact_count_split), N from 0 to 16, or -1: a plain first count, then the rows that ran '
                         'out of its reads once more at a depth that fills the GPU; the same counts and marginals, "count_work" summed over the cubes, '
                         '"count_split_depth" on the rows counted at a depth above 0', type=int, default=None)
+    parser.add_argument('--complete-min-unsat-split', dest='complete_min_unsat_split', help='With --complete --complete-min-unsat: spread the branch '
+                        'and bound of every row over 2^N waves that share the best cost found (pdp_exact_min_unsat_split), N from 0 to 16, or -1: a '
+                        'plain first stage, then the rows whose optimum is not proved once more, from the cost reached, at a depth that fills the '
+                        'GPU; "min_unsat" and "min_unsat_proved" mean the same, "min_unsat_work" is summed over the cubes, '
+                        '"min_unsat_split_depth" on the rows searched at a depth above 0', type=int, default=None)
     parser.add_argument('--complete-sample', dest='complete_sample', help='With --complete --complete-count: every row whose count is proved and '
                         'exact (at most 2^53) gains "samples", K models in the format of "solution" drawn uniformly, with replacement, from all its '
                         'models (pdp_exact_models_at at uniform ranks below the count; the seed is -s), and "sample_ranks", the ranks drawn',
@@ -180,6 +188,11 @@ def main(argv=None):
             parser.error("--complete-count-split spreads the count of --complete-count: give --complete-count as well")
         if not -1 <= args['complete_count_split'] <= 16:
             parser.error("--complete-count-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows that ran out")
+    if args['complete_min_unsat_split'] is not None:
+        if not args['complete_min_unsat']:
+            parser.error("--complete-min-unsat-split spreads the search of --complete-min-unsat: give --complete-min-unsat as well")
+        if not -1 <= args['complete_min_unsat_split'] <= 16:
+            parser.error("--complete-min-unsat-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows left unproved")
     if args['complete_sample'] is not None:
         if not args['complete_count']:
             parser.error("--complete-sample draws from the models --complete-count counts: give --complete-count as well")

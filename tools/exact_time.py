@@ -60,6 +60,15 @@ count_models(split='auto') on row ``ca`` over AUTO_COUNT_STAGE1_BUDGET = 2^20 / 
 budget of PDP_CSD_BUDGET reads per stage-1 instance and per cube (default and cap 2^28), one timed call: how many instances end with a
 complete count, next to the plain count under the same budget per instance.
 
+Split minimum rows (pdp_exact_min_unsat_split; never part of the default): ``xsa`` / ``xsb`` = the 1 / 8 instances of row ``xa`` with the largest
+plain work as a batch of their own, same incumbents: kernel time of pdp_exact_min_unsat and of the split call at depths 4 / 8 / 12 on the
+same problem (each after an untimed call with a budget of one read), proved counts, costs, the reads against the plain call's, the
+largest cube's share of its instance's plain work; every model checked by pdp_cnf_eval.  ``xsauto`` = whole rows (PDP_XS_ROWS=a,m100;
+default a): host wall time of exact.min_unsat and of exact.min_unsat(split='auto'), and how many unproved optima become proved.
+``xsweep`` = the same on row ``xa`` over AUTO_MIN_STAGE1_BUDGET = 2^18 / 2^22 / 2^26.  PDP_XS_CACHE=<path> keeps the picked instances between
+processes, PDP_MIN_SPLIT_ONLY=plain / split:<depth> times that one call alone (a fresh process per measurement of an alternating
+comparison), PDP_XS_BUDGET=<reads> replaces the default budget.
+
 Rank rows (pdp_exact_models_at; never part of the default): ``ra`` = the batch of row ``ca`` in one process: pdp_exact_count, then
 pdp_exact_models_at with one and with 1 000 uniformly drawn ranks per instance (exact.sample_ranks, sorted), one timed call each after a
 call with a budget of one read that does the one-time preparation: kernel time (the call's validation kernels and its one synchronisation
@@ -705,6 +714,104 @@ def run_count_split(key):
               flush=True)
 
 
+MIN_SPLIT_ROWS = ('xsa', 'xsb', 'xsauto', 'xsweep')
+
+
+def _unsat_with_incumbents(key):
+    "the instances of a row that the search answers 0 (the batch of row x<key>) with their slices of one p-d-p forward, and the row's title"
+    import pickle
+    from pdp import exact
+    cache = os.environ.get('PDP_XS_CACHE')
+    if cache and os.path.exists(cache + '.' + key):
+        with open(cache + '.' + key, 'rb') as f:
+            return pickle.load(f)
+    modular = key in MODULAR
+    title, make = MODULAR[key] if modular else ROWS[key]
+    items = make()
+    pred = np.concatenate([g[0].cpu().numpy() for g in _pdp_forward(items)])
+    status = exact.solve_items(items, learn=modular)[0]
+    pick = np.nonzero(status == 0)[0]
+    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in items])])
+    out = title, [items[i] for i in pick], [pred[voff[i]:voff[i + 1]].copy() for i in pick]
+    if cache:
+        with open(cache + '.' + key, 'wb') as f:
+            pickle.dump(out, f)
+    return out
+
+
+def run_min_split(key):
+    """xsa / xsb: the 1 / 8 instances of row xa with the largest plain work; xsauto [row ...]: exact.min_unsat(split='auto') against
+    exact.min_unsat on whole rows (default a; PDP_XS_ROWS=a,m100); xsweep: AUTO_MIN_STAGE1_BUDGET on row xa.  PDP_XS_CACHE=<path> keeps
+    the picked instances between the processes of an alternating comparison; PDP_MIN_SPLIT_ONLY=plain / split:<depth> times that one call
+    alone; PDP_XS_BUDGET=<reads> replaces the default budget (per instance, and per cube)."""
+    import pickle
+    from pdp import exact
+    budget = int(os.environ.get('PDP_XS_BUDGET', 0))
+    if key in ('xsauto', 'xsweep'):
+        for row in (os.environ.get('PDP_XS_ROWS', 'a').split(',') if key == 'xsauto' else ['a']):
+            title, sub, hints = _unsat_with_incumbents(row)
+            exact.min_unsat(sub[:8], budget=1, hints=hints[:8], split=1)                 # the context, the library and both kernels are loaded
+            ms0, plain = _wall(lambda: exact.min_unsat(sub, budget=budget, hints=hints))
+            print("(%s) the %d unsatisfiable instances of %s: min_unsat wall %.1f ms  proved %d  not proved %d  reads %d"
+                  % (key, len(sub), title, ms0, int((plain[0] == 1).sum()), int((plain[0] == -1).sum()), int(plain[3].sum())), flush=True)
+            for stage1 in ((1 << 18, 1 << 22, 1 << 26) if key == 'xsweep' else (exact.AUTO_MIN_STAGE1_BUDGET,)):
+                exact.AUTO_MIN_STAGE1_BUDGET = stage1
+                ms, out = _wall(lambda: exact.min_unsat(sub, budget=budget, hints=hints, split='auto', depths=True))
+                both = (plain[0] == 1) & (out[0] == 1)
+                assert np.array_equal(plain[1][both], out[1][both]) and (out[1][out[0] == 1] <= plain[1][out[0] == 1]).all(), "a proved cost differs"
+                print("    split='auto' stage 1 budget 2^%d: wall %.1f ms (%.3f of the plain call)  proved %d  not proved %d  of the plain call's "
+                      "unproved %d become proved  searched again %d at depth %s  reads %d"
+                      % (stage1.bit_length() - 1, ms, ms / ms0, int((out[0] == 1).sum()), int((out[0] == -1).sum()),
+                         int(((plain[0] == -1) & (out[0] == 1)).sum()), int((out[4] > 0).sum()), sorted(set(out[4][out[4] > 0].tolist())),
+                         int(out[3].sum())), flush=True)
+        return
+    cache = os.environ.get('PDP_XS_CACHE')
+    if cache and os.path.exists(cache + '.' + key):
+        with open(cache + '.' + key, 'rb') as f:
+            title, part, hint = pickle.load(f)
+    else:
+        title, sub, hints = _unsat_with_incumbents('a')
+        work = exact.min_unsat(sub, hints=hints)[3]
+        for name, count in (('xsa', 1), ('xsb', 8)):
+            top = np.argsort(-work, kind='stable')[:count]
+            picked = title, [sub[i] for i in top], np.concatenate([hints[i] for i in top])
+            if cache:
+                with open(cache + '.' + name, 'wb') as f:
+                    pickle.dump(picked, f)
+            if name == key:
+                _, part, hint = picked
+    b = dataset.to_torch(dataset.collate_segment(part), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(part))
+    h = torch.from_numpy(hint).to(p.device)
+    p.exact_min_unsat(1, hints=h)                                                     # the one-time preparation is not timed
+    p.exact_min_unsat_split(1, hints=h, depth=1)
+    torch.cuda.synchronize()
+    only = os.environ.get('PDP_MIN_SPLIT_ONLY')
+    if only:
+        depth = None if only == 'plain' else int(only.split(':')[1])
+        ms, out = _event_ms((lambda: p.exact_min_unsat(budget, hints=h)) if depth is None else
+                            (lambda: p.exact_min_unsat_split(budget, hints=h, depth=depth)))
+        print("(%s, %s alone) the %d instances of row xa with the largest work: kernel %.2f ms  status %s  cost %s  reads %d"
+              % (key, only, len(part), ms, out[0].cpu().numpy().tolist(), out[1].cpu().numpy().tolist(), int(out[3].sum().item())), flush=True)
+        return
+    ms0, out = _event_ms(lambda: p.exact_min_unsat(budget, hints=h, stats=True))
+    st0, co0, _, wk0, imp0 = [t.cpu().numpy() for t in out]
+    print("(%s) the %d instances of row xa (%s, unsatisfiable) with the largest work, incumbent = p-d-p forward: pdp_exact_min_unsat kernel %.2f ms  "
+          "proved %d  cost %s  work %s  total %d  improvements %s"
+          % (key, len(part), title, ms0, int((st0 == 1).sum()), co0.tolist(), _q(wk0), int(wk0.sum()), imp0.tolist()), flush=True)
+    for depth in SPLIT_DEPTHS:
+        ms, out = _event_ms(lambda: p.exact_min_unsat_split(budget, hints=h, depth=depth, stats=True))
+        st, co, model, wk, imp, first, du, off, cst, cco, cwk, cimp = [t.cpu().numpy() for t in out]
+        both = (st == 1) & (st0 == 1)
+        assert np.array_equal(co[both], co0[both]) and (co[st == 1] <= co0[st == 1]).all(), "a proved cost differs"
+        assert np.array_equal(p.cnf_eval(torch.from_numpy(model).to(p.device))[1].cpu().numpy().reshape(-1).astype(np.int64), co.astype(np.int64))
+        share = max(float(cwk[off[j]:off[j + 1]].max()) / max(1.0, float(wk0[j])) for j in range(len(st)))
+        print("    split depth %2d: kernel %.2f ms (%.3f of pdp_exact_min_unsat)  proved %d  cost %s  cubes %d  at their budget %d  with an "
+              "improvement %d  reads %d (%.3f of the plain call's)  largest cube's share of its instance's plain work %.4f  grid %d"
+              % (depth, ms, ms / ms0, int((st == 1).sum()), co.tolist(), cst.size, int((cst == -1).sum()), int((cimp > 0).sum()), int(wk.sum()),
+                 float(wk.sum()) / float(wk0.sum()), share, p.exact_last_grid()), flush=True)
+
+
 RANK_ROWS = ('ra',)
 RANK_MANY = 1000
 
@@ -749,6 +856,9 @@ if __name__ == '__main__':
             continue
         if k in COUNT_SPLIT_ROWS:
             run_count_split(k)
+            continue
+        if k in MIN_SPLIT_ROWS:
+            run_min_split(k)
             continue
         if k in SPLIT_ROWS or k == 'sweep':
             run_split(k) if k in SPLIT_ROWS else run_split_sweep()
