@@ -84,6 +84,12 @@ enum {
     FL_COUNT = 32
 };
 
+// What a split call of the complete solver keeps on the handle (pdp_exact.hip): blob = the fixed block its setup kernel fills (check reads,
+// cube offsets, the word the cubes of an instance share, depth used, route), allocated on first use; cubes = the per-cube records of the
+// last call, cube_bytes long, grown on demand; total = the cubes of that call (0: no call yet, or the last one failed); status_off =
+// where their status bytes start in cubes.
+struct pdp_exact_cubes { char *blob, *cubes; size_t cube_bytes, status_off; int64_t total; };
+
 // ---- handle -------------------------------------------------------------------------------------
 struct pdp_problem {
     int E, V, F, B, R;          // sizes of the (replicated) batch
@@ -151,17 +157,10 @@ struct pdp_problem {
     int ext_ready, ext_nbig; size_t ext_lds_bytes; char *ext_blob;
     // counting complete solver (pdp_exact.hip::exn_prepare): ex_prepare's routing; the slab bytes of its own layout and the HBM route's F and snap
     int exn_ready; size_t exn_lds_bytes; char *exn_blob;
-    // split complete solver (pdp_exact.hip::exs_launch): ex_prepare's routing; a fixed block (depth used, route, best, check reads, cube offsets)
-    // and the per-cube records of the last call (work, model rows, status), grown on demand; exs_total = the cubes of that call
-    // (0: no call yet, or the last one failed), exs_status_off = where their status bytes start in exs_cubes
-    char *exs_blob, *exs_cubes; size_t exs_cube_bytes, exs_status_off; int64_t exs_total;
-    // split counting solver (pdp_exact.hip::exns_launch): exn_prepare's routing and slab; a fixed block (cube offsets, depth used, route) and the
-    // per-cube records of the last call (count, work, leaves, true_count rows, status), grown on demand; exns_total and exns_status_off as above
-    char *exns_blob, *exns_cubes; size_t exns_cube_bytes, exns_status_off; int64_t exns_total;
-    // split optimising solver (pdp_exact.hip::exms_launch): ex_prepare's routing; a fixed block (check reads, cube offsets, the shared best
-    // costs, depth used, route) and the per-cube records of the last call (work, cost, improvements, model rows, status), grown on demand;
-    // exms_total and exms_status_off as above, exms_words = the words of one model row
-    char *exms_blob, *exms_cubes; size_t exms_cube_bytes, exms_status_off, exms_words; int64_t exms_total;
+    // the split calls of the complete solver, one pdp_exact_cubes each: exs the deciding one (pdp_exact.hip::exs_launch; records: work,
+    // model rows, status), exns the counting one (exns_launch, on exn_prepare's routing and slab; records: count, work, leaves,
+    // true_count rows, status), exms the optimising one (exms_launch; records: work, cost, improvements, model rows, status)
+    pdp_exact_cubes exs, exns, exms;
     // k-th models of the counting search (pdp_exact.hip::exr_launch): ex_prepare's routing and slab; the rows' byte offsets [B+1] and the
     // validation words of the last call, one block allocated on first use
     char *exr_blob;

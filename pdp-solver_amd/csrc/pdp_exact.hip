@@ -78,20 +78,42 @@ __host__ __device__ inline ExLds ex_lds_layout(int n, int m, int e)
 // u16 literal codes need n < 32768, u16 clause offsets e <= 65535
 inline bool ex_fits_lds(int n, int m, int e) { return n < 32768 && e <= 65535 && ex_lds_layout(n, m, e).bytes <= EX_LDS_LIMIT; }
 
+// working arrays of the HBM route, indexed by the problem's global ids (only the HBM-routed instances' slices are used); every DPLL
+// kernel's parameters embed one.  All NULL when no instance of the problem is HBM-routed.
+struct ExHbm {
+    uint32_t *lit;              // [E]
+    uint8_t *val;               // [V]
+    uint32_t *pend, *cnt;       // [V], [2V]
+    int32_t *trail;             // [V]
+    int32_t *mark;              // [V+B] (instance b at v0 + b: n+1 entries)
+    uint32_t *dvar;             // [V+B]
+};
+
+// carved from ex_prepare's block: lit [E] | pend [V] | cnt [2V] | trail [V] | mark [V+B] | dvar [V+B] | val [V]
+inline ExHbm ex_hbm(const pdp_problem *p)
+{
+    ExHbm H = {};
+    if (!p->ex_h_lit) return H;
+    const size_t V = p->V, E = p->E, B = p->B;
+    char *q = (char *)p->ex_h_lit;
+    H.lit = (uint32_t *)q;              q += E * 4;
+    H.pend = (uint32_t *)q;             q += V * 4;
+    H.cnt = (uint32_t *)q;              q += V * 8;
+    H.trail = (int32_t *)q;             q += V * 4;
+    H.mark = (int32_t *)q;              q += (V + B) * 4;
+    H.dvar = (uint32_t *)q;             q += (V + B) * 4;
+    H.val = (uint8_t *)q;
+    return H;
+}
+
 struct ExParams {
     const int32_t *order;       // [B] instance ids: the nbig HBM-routed ones first, then the LDS-routed ones, each by edges descending
     int nbig, B;
     uint32_t *next;             // the "next instance" counter (zeroed before the launch)
     int64_t budget;
     int8_t *status; float *model; int64_t *work;
-    // working arrays of the HBM route, indexed by the problem's global ids (only the HBM-routed instances' slices are used)
-    uint32_t *h_lit;            // [E]
-    uint8_t *h_val;             // [V]
-    uint32_t *h_pend, *h_cnt;   // [V], [2V]
-    int32_t *h_trail;           // [V]
-    int32_t *h_mark;            // [V+B] (instance b at v0 + b: n+1 entries)
-    uint32_t *h_dvar;           // [V+B]
-    const float *hint;          // [V] phase hints, read by k_exact<true> only (NULL: none); last, so the fields above keep their offsets
+    ExHbm h;
+    const float *hint;          // [V] phase hints, read by k_exact<true> only (NULL: none)
 };
 
 template <typename LitT, typename PtrT>
@@ -100,6 +122,44 @@ struct ExInst {
     uint8_t *val; uint32_t *pend, *cnt; int32_t *trail, *mark; uint32_t *dvar;
     int n, m, e;
 };
+
+// the instance's slices of the HBM route's arrays; the clause offsets are the problem's own
+__device__ __forceinline__ ExInst<uint32_t, int32_t> ex_bind_hbm(const ExHbm &H, const Inst &I)
+{
+    ExInst<uint32_t, int32_t> X;
+    X.lit = H.lit + I.e0; X.cptr = I.f_ptr;
+    X.val = H.val + I.v0; X.pend = H.pend + I.v0; X.cnt = H.cnt + 2 * (size_t)I.v0; X.trail = H.trail + I.v0;
+    X.mark = H.mark + I.v0 + I.b; X.dvar = H.dvar + I.v0 + I.b;
+    X.n = I.n; X.m = I.m; X.e = I.e;
+    return X;
+}
+
+// the instance's arrays in the workgroup's slab of LDS, laid out by ex_lds_layout
+__device__ __forceinline__ ExInst<uint16_t, uint16_t> ex_bind_lds(unsigned char *slab, const Inst &I)
+{
+    const ExLds L = ex_lds_layout(I.n, I.m, I.e);
+    ExInst<uint16_t, uint16_t> X;
+    X.lit = (uint16_t *)(slab + L.lit); X.cptr = (const uint16_t *)(slab + L.cptr);
+    X.val = slab + L.val; X.pend = (uint32_t *)(slab + L.pend); X.cnt = (uint32_t *)(slab + L.cnt);
+    X.trail = (int32_t *)(slab + L.trail); X.mark = (int32_t *)(slab + L.mark); X.dvar = (uint32_t *)(slab + L.dvar);
+    X.n = I.n; X.m = I.m; X.e = I.e;
+    return X;
+}
+
+// The instance's literals in clause order (f_ptr / f_edges: any edge order of the problem); on the LDS route the clause offsets too.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ __forceinline__ void ex_fill(const Inst &I, const ExInst<LitT, PtrT> &X)
+{
+    const int lane = (int)threadIdx.x;
+    if constexpr (!HBM) {
+        PtrT *cptr = const_cast<PtrT *>(X.cptr);                    // the slab's own offsets; the HBM route reads the problem's in place
+        for (int c = lane; c <= I.m; c += EX_NT) cptr[c] = (PtrT)I.f_ptr[c];
+    }
+    for (int k = lane; k < I.e; k += EX_NT) {
+        const int ed = I.f_edges[k];
+        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
+    }
+}
 
 // Between two phases of the search every lane must see what the others wrote: a barrier of the (one-wave) workgroup; the HBM route also
 // needs the agent-scope fence (waits for the stores, invalidates the CU's L1) so that plain loads see the other lanes' stores.
@@ -128,22 +188,222 @@ __device__ __forceinline__ unsigned long long ex_max64(unsigned long long x)
 
 constexpr uint32_t EX_HINT_SHIFT = 8;            // bits 8-9 of pend[v]: the hint code of v (0 none, 1 true, 2 false); bits 0-1 are the unit bits
 
-// The DPLL search of one instance by the calling wave.  Returns 1 (satisfiable: val holds a model), 0 (unsatisfiable) or -1 (budget spent);
-// *work_out = the clause-literal reads made.  The budget is checked before every propagation pass.
-// HINT: pend[v] carries the hint codes; `check` (wave-uniform: every variable has a hint) asks for the check pass, which runs before the
-// first budget check: the hint is written into val and every clause is read up to its first true literal; if every clause has one, that
-// assignment is the model, otherwise val is cleared and the search starts from nothing with the reads counted.
+// ---- the blocks every DPLL search below is built from, each written once ---------------------------------------------------------------
+// ex_search (deciding), ex_search_min (optimising), ex_search_count (counting) and ex_search_rank (k-th model) share them; the learning
+// search, the checker and the trimmer further down keep state layouts and passes of their own.
+
+// What one lane met in a unit-propagation pass over its clauses.
+struct ExPass { int reads, conflict, unit, wmin; };
+
+// One unit-propagation pass: lane l reads clauses l, l+64, ... up to their first true literal.  A clause with every literal false is a
+// conflict; one whose unassigned literals are all the same literal raises that literal's bit in pend; wmin is the least number of
+// unassigned literals of the lane's other open clauses (INT_MAX: none).
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ ExPass ex_propagate(const ExInst<LitT, PtrT> &X)
+{
+    int reads = 0, conflict = 0, unit = 0, wmin = 0x7fffffff;
+    for (int c = (int)threadIdx.x; c < X.m; c += EX_NT) {
+        const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+        int nfree = 0, sat = 0, k = a, distinct = 0;
+        uint32_t first = 0;
+        for (; k < z; ++k) {
+            const uint32_t L = X.lit[k];
+            const uint32_t x = X.val[L >> 1];
+            if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
+            else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+        }
+        reads += k - a;
+        if (sat) continue;
+        if (nfree == 0) conflict = 1;
+        else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
+        else wmin = nfree < wmin ? nfree : wmin;
+    }
+    return ExPass{reads, conflict, unit, wmin};
+}
+
+// Assign the pending set of a pass, in index order on the trail, and clear its unit bits.  HINT: the unit bits are bits 0-1 of pend[v]
+// (the hint code stays); otherwise they are the whole word.  Returns whether a variable was asked for both polarities (wave-uniform).
+// The caller has passed a barrier since the pass; the barrier behind the stores is this block's.
 template <bool HBM, bool HINT, typename LitT, typename PtrT>
-__device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, bool check, int64_t *work_out)
+__device__ __forceinline__ bool ex_assign_pending(const ExInst<LitT, PtrT> &X, int &tlen)
 {
     const int lane = (int)threadIdx.x;
     const unsigned long long below = (1ull << lane) - 1ull;
-    // the unit bits of pend[v]; without hints they are the whole word
     constexpr uint32_t UNIT = HINT ? 3u : ~0u;
+    int bad = 0;
+    for (int base = 0; base < X.n; base += EX_NT) {
+        const int v = base + lane;
+        const uint32_t word = v < X.n ? X.pend[v] : 0u;
+        const uint32_t bits = word & UNIT;
+        const unsigned long long mask = __ballot(bits != 0u);
+        if (bits) {
+            X.pend[v] = word & ~UNIT;
+            X.val[v] = (bits & 1u) ? 1 : 2;
+            bad |= bits == 3u;
+            X.trail[tlen + __popcll(mask & below)] = v;
+        }
+        tlen += __popcll(mask);
+    }
+    const bool both = __ballot(bad) != 0ull;
+    ex_sync<HBM>();
+    return both;
+}
+
+// What a search does with a level that backtracking undoes, and with one it opens.  The deciding searches do nothing; the counting
+// search's ExnCredit (below) credits the level's models to its variables.
+struct ExNoCredit {
+    __device__ __forceinline__ void load(int) {}                                                   // before the barrier: what the level holds
+    template <typename LitT, typename PtrT>
+    __device__ __forceinline__ void undo(const ExInst<LitT, PtrT> &, int, int) const {}            // behind it, before val is cleared
+    __device__ __forceinline__ void open(int) const {}                                             // lane 0, with a decision or its flip
+};
+
+// Chronological backtracking: undo levels until one whose second polarity is untried, and take that.  A level pinned by a cube carries
+// the flipped bit from the start, so the loop pops through it.  Returns false when no level is left.
+template <bool HBM, typename LitT, typename PtrT, typename Credit>
+__device__ __forceinline__ bool ex_backtrack(const ExInst<LitT, PtrT> &X, int &level, int &tlen, Credit &credit)
+{
+    const int lane = (int)threadIdx.x;
+    bool resumed = false;
+    while (level > 0) {
+        const uint32_t d = X.dvar[level];
+        const int v = (int)(d & 0x7fffffffu);
+        const int from = X.mark[level];
+        const uint32_t first = X.val[v];
+        credit.load(level);
+        ex_sync<HBM>();                                             // every lane has read the level before it is undone
+        credit.undo(X, from, tlen);
+        for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;      // the same lane as the credit
+        tlen = from;
+        if (!(d & 0x80000000u)) {
+            ex_sync<HBM>();
+            if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; credit.open(level); }
+            ++tlen;
+            ex_sync<HBM>();
+            resumed = true;
+            break;
+        }
+        --level;
+    }
+    return resumed;
+}
+
+// The first polarity of a decision: by occurrences (true when they are at least as many), the hint's where the variable has one, or
+// the incumbent's (every variable has a code).
+enum ExPhase { EX_PHASE_COUNT, EX_PHASE_HINT, EX_PHASE_INCUMBENT };
+
+// The branch variable from the counters a branching pass left in cnt (cleared here): a wave maximum of unique 64-bit keys, the score,
+// then the lower index, then the polarity in bit 0.  0: no variable was counted.
+template <ExPhase PHASE, typename LitT, typename PtrT>
+__device__ __forceinline__ unsigned long long ex_pick(const ExInst<LitT, PtrT> &X)
+{
+    unsigned long long best = 0ull;
+    for (int v = (int)threadIdx.x; v < X.n; v += EX_NT) {
+        const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
+        if (p | q) {
+            X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+            bool pos = p >= q;
+            if constexpr (PHASE != EX_PHASE_COUNT) {
+                const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
+                if constexpr (PHASE == EX_PHASE_INCUMBENT) pos = code == 1u;
+                else if (code) pos = code == 1u;
+            }
+            const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
+                                           (pos ? 1ull : 0ull);
+            best = key > best ? key : best;
+        }
+    }
+    return ex_max64(best);
+}
+
+// Branching: the unassigned variable with the most occurrences in the open clauses of minimum width wmin (>= 2: the units are assigned).
+// Its reads go to `work`.  Returns ex_pick's key.
+template <bool HBM, ExPhase PHASE, typename LitT, typename PtrT>
+__device__ __forceinline__ unsigned long long ex_branch(const ExInst<LitT, PtrT> &X, int wmin, int64_t &work)
+{
+    int reads = 0;
+    for (int c = (int)threadIdx.x; c < X.m; c += EX_NT) {
+        const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+        int nfree = 0, sat = 0, k = a;
+        for (; k < z; ++k) {
+            const uint32_t L = X.lit[k];
+            const uint32_t x = X.val[L >> 1];
+            if (x == 0u) ++nfree;
+            else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
+        }
+        reads += k - a;
+        if (sat || nfree != wmin) continue;
+        for (int j = a; j < z; ++j) {
+            const uint32_t L = X.lit[j];
+            if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
+        }
+        reads += z - a;
+    }
+    work += ex_sum(reads);
+    ex_sync<HBM>();
+    return ex_pick<PHASE>(X);
+}
+
+// What a cube of a split call knows: a prefix of its instance's own search tree, levels 1 .. depth decided by the bits of `index`.
+// `word` is the one word the cubes of an instance share (best[b] or ub[b]; the count's cubes share none), `seen` its value when the
+// cube was picked up, `spent` the reads of the instance's check pass, which count against the budget.  A plain call has no cube.
+template <bool SPLIT> struct ExCube {};
+template <> struct ExCube<true> { int depth, index; int64_t spent; int32_t *word; int seen; };
+
+__device__ __forceinline__ int ex_shared_load(const int32_t *word)
+{
+    return __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a leaf met with fewer than `depth` levels open is reached by every cube with these levels' bits: the one whose remaining bits are 0 owns it
+__device__ __forceinline__ bool ex_owns_leaf(const ExCube<true> &Q, int level)
+{
+    const int rest = Q.depth - level;
+    return rest <= 0 || (Q.index & ((1 << rest) - 1)) == 0;
+}
+
+// The decision push: open a level on the variable and polarity of ex_pick's key (never 0).  SPLIT: a level L <= depth takes the polarity
+// bit (index >> (depth - L)) & 1 asks for (0: the key's, 1: the other) and is recorded as already flipped.
+template <bool HBM, bool SPLIT, typename LitT, typename PtrT, typename Credit>
+__device__ __forceinline__ void ex_decide(const ExInst<LitT, PtrT> &X, const ExCube<SPLIT> &Q, unsigned long long best, int &level, int &tlen,
+                                          const Credit &credit)
+{
+    const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+    ++level;
+    bool pos = (best & 1ull) != 0ull;
+    uint32_t d = (uint32_t)v;
+    if constexpr (SPLIT) {
+        const bool pinned = level <= Q.depth;
+        const bool other = pinned && ((Q.index >> (Q.depth - level)) & 1) != 0;
+        pos = pos != other;
+        d |= pinned ? 0x80000000u : 0u;
+    }
+    ex_sync<HBM>();
+    if (threadIdx.x == 0) { X.mark[level] = tlen; X.dvar[level] = d; X.val[v] = pos ? 1 : 2; X.trail[tlen] = v; credit.open(level); }
+    ++tlen;
+    ex_sync<HBM>();
+}
+
+// The DPLL search of one instance, or of one cube of it, by the calling wave.  Returns 1 (satisfiable: val holds a model), 0
+// (unsatisfiable / the cube has no model) or -1 (budget spent); *work_out = the clause-literal reads made.  The budget is checked before
+// every propagation pass.
+// HINT: pend[v] carries the hint codes; `check` (wave-uniform: every variable has a hint) asks for the check pass, which runs before the
+// first budget check: the hint is written into val and every clause is read up to its first true literal; if every clause has one, that
+// assignment is the model, otherwise val is cleared and the search starts from nothing with the reads counted.
+// SPLIT (with HINT; the check pass has run once per instance in k_exact_split_check, check = false): also returns -2 (stopped: a lower
+// cube has answered 1).  best[b] is loaded by lane 0 one pass ahead of the budget check that reads it, so the load's latency lies behind
+// a pass; an older value only stops the cube a pass later.
+template <bool HBM, bool HINT, bool SPLIT, typename LitT, typename PtrT>
+__device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, bool check, const ExCube<SPLIT> &Q, int64_t *work_out)
+{
+    const int lane = (int)threadIdx.x;
     int level = 0, tlen = 0;
+    [[maybe_unused]] int seen = 0;
+    if constexpr (SPLIT) seen = Q.seen;
     int64_t work = 0;
     int result = -1;
-    if constexpr (HINT) {
+    ExNoCredit none;
+    if constexpr (HINT && !SPLIT) {
         if (check) {
             for (int v = lane; v < X.n; v += EX_NT) X.val[v] = (uint8_t)((X.pend[v] >> EX_HINT_SHIFT) & 3u);
             ex_sync<HBM>();
@@ -166,138 +426,44 @@ __device__ int ex_search(const ExInst<LitT, PtrT> &X, int64_t budget, bool check
         }
     }
     for (;;) {
-        if (work >= budget) break;
-        // ---- one unit-propagation pass
-        int reads = 0, conflict = 0, unit = 0, wmin = 0x7fffffff;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a, distinct = 0;
-            uint32_t first = 0;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat) continue;
-            if (nfree == 0) conflict = 1;
-            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
-            else wmin = nfree < wmin ? nfree : wmin;
+        if constexpr (SPLIT) {
+            if (Q.spent + work >= budget) break;
+            seen = __shfl(seen, 0);
+            if (Q.index > seen) { result = -2; break; }             // wave-uniform; ends where the budget's break ends
+            if (lane == 0) seen = ex_shared_load(Q.word);
+        } else {
+            if (work >= budget) break;
         }
-        work += ex_sum(reads);
-        bool any_conflict = __ballot(conflict) != 0ull;
-        const bool any_unit = __ballot(unit) != 0ull;
+        const ExPass P = ex_propagate(X);
+        work += ex_sum(P.reads);
+        bool any_conflict = __ballot(P.conflict) != 0ull;
+        const bool any_unit = __ballot(P.unit) != 0ull;
         if (any_unit) {
-            // assign the pending set of the pass; a variable asked for both polarities is a conflict
             ex_sync<HBM>();
-            int bad = 0;
-            for (int base = 0; base < X.n; base += EX_NT) {
-                const int v = base + lane;
-                const uint32_t word = v < X.n ? X.pend[v] : 0u;
-                const uint32_t bits = word & UNIT;
-                const unsigned long long mask = __ballot(bits != 0u);
-                if (bits) {
-                    X.pend[v] = word & ~UNIT;
-                    X.val[v] = (bits & 1u) ? 1 : 2;
-                    bad |= bits == 3u;
-                    X.trail[tlen + __popcll(mask & below)] = v;
-                }
-                tlen += __popcll(mask);
-            }
-            any_conflict = any_conflict || __ballot(bad) != 0ull;
-            ex_sync<HBM>();
+            const bool both = ex_assign_pending<HBM, HINT>(X, tlen);
+            any_conflict = any_conflict || both;
         }
         if (any_conflict) {
-            // chronological backtracking: undo levels until one whose second polarity is untried
-            // (ex_search_min below carries a copy of this block: a fix here belongs there too)
-            bool resumed = false;
-            while (level > 0) {
-                const uint32_t d = X.dvar[level];
-                const int v = (int)(d & 0x7fffffffu);
-                const int from = X.mark[level];
-                const uint32_t first = X.val[v];
-                ex_sync<HBM>();                                     // every lane has read the level before it is undone
-                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
-                tlen = from;
-                if (!(d & 0x80000000u)) {
-                    ex_sync<HBM>();
-                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
-                    ++tlen;
-                    ex_sync<HBM>();
-                    resumed = true;
-                    break;
-                }
-                --level;
-            }
-            if (!resumed) { result = 0; break; }
+            if (!ex_backtrack<HBM>(X, level, tlen, none)) { result = 0; break; }
             continue;
         }
         if (any_unit) continue;
-        wmin = ex_min(wmin);
-        if (wmin == 0x7fffffff) { result = 1; break; }          // no open clause: every clause is satisfied
-        // ---- branching: the unassigned variable with the most occurrences in the open clauses of minimum width
-        reads = 0;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) ++nfree;
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat || nfree != wmin) continue;
-            for (int j = a; j < z; ++j) {
-                const uint32_t L = X.lit[j];
-                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
-            }
-            reads += z - a;
-        }
-        work += ex_sum(reads);
-        ex_sync<HBM>();
-        unsigned long long best = 0ull;
-        for (int v = lane; v < X.n; v += EX_NT) {
-            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
-            if (p | q) {
-                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
-                // score, then the lower index, then the polarity (true when its occurrences are at least as many; the hint's if v has one)
-                // (ex_search_min below builds the same key, with the incumbent's polarity: a fix here belongs there too)
-                bool pos = p >= q;
-                if constexpr (HINT) {
-                    const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
-                    if (code) pos = code == 1u;
-                }
-                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
-                                               (pos ? 1ull : 0ull);
-                best = key > best ? key : best;
-            }
-        }
-        best = ex_max64(best);
+        const int wmin = ex_min(P.wmin);
+        if (wmin == 0x7fffffff) { result = 1; break; }              // no open clause: every clause is satisfied
+        const unsigned long long best = ex_branch<HBM, HINT ? EX_PHASE_HINT : EX_PHASE_COUNT>(X, wmin, work);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        const int v =(int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
-        ++level;
-        ex_sync<HBM>();
-        if (lane == 0) { X.mark[level] = tlen; X.dvar[level] = (uint32_t)v; X.val[v] = (best & 1ull) ? 1 : 2; X.trail[tlen] = v; }
-        ++tlen;
-        ex_sync<HBM>();
+        ex_decide<HBM, SPLIT>(X, Q, best, level, tlen, none);
     }
     *work_out = work;
     return result;
 }
 
-// copy the instance's literals in clause order (f_ptr / f_edges: any edge order of the problem), clear the state (HINT: pend starts as the
-// hint codes), search, write the results
+// copy the instance (ex_fill), clear the state (HINT: pend starts as the hint codes), search, write the results
 template <bool HBM, bool HINT, typename LitT, typename PtrT>
-__device__ void ex_solve(const PView &pv, const ExParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill)
+__device__ void ex_solve(const ExParams &xp, const Inst &I, ExInst<LitT, PtrT> X)
 {
     const int lane = (int)threadIdx.x;
-    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
-    for (int k = lane; k < I.e; k += EX_NT) {
-        const int ed = I.f_edges[k];
-        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
-    }
+    ex_fill<HBM>(I, X);
     bool check = false;
     if constexpr (HINT) {
         int none = xp.hint == nullptr;
@@ -313,7 +479,7 @@ __device__ void ex_solve(const PView &pv, const ExParams &xp, const Inst &I, ExI
     }
     ex_sync<HBM>();
     int64_t work = 0;
-    const int st = ex_search<HBM, HINT>(X, xp.budget, check, &work);
+    const int st = ex_search<HBM, HINT, false>(X, xp.budget, check, ExCube<false>{}, &work);
     for (int v = lane; v < I.n; v += EX_NT) xp.model[I.v0 + v] = (st == 1 && X.val[v] == 1) ? 1.0f : 0.0f;
     if (lane == 0) {
         xp.status[I.b] = (int8_t)st;
@@ -332,24 +498,30 @@ __global__ void __launch_bounds__(EX_NT) k_exact(PView pv, ExParams xp)
         i = __shfl(i, 0);
         if (i >= xp.B) break;
         const Inst I = load_inst(pv, xp.order[i]);
-        if (i < xp.nbig) {
-            ExInst<uint32_t, int32_t> X;
-            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
-            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
-            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve<true, HINT, uint32_t, int32_t>(pv, xp, I, X, (int32_t *)nullptr);
-        } else {
-            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
-            ExInst<uint16_t, uint16_t> X;
-            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
-            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
-            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve<false, HINT, uint16_t, uint16_t>(pv, xp, I, X, (uint16_t *)(ex_slab + L.cptr));
-        }
+        if (i < xp.nbig) ex_solve<true, HINT>(xp, I, ex_bind_hbm(xp.h, I));
+        else ex_solve<false, HINT>(xp, I, ex_bind_lds(ex_slab, I));
     }
 }
+
+// The tail of every persistent launch: the LDS attribute above 64 KiB, the grid from the kernel's occupancy at `lds` bytes of slab and
+// the number of work items (instances or cubes), PDP_EXACT_GRID, the counter cleared, the launch, and the grid kept for
+// pdp_exact_last_grid.
+template <typename Params>
+int ex_launch_persistent(pdp_problem *p, void (*kernel)(PView, Params), const Params &xp, int64_t items, size_t lds_bytes, hipStream_t st)
+{
+    const int lds = (int)lds_bytes;
+    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kernel, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int64_t grid = ex_grid(std::min<int64_t>(items, (int64_t)pdp_device_cus() * per_cu));
+    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    p->ex_last_grid = (int32_t)grid;
+    return PDP_OK;
+}
+
+inline int64_t ex_budget(int64_t budget) { return budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET; }
 
 // Routing, instance order and working arrays: once per problem (the only host synchronisation of the entry point).
 int ex_prepare(pdp_problem *p)
@@ -395,41 +567,18 @@ template <bool HINT>
 int ex_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
 {
     { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
-    const hipStream_t st = ST(stream);
     ExParams xp;
     xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.budget = ex_budget(budget);
     xp.status = status; xp.model = model; xp.work = work; xp.hint = hint;
-    const size_t V = p->V, E = p->E, B = p->B;
-    if (p->ex_h_lit) {
-        char *q = (char *)p->ex_h_lit;
-        xp.h_lit = (uint32_t *)q;            q += E * 4;
-        xp.h_pend = (uint32_t *)q;           q += V * 4;
-        xp.h_cnt = (uint32_t *)q;            q += V * 8;
-        xp.h_trail = (int32_t *)q;           q += V * 4;
-        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
-        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
-        xp.h_val = (uint8_t *)q;
-    } else {
-        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
-        xp.h_val = nullptr;
-    }
-    const int lds = (int)p->ex_lds_bytes;
-    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact<HINT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact<HINT>, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
-    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact<HINT>, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
-    p->ex_last_grid = (int32_t)grid;
-    return PDP_OK;
+    xp.h = ex_hbm(p);
+    return ex_launch_persistent(p, k_exact<HINT>, xp, (int64_t)p->B, p->ex_lds_bytes, ST(stream));
 }
 
 // ---- pdp_exact_min_unsat: the fewest unsatisfied clauses by depth-first branch and bound over the same passes --------------------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_min_unsat_model.py).  Its own search, kernel and launch path: nothing above
-// is touched.  The state is ex_search's, array for array: the incumbent lives in the output model in HBM (written by the check pass,
-// rewritten on an improvement only) and the hint codes in bits 8-9 of pend[v], so the slab, the routing and the occupancy by LDS are
+// (specification: include/pdp_hip.h; plain Python: tests/exact_min_unsat_model.py).  ex_search_min is the search of this call and, with
+// SPLIT, of pdp_exact_min_unsat_split's cubes.  The state is ex_search's, array for array: the incumbent lives in the output model in
+// HBM (written by the check pass, rewritten on an improvement only) and the hint codes in bits 8-9 of pend[v], so the slab, the routing and the occupancy by LDS are
 // k_exact's.  A pass also counts the falsified clauses (cost, a wave sum) where ex_search raises a flag, and the pending words with both
 // unit bits (contra); cost + contra >= ub prunes, the units are assigned only where leaving one out would reach ub, and every other state
 // with an open clause branches, on a clause of width 1 too.
@@ -439,25 +588,61 @@ struct ExmParams {
     uint32_t *next;
     int64_t budget;
     int8_t *status; int32_t *cost; float *model; int64_t *work; int32_t *improvements;
-    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+    ExHbm h;
     const float *hint;          // [V] the incumbents (NULL: all false)
 };
 
-// The optimising search of one instance by the calling wave.  pend[v] carries the code of the incumbent (1 true, 2 false: never 0), model
-// points at the instance's slice of the output.  Returns 1 (*cost_out is the minimum) or -1 (budget spent: an upper bound); model holds
-// an assignment that leaves exactly *cost_out clauses unsatisfied either way.
-template <bool HBM, typename LitT, typename PtrT>
-__device__ int ex_search_min(const ExInst<LitT, PtrT> &X, int64_t budget, float *model, int64_t *work_out, int *cost_out, int *improved_out)
+constexpr int EXMS_NO_COST = -1;                // cube_cost of pdp_exact_min_unsat_split: the cube accepted no improvement
+
+// val as one bit per variable (1: true), 32 to a word; every lane runs every chunk, so the ballots are whole
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ void ex_pack_row(const ExInst<LitT, PtrT> &X, uint32_t *row)
 {
     const int lane = (int)threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int base = 0; base < X.n; base += EX_NT) {
+        const int v = base + lane;
+        const unsigned long long mask = __ballot(v < X.n && X.val[v] == 1);
+        if (lane == 0) {
+            row[base >> 5] = (uint32_t)mask;
+            if (base + 32 < X.n) row[(base >> 5) + 1] = (uint32_t)(mask >> 32);
+        }
+    }
+}
+
+// the assignment in val as a new incumbent, unassigned variables false: floats into `model`, or bits into `row` where model is NULL
+// (a cube of an instance that has several)
+template <bool SPLIT, typename LitT, typename PtrT>
+__device__ __forceinline__ void ex_store_incumbent(const ExInst<LitT, PtrT> &X, float *model, uint32_t *row)
+{
+    if (!SPLIT || model) { for (int v = (int)threadIdx.x; v < X.n; v += EX_NT) model[v] = X.val[v] == 1 ? 1.0f : 0.0f; }
+    else ex_pack_row(X, row);
+}
+
+// The optimising search of one instance, or of one cube of it, by the calling wave.  pend[v] carries the code of the incumbent (1 true,
+// 2 false: never 0).  Its pass is its own (it counts cost and contra); backtracking, the key and the decision push are the shared blocks.
+// Plain: `model` points at the instance's slice of the output; the check pass (the incumbent's reads and its unsatisfied clauses) always
+// runs, before the first budget check.  Returns 1 (*cost_out is the minimum) or -1 (budget spent: an upper bound); model holds an
+// assignment that leaves exactly *cost_out clauses unsatisfied either way.
+// SPLIT: the check pass has run once per instance in k_exact_min_split_check.  `ub` is the cube's view of the shared ub[b]: it comes in
+// as the value loaded before the instance was copied (not 0), is lowered by one atomicMin per improvement, and is re-read by lane 0 at
+// the budget checks, one pass ahead of its use.  It prunes at every level; forcing the units uses ub0 while level < depth and ub from then
+// on, so the decisions of the pinned levels are taken in states that depend on the instance and its hint alone.  An accepted improvement
+// writes the assignment to `model` (depth 0) or bit-packed to `row` (model NULL).  Returns 1 (the cube is exhausted, or some cube has
+// reached cost 0) or -1 (budget spent); *cost_out = the cube's last accepted cost (EXMS_NO_COST: none).
+template <bool HBM, bool SPLIT, typename LitT, typename PtrT>
+__device__ int ex_search_min(const ExInst<LitT, PtrT> &X, int64_t budget, const ExCube<SPLIT> &Q, [[maybe_unused]] int ub0, float *model,
+                             [[maybe_unused]] uint32_t *row, int64_t *work_out, int *cost_out, int *improved_out)
+{
+    const int lane = (int)threadIdx.x;
     constexpr uint32_t UNIT = 3u;
     constexpr int INF = 0x7fffffff;
     int level = 0, tlen = 0, ub = 0, improved = 0;
+    [[maybe_unused]] int accepted = EXMS_NO_COST, seen = 0;
+    if constexpr (SPLIT) { ub = Q.seen; seen = Q.seen; }
     int64_t work = 0;
     int result = -1;
-    {
-        // the check pass: the incumbent's reads and its unsatisfied clauses; it always runs, before the first budget check
+    ExNoCredit none;
+    if constexpr (!SPLIT) {
         for (int v = lane; v < X.n; v += EX_NT) {
             const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
             X.val[v] = (uint8_t)code;
@@ -483,7 +668,15 @@ __device__ int ex_search_min(const ExInst<LitT, PtrT> &X, int64_t budget, float 
         ex_sync<HBM>();
     }
     for (;;) {
-        if (work >= budget) break;
+        if constexpr (SPLIT) {
+            seen = __shfl(seen, 0);
+            ub = seen < ub ? seen : ub;
+            if (ub == 0) { result = 1; break; }                     // some cube has satisfied every clause
+            if (Q.spent + work >= budget) break;
+            if (lane == 0) seen = ex_shared_load(Q.word);           // used at the next check: its latency lies behind the pass
+        } else {
+            if (work >= budget) break;
+        }
         // ---- one pass: falsified clauses, unit requests, the minimum width of the open clauses (a unit has width 1)
         int reads = 0, cost = 0, unit = 0, wmin = INF;
         for (int c = lane; c < X.m; c += EX_NT) {
@@ -512,22 +705,12 @@ __device__ int ex_search_min(const ExInst<LitT, PtrT> &X, int64_t budget, float 
             for (int v = lane; v < X.n; v += EX_NT) contra += (X.pend[v] & UNIT) == UNIT;
             contra = ex_sum(contra);
         }
+        int rule = ub;
+        if constexpr (SPLIT) rule = level < Q.depth ? ub0 : ub;
         bool prune = cost + contra >= ub;
-        if (!prune && cost == ub - 1 && any_unit) {
-            // leaving any unit out reaches ub: the pending set is assigned as in ex_search (no variable is asked for twice: that was pruned)
-            for (int base = 0; base < X.n; base += EX_NT) {
-                const int v = base + lane;
-                const uint32_t word = v < X.n ? X.pend[v] : 0u;
-                const uint32_t bits = word & UNIT;
-                const unsigned long long mask = __ballot(bits != 0u);
-                if (bits) {
-                    X.pend[v] = word & ~UNIT;
-                    X.val[v] = (bits & 1u) ? 1 : 2;
-                    X.trail[tlen + __popcll(mask & below)] = v;
-                }
-                tlen += __popcll(mask);
-            }
-            ex_sync<HBM>();
+        if (!prune && cost == rule - 1 && any_unit) {
+            // leaving any unit out reaches rule >= ub: the pending set is assigned (no variable is asked for twice: that was pruned)
+            ex_assign_pending<HBM, true>(X, tlen);
             continue;
         }
         if (any_unit) {
@@ -536,36 +719,33 @@ __device__ int ex_search_min(const ExInst<LitT, PtrT> &X, int64_t budget, float 
             ex_sync<HBM>();
         }
         if (!prune && wmin == INF) {
-            // a leaf below ub: the new incumbent, unassigned variables false
-            ub = cost;
-            ++improved;
-            for (int v = lane; v < X.n; v += EX_NT) model[v] = X.val[v] == 1 ? 1.0f : 0.0f;
-            if (ub == 0) { result = 1; break; }
+            // a leaf below ub: a new incumbent, unassigned variables false
+            if constexpr (SPLIT) {
+                // the cubes that do not own the leaf end (every open level is pinned) with nothing credited
+                if (ex_owns_leaf(Q, level)) {
+                    int old = 0;
+                    if (lane == 0) old = atomicMin(Q.word, cost);
+                    old = __shfl(old, 0);
+                    if (old > cost) {
+                        ex_store_incumbent<true>(X, model, row);
+                        accepted = cost;
+                        ++improved;
+                        ub = cost;
+                    } else {
+                        ub = old;                                   // another cube was there first
+                    }
+                }
+            } else {
+                ub = cost;
+                ++improved;
+                ex_store_incumbent<false>(X, model, row);
+                if (ub == 0) { result = 1; break; }
+            }
             prune = true;
         }
         if (prune) {
-            // chronological backtracking, a copy of ex_search's block (its device code must not move, so nothing is shared): keep the
-            // two in step; out of levels: ub is the minimum
-            bool resumed = false;
-            while (level > 0) {
-                const uint32_t d = X.dvar[level];
-                const int v = (int)(d & 0x7fffffffu);
-                const int from = X.mark[level];
-                const uint32_t first = X.val[v];
-                ex_sync<HBM>();                                     // every lane has read the level before it is undone
-                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
-                tlen = from;
-                if (!(d & 0x80000000u)) {
-                    ex_sync<HBM>();
-                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
-                    ++tlen;
-                    ex_sync<HBM>();
-                    resumed = true;
-                    break;
-                }
-                --level;
-            }
-            if (!resumed) { result = 1; break; }
+            // out of levels: ub is the minimum / the cube is exhausted
+            if (!ex_backtrack<HBM>(X, level, tlen, none)) { result = 1; break; }
             continue;
         }
         // ---- branching: the unassigned variable with the most occurrences in the open clauses of width wmin (1: the units)
@@ -590,41 +770,20 @@ __device__ int ex_search_min(const ExInst<LitT, PtrT> &X, int64_t budget, float 
         }
         work += ex_sum(reads);
         ex_sync<HBM>();
-        unsigned long long best = 0ull;
-        for (int v = lane; v < X.n; v += EX_NT) {
-            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
-            if (p | q) {
-                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
-                // ex_search's key (keep the two in step): score, then the lower index, then the polarity, here the incumbent's
-                const bool pos = ((X.pend[v] >> EX_HINT_SHIFT) & 3u) == 1u;
-                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
-                                               (pos ? 1ull : 0ull);
-                best = key > best ? key : best;
-            }
-        }
-        best = ex_max64(best);
+        const unsigned long long best = ex_pick<EX_PHASE_INCUMBENT>(X);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has an unassigned literal); never index with it
-        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
-        ++level;
-        ex_sync<HBM>();
-        if (lane == 0) { X.mark[level] = tlen; X.dvar[level] = (uint32_t)v; X.val[v] = (best & 1ull) ? 1 : 2; X.trail[tlen] = v; }
-        ++tlen;
-        ex_sync<HBM>();
+        ex_decide<HBM, SPLIT>(X, Q, best, level, tlen, none);
     }
-    *work_out = work; *cost_out = ub; *improved_out = improved;
+    *work_out = work; *cost_out = SPLIT ? accepted : ub; *improved_out = improved;
     return result;
 }
 
-// copy the instance's literals in clause order, clear the state (pend starts as the incumbent's codes), search, write the results
+// copy the instance (ex_fill), clear the state (pend starts as the incumbent's codes), search, write the results
 template <bool HBM, typename LitT, typename PtrT>
-__device__ void ex_solve_min(const ExmParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill)
+__device__ void ex_solve_min(const ExmParams &xp, const Inst &I, ExInst<LitT, PtrT> X)
 {
     const int lane = (int)threadIdx.x;
-    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
-    for (int k = lane; k < I.e; k += EX_NT) {
-        const int ed = I.f_edges[k];
-        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
-    }
+    ex_fill<HBM>(I, X);
     for (int v = lane; v < I.n; v += EX_NT) {
         const uint32_t code = (xp.hint && xp.hint[I.v0 + v] > 0.5f) ? 1u : 2u;          // NaN compares false
         X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
@@ -632,7 +791,7 @@ __device__ void ex_solve_min(const ExmParams &xp, const Inst &I, ExInst<LitT, Pt
     ex_sync<HBM>();
     int64_t work = 0;
     int cost = 0, improved = 0;
-    const int st = ex_search_min<HBM>(X, xp.budget, xp.model + I.v0, &work, &cost, &improved);
+    const int st = ex_search_min<HBM, false>(X, xp.budget, ExCube<false>{}, 0, xp.model + I.v0, nullptr, &work, &cost, &improved);
     if (lane == 0) {
         xp.status[I.b] = (int8_t)st;
         xp.cost[I.b] = cost;
@@ -651,22 +810,8 @@ __global__ void __launch_bounds__(EX_NT) k_exact_min(PView pv, ExmParams xp)
         i = __shfl(i, 0);
         if (i >= xp.B) break;
         const Inst I = load_inst(pv, xp.order[i]);
-        if (i < xp.nbig) {
-            ExInst<uint32_t, int32_t> X;
-            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
-            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
-            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve_min<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr);
-        } else {
-            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
-            ExInst<uint16_t, uint16_t> X;
-            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
-            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
-            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve_min<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ex_slab + L.cptr));
-        }
+        if (i < xp.nbig) ex_solve_min<true>(xp, I, ex_bind_hbm(xp.h, I));
+        else ex_solve_min<false>(xp, I, ex_bind_lds(ex_slab, I));
     }
 }
 
@@ -675,40 +820,17 @@ int exm_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status
                int32_t *improvements, void *stream)
 {
     { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
-    const hipStream_t st = ST(stream);
     ExmParams xp;
     xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.budget = ex_budget(budget);
     xp.status = status; xp.cost = cost; xp.model = model; xp.work = work; xp.improvements = improvements; xp.hint = hint;
-    const size_t V = p->V, E = p->E, B = p->B;
-    if (p->ex_h_lit) {
-        char *q = (char *)p->ex_h_lit;
-        xp.h_lit = (uint32_t *)q;            q += E * 4;
-        xp.h_pend = (uint32_t *)q;           q += V * 4;
-        xp.h_cnt = (uint32_t *)q;            q += V * 8;
-        xp.h_trail = (int32_t *)q;           q += V * 4;
-        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
-        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
-        xp.h_val = (uint8_t *)q;
-    } else {
-        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
-        xp.h_val = nullptr;
-    }
-    const int lds = (int)p->ex_lds_bytes;
-    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_min, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_min, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
-    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact_min, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
-    p->ex_last_grid = (int32_t)grid;
-    return PDP_OK;
+    xp.h = ex_hbm(p);
+    return ex_launch_persistent(p, k_exact_min, xp, (int64_t)p->B, p->ex_lds_bytes, ST(stream));
 }
 
 // ---- pdp_exact_count: exact model counts and per-variable counts by the same passes, without stopping at the first model ---------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_count_model.py).  Its own search, kernel and launch path: nothing above is
-// touched.  The state is ex_search's, array for array, plus three arrays of doubles: snap [n+1], the count when a level was opened or its
+// (specification: include/pdp_hip.h; plain Python: tests/exact_count_model.py).  ex_search_count is ex_search's loop from the same blocks,
+// with a leaf and a credit hook of its own; with SPLIT it is the search of pdp_exact_count_split's cubes.  The state is ex_search's, array for array, plus three arrays of doubles: snap [n+1], the count when a level was opened or its
 // decision flipped, and T [n] / F [n], the models counted under v = true / v = false while v was assigned.  On the LDS route they follow
 // ex_lds_layout's slab (24 n + 8 bytes of this kernel's own; an instance that is searched has n <= 1023, so the slab stays below 73 KiB
 // and ex_prepare's routing holds as it is); on the HBM route T is the instance's slice of the true_count output, F and snap are working
@@ -736,12 +858,29 @@ struct ExnParams {
     uint32_t *next;
     int64_t budget;
     int8_t *status; double *count; double *true_count; int64_t *work; int64_t *leaves;
-    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+    ExHbm h;
     double *h_F;                // [V]   (HBM route; its T is true_count)
     double *h_snap;             // [V+B] (instance b at v0 + b: n+1 entries)
 };
 
 struct ExnAcc { double *T, *F, *snap; };
+
+// the accumulators of an HBM-routed instance: T is its slice of the true_count output, F and snap are exn_prepare's arrays
+__device__ __forceinline__ ExnAcc exn_bind_hbm(double *true_count, double *h_F, double *h_snap, const Inst &I)
+{
+    ExnAcc A;
+    A.T = true_count + I.v0; A.F = h_F + I.v0; A.snap = h_snap + I.v0 + I.b;
+    return A;
+}
+
+// the accumulators of an LDS-routed instance, behind ex_lds_layout's slab
+__device__ __forceinline__ ExnAcc exn_bind_lds(unsigned char *slab, const Inst &I)
+{
+    const ExnLds N = exn_lds_layout(I.n, I.m, I.e);
+    ExnAcc A;
+    A.T = (double *)(slab + N.T); A.F = (double *)(slab + N.F); A.snap = (double *)(slab + N.snap);
+    return A;
+}
 
 // The models counted since `level` was opened go to the variables on trail[from .. tlen): T[u] if u is true, F[u] if false.  d == 0 adds
 // nothing to a non-negative sum, bit for bit, so the loads and stores are skipped then (d is uniform over the wave).
@@ -756,142 +895,66 @@ __device__ __forceinline__ void exn_credit(const ExInst<LitT, PtrT> &X, const Ex
     }
 }
 
-// The counting search of one instance by the calling wave: ex_search<HBM, false> where a state without an open clause is a leaf that adds
-// 2^(unassigned variables) to the count and backtracks.  Returns 1 (complete) or -1 (budget spent); T and F hold every level's credit.
-template <bool HBM, typename LitT, typename PtrT>
-__device__ int ex_search_count(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int64_t budget, int64_t *work_out, double *count_out,
-                               int64_t *leaves_out)
+// ex_backtrack's and ex_decide's hook of the counting search: the models counted while a level was open are credited when it is undone,
+// and snap[level] restarts at `count` when the level is opened or its decision flipped (the level stays open: its first half is
+// credited once).  `count` is the search's running count, uniform over the wave.
+struct ExnCredit {
+    const ExnAcc &A;
+    const double &count;
+    double since;
+    __device__ __forceinline__ void load(int level) { since = count - A.snap[level]; }
+    template <typename LitT, typename PtrT>
+    __device__ __forceinline__ void undo(const ExInst<LitT, PtrT> &X, int from, int tlen) const { exn_credit(X, A, from, tlen, since); }
+    __device__ __forceinline__ void open(int level) const { A.snap[level] = count; }
+};
+
+// The counting search of one instance, or of one cube of it, by the calling wave: ex_search<HBM, false> where a state without an open
+// clause is a leaf that adds 2^(unassigned variables) to the count and backtracks.  Returns 1 (complete) or -1 (budget spent); T and F
+// hold every level's credit.  SPLIT: a leaf met with fewer than `depth` levels open counts only in the cube that owns it (ex_owns_leaf);
+// either way the search goes on as after a conflict (every open level is pinned then, so that ends the cube).
+template <bool HBM, bool SPLIT, typename LitT, typename PtrT>
+__device__ int ex_search_count(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int64_t budget, const ExCube<SPLIT> &Q, int64_t *work_out,
+                               double *count_out, int64_t *leaves_out)
 {
-    const int lane = (int)threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
     constexpr int INF = 0x7fffffff;
     int level = 0, tlen = 0;
     int64_t work = 0, leaves = 0;
     double count = 0.0;
     int result = -1;
+    ExnCredit credit{A, count, 0.0};
     for (;;) {
         if (work >= budget) break;
-        // ---- one unit-propagation pass (ex_search's: keep the two in step)
-        int reads = 0, conflict = 0, unit = 0, wmin = INF;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a, distinct = 0;
-            uint32_t first = 0;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat) continue;
-            if (nfree == 0) conflict = 1;
-            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
-            else wmin = nfree < wmin ? nfree : wmin;
-        }
-        work += ex_sum(reads);
-        bool any_conflict = __ballot(conflict) != 0ull;
-        const bool any_unit = __ballot(unit) != 0ull;
+        const ExPass P = ex_propagate(X);
+        work += ex_sum(P.reads);
+        bool any_conflict = __ballot(P.conflict) != 0ull;
+        const bool any_unit = __ballot(P.unit) != 0ull;
         if (any_unit) {
-            // assign the pending set of the pass; a variable asked for both polarities is a conflict
             ex_sync<HBM>();
-            int bad = 0;
-            for (int base = 0; base < X.n; base += EX_NT) {
-                const int v = base + lane;
-                const uint32_t bits = v < X.n ? X.pend[v] : 0u;
-                const unsigned long long mask = __ballot(bits != 0u);
-                if (bits) {
-                    X.pend[v] = 0u;
-                    X.val[v] = (bits & 1u) ? 1 : 2;
-                    bad |= bits == 3u;
-                    X.trail[tlen + __popcll(mask & below)] = v;
-                }
-                tlen += __popcll(mask);
-            }
-            any_conflict = any_conflict || __ballot(bad) != 0ull;
-            ex_sync<HBM>();
+            const bool both = ex_assign_pending<HBM, false>(X, tlen);
+            any_conflict = any_conflict || both;
         }
+        int wmin = INF;
         if (!any_conflict) {
             if (any_unit) continue;
-            wmin = ex_min(wmin);
+            wmin = ex_min(P.wmin);
             if (wmin == INF) {
                 // a leaf: every clause has a true literal and the unassigned variables are free; then as after a conflict
-                count = count + ldexp(1.0, X.n - tlen);
-                ++leaves;
+                bool mine = true;
+                if constexpr (SPLIT) mine = ex_owns_leaf(Q, level);
+                if (mine) {
+                    count = count + ldexp(1.0, X.n - tlen);
+                    ++leaves;
+                }
                 any_conflict = true;
             }
         }
         if (any_conflict) {
-            // chronological backtracking, ex_search's block with the credit of every undone level (keep the two in step)
-            bool resumed = false;
-            while (level > 0) {
-                const uint32_t d = X.dvar[level];
-                const int v = (int)(d & 0x7fffffffu);
-                const int from = X.mark[level];
-                const uint32_t first = X.val[v];
-                const double since = count - A.snap[level];
-                ex_sync<HBM>();                                     // every lane has read the level before it is undone
-                exn_credit(X, A, from, tlen, since);
-                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;      // the same lane as the credit
-                tlen = from;
-                if (!(d & 0x80000000u)) {
-                    ex_sync<HBM>();
-                    if (lane == 0) {
-                        X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v;
-                        A.snap[level] = count;                      // the level stays open: its first half is credited once
-                    }
-                    ++tlen;
-                    ex_sync<HBM>();
-                    resumed = true;
-                    break;
-                }
-                --level;
-            }
-            if (!resumed) { result = 1; break; }
+            if (!ex_backtrack<HBM>(X, level, tlen, credit)) { result = 1; break; }
             continue;
         }
-        // ---- branching: ex_search's, without hints (keep the two in step)
-        reads = 0;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) ++nfree;
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat || nfree != wmin) continue;
-            for (int j = a; j < z; ++j) {
-                const uint32_t L = X.lit[j];
-                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
-            }
-            reads += z - a;
-        }
-        work += ex_sum(reads);
-        ex_sync<HBM>();
-        unsigned long long best = 0ull;
-        for (int v = lane; v < X.n; v += EX_NT) {
-            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
-            if (p | q) {
-                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
-                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
-                                               (p >= q ? 1ull : 0ull);
-                best = key > best ? key : best;
-            }
-        }
-        best = ex_max64(best);
+        const unsigned long long best = ex_branch<HBM, EX_PHASE_COUNT>(X, wmin, work);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
-        ++level;
-        ex_sync<HBM>();
-        if (lane == 0) {
-            X.mark[level] = tlen; X.dvar[level] = (uint32_t)v; X.val[v] = (best & 1ull) ? 1 : 2; X.trail[tlen] = v;
-            A.snap[level] = count;
-        }
-        ++tlen;
-        ex_sync<HBM>();
+        ex_decide<HBM, SPLIT>(X, Q, best, level, tlen, credit);
     }
     // the end: every open level is flushed, the newest first; level 0 holds the variables of the first propagation (mark 0, snap 0.0).
     // The levels' variables are disjoint and every path here has passed a barrier since the last write of mark, snap, trail and val.
@@ -906,14 +969,10 @@ __device__ int ex_search_count(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int
 
 // copy the instance's literals in clause order, clear the state, search, write the results
 template <bool HBM, typename LitT, typename PtrT>
-__device__ void ex_solve_count(const ExnParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExnAcc A, PtrT *cptr_fill)
+__device__ void ex_solve_count(const ExnParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExnAcc A)
 {
     const int lane = (int)threadIdx.x;
-    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
-    for (int k = lane; k < I.e; k += EX_NT) {
-        const int ed = I.f_edges[k];
-        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
-    }
+    ex_fill<HBM>(I, X);
     for (int v = lane; v < I.n; v += EX_NT) {
         X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
         A.T[v] = 0.0; A.F[v] = 0.0;
@@ -922,7 +981,7 @@ __device__ void ex_solve_count(const ExnParams &xp, const Inst &I, ExInst<LitT, 
     ex_sync<HBM>();
     int64_t work = 0, leaves = 0;
     double count = 0.0;
-    const int st = ex_search_count<HBM>(X, A, xp.budget, &work, &count, &leaves);
+    const int st = ex_search_count<HBM, false>(X, A, xp.budget, ExCube<false>{}, &work, &count, &leaves);
     ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
     for (int v = lane; v < I.n; v += EX_NT) {
         const double t = A.T[v];
@@ -959,25 +1018,9 @@ __global__ void __launch_bounds__(EX_NT) k_exact_count(PView pv, ExnParams xp)
             }
             ex_sync<false>();
         } else if (i < xp.nbig) {
-            ExInst<uint32_t, int32_t> X;
-            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
-            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
-            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ExnAcc A;
-            A.T = xp.true_count + I.v0; A.F = xp.h_F + I.v0; A.snap = xp.h_snap + I.v0 + I.b;
-            ex_solve_count<true, uint32_t, int32_t>(xp, I, X, A, (int32_t *)nullptr);
+            ex_solve_count<true>(xp, I, ex_bind_hbm(xp.h, I), exn_bind_hbm(xp.true_count, xp.h_F, xp.h_snap, I));
         } else {
-            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
-            const ExnLds N = exn_lds_layout(I.n, I.m, I.e);
-            ExInst<uint16_t, uint16_t> X;
-            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
-            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
-            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ExnAcc A;
-            A.T = (double *)(ex_slab + N.T); A.F = (double *)(ex_slab + N.F); A.snap = (double *)(ex_slab + N.snap);
-            ex_solve_count<false, uint16_t, uint16_t>(xp, I, X, A, (uint16_t *)(ex_slab + L.cptr));
+            ex_solve_count<false>(xp, I, ex_bind_lds(ex_slab, I), exn_bind_lds(ex_slab, I));
         }
     }
 }
@@ -1011,42 +1054,19 @@ int exn_prepare(pdp_problem *p)
 int exn_launch(pdp_problem *p, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work, int64_t *leaves, void *stream)
 {
     { const int st_ = exn_prepare(p); if (st_ != PDP_OK) return st_; }
-    const hipStream_t st = ST(stream);
     ExnParams xp;
     xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.budget = ex_budget(budget);
     xp.status = status; xp.count = count; xp.true_count = true_count; xp.work = work; xp.leaves = leaves;
-    const size_t V = p->V, E = p->E, B = p->B;
-    if (p->ex_h_lit) {
-        char *q = (char *)p->ex_h_lit;
-        xp.h_lit = (uint32_t *)q;            q += E * 4;
-        xp.h_pend = (uint32_t *)q;           q += V * 4;
-        xp.h_cnt = (uint32_t *)q;            q += V * 8;
-        xp.h_trail = (int32_t *)q;           q += V * 4;
-        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
-        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
-        xp.h_val = (uint8_t *)q;
-        xp.h_F = (double *)p->exn_blob;
-        xp.h_snap = (double *)(p->exn_blob + V * 8);
-    } else {
-        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
-        xp.h_val = nullptr; xp.h_F = nullptr; xp.h_snap = nullptr;
-    }
-    const int lds = (int)p->exn_lds_bytes;
-    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_count, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_count, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
-    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact_count, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
-    p->ex_last_grid = (int32_t)grid;
-    return PDP_OK;
+    xp.h = ex_hbm(p);
+    xp.h_F = p->exn_blob ? (double *)p->exn_blob : nullptr;
+    xp.h_snap = p->exn_blob ? (double *)(p->exn_blob + (size_t)p->V * 8) : nullptr;
+    return ex_launch_persistent(p, k_exact_count, xp, (int64_t)p->B, p->exn_lds_bytes, ST(stream));
 }
 
 // ---- pdp_exact_solve_learn: the same passes, branching rule, hints and budget with conflict clause learning and backjumping -------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_learn_model.py).  Its own state, search, kernel and launch path: nothing
-// above is touched.  On top of the DPLL state an instance has
+// (specification: include/pdp_hip.h; plain Python: tests/exact_learn_model.py).  Its own state layout, passes, search, kernel and launch
+// path; it shares none of the blocks above.  On top of the DPLL state an instance has
 //   lev [n]   decision level of an assigned variable        rsn [n]   clause that implied it (EXL_NONE: a decision)
 //   req [2n]  per literal, the lowest clause index that asked for it as a unit in the current pass (EXL_NONE between passes)
 //   ar  [A]   the arena: the learned clauses' literals grow from word 0, their end offsets from word A - 1 downwards (clause j ends at
@@ -2355,60 +2375,43 @@ int ext_launch(pdp_problem *p, const int8_t *status, const int64_t *proof_off, c
 }
 
 // ---- pdp_exact_solve_split: one instance's deciding search spread over 2^depth cubes, one wave per cube ------------------------------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_split_model.py).  Its own search, kernels and launch path: nothing above is
-// touched.  A cube is ex_search<HBM, true> with the decisions of levels 1..depth pinned by the bits of the cube's index and recorded as
-// already flipped; a wave re-derives its prefix by running the ordinary search.  The state, the slab, the routing and the occupancy by LDS
-// are k_exact's.  Four launches on one stream: the setup (depth_used, route, cube_off), the check pass (once per instance: best[b] = -1
-// where it accepts, INT_MAX elsewhere), the cubes (one counter hands out cube ids: instance order, ascending index), the finish (first,
-// status, the work sum and the model of every instance from the per-cube records).
+// (specification: include/pdp_hip.h; plain Python: tests/exact_split_model.py).  A cube is ex_search<HBM, true, true>: the hinted search
+// with the decisions of levels 1..depth pinned by the bits of the cube's index and recorded as already flipped; a wave re-derives its
+// prefix by running the ordinary search.  The state, the slab, the routing and the occupancy by LDS are k_exact's.  Four launches on one
+// stream: the setup (depth_used, route, cube_off), the check pass (once per instance: best[b] = -1 where it accepts, INT_MAX elsewhere),
+// the cubes (one counter hands out cube ids: instance order, ascending index), the finish (first, status, the work sum and the model of
+// every instance from the per-cube records).
 // The only word two waves share is best[b]: a cube that answers 1 lowers it to its index (atomicMin), and a cube stops at a budget check
 // when a LOWER cube has answered 1.  No wave waits for another.  Cubes 0..first never stop, so everything the finish kernel reads is a
 // function of the instance, its hints, its depth and the budget alone.
+//
+// The three split calls (this one, pdp_exact_count_split and pdp_exact_min_unsat_split further down) share what comes first: the setup
+// kernel, the fixed block it fills, the per-cube record block on the handle and the bisection that maps a cube id to its instance.
 constexpr int EXS_MAX_DEPTH = 16;
 constexpr int64_t EXS_MAX_CUBES = (int64_t)1 << 22;
 constexpr int EXS_NONE = 0x7fffffff;            // best[b]: no cube has answered 1 (-1: the check pass accepted the hints)
 constexpr int EXS_SETUP_NT = 1024;
+constexpr int EXS_INFO = 5;
 
-struct ExsParams {
-    int B;
-    uint32_t total;             // cubes of the call
-    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
-    int64_t budget;
-    const float *hint;          // [V] phase hints (NULL: none)
-    const int8_t *du;           // [B] depth used
-    const uint8_t *route;       // [B] 1: the HBM route
-    const int64_t *cube_off;    // [B+1] first cube id of every instance
-    const int64_t *chk;         // [B] reads of the rejected or accepted check pass (0: it did not run)
-    int32_t *best;              // [B]
-    int8_t *cube_status;        // [total] 1 / 0 / -1, -2 stopped early
-    int64_t *cube_work;         // [total]
-    uint32_t *rows;             // [total][words] bit-packed assignment of every cube that answered 1 (instances of depth > 0)
-    int words;
-    float *model;               // [V] written by the cube of a depth-0 instance, by the finish kernel elsewhere
-    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
-};
-
-__device__ __forceinline__ int exs_best(const int32_t *best)
-{
-    return __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// depth_used, route and cube_off of the call, by one workgroup.  info[0] = the lowest instance whose depth is out of range, info[1] = the
-// lowest instance at which the running cube count passes 2^22 (EXS_NONE: none), info[2] = cubes, info[3] = the most variables of an
-// instance with depth_used > 0.
-__global__ void __launch_bounds__(EXS_SETUP_NT) k_exact_split_setup(PView pv, const int8_t *depth, const int32_t *order, int nbig, int8_t *du,
-                                                                    uint8_t *route, int64_t *cube_off, int8_t *depth_used, int64_t *info)
+// depth_used, route and cube_off of a split call, by one workgroup.  An instance on the HBM route (per-instance arrays) or with more
+// than n_cap variables gets depth 0.  info[0] = the lowest instance whose depth is out of range, info[1] = the lowest instance at which
+// the running cube count passes 2^22, info[4] = the lowest instance at which the running size of per-cube rows of n_max items,
+// cube_off[b + 1] * n_max * row_item bytes, passes row_cap (row_cap 0: no such rows) (EXS_NONE: none), info[2] = cubes, info[3] = n_max,
+// the most variables of an instance with depth_used > 0.
+__global__ void __launch_bounds__(EXS_SETUP_NT) k_exact_split_setup(PView pv, const int8_t *depth, const int32_t *order, int nbig, int n_cap,
+                                                                    int64_t row_item, int64_t row_cap, int8_t *du, uint8_t *route,
+                                                                    int64_t *cube_off, int8_t *depth_used, int64_t *info)
 {
     __shared__ int64_t s[EXS_SETUP_NT];
-    __shared__ int bad, over, nmax;
+    __shared__ int bad, over, wide, nmax;
     const int t = (int)threadIdx.x, B = pv.B;
-    if (t == 0) { bad = EXS_NONE; over = EXS_NONE; nmax = 0; cube_off[0] = 0; }
+    if (t == 0) { bad = EXS_NONE; over = EXS_NONE; wide = EXS_NONE; nmax = 0; cube_off[0] = 0; }
     __syncthreads();
     for (int b = t; b < B; b += EXS_SETUP_NT) {
         const int d = depth ? (int)depth[b] : 0;
         const bool ok = d >= 0 && d <= EXS_MAX_DEPTH;
         if (!ok) atomicMin(&bad, b);
-        du[b] = (int8_t)(ok ? d : 0);
+        du[b] = (int8_t)(ok && pv.inst_v0[b + 1] - pv.inst_v0[b] <= n_cap ? d : 0);
         route[b] = 0;
     }
     __syncthreads();
@@ -2436,8 +2439,116 @@ __global__ void __launch_bounds__(EXS_SETUP_NT) k_exact_split_setup(PView pv, co
         running += s[EXS_SETUP_NT - 1];
         __syncthreads();
     }
-    if (t == 0) { info[0] = bad; info[1] = over; info[2] = running; info[3] = nmax; }
+    // cube_off[b + 1] <= 2^16 * B and, where rows are asked for, n_max <= n_cap = 1023: the product stays far inside int64
+    if (row_cap > 0)
+        for (int b = t; b < B; b += EXS_SETUP_NT)
+            if (cube_off[b + 1] * (int64_t)nmax * row_item > row_cap) atomicMin(&wide, b);
+    __syncthreads();
+    if (t == 0) { info[0] = bad; info[1] = over; info[2] = running; info[3] = nmax; info[4] = wide; }
 }
+
+// the fixed block of a split call, once per problem and call kind, widest words first:
+// chk [B] | cube_off [B+1] | info [EXS_INFO] | word [B] | word0 [B] | du [B] | route [B]
+// One layout for the three calls: the count, which has no check pass and no shared word, leaves chk, word and word0 (16 B per instance)
+// unused, and the deciding call leaves word0 unused.
+struct ExsFixed {
+    int64_t *chk;               // reads of the instance's check pass
+    int64_t *cube_off, *info;
+    int32_t *word, *word0;      // the word the cubes of an instance share (best[b] / ub[b]) and, for ub, its value before the cubes
+    int8_t *du; uint8_t *route;
+};
+
+inline ExsFixed exs_fixed(const pdp_problem *p, const pdp_exact_cubes &S)
+{
+    const size_t B = p->B;
+    ExsFixed F;
+    char *q = S.blob;
+    F.chk = (int64_t *)q;       q += B * 8;
+    F.cube_off = (int64_t *)q;  q += (B + 1) * 8;
+    F.info = (int64_t *)q;      q += EXS_INFO * 8;
+    F.word = (int32_t *)q;      q += B * 4;
+    F.word0 = (int32_t *)q;     q += B * 4;
+    F.du = (int8_t *)q;         q += B;
+    F.route = (uint8_t *)q;
+    return F;
+}
+
+// The first stage of a split call `name`: the fixed block (allocated on first use), the setup kernel and the one synchronisation of the
+// call (the cube count sizes the records and the grid), then the errors the setup found.  info: k_exact_split_setup's.
+int exs_setup(pdp_problem *p, pdp_exact_cubes &S, const char *name, const int8_t *depth, int8_t *depth_used, int n_cap, int64_t row_item,
+              int64_t row_cap, hipStream_t st, ExsFixed &F, int64_t info[EXS_INFO])
+{
+    const size_t B = p->B;
+    if (!S.blob) {
+        const int st_ = pdp_dev_alloc((void **)&S.blob, (B * 8 + (B + 1) * 8 + EXS_INFO * 8 + 2 * B * 4 + 2 * B + 15) & ~(size_t)15);
+        if (st_ != PDP_OK) return st_;
+    }
+    F = exs_fixed(p, S);
+    S.total = 0;                                                    // no records to hand out until this call has launched its cubes
+    hipLaunchKernelGGL(k_exact_split_setup, dim3(1), dim3(EXS_SETUP_NT), 0, st, make_view(p), depth, p->ex_order, p->ex_nbig, n_cap, row_item,
+                       row_cap, F.du, F.route, F.cube_off, depth_used, F.info);
+    PDP_LAUNCH_CHECK();
+    PDP_HIP_CHECK(hipMemcpyAsync(info, F.info, EXS_INFO * 8, hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));
+    if (info[0] != EXS_NONE) {
+        pdp_set_error("%s: the depth of instance %lld is not in 0 .. %d", name, (long long)info[0], EXS_MAX_DEPTH);
+        return PDP_ERR_INVALID;
+    }
+    if (info[1] != EXS_NONE) {
+        pdp_set_error("%s: more than 2^22 cubes in one call (reached at instance %lld); lower the depths or split the batch", name,
+                      (long long)info[1]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[4] != EXS_NONE) {
+        pdp_set_error("%s: the per-cube rows (cubes x %lld variables x %lld bytes) pass 2^31 bytes at instance %lld; lower the depths or split "
+                      "the batch", name, (long long)info[3], (long long)row_item, (long long)info[4]);
+        return PDP_ERR_INVALID;
+    }
+    return PDP_OK;
+}
+
+// the per-cube records of a call, kept on the handle for its *_cubes entry point and grown on demand
+int exs_records(pdp_exact_cubes &S, size_t bytes)
+{
+    const size_t need = (bytes + 15) & ~(size_t)15;
+    if (need > S.cube_bytes) {
+        if (S.cubes) { pdp_dev_free(S.cubes); S.cubes = nullptr; S.cube_bytes = 0; }
+        const int st_ = pdp_dev_alloc((void **)&S.cubes, need);
+        if (st_ != PDP_OK) return st_;
+        S.cube_bytes = need;
+    }
+    return PDP_OK;
+}
+
+// the instance of cube q: cube_off[b] <= q < cube_off[b + 1]
+__device__ __forceinline__ int exs_instance(const int64_t *cube_off, int B, uint32_t q)
+{
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cube_off[mid] <= (int64_t)q) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+struct ExsParams {
+    int B;
+    uint32_t total;             // cubes of the call
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;
+    const float *hint;          // [V] phase hints (NULL: none)
+    const int8_t *du;           // [B] depth used
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    const int64_t *chk;         // [B] reads of the rejected or accepted check pass (0: it did not run)
+    int32_t *best;              // [B]
+    int8_t *cube_status;        // [total] 1 / 0 / -1, -2 stopped early
+    int64_t *cube_work;         // [total]
+    uint32_t *rows;             // [total][words] bit-packed assignment of every cube that answered 1 (instances of depth > 0)
+    int words;
+    float *model;               // [V] written by the cube of a depth-0 instance, by the finish kernel elsewhere
+    ExHbm h;
+};
 
 // The check pass of pdp_exact_solve_hinted, once per instance, straight from the problem's arrays: it runs when every variable of the
 // instance has a hint, reads every clause up to its first true literal under the thresholded hints, and accepts when every clause has one.
@@ -2468,186 +2579,33 @@ __global__ void __launch_bounds__(EX_NT) k_exact_split_check(PView pv, const flo
     }
 }
 
-// One cube of one instance by the calling wave: ex_search<HBM, true> without its check pass (keep the two in step), where a level
-// L <= depth takes the polarity bit (index >> (depth - L)) & 1 asks for (0: the search's first, 1: the other) and is recorded as already
-// flipped, so backtracking pops through it.  Returns 1 (val holds a model), 0 (the cube has none), -1 (budget spent) or -2 (stopped: a
-// lower cube has answered 1); *work_out = the cube's own reads.  `spent` (the check pass's reads) counts against the budget.  best[b] is
-// loaded by lane 0 one pass ahead of the budget check that reads it, so the load's latency lies behind a pass; an older value only stops
-// the cube a pass later.
+// cube q = (instance I.b, index): unless a lower cube has answered already, copy the instance (ex_fill), clear the state (pend starts as
+// the hint codes) and search; then the cube's record, and where it answers 1 the minimum on best[b] and its assignment: the instance's
+// slice of the model when the instance has this one cube, the cube's own row of bits otherwise.  Both arms end in the records and the
+// barrier below.
 template <bool HBM, typename LitT, typename PtrT>
-__device__ int ex_search_split(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t spent, int depth, int index, const int32_t *bestp, int seen,
-                               int64_t *work_out)
-{
-    const int lane = (int)threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    constexpr uint32_t UNIT = 3u;
-    int level = 0, tlen = 0;
-    int64_t work = 0;
-    int result = -1;
-    for (;;) {
-        if (spent + work >= budget) break;
-        seen = __shfl(seen, 0);
-        if (index > seen) { result = -2; break; }                   // wave-uniform; ends where the budget's break ends
-        if (lane == 0) seen = exs_best(bestp);
-        // ---- one unit-propagation pass
-        int reads = 0, conflict = 0, unit = 0, wmin = 0x7fffffff;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a, distinct = 0;
-            uint32_t first = 0;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat) continue;
-            if (nfree == 0) conflict = 1;
-            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
-            else wmin = nfree < wmin ? nfree : wmin;
-        }
-        work += ex_sum(reads);
-        bool any_conflict = __ballot(conflict) != 0ull;
-        const bool any_unit = __ballot(unit) != 0ull;
-        if (any_unit) {
-            // assign the pending set of the pass; a variable asked for both polarities is a conflict
-            ex_sync<HBM>();
-            int bad = 0;
-            for (int base = 0; base < X.n; base += EX_NT) {
-                const int v = base + lane;
-                const uint32_t word = v < X.n ? X.pend[v] : 0u;
-                const uint32_t bits = word & UNIT;
-                const unsigned long long mask = __ballot(bits != 0u);
-                if (bits) {
-                    X.pend[v] = word & ~UNIT;
-                    X.val[v] = (bits & 1u) ? 1 : 2;
-                    bad |= bits == 3u;
-                    X.trail[tlen + __popcll(mask & below)] = v;
-                }
-                tlen += __popcll(mask);
-            }
-            any_conflict = any_conflict || __ballot(bad) != 0ull;
-            ex_sync<HBM>();
-        }
-        if (any_conflict) {
-            // chronological backtracking, a copy of ex_search's block: a pinned level carries the flipped bit from the start
-            bool resumed = false;
-            while (level > 0) {
-                const uint32_t d = X.dvar[level];
-                const int v = (int)(d & 0x7fffffffu);
-                const int from = X.mark[level];
-                const uint32_t first = X.val[v];
-                ex_sync<HBM>();                                     // every lane has read the level before it is undone
-                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
-                tlen = from;
-                if (!(d & 0x80000000u)) {
-                    ex_sync<HBM>();
-                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
-                    ++tlen;
-                    ex_sync<HBM>();
-                    resumed = true;
-                    break;
-                }
-                --level;
-            }
-            if (!resumed) { result = 0; break; }
-            continue;
-        }
-        if (any_unit) continue;
-        wmin = ex_min(wmin);
-        if (wmin == 0x7fffffff) { result = 1; break; }          // no open clause: every clause is satisfied
-        // ---- branching: ex_search's rule
-        reads = 0;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) ++nfree;
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat || nfree != wmin) continue;
-            for (int j = a; j < z; ++j) {
-                const uint32_t L = X.lit[j];
-                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
-            }
-            reads += z - a;
-        }
-        work += ex_sum(reads);
-        ex_sync<HBM>();
-        unsigned long long best = 0ull;
-        for (int v = lane; v < X.n; v += EX_NT) {
-            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
-            if (p | q) {
-                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
-                bool pos = p >= q;
-                const uint32_t code = (X.pend[v] >> EX_HINT_SHIFT) & 3u;
-                if (code) pos = code == 1u;
-                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
-                                               (pos ? 1ull : 0ull);
-                best = key > best ? key : best;
-            }
-        }
-        best = ex_max64(best);
-        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
-        ++level;
-        const bool pinned = level <= depth;
-        const bool other = pinned && ((index >> (depth - level)) & 1) != 0;
-        const bool pos = ((best & 1ull) != 0ull) != other;
-        ex_sync<HBM>();
-        if (lane == 0) {
-            X.mark[level] = tlen; X.dvar[level] = (uint32_t)v | (pinned ? 0x80000000u : 0u); X.val[v] = pos ? 1 : 2; X.trail[tlen] = v;
-        }
-        ++tlen;
-        ex_sync<HBM>();
-    }
-    *work_out = work;
-    return result;
-}
-
-// cube q = (instance I.b, index): unless a lower cube has answered already, copy the instance's literals in clause order, clear the state
-// (pend starts as the hint codes) and search; then the cube's record, and where it answers 1 the minimum on best[b] and its assignment: the
-// instance's slice of the model when the instance has this one cube, the cube's own row of bits otherwise.  Both arms end in the records
-// and the barrier below.
-template <bool HBM, typename LitT, typename PtrT>
-__device__ void ex_solve_split(const ExsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill, uint32_t q, int depth, int index)
+__device__ void ex_solve_split(const ExsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, uint32_t q, int depth, int index)
 {
     const int lane = (int)threadIdx.x;
     int seen = 0;
-    if (lane == 0) seen = exs_best(xp.best + I.b);
+    if (lane == 0) seen = ex_shared_load(xp.best + I.b);
     seen = __shfl(seen, 0);
     int st = -2;
     int64_t work = 0;
     if (index <= seen) {
-        if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
-        for (int k = lane; k < I.e; k += EX_NT) {
-            const int ed = I.f_edges[k];
-            X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
-        }
+        ex_fill<HBM>(I, X);
         for (int v = lane; v < I.n; v += EX_NT) {
             uint32_t code = 0u;
             if (xp.hint) { const float h = xp.hint[I.v0 + v]; code = h != h ? 0u : (h > 0.5f ? 1u : 2u); }
             X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
         }
         ex_sync<HBM>();
-        st = ex_search_split<HBM>(X, xp.budget, xp.chk[I.b], depth, index, xp.best + I.b, seen, &work);
+        st = ex_search<HBM, true, true>(X, xp.budget, false, ExCube<true>{depth, index, xp.chk[I.b], xp.best + I.b, seen}, &work);
     }
     if (depth == 0) {
         for (int v = lane; v < I.n; v += EX_NT) xp.model[I.v0 + v] = (st == 1 && X.val[v] == 1) ? 1.0f : 0.0f;
     } else if (st == 1) {
-        uint32_t *row = xp.rows + (size_t)q * (size_t)xp.words;
-        for (int base = 0; base < I.n; base += EX_NT) {
-            const int v = base + lane;
-            const unsigned long long mask = __ballot(v < I.n && X.val[v] == 1);
-            if (lane == 0) {
-                row[base >> 5] = (uint32_t)mask;
-                if (base + 32 < I.n) row[(base >> 5) + 1] = (uint32_t)(mask >> 32);
-            }
-        }
+        ex_pack_row(X, xp.rows + (size_t)q * (size_t)xp.words);
     }
     if (lane == 0) {
         if (st == 1) atomicMin(xp.best + I.b, index);
@@ -2665,29 +2623,11 @@ __global__ void __launch_bounds__(EX_NT) k_exact_split(PView pv, ExsParams xp)
         if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
         q = __shfl(q, 0);
         if (q >= xp.total) break;
-        int lo = 0, hi = xp.B;                                      // cube_off[lo] <= q < cube_off[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (xp.cube_off[mid] <= (int64_t)q) lo = mid; else hi = mid;
-        }
+        const int lo = exs_instance(xp.cube_off, xp.B, q);
         const Inst I = load_inst(pv, lo);
         const int depth = (int)xp.du[lo], index = (int)((int64_t)q - xp.cube_off[lo]);
-        if (xp.route[lo]) {
-            ExInst<uint32_t, int32_t> X;
-            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
-            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
-            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve_split<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr, q, depth, index);
-        } else {
-            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
-            ExInst<uint16_t, uint16_t> X;
-            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
-            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
-            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve_split<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ex_slab + L.cptr), q, depth, index);
-        }
+        if (xp.route[lo]) ex_solve_split<true>(xp, I, ex_bind_hbm(xp.h, I), q, depth, index);
+        else ex_solve_split<false>(xp, I, ex_bind_lds(ex_slab, I), q, depth, index);
     }
 }
 
@@ -2733,106 +2673,45 @@ __global__ void __launch_bounds__(EX_NT) k_exact_split_finish(PView pv, ExsParam
     }
 }
 
-// fixed block of the split call, once per problem, widest words first: chk [B] | cube_off [B+1] | info [4] | best [B] | du [B] | route [B]
-struct ExsFixed { int8_t *du; uint8_t *route; int32_t *best; int64_t *chk, *cube_off, *info; };
-
-inline ExsFixed exs_fixed(const pdp_problem *p)
-{
-    const size_t B = p->B;
-    ExsFixed F;
-    char *q = p->exs_blob;
-    F.chk = (int64_t *)q;       q += B * 8;
-    F.cube_off = (int64_t *)q;  q += (B + 1) * 8;
-    F.info = (int64_t *)q;      q += 4 * 8;
-    F.best = (int32_t *)q;      q += B * 4;
-    F.du = (int8_t *)q;         q += B;
-    F.route = (uint8_t *)q;
-    return F;
-}
-
 int exs_launch(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, float *model, int64_t *work, int32_t *first,
                int8_t *depth_used, void *stream)
 {
     { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
     const hipStream_t st = ST(stream);
-    const size_t V = p->V, E = p->E, B = p->B;
-    if (!p->exs_blob) {
-        const int st_ = pdp_dev_alloc((void **)&p->exs_blob, (B * 8 + (B + 1) * 8 + 32 + B * 4 + 2 * B + 15) & ~(size_t)15);
-        if (st_ != PDP_OK) return st_;
-    }
-    const ExsFixed F = exs_fixed(p);
-    p->exs_total = 0;                                                // no records to hand out until this call has launched its cubes
-    hipLaunchKernelGGL(k_exact_split_setup, dim3(1), dim3(EXS_SETUP_NT), 0, st, make_view(p), depth, p->ex_order, p->ex_nbig, F.du, F.route,
-                       F.cube_off, depth_used, F.info);
-    PDP_LAUNCH_CHECK();
-    int64_t info[4];
-    PDP_HIP_CHECK(hipMemcpyAsync(info, F.info, sizeof(info), hipMemcpyDeviceToHost, st));
-    PDP_HIP_CHECK(hipStreamSynchronize(st));                        // the cube count sizes the records and the grid
-    if (info[0] != EXS_NONE) {
-        pdp_set_error("pdp_exact_solve_split: the depth of instance %lld is not in 0 .. %d", (long long)info[0], EXS_MAX_DEPTH);
-        return PDP_ERR_INVALID;
-    }
-    if (info[1] != EXS_NONE) {
-        pdp_set_error("pdp_exact_solve_split: more than 2^22 cubes in one call (reached at instance %lld); lower the depths or split the batch",
-                      (long long)info[1]);
-        return PDP_ERR_INVALID;
-    }
+    const size_t B = p->B;
+    ExsFixed F;
+    int64_t info[EXS_INFO];
+    { const int st_ = exs_setup(p, p->exs, "pdp_exact_solve_split", depth, depth_used, 0x7fffffff, 0, 0, st, F, info); if (st_ != PDP_OK) return st_; }
     const size_t total = (size_t)info[2], words = ((size_t)info[3] + 31) / 32;
-    // per-cube records: work [total] | rows [total][words] | status [total]; grown on demand
-    const size_t need = (total * 8 + total * words * 4 + total + 15) & ~(size_t)15;
-    if (need > p->exs_cube_bytes) {
-        if (p->exs_cubes) { pdp_dev_free(p->exs_cubes); p->exs_cubes = nullptr; p->exs_cube_bytes = 0; }
-        const int st_ = pdp_dev_alloc((void **)&p->exs_cubes, need);
-        if (st_ != PDP_OK) return st_;
-        p->exs_cube_bytes = need;
-    }
+    // per-cube records: work [total] | rows [total][words] | status [total]
+    { const int st_ = exs_records(p->exs, total * 8 + total * words * 4 + total); if (st_ != PDP_OK) return st_; }
     ExsParams xp;
     xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
-    xp.hint = hint; xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off; xp.chk = F.chk; xp.best = F.best;
-    xp.cube_work = (int64_t *)p->exs_cubes;
-    xp.rows = (uint32_t *)(p->exs_cubes + total * 8);
-    xp.cube_status = (int8_t *)(p->exs_cubes + total * 8 + total * words * 4);
+    xp.budget = ex_budget(budget);
+    xp.hint = hint; xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off; xp.chk = F.chk; xp.best = F.word;
+    xp.cube_work = (int64_t *)p->exs.cubes;
+    xp.rows = (uint32_t *)(p->exs.cubes + total * 8);
+    xp.cube_status = (int8_t *)(p->exs.cubes + total * 8 + total * words * 4);
     xp.words = (int)words;
     xp.model = model;
-    if (p->ex_h_lit) {
-        char *q = (char *)p->ex_h_lit;
-        xp.h_lit = (uint32_t *)q;            q += E * 4;
-        xp.h_pend = (uint32_t *)q;           q += V * 4;
-        xp.h_cnt = (uint32_t *)q;            q += V * 8;
-        xp.h_trail = (int32_t *)q;           q += V * 4;
-        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
-        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
-        xp.h_val = (uint8_t *)q;
-    } else {
-        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
-        xp.h_val = nullptr;
-    }
+    xp.h = ex_hbm(p);
     const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
-    hipLaunchKernelGGL(k_exact_split_check, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), hint, F.chk, F.best);
+    hipLaunchKernelGGL(k_exact_split_check, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), hint, F.chk, F.word);
     PDP_LAUNCH_CHECK();
-    const int lds = (int)p->ex_lds_bytes;
-    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_split, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_split, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)total, (int64_t)pdp_device_cus() * per_cu));
-    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact_split, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
+    { const int st_ = ex_launch_persistent(p, k_exact_split, xp, (int64_t)total, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
     hipLaunchKernelGGL(k_exact_split_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp, status, work, first);
     PDP_LAUNCH_CHECK();
-    p->ex_last_grid = (int32_t)grid;
-    p->exs_total = (int64_t)total;
-    p->exs_status_off = total * 8 + total * words * 4;
+    p->exs.total = (int64_t)total;
+    p->exs.status_off = total * 8 + total * words * 4;
     return PDP_OK;
 }
 
 // ---- pdp_exact_count_split: one instance's model count spread over 2^depth cubes, one wave per cube ------------------------------------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_count_split_model.py).  Its own search, kernels and launch path: nothing above
-// is touched.  A cube is ex_search_count with the decisions of levels 1..depth pinned as in ex_search_split, and a leaf met with fewer than
-// `depth` levels open credited to the one cube whose remaining index bits are 0.  Every cube runs to its own end: no word is shared between
-// two waves, there is no check pass and no early stop.  The state, the slab (exn_lds_layout), the routing and the HBM arrays are
-// k_exact_count's.  Three launches on one stream: the setup (depth_used, cube_off, the caps), the cubes (one counter hands out cube ids;
+// (specification: include/pdp_hip.h; plain Python: tests/exact_count_split_model.py).  A cube is ex_search_count<HBM, true>: the counting
+// search with the decisions of levels 1..depth pinned as in pdp_exact_solve_split, and a leaf met with fewer than `depth` levels open
+// credited to the one cube whose remaining index bits are 0.  Every cube runs to its own end: no word is shared between two waves, there
+// is no check pass and no early stop.  The state, the slab (exn_lds_layout), the routing and the HBM arrays are k_exact_count's.  Three
+// launches on one stream: k_exact_split_setup (depth_used, cube_off, the caps), the cubes (one counter hands out cube ids;
 // every cube leaves a record, and where its instance has more than one cube and its count is not 0.0, its row of n per-variable counts),
 // the finish (per instance of depth > 0: the records and rows summed in ascending cube order).  An instance at depth 0 has one cube, which
 // writes the instance's outputs itself exactly as k_exact_count does.  No double goes through an atomic or a reduction across lanes: the
@@ -2854,229 +2733,18 @@ struct ExnsParams {
     double *rows;               // [total][n_max] true_count of every cube of an instance with depth_used > 0 whose count is not 0.0
     int n_max;
     int8_t *status; double *count; double *true_count; int64_t *work; int64_t *leaves;      // the instance's outputs
-    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+    ExHbm h;
     double *h_F, *h_snap;       // as ExnParams
 };
 
-// k_exact_split_setup's job for the count: depth_used (0 on the HBM route and for n > 1023), route and cube_off, by one workgroup.
-// info[0] = the lowest instance whose depth is out of range, info[1] = the lowest instance at which the running cube count passes 2^22,
-// info[4] = the lowest instance at which the running size of the rows, cube_off[b + 1] * n_max * 8 bytes, passes 2^31 (EXS_NONE: none),
-// info[2] = cubes, info[3] = n_max, the most variables of an instance with depth_used > 0.
-__global__ void __launch_bounds__(EXS_SETUP_NT) k_exact_count_split_setup(PView pv, const int8_t *depth, const int32_t *order, int nbig, int8_t *du,
-                                                                          uint8_t *route, int64_t *cube_off, int8_t *depth_used, int64_t *info)
-{
-    __shared__ int64_t s[EXS_SETUP_NT];
-    __shared__ int bad, over, wide, nmax;
-    const int t = (int)threadIdx.x, B = pv.B;
-    if (t == 0) { bad = EXS_NONE; over = EXS_NONE; wide = EXS_NONE; nmax = 0; cube_off[0] = 0; }
-    __syncthreads();
-    for (int b = t; b < B; b += EXS_SETUP_NT) {
-        const int d = depth ? (int)depth[b] : 0;
-        const bool ok = d >= 0 && d <= EXS_MAX_DEPTH;
-        if (!ok) atomicMin(&bad, b);
-        du[b] = (int8_t)(ok && pv.inst_v0[b + 1] - pv.inst_v0[b] <= EXN_MAX_N ? d : 0);
-        route[b] = 0;
-    }
-    __syncthreads();
-    for (int i = t; i < nbig; i += EXS_SETUP_NT) { const int b = order[i]; du[b] = 0; route[b] = 1; }      // the HBM route: per-instance arrays
-    __syncthreads();
-    int64_t running = 0;
-    for (int base = 0; base < B; base += EXS_SETUP_NT) {
-        const int b = base + t;
-        const int d = b < B ? (int)du[b] : 0;
-        s[t] = b < B ? (int64_t)1 << d : 0;
-        __syncthreads();
-        for (int o = 1; o < EXS_SETUP_NT; o <<= 1) {
-            const int64_t x = t >= o ? s[t - o] : 0;
-            __syncthreads();
-            s[t] += x;
-            __syncthreads();
-        }
-        if (b < B) {
-            const int64_t end = running + s[t];
-            cube_off[b + 1] = end;
-            if (end > EXS_MAX_CUBES) atomicMin(&over, b);
-            if (d > 0) atomicMax(&nmax, pv.inst_v0[b + 1] - pv.inst_v0[b]);
-            if (depth_used) depth_used[b] = (int8_t)d;
-        }
-        running += s[EXS_SETUP_NT - 1];
-        __syncthreads();
-    }
-    // cube_off[b + 1] <= 2^22 * B and n_max <= 1023: the product stays far inside int64
-    for (int b = t; b < B; b += EXS_SETUP_NT)
-        if (cube_off[b + 1] * (int64_t)nmax * 8 > EXNS_MAX_ROW_BYTES) atomicMin(&wide, b);
-    __syncthreads();
-    if (t == 0) { info[0] = bad; info[1] = over; info[2] = running; info[3] = nmax; info[4] = wide; }
-}
-
-// One cube of one instance by the calling wave: ex_search_count (keep the two in step) where a level L <= depth takes the polarity that bit
-// (index >> (depth - L)) & 1 asks for (0: the search's first, 1: the other) and is recorded as already flipped, and where a leaf met with
-// level < depth levels open counts only if index's low depth - level bits are 0.  Returns 1 (complete) or -1 (the cube's budget is spent).
+// cube q = (instance I.b, index): copy the instance (ex_fill), clear the state, search; then the cube's record, and its per-variable
+// counts: the instance's slice of true_count and the instance's other outputs when this is its one cube (depth 0), the cube's own row
+// otherwise, skipped when the count is 0.0 (every entry is then +0.0, and the finish kernel skips the row as well).
 template <bool HBM, typename LitT, typename PtrT>
-__device__ int ex_search_count_split(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int64_t budget, int depth, int index, int64_t *work_out,
-                                     double *count_out, int64_t *leaves_out)
+__device__ void ex_solve_count_split(const ExnsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExnAcc A, uint32_t q, int depth, int index)
 {
     const int lane = (int)threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    constexpr int INF = 0x7fffffff;
-    int level = 0, tlen = 0;
-    int64_t work = 0, leaves = 0;
-    double count = 0.0;
-    int result = -1;
-    for (;;) {
-        if (work >= budget) break;
-        // ---- one unit-propagation pass
-        int reads = 0, conflict = 0, unit = 0, wmin = INF;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a, distinct = 0;
-            uint32_t first = 0;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat) continue;
-            if (nfree == 0) conflict = 1;
-            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
-            else wmin = nfree < wmin ? nfree : wmin;
-        }
-        work += ex_sum(reads);
-        bool any_conflict = __ballot(conflict) != 0ull;
-        const bool any_unit = __ballot(unit) != 0ull;
-        if (any_unit) {
-            // assign the pending set of the pass; a variable asked for both polarities is a conflict
-            ex_sync<HBM>();
-            int bad = 0;
-            for (int base = 0; base < X.n; base += EX_NT) {
-                const int v = base + lane;
-                const uint32_t bits = v < X.n ? X.pend[v] : 0u;
-                const unsigned long long mask = __ballot(bits != 0u);
-                if (bits) {
-                    X.pend[v] = 0u;
-                    X.val[v] = (bits & 1u) ? 1 : 2;
-                    bad |= bits == 3u;
-                    X.trail[tlen + __popcll(mask & below)] = v;
-                }
-                tlen += __popcll(mask);
-            }
-            any_conflict = any_conflict || __ballot(bad) != 0ull;
-            ex_sync<HBM>();
-        }
-        if (!any_conflict) {
-            if (any_unit) continue;
-            wmin = ex_min(wmin);
-            if (wmin == INF) {
-                // a leaf.  Inside the prefix every cube with these levels' bits arrives here: the one whose remaining bits are 0 takes it.
-                // Either way the search goes on as after a conflict (every open level is pinned then, so that ends the cube)
-                const int rest = depth - level;
-                if (rest <= 0 || (index & ((1 << rest) - 1)) == 0) {
-                    count = count + ldexp(1.0, X.n - tlen);
-                    ++leaves;
-                }
-                any_conflict = true;
-            }
-        }
-        if (any_conflict) {
-            // chronological backtracking with the credit of every undone level: a pinned level carries the flipped bit from the start
-            bool resumed = false;
-            while (level > 0) {
-                const uint32_t d = X.dvar[level];
-                const int v = (int)(d & 0x7fffffffu);
-                const int from = X.mark[level];
-                const uint32_t first = X.val[v];
-                const double since = count - A.snap[level];
-                ex_sync<HBM>();                                     // every lane has read the level before it is undone
-                exn_credit(X, A, from, tlen, since);
-                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;      // the same lane as the credit
-                tlen = from;
-                if (!(d & 0x80000000u)) {
-                    ex_sync<HBM>();
-                    if (lane == 0) {
-                        X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v;
-                        A.snap[level] = count;                      // the level stays open: its first half is credited once
-                    }
-                    ++tlen;
-                    ex_sync<HBM>();
-                    resumed = true;
-                    break;
-                }
-                --level;
-            }
-            if (!resumed) { result = 1; break; }
-            continue;
-        }
-        // ---- branching: ex_search_count's rule, then the cube's bit on a pinned level
-        reads = 0;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) ++nfree;
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat || nfree != wmin) continue;
-            for (int j = a; j < z; ++j) {
-                const uint32_t L = X.lit[j];
-                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
-            }
-            reads += z - a;
-        }
-        work += ex_sum(reads);
-        ex_sync<HBM>();
-        unsigned long long best = 0ull;
-        for (int v = lane; v < X.n; v += EX_NT) {
-            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
-            if (p | q) {
-                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
-                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
-                                               (p >= q ? 1ull : 0ull);
-                best = key > best ? key : best;
-            }
-        }
-        best = ex_max64(best);
-        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
-        ++level;
-        const bool pinned = level <= depth;
-        const bool other = pinned && ((index >> (depth - level)) & 1) != 0;
-        const bool pos = ((best & 1ull) != 0ull) != other;
-        ex_sync<HBM>();
-        if (lane == 0) {
-            X.mark[level] = tlen; X.dvar[level] = (uint32_t)v | (pinned ? 0x80000000u : 0u); X.val[v] = pos ? 1 : 2; X.trail[tlen] = v;
-            A.snap[level] = count;
-        }
-        ++tlen;
-        ex_sync<HBM>();
-    }
-    // the end: every open level is flushed, the newest first, as in ex_search_count
-    for (; level >= 0; --level) {
-        const int from = level > 0 ? X.mark[level] : 0;
-        exn_credit(X, A, from, tlen, count - A.snap[level]);
-        tlen = from;
-    }
-    *work_out = work; *count_out = count; *leaves_out = leaves;
-    return result;
-}
-
-// cube q = (instance I.b, index): copy the instance's literals in clause order, clear the state, search; then the cube's record, and its
-// per-variable counts: the instance's slice of true_count and the instance's other outputs when this is its one cube (depth 0), the cube's
-// own row otherwise, skipped when the count is 0.0 (every entry is then +0.0, and the finish kernel skips the row as well).
-template <bool HBM, typename LitT, typename PtrT>
-__device__ void ex_solve_count_split(const ExnsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExnAcc A, PtrT *cptr_fill, uint32_t q,
-                                     int depth, int index)
-{
-    const int lane = (int)threadIdx.x;
-    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
-    for (int k = lane; k < I.e; k += EX_NT) {
-        const int ed = I.f_edges[k];
-        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
-    }
+    ex_fill<HBM>(I, X);
     for (int v = lane; v < I.n; v += EX_NT) {
         X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
         A.T[v] = 0.0; A.F[v] = 0.0;
@@ -3085,7 +2753,7 @@ __device__ void ex_solve_count_split(const ExnsParams &xp, const Inst &I, ExInst
     ex_sync<HBM>();
     int64_t work = 0, leaves = 0;
     double count = 0.0;
-    const int st = ex_search_count_split<HBM>(X, A, xp.budget, depth, index, &work, &count, &leaves);
+    const int st = ex_search_count<HBM, true>(X, A, xp.budget, ExCube<true>{depth, index, 0, nullptr, 0}, &work, &count, &leaves);
     ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
     if (depth == 0 || count != 0.0) {
         double *out = depth == 0 ? xp.true_count + I.v0 : xp.rows + (size_t)q * (size_t)xp.n_max;
@@ -3117,11 +2785,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact_count_split(PView pv, ExnsParam
         if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
         q = __shfl(q, 0);
         if (q >= xp.total) break;
-        int lo = 0, hi = xp.B;                                      // cube_off[lo] <= q < cube_off[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (xp.cube_off[mid] <= (int64_t)q) lo = mid; else hi = mid;
-        }
+        const int lo = exs_instance(xp.cube_off, xp.B, q);
         const Inst I = load_inst(pv, lo);
         const int depth = (int)xp.du[lo], index = (int)((int64_t)q - xp.cube_off[lo]);
         // every arm ends in the barrier every arm ends in and falls through to the end of the loop body (see k_exact_count)
@@ -3136,25 +2800,9 @@ __global__ void __launch_bounds__(EX_NT) k_exact_count_split(PView pv, ExnsParam
             }
             ex_sync<false>();
         } else if (xp.route[lo]) {
-            ExInst<uint32_t, int32_t> X;
-            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
-            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
-            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ExnAcc A;
-            A.T = xp.true_count + I.v0; A.F = xp.h_F + I.v0; A.snap = xp.h_snap + I.v0 + I.b;
-            ex_solve_count_split<true, uint32_t, int32_t>(xp, I, X, A, (int32_t *)nullptr, q, 0, 0);
+            ex_solve_count_split<true>(xp, I, ex_bind_hbm(xp.h, I), exn_bind_hbm(xp.true_count, xp.h_F, xp.h_snap, I), q, 0, 0);
         } else {
-            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
-            const ExnLds N = exn_lds_layout(I.n, I.m, I.e);
-            ExInst<uint16_t, uint16_t> X;
-            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
-            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
-            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ExnAcc A;
-            A.T = (double *)(ex_slab + N.T); A.F = (double *)(ex_slab + N.F); A.snap = (double *)(ex_slab + N.snap);
-            ex_solve_count_split<false, uint16_t, uint16_t>(xp, I, X, A, (uint16_t *)(ex_slab + L.cptr), q, depth, index);
+            ex_solve_count_split<false>(xp, I, ex_bind_lds(ex_slab, I), exn_bind_lds(ex_slab, I), q, depth, index);
         }
     }
 }
@@ -3221,108 +2869,47 @@ __global__ void __launch_bounds__(EX_NT) k_exact_count_split_finish(PView pv, Ex
     }
 }
 
-// fixed block of the split count, once per problem, widest words first: cube_off [B+1] | info [5] | du [B] | route [B]
-struct ExnsFixed { int8_t *du; uint8_t *route; int64_t *cube_off, *info; };
-
-inline ExnsFixed exns_fixed(const pdp_problem *p)
-{
-    const size_t B = p->B;
-    ExnsFixed F;
-    char *q = p->exns_blob;
-    F.cube_off = (int64_t *)q;  q += (B + 1) * 8;
-    F.info = (int64_t *)q;      q += 5 * 8;
-    F.du = (int8_t *)q;         q += B;
-    F.route = (uint8_t *)q;
-    return F;
-}
-
 int exns_launch(pdp_problem *p, const int8_t *depth, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work,
                 int64_t *leaves, int8_t *depth_used, void *stream)
 {
     { const int st_ = exn_prepare(p); if (st_ != PDP_OK) return st_; }
     const hipStream_t st = ST(stream);
-    const size_t V = p->V, E = p->E, B = p->B;
-    if (!p->exns_blob) {
-        const int st_ = pdp_dev_alloc((void **)&p->exns_blob, ((B + 1) * 8 + 40 + 2 * B + 15) & ~(size_t)15);
+    const size_t B = p->B;
+    ExsFixed F;
+    int64_t info[EXS_INFO];
+    {
+        const int st_ = exs_setup(p, p->exns, "pdp_exact_count_split", depth, depth_used, EXN_MAX_N, 8, EXNS_MAX_ROW_BYTES, st, F, info);
         if (st_ != PDP_OK) return st_;
-    }
-    const ExnsFixed F = exns_fixed(p);
-    p->exns_total = 0;                                               // no records to hand out until this call has launched its cubes
-    hipLaunchKernelGGL(k_exact_count_split_setup, dim3(1), dim3(EXS_SETUP_NT), 0, st, make_view(p), depth, p->ex_order, p->ex_nbig, F.du, F.route,
-                       F.cube_off, depth_used, F.info);
-    PDP_LAUNCH_CHECK();
-    int64_t info[5];
-    PDP_HIP_CHECK(hipMemcpyAsync(info, F.info, sizeof(info), hipMemcpyDeviceToHost, st));
-    PDP_HIP_CHECK(hipStreamSynchronize(st));                        // the cube count sizes the records and the grid
-    if (info[0] != EXS_NONE) {
-        pdp_set_error("pdp_exact_count_split: the depth of instance %lld is not in 0 .. %d", (long long)info[0], EXS_MAX_DEPTH);
-        return PDP_ERR_INVALID;
-    }
-    if (info[1] != EXS_NONE) {
-        pdp_set_error("pdp_exact_count_split: more than 2^22 cubes in one call (reached at instance %lld); lower the depths or split the batch",
-                      (long long)info[1]);
-        return PDP_ERR_INVALID;
-    }
-    if (info[4] != EXS_NONE) {
-        pdp_set_error("pdp_exact_count_split: the per-cube rows (cubes x %lld variables x 8 bytes) pass 2^31 bytes at instance %lld; lower the "
-                      "depths or split the batch", (long long)info[3], (long long)info[4]);
-        return PDP_ERR_INVALID;
     }
     const size_t total = (size_t)info[2], nmax = (size_t)info[3];
-    // per-cube records: count [total] | work [total] | leaves [total] | rows [total][n_max] | status [total]; grown on demand
-    const size_t need = (total * 24 + total * nmax * 8 + total + 15) & ~(size_t)15;
-    if (need > p->exns_cube_bytes) {
-        if (p->exns_cubes) { pdp_dev_free(p->exns_cubes); p->exns_cubes = nullptr; p->exns_cube_bytes = 0; }
-        const int st_ = pdp_dev_alloc((void **)&p->exns_cubes, need);
-        if (st_ != PDP_OK) return st_;
-        p->exns_cube_bytes = need;
-    }
+    // per-cube records: count [total] | work [total] | leaves [total] | rows [total][n_max] | status [total]
+    { const int st_ = exs_records(p->exns, total * 24 + total * nmax * 8 + total); if (st_ != PDP_OK) return st_; }
     ExnsParams xp;
     xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.budget = ex_budget(budget);
     xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off;
-    xp.cube_count = (double *)p->exns_cubes;
-    xp.cube_work = (int64_t *)(p->exns_cubes + total * 8);
-    xp.cube_leaves = (int64_t *)(p->exns_cubes + total * 16);
-    xp.rows = (double *)(p->exns_cubes + total * 24);
-    xp.cube_status = (int8_t *)(p->exns_cubes + total * 24 + total * nmax * 8);
+    xp.cube_count = (double *)p->exns.cubes;
+    xp.cube_work = (int64_t *)(p->exns.cubes + total * 8);
+    xp.cube_leaves = (int64_t *)(p->exns.cubes + total * 16);
+    xp.rows = (double *)(p->exns.cubes + total * 24);
+    xp.cube_status = (int8_t *)(p->exns.cubes + total * 24 + total * nmax * 8);
     xp.n_max = (int)nmax;
     xp.status = status; xp.count = count; xp.true_count = true_count; xp.work = work; xp.leaves = leaves;
-    if (p->ex_h_lit) {
-        char *q = (char *)p->ex_h_lit;
-        xp.h_lit = (uint32_t *)q;            q += E * 4;
-        xp.h_pend = (uint32_t *)q;           q += V * 4;
-        xp.h_cnt = (uint32_t *)q;            q += V * 8;
-        xp.h_trail = (int32_t *)q;           q += V * 4;
-        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
-        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
-        xp.h_val = (uint8_t *)q;
-        xp.h_F = (double *)p->exn_blob;
-        xp.h_snap = (double *)(p->exn_blob + V * 8);
-    } else {
-        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
-        xp.h_val = nullptr; xp.h_F = nullptr; xp.h_snap = nullptr;
-    }
-    const int lds = (int)p->exn_lds_bytes;
-    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_count_split, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_count_split, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)total, (int64_t)pdp_device_cus() * per_cu));
-    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact_count_split, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
+    xp.h = ex_hbm(p);
+    xp.h_F = p->exn_blob ? (double *)p->exn_blob : nullptr;
+    xp.h_snap = p->exn_blob ? (double *)(p->exn_blob + (size_t)p->V * 8) : nullptr;
+    { const int st_ = ex_launch_persistent(p, k_exact_count_split, xp, (int64_t)total, p->exn_lds_bytes, st); if (st_ != PDP_OK) return st_; }
     const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
     hipLaunchKernelGGL(k_exact_count_split_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
     PDP_LAUNCH_CHECK();
-    p->ex_last_grid = (int32_t)grid;
-    p->exns_total = (int64_t)total;
-    p->exns_status_off = total * 24 + total * nmax * 8;
+    p->exns.total = (int64_t)total;
+    p->exns.status_off = total * 24 + total * nmax * 8;
     return PDP_OK;
 }
 
 // ---- pdp_exact_models_at: the models of given ranks in the counting search's own order -------------------------------------------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_rank_model.py).  Its own search, kernel and launch path:
-// nothing above is touched.  The state is ex_search's, array for array, in ex_lds_layout's slab (no doubles per variable: count and
+// (specification: include/pdp_hip.h; plain Python: tests/exact_rank_model.py).  ex_search_rank is the shared blocks
+// around a leaf of its own.  The state is ex_search's, array for array, in ex_lds_layout's slab (no doubles per variable: count and
 // before are uniform over the wave, and nothing is credited).  The ranks of an instance are non-decreasing, so one cursor walks them while
 // the search walks its leaves: a leaf that raises count from `before` to `count` answers every rank below count that is still open.  The
 // cursor and the ranks are read from HBM by the whole wave at once (one address); a model goes out as one row of bytes, one lane per
@@ -3342,7 +2929,7 @@ struct ExrParams {
     const int64_t *ranks;       // [rank_off[B]]
     const int64_t *model_off;   // [B+1] first byte of every instance's rows in models
     int8_t *status; double *count_seen; int8_t *found; uint8_t *models; int64_t *work; int64_t *leaves;
-    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+    ExHbm h;
 };
 
 // rank_off and the sizes, by one workgroup: model_off [B+1] = the running sum of K_b * n_b bytes; info[0] = 1 if rank_off[0] != 0,
@@ -3430,65 +3017,36 @@ __device__ __forceinline__ void exr_emit(const ExInst<LitT, PtrT> &X, uint64_t o
     }
 }
 
-// The search of one instance by the calling wave: ex_search_count without the crediting, with the cursor `cur` over ranks[0 .. K), K >= 1.
-// Returns 1 (the last rank is answered, or the tree is exhausted: the open ranks get found 0) or -1 (budget spent: the open ranks get
-// found -1).  rows: K rows of n bytes, zero on entry; only answered ranks are written.
+// The search of one instance by the calling wave: ex_search_count<HBM, false> without the crediting, with the cursor `cur` over
+// ranks[0 .. K), K >= 1.  Built from the same blocks; only the leaf is its own.  Returns 1 (the last rank is answered, or the tree is
+// exhausted: the open ranks get found 0) or -1 (budget spent: the open ranks get found -1).  rows: K rows of n bytes, zero on entry;
+// only answered ranks are written.
 template <bool HBM, typename LitT, typename PtrT>
 __device__ int ex_search_rank(const ExInst<LitT, PtrT> &X, int64_t budget, const int64_t *ranks, int64_t K, int8_t *found, uint8_t *rows,
                               int64_t *work_out, double *count_out, int64_t *leaves_out)
 {
     const int lane = (int)threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
     constexpr int INF = 0x7fffffff;
     int level = 0, tlen = 0;
     int64_t work = 0, leaves = 0, cur = 0;
     double count = 0.0;
     int result = -1;
+    ExNoCredit none;
     for (;;) {
         if (work >= budget) break;
-        // ---- one unit-propagation pass (ex_search's: keep the two in step)
-        int reads = 0, conflict = 0, unit = 0, wmin = INF;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a, distinct = 0;
-            uint32_t first = 0;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat) continue;
-            if (nfree == 0) conflict = 1;
-            else if (!distinct) { unit = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
-            else wmin = nfree < wmin ? nfree : wmin;
-        }
-        work += ex_sum(reads);
-        bool any_conflict = __ballot(conflict) != 0ull;
-        const bool any_unit = __ballot(unit) != 0ull;
+        const ExPass P = ex_propagate(X);
+        work += ex_sum(P.reads);
+        bool any_conflict = __ballot(P.conflict) != 0ull;
+        const bool any_unit = __ballot(P.unit) != 0ull;
         if (any_unit) {
-            // assign the pending set of the pass; a variable asked for both polarities is a conflict
             ex_sync<HBM>();
-            int bad = 0;
-            for (int base = 0; base < X.n; base += EX_NT) {
-                const int v = base + lane;
-                const uint32_t bits = v < X.n ? X.pend[v] : 0u;
-                const unsigned long long mask = __ballot(bits != 0u);
-                if (bits) {
-                    X.pend[v] = 0u;
-                    X.val[v] = (bits & 1u) ? 1 : 2;
-                    bad |= bits == 3u;
-                    X.trail[tlen + __popcll(mask & below)] = v;
-                }
-                tlen += __popcll(mask);
-            }
-            any_conflict = any_conflict || __ballot(bad) != 0ull;
-            ex_sync<HBM>();
+            const bool both = ex_assign_pending<HBM, false>(X, tlen);
+            any_conflict = any_conflict || both;
         }
+        int wmin = INF;
         if (!any_conflict) {
             if (any_unit) continue;
-            wmin = ex_min(wmin);
+            wmin = ex_min(P.wmin);
             if (wmin == INF) {
                 // a leaf: its models are the ranks before .. count - 1; every open rank below count is answered here
                 const double before = count;
@@ -3507,68 +3065,12 @@ __device__ int ex_search_rank(const ExInst<LitT, PtrT> &X, int64_t budget, const
             }
         }
         if (any_conflict) {
-            // chronological backtracking, ex_search's block (keep the two in step)
-            bool resumed = false;
-            while (level > 0) {
-                const uint32_t d = X.dvar[level];
-                const int v = (int)(d & 0x7fffffffu);
-                const int from = X.mark[level];
-                const uint32_t first = X.val[v];
-                ex_sync<HBM>();                                     // every lane has read the level before it is undone
-                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
-                tlen = from;
-                if (!(d & 0x80000000u)) {
-                    ex_sync<HBM>();
-                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
-                    ++tlen;
-                    ex_sync<HBM>();
-                    resumed = true;
-                    break;
-                }
-                --level;
-            }
-            if (!resumed) { result = 1; break; }
+            if (!ex_backtrack<HBM>(X, level, tlen, none)) { result = 1; break; }
             continue;
         }
-        // ---- branching: ex_search's, without hints (keep the two in step)
-        reads = 0;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) ++nfree;
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat || nfree != wmin) continue;
-            for (int j = a; j < z; ++j) {
-                const uint32_t L = X.lit[j];
-                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
-            }
-            reads += z - a;
-        }
-        work += ex_sum(reads);
-        ex_sync<HBM>();
-        unsigned long long best = 0ull;
-        for (int v = lane; v < X.n; v += EX_NT) {
-            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
-            if (p | q) {
-                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
-                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
-                                               (p >= q ? 1ull : 0ull);
-                best = key > best ? key : best;
-            }
-        }
-        best = ex_max64(best);
+        const unsigned long long best = ex_branch<HBM, EX_PHASE_COUNT>(X, wmin, work);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
-        ++level;
-        ex_sync<HBM>();
-        if (lane == 0) { X.mark[level] = tlen; X.dvar[level] = (uint32_t)v; X.val[v] = (best & 1ull) ? 1 : 2; X.trail[tlen] = v; }
-        ++tlen;
-        ex_sync<HBM>();
+        ex_decide<HBM, false>(X, ExCube<false>{}, best, level, tlen, none);
     }
     // the ranks the search did not reach: no such model (the tree is exhausted), or not known (the budget is spent)
     for (int64_t i = cur + lane; i < K; i += EX_NT) found[i] = (int8_t)(result == 1 ? 0 : -1);
@@ -3576,16 +3078,12 @@ __device__ int ex_search_rank(const ExInst<LitT, PtrT> &X, int64_t budget, const
     return result;
 }
 
-// copy the instance's literals in clause order, clear the state, search, write the results
+// copy the instance (ex_fill), clear the state, search, write the results
 template <bool HBM, typename LitT, typename PtrT>
-__device__ void ex_solve_rank(const ExrParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill, int64_t r0, int64_t K)
+__device__ void ex_solve_rank(const ExrParams &xp, const Inst &I, ExInst<LitT, PtrT> X, int64_t r0, int64_t K)
 {
     const int lane = (int)threadIdx.x;
-    if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
-    for (int k = lane; k < I.e; k += EX_NT) {
-        const int ed = I.f_edges[k];
-        X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
-    }
+    ex_fill<HBM>(I, X);
     for (int v = lane; v < I.n; v += EX_NT) { X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u; }
     ex_sync<HBM>();
     int64_t work = 0, leaves = 0;
@@ -3624,20 +3122,9 @@ __global__ void __launch_bounds__(EX_NT) k_exact_models(PView pv, ExrParams xp)
             }
             ex_sync<false>();
         } else if (i < xp.nbig) {
-            ExInst<uint32_t, int32_t> X;
-            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
-            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
-            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve_rank<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr, r0, K);
+            ex_solve_rank<true>(xp, I, ex_bind_hbm(xp.h, I), r0, K);
         } else {
-            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
-            ExInst<uint16_t, uint16_t> X;
-            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
-            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
-            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve_rank<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ex_slab + L.cptr), r0, K);
+            ex_solve_rank<false>(xp, I, ex_bind_lds(ex_slab, I), r0, K);
         }
     }
 }
@@ -3647,7 +3134,7 @@ int exr_launch(pdp_problem *p, const int64_t *rank_off, const int64_t *ranks, in
 {
     { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
     const hipStream_t st = ST(stream);
-    const size_t V = p->V, E = p->E, B = p->B;
+    const size_t B = p->B;
     // model_off [B+1] | info [EXR_INFO], once per problem
     if (!p->exr_blob) {
         const int st_ = pdp_dev_alloc((void **)&p->exr_blob, ((B + 1 + EXR_INFO) * 8 + 15) & ~(size_t)15);
@@ -3689,46 +3176,24 @@ int exr_launch(pdp_problem *p, const int64_t *rank_off, const int64_t *ranks, in
     }
     ExrParams xp;
     xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
+    xp.budget = ex_budget(budget);
     xp.rank_off = rank_off; xp.ranks = ranks; xp.model_off = model_off;
     xp.status = status; xp.count_seen = count_seen; xp.found = found; xp.models = models; xp.work = work; xp.leaves = leaves;
-    if (p->ex_h_lit) {
-        char *q = (char *)p->ex_h_lit;
-        xp.h_lit = (uint32_t *)q;            q += E * 4;
-        xp.h_pend = (uint32_t *)q;           q += V * 4;
-        xp.h_cnt = (uint32_t *)q;            q += V * 8;
-        xp.h_trail = (int32_t *)q;           q += V * 4;
-        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
-        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
-        xp.h_val = (uint8_t *)q;
-    } else {
-        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
-        xp.h_val = nullptr;
-    }
-    const int lds = (int)p->ex_lds_bytes;
-    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_models, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_models, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * per_cu));
-    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact_models, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
-    p->ex_last_grid = (int32_t)grid;
-    return PDP_OK;
+    xp.h = ex_hbm(p);
+    return ex_launch_persistent(p, k_exact_models, xp, (int64_t)p->B, p->ex_lds_bytes, st);
 }
 
 // ---- pdp_exact_min_unsat_split: one instance's branch and bound spread over 2^depth cubes, one wave per cube ----------------------------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_min_unsat_split_model.py).  Its own search, kernels and launch path: nothing
-// above is touched (k_exact_split_setup is launched as it is).  A cube is ex_search_min with the decisions of levels 1..depth pinned as in
-// ex_search_split.  The state, the slab, the routing and the occupancy by LDS are k_exact's.  Four launches on one stream: the setup
-// (depth_used, route, cube_off), the check pass (once per instance: the thresholded hint into model, its reads into chk[b], its
-// unsatisfied clauses into ub0[b] and ub[b]), the cubes (one counter hands out cube ids: instance order, ascending index), the finish.
+// (specification: include/pdp_hip.h; plain Python: tests/exact_min_unsat_split_model.py).  A cube is ex_search_min<HBM, true>: the
+// branch and bound with the decisions of levels 1..depth pinned as in pdp_exact_solve_split.  The state, the slab, the routing and the
+// occupancy by LDS are k_exact's.  Four launches on one stream: k_exact_split_setup (depth_used, route, cube_off), the check pass (once per
+// instance: the thresholded hint into model, its reads into chk[b], its unsatisfied clauses into ub0[b] and ub[b]), the cubes (one
+// counter hands out cube ids: instance order, ascending index), the finish.
 // The only word two waves share is ub[b], the best cost any cube of instance b has found: lowered by one atomicMin per improvement, read
-// by lane 0 at the budget checks with a relaxed agent-scope load, one pass ahead of its use.  No wave waits for another.  `live` is the
-// cube's view of it and prunes at every level; forcing the units uses ub0 while level < depth and live from then on, so the decisions of
-// the pinned levels are taken in states that depend on the instance and its hint alone and the cubes partition one prefix tree whatever
-// the timing.  Every condition below is uniform over the wave, and both arms of ex_solve_min_split end in its one barrier.
-constexpr int EXMS_NO_COST = -1;                // cube_cost: the cube accepted no improvement
+// by lane 0 at the budget checks with a relaxed agent-scope load, one pass ahead of its use.  No wave waits for another.  The cube's view
+// of it prunes at every level; forcing the units uses ub0 while level < depth and the view from then on, so the decisions of the pinned
+// levels are taken in states that depend on the instance and its hint alone and the cubes partition one prefix tree whatever the timing.
+// Every condition of the search is uniform over the wave, and both arms of ex_solve_min_split end in its one barrier.
 
 struct ExmsParams {
     int B;
@@ -3749,13 +3214,8 @@ struct ExmsParams {
     uint32_t *rows;             // [total][words] bit-packed assignment of the cube's last accepted cost (instances of depth > 0)
     int words;
     float *model;               // [V] written by the check pass; by the cube of a depth-0 instance, by the finish kernel elsewhere
-    uint32_t *h_lit; uint8_t *h_val; uint32_t *h_pend, *h_cnt; int32_t *h_trail, *h_mark; uint32_t *h_dvar;     // the HBM route's, as ExParams
+    ExHbm h;
 };
-
-__device__ __forceinline__ int exms_load(const int32_t *ub)
-{
-    return __hip_atomic_load(ub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // The check pass of pdp_exact_min_unsat, once per instance, straight from the problem's arrays: the thresholded hint is the first
 // incumbent; every clause is read up to its first true literal.
@@ -3783,209 +3243,25 @@ __global__ void __launch_bounds__(EX_NT) k_exact_min_split_check(PView pv, const
     }
 }
 
-// One cube of one instance by the calling wave: ex_search_min without its check pass (keep the two in step), where a level L <= depth
-// takes the polarity bit (index >> (depth - L)) & 1 asks for (0: the incumbent's, 1: the other) and is recorded as already flipped.
-// `live` comes in as the value of *ubp loaded before the instance was copied (not 0).  An accepted improvement writes the assignment to
-// `model` (the instance's slice of the output: depth 0) or bit-packed to `row` (depth > 0).  Returns 1 (the cube is exhausted, or some
-// cube has reached cost 0) or -1 (budget spent); `spent` (the check pass's reads) counts against the budget.
+// cube q = (instance I.b, index): load ub[b]; unless it is 0 already, copy the instance (ex_fill), clear the state (pend starts as the
+// incumbent's codes) and search; then the cube's record.  Both arms end in the record and the barrier below.
 template <bool HBM, typename LitT, typename PtrT>
-__device__ int ex_search_min_split(const ExInst<LitT, PtrT> &X, int64_t budget, int64_t spent, int depth, int index, int32_t *ubp, int ub0, int live,
-                                   float *model, uint32_t *row, int64_t *work_out, int *cost_out, int *improved_out)
-{
-    const int lane = (int)threadIdx.x;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    constexpr uint32_t UNIT = 3u;
-    constexpr int INF = 0x7fffffff;
-    int level = 0, tlen = 0, improved = 0, accepted = EXMS_NO_COST, seen = live;
-    int64_t work = 0;
-    int result = -1;
-    for (;;) {
-        seen = __shfl(seen, 0);
-        live = seen < live ? seen : live;
-        if (live == 0) { result = 1; break; }                       // some cube has satisfied every clause
-        if (spent + work >= budget) break;
-        if (lane == 0) seen = exms_load(ubp);                       // used at the next check: its latency lies behind the pass
-        // ---- one pass: falsified clauses, unit requests, the minimum width of the open clauses (a unit has width 1)
-        int reads = 0, cost = 0, unit = 0, wmin = INF;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a, distinct = 0;
-            uint32_t first = 0;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat) continue;
-            if (nfree == 0) { ++cost; continue; }
-            if (!distinct) { unit = 1; nfree = 1; atomicOr(&X.pend[first >> 1], 1u << (first & 1u)); }
-            wmin = nfree < wmin ? nfree : wmin;
-        }
-        work += ex_sum(reads);
-        cost = ex_sum(cost);
-        wmin = ex_min(wmin);
-        const bool any_unit = __ballot(unit) != 0ull;
-        int contra = 0;
-        if (any_unit) {
-            ex_sync<HBM>();
-            for (int v = lane; v < X.n; v += EX_NT) contra += (X.pend[v] & UNIT) == UNIT;
-            contra = ex_sum(contra);
-        }
-        const int rule = level < depth ? ub0 : live;
-        bool prune = cost + contra >= live;
-        if (!prune && cost == rule - 1 && any_unit) {
-            // leaving any unit out reaches rule >= live: the pending set is assigned (no variable is asked for twice: that was pruned)
-            for (int base = 0; base < X.n; base += EX_NT) {
-                const int v = base + lane;
-                const uint32_t word = v < X.n ? X.pend[v] : 0u;
-                const uint32_t bits = word & UNIT;
-                const unsigned long long mask = __ballot(bits != 0u);
-                if (bits) {
-                    X.pend[v] = word & ~UNIT;
-                    X.val[v] = (bits & 1u) ? 1 : 2;
-                    X.trail[tlen + __popcll(mask & below)] = v;
-                }
-                tlen += __popcll(mask);
-            }
-            ex_sync<HBM>();
-            continue;
-        }
-        if (any_unit) {
-            // every other path drops the unit requests
-            for (int v = lane; v < X.n; v += EX_NT) { const uint32_t word = X.pend[v]; if (word & UNIT) X.pend[v] = word & ~UNIT; }
-            ex_sync<HBM>();
-        }
-        if (!prune && wmin == INF) {
-            // a leaf below live.  Inside the prefix every cube with these levels' bits arrives here: the one whose remaining bits are 0
-            // takes it, the others end (every open level is pinned) with nothing credited
-            if (level >= depth || (index & ((1 << (depth - level)) - 1)) == 0) {
-                int old = 0;
-                if (lane == 0) old = atomicMin(ubp, cost);
-                old = __shfl(old, 0);
-                if (old > cost) {
-                    // accepted: the assignment of this cost, unassigned variables false
-                    if (model) {
-                        for (int v = lane; v < X.n; v += EX_NT) model[v] = X.val[v] == 1 ? 1.0f : 0.0f;
-                    } else {
-                        for (int base = 0; base < X.n; base += EX_NT) {
-                            const int v = base + lane;
-                            const unsigned long long mask = __ballot(v < X.n && X.val[v] == 1);
-                            if (lane == 0) {
-                                row[base >> 5] = (uint32_t)mask;
-                                if (base + 32 < X.n) row[(base >> 5) + 1] = (uint32_t)(mask >> 32);
-                            }
-                        }
-                    }
-                    accepted = cost;
-                    ++improved;
-                    live = cost;
-                } else {
-                    live = old;                                     // another cube was there first
-                }
-            }
-            prune = true;
-        }
-        if (prune) {
-            // chronological backtracking, a copy of ex_search_min's block: a pinned level carries the flipped bit from the start; out of
-            // levels: the cube is exhausted
-            bool resumed = false;
-            while (level > 0) {
-                const uint32_t d = X.dvar[level];
-                const int v = (int)(d & 0x7fffffffu);
-                const int from = X.mark[level];
-                const uint32_t first = X.val[v];
-                ex_sync<HBM>();                                     // every lane has read the level before it is undone
-                for (int i = from + lane; i < tlen; i += EX_NT) X.val[X.trail[i]] = 0;
-                tlen = from;
-                if (!(d & 0x80000000u)) {
-                    ex_sync<HBM>();
-                    if (lane == 0) { X.dvar[level] = d | 0x80000000u; X.val[v] = (uint8_t)(3u - first); X.trail[tlen] = v; }
-                    ++tlen;
-                    ex_sync<HBM>();
-                    resumed = true;
-                    break;
-                }
-                --level;
-            }
-            if (!resumed) { result = 1; break; }
-            continue;
-        }
-        // ---- branching: ex_search_min's rule
-        reads = 0;
-        for (int c = lane; c < X.m; c += EX_NT) {
-            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
-            int nfree = 0, sat = 0, k = a, distinct = 0;
-            uint32_t first = 0;
-            for (; k < z; ++k) {
-                const uint32_t L = X.lit[k];
-                const uint32_t x = X.val[L >> 1];
-                if (x == 0u) { if (nfree == 0) first = L; else if (L != first) distinct = 1; ++nfree; }
-                else if (x == 1u + (L & 1u)) { sat = 1; ++k; break; }
-            }
-            reads += k - a;
-            if (sat || nfree == 0 || (distinct ? nfree : 1) != wmin) continue;
-            for (int j = a; j < z; ++j) {
-                const uint32_t L = X.lit[j];
-                if (X.val[L >> 1] == 0u) atomicAdd(&X.cnt[L], 1u);
-            }
-            reads += z - a;
-        }
-        work += ex_sum(reads);
-        ex_sync<HBM>();
-        unsigned long long best = 0ull;
-        for (int v = lane; v < X.n; v += EX_NT) {
-            const uint32_t p = X.cnt[2 * v], q = X.cnt[2 * v + 1];
-            if (p | q) {
-                X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
-                const bool pos = ((X.pend[v] >> EX_HINT_SHIFT) & 3u) == 1u;
-                const unsigned long long key = ((unsigned long long)(p + q) << 32) | ((unsigned long long)(0x7fffffffu - (uint32_t)v) << 1) |
-                                               (pos ? 1ull : 0ull);
-                best = key > best ? key : best;
-            }
-        }
-        best = ex_max64(best);
-        if (best == 0ull) break;            // unreachable (an open clause of width wmin has an unassigned literal); never index with it
-        const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
-        ++level;
-        const bool pinned = level <= depth;
-        const bool other = pinned && ((index >> (depth - level)) & 1) != 0;
-        const bool pos = ((best & 1ull) != 0ull) != other;
-        ex_sync<HBM>();
-        if (lane == 0) {
-            X.mark[level] = tlen; X.dvar[level] = (uint32_t)v | (pinned ? 0x80000000u : 0u); X.val[v] = pos ? 1 : 2; X.trail[tlen] = v;
-        }
-        ++tlen;
-        ex_sync<HBM>();
-    }
-    *work_out = work; *cost_out = accepted; *improved_out = improved;
-    return result;
-}
-
-// cube q = (instance I.b, index): load ub[b]; unless it is 0 already, copy the instance's literals in clause order, clear the state (pend
-// starts as the incumbent's codes) and search; then the cube's record.  Both arms end in the record and the barrier below.
-template <bool HBM, typename LitT, typename PtrT>
-__device__ void ex_solve_min_split(const ExmsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, PtrT *cptr_fill, uint32_t q, int depth, int index)
+__device__ void ex_solve_min_split(const ExmsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, uint32_t q, int depth, int index)
 {
     const int lane = (int)threadIdx.x;
     int live = 0;
-    if (lane == 0) live = exms_load(xp.ub + I.b);
+    if (lane == 0) live = ex_shared_load(xp.ub + I.b);
     live = __shfl(live, 0);
     int st = 1, cost = EXMS_NO_COST, improved = 0;
     int64_t work = 0;
     if (live != 0) {
-        if (cptr_fill) for (int c = lane; c <= I.m; c += EX_NT) cptr_fill[c] = (PtrT)I.f_ptr[c];
-        for (int k = lane; k < I.e; k += EX_NT) {
-            const int ed = I.f_edges[k];
-            X.lit[k] = (LitT)(((uint32_t)I.e_var[ed] << 1) | (I.sgn[ed] < 0 ? 1u : 0u));
-        }
+        ex_fill<HBM>(I, X);
         for (int v = lane; v < I.n; v += EX_NT) {
             const uint32_t code = (xp.hint && xp.hint[I.v0 + v] > 0.5f) ? 1u : 2u;          // NaN compares false
             X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
         }
         ex_sync<HBM>();
-        st = ex_search_min_split<HBM>(X, xp.budget, xp.chk[I.b], depth, index, xp.ub + I.b, xp.ub0[I.b], live,
+        st = ex_search_min<HBM, true>(X, xp.budget, ExCube<true>{depth, index, xp.chk[I.b], xp.ub + I.b, live}, xp.ub0[I.b],
                                       depth == 0 ? xp.model + I.v0 : (float *)nullptr, xp.rows + (size_t)q * (size_t)xp.words, &work, &cost,
                                       &improved);
     }
@@ -4006,29 +3282,11 @@ __global__ void __launch_bounds__(EX_NT) k_exact_min_split(PView pv, ExmsParams 
         if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
         q = __shfl(q, 0);
         if (q >= xp.total) break;
-        int lo = 0, hi = xp.B;                                      // cube_off[lo] <= q < cube_off[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (xp.cube_off[mid] <= (int64_t)q) lo = mid; else hi = mid;
-        }
+        const int lo = exs_instance(xp.cube_off, xp.B, q);
         const Inst I = load_inst(pv, lo);
         const int depth = (int)xp.du[lo], index = (int)((int64_t)q - xp.cube_off[lo]);
-        if (xp.route[lo]) {
-            ExInst<uint32_t, int32_t> X;
-            X.lit = xp.h_lit + I.e0; X.cptr = I.f_ptr;
-            X.val = xp.h_val + I.v0; X.pend = xp.h_pend + I.v0; X.cnt = xp.h_cnt + 2 * (size_t)I.v0; X.trail = xp.h_trail + I.v0;
-            X.mark = xp.h_mark + I.v0 + I.b; X.dvar = xp.h_dvar + I.v0 + I.b;
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve_min_split<true, uint32_t, int32_t>(xp, I, X, (int32_t *)nullptr, q, depth, index);
-        } else {
-            const ExLds L = ex_lds_layout(I.n, I.m, I.e);
-            ExInst<uint16_t, uint16_t> X;
-            X.lit = (uint16_t *)(ex_slab + L.lit); X.cptr = (const uint16_t *)(ex_slab + L.cptr);
-            X.val = ex_slab + L.val; X.pend = (uint32_t *)(ex_slab + L.pend); X.cnt = (uint32_t *)(ex_slab + L.cnt);
-            X.trail = (int32_t *)(ex_slab + L.trail); X.mark = (int32_t *)(ex_slab + L.mark); X.dvar = (uint32_t *)(ex_slab + L.dvar);
-            X.n = I.n; X.m = I.m; X.e = I.e;
-            ex_solve_min_split<false, uint16_t, uint16_t>(xp, I, X, (uint16_t *)(ex_slab + L.cptr), q, depth, index);
-        }
+        if (xp.route[lo]) ex_solve_min_split<true>(xp, I, ex_bind_hbm(xp.h, I), q, depth, index);
+        else ex_solve_min_split<false>(xp, I, ex_bind_lds(ex_slab, I), q, depth, index);
     }
 }
 
@@ -4069,102 +3327,42 @@ __global__ void __launch_bounds__(EX_NT) k_exact_min_split_finish(PView pv, Exms
     }
 }
 
-// fixed block of the call, once per problem, widest words first: chk [B] | cube_off [B+1] | info [4] | ub [B] | ub0 [B] | du [B] | route [B]
-struct ExmsFixed { int8_t *du; uint8_t *route; int32_t *ub, *ub0; int64_t *chk, *cube_off, *info; };
-
-inline ExmsFixed exms_fixed(const pdp_problem *p)
-{
-    const size_t B = p->B;
-    ExmsFixed F;
-    char *q = p->exms_blob;
-    F.chk = (int64_t *)q;       q += B * 8;
-    F.cube_off = (int64_t *)q;  q += (B + 1) * 8;
-    F.info = (int64_t *)q;      q += 4 * 8;
-    F.ub = (int32_t *)q;        q += B * 4;
-    F.ub0 = (int32_t *)q;       q += B * 4;
-    F.du = (int8_t *)q;         q += B;
-    F.route = (uint8_t *)q;
-    return F;
-}
-
 int exms_launch(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, int32_t *cost, float *model, int64_t *work,
                 int32_t *improvements, int32_t *first, int8_t *depth_used, void *stream)
 {
     { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
     const hipStream_t st = ST(stream);
-    const size_t V = p->V, E = p->E, B = p->B;
-    if (!p->exms_blob) {
-        const int st_ = pdp_dev_alloc((void **)&p->exms_blob, (B * 8 + (B + 1) * 8 + 32 + 2 * B * 4 + 2 * B + 15) & ~(size_t)15);
+    const size_t B = p->B;
+    ExsFixed F;
+    int64_t info[EXS_INFO];
+    {
+        const int st_ = exs_setup(p, p->exms, "pdp_exact_min_unsat_split", depth, depth_used, 0x7fffffff, 0, 0, st, F, info);
         if (st_ != PDP_OK) return st_;
-    }
-    const ExmsFixed F = exms_fixed(p);
-    p->exms_total = 0;                                               // no records to hand out until this call has launched its cubes
-    hipLaunchKernelGGL(k_exact_split_setup, dim3(1), dim3(EXS_SETUP_NT), 0, st, make_view(p), depth, p->ex_order, p->ex_nbig, F.du, F.route,
-                       F.cube_off, depth_used, F.info);
-    PDP_LAUNCH_CHECK();
-    int64_t info[4];
-    PDP_HIP_CHECK(hipMemcpyAsync(info, F.info, sizeof(info), hipMemcpyDeviceToHost, st));
-    PDP_HIP_CHECK(hipStreamSynchronize(st));                        // the cube count sizes the records and the grid
-    if (info[0] != EXS_NONE) {
-        pdp_set_error("pdp_exact_min_unsat_split: the depth of instance %lld is not in 0 .. %d", (long long)info[0], EXS_MAX_DEPTH);
-        return PDP_ERR_INVALID;
-    }
-    if (info[1] != EXS_NONE) {
-        pdp_set_error("pdp_exact_min_unsat_split: more than 2^22 cubes in one call (reached at instance %lld); lower the depths or split the "
-                      "batch", (long long)info[1]);
-        return PDP_ERR_INVALID;
     }
     const size_t total = (size_t)info[2], words = ((size_t)info[3] + 31) / 32;
-    // per-cube records: work [total] | cost [total] | improvements [total] | rows [total][words] | status [total]; grown on demand
-    const size_t need = (total * 16 + total * words * 4 + total + 15) & ~(size_t)15;
-    if (need > p->exms_cube_bytes) {
-        if (p->exms_cubes) { pdp_dev_free(p->exms_cubes); p->exms_cubes = nullptr; p->exms_cube_bytes = 0; }
-        const int st_ = pdp_dev_alloc((void **)&p->exms_cubes, need);
-        if (st_ != PDP_OK) return st_;
-        p->exms_cube_bytes = need;
-    }
+    // per-cube records: work [total] | cost [total] | improvements [total] | rows [total][words] | status [total]
+    { const int st_ = exs_records(p->exms, total * 16 + total * words * 4 + total); if (st_ != PDP_OK) return st_; }
     ExmsParams xp;
     xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_DEFAULT_BUDGET;
-    xp.hint = hint; xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off; xp.chk = F.chk; xp.ub0 = F.ub0; xp.ub = F.ub;
-    xp.cube_work = (int64_t *)p->exms_cubes;
-    xp.cube_cost = (int32_t *)(p->exms_cubes + total * 8);
-    xp.cube_imp = (int32_t *)(p->exms_cubes + total * 12);
-    xp.rows = (uint32_t *)(p->exms_cubes + total * 16);
-    xp.cube_status = (int8_t *)(p->exms_cubes + total * 16 + total * words * 4);
+    xp.budget = ex_budget(budget);
+    xp.hint = hint; xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off; xp.chk = F.chk; xp.ub0 = F.word0; xp.ub = F.word;
+    xp.cube_work = (int64_t *)p->exms.cubes;
+    xp.cube_cost = (int32_t *)(p->exms.cubes + total * 8);
+    xp.cube_imp = (int32_t *)(p->exms.cubes + total * 12);
+    xp.rows = (uint32_t *)(p->exms.cubes + total * 16);
+    xp.cube_status = (int8_t *)(p->exms.cubes + total * 16 + total * words * 4);
     xp.words = (int)words;
     xp.model = model;
-    if (p->ex_h_lit) {
-        char *q = (char *)p->ex_h_lit;
-        xp.h_lit = (uint32_t *)q;            q += E * 4;
-        xp.h_pend = (uint32_t *)q;           q += V * 4;
-        xp.h_cnt = (uint32_t *)q;            q += V * 8;
-        xp.h_trail = (int32_t *)q;           q += V * 4;
-        xp.h_mark = (int32_t *)q;            q += (V + B) * 4;
-        xp.h_dvar = (uint32_t *)q;           q += (V + B) * 4;
-        xp.h_val = (uint8_t *)q;
-    } else {
-        xp.h_lit = nullptr; xp.h_pend = nullptr; xp.h_cnt = nullptr; xp.h_trail = nullptr; xp.h_mark = nullptr; xp.h_dvar = nullptr;
-        xp.h_val = nullptr;
-    }
+    xp.h = ex_hbm(p);
     const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
-    hipLaunchKernelGGL(k_exact_min_split_check, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), hint, F.chk, F.ub0, F.ub, model);
+    hipLaunchKernelGGL(k_exact_min_split_check, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), hint, F.chk, F.word0, F.word, model);
     PDP_LAUNCH_CHECK();
-    const int lds = (int)p->ex_lds_bytes;
-    if (lds > 64 * 1024) PDP_HIP_CHECK(hipFuncSetAttribute((const void *)k_exact_min_split, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_exact_min_split, EX_NT, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int64_t grid = ex_grid(std::min<int64_t>((int64_t)total, (int64_t)pdp_device_cus() * per_cu));
-    PDP_HIP_CHECK(hipMemsetAsync(p->ex_next, 0, 4, st));
-    hipLaunchKernelGGL(k_exact_min_split, dim3((unsigned)grid), dim3(EX_NT), (size_t)lds, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
+    { const int st_ = ex_launch_persistent(p, k_exact_min_split, xp, (int64_t)total, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
     hipLaunchKernelGGL(k_exact_min_split_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp, status, cost, work, improvements,
                        first);
     PDP_LAUNCH_CHECK();
-    p->ex_last_grid = (int32_t)grid;
-    p->exms_total = (int64_t)total;
-    p->exms_status_off = total * 16 + total * words * 4;
-    p->exms_words = words;
+    p->exms.total = (int64_t)total;
+    p->exms.status_off = total * 16 + total * words * 4;
     return PDP_OK;
 }
 
@@ -4289,12 +3487,12 @@ extern "C" int pdp_exact_solve_split(pdp_problem *p, const float *hint, const in
 extern "C" int pdp_exact_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int64_t *cube_work, void *stream)
 {
     PDP_REQUIRE(p && cube_off && cube_status && cube_work, "NULL argument");
-    PDP_REQUIRE(p->exs_total > 0, "pdp_exact_split_cubes: no pdp_exact_solve_split call on this problem yet");
-    const size_t B = p->B, total = (size_t)p->exs_total;
-    const ExsFixed F = exs_fixed(p);
+    PDP_REQUIRE(p->exs.total > 0, "pdp_exact_split_cubes: no pdp_exact_solve_split call on this problem yet");
+    const size_t B = p->B, total = (size_t)p->exs.total;
+    const ExsFixed F = exs_fixed(p, p->exs);
     PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exs_cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exs_cubes + p->exs_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exs.cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exs.cubes + p->exs.status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
     return PDP_OK;
 }
 
@@ -4313,14 +3511,14 @@ extern "C" int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, in
                                            int64_t *cube_leaves, void *stream)
 {
     PDP_REQUIRE(p && cube_off && cube_status && cube_count && cube_work && cube_leaves, "NULL argument");
-    PDP_REQUIRE(p->exns_total > 0, "pdp_exact_count_split_cubes: no pdp_exact_count_split call on this problem yet");
-    const size_t B = p->B, total = (size_t)p->exns_total;
-    const ExnsFixed F = exns_fixed(p);
+    PDP_REQUIRE(p->exns.total > 0, "pdp_exact_count_split_cubes: no pdp_exact_count_split call on this problem yet");
+    const size_t B = p->B, total = (size_t)p->exns.total;
+    const ExsFixed F = exs_fixed(p, p->exns);
     PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_count, p->exns_cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exns_cubes + total * 8, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, p->exns_cubes + total * 16, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exns_cubes + p->exns_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_count, p->exns.cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exns.cubes + total * 8, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, p->exns.cubes + total * 16, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exns.cubes + p->exns.status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
     return PDP_OK;
 }
 
@@ -4339,14 +3537,14 @@ extern "C" int pdp_exact_min_unsat_split_cubes(pdp_problem *p, int64_t *cube_off
                                                int32_t *cube_improvements, void *stream)
 {
     PDP_REQUIRE(p && cube_off && cube_status && cube_cost && cube_work && cube_improvements, "NULL argument");
-    PDP_REQUIRE(p->exms_total > 0, "pdp_exact_min_unsat_split_cubes: no pdp_exact_min_unsat_split call on this problem yet");
-    const size_t B = p->B, total = (size_t)p->exms_total;
-    const ExmsFixed F = exms_fixed(p);
+    PDP_REQUIRE(p->exms.total > 0, "pdp_exact_min_unsat_split_cubes: no pdp_exact_min_unsat_split call on this problem yet");
+    const size_t B = p->B, total = (size_t)p->exms.total;
+    const ExsFixed F = exs_fixed(p, p->exms);
     PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exms_cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_cost, p->exms_cubes + total * 8, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_improvements, p->exms_cubes + total * 12, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
-    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exms_cubes + p->exms_status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exms.cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_cost, p->exms.cubes + total * 8, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_improvements, p->exms.cubes + total * 12, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exms.cubes + p->exms.status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
     return PDP_OK;
 }
 

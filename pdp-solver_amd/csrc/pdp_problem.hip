@@ -347,12 +347,10 @@ extern "C" int pdp_problem_destroy(pdp_problem *p)
     if (p->exc_blob) pdp_dev_free(p->exc_blob);
     if (p->ext_blob) pdp_dev_free(p->ext_blob);
     if (p->exn_blob) pdp_dev_free(p->exn_blob);
-    if (p->exs_blob) pdp_dev_free(p->exs_blob);
-    if (p->exs_cubes) pdp_dev_free(p->exs_cubes);
-    if (p->exns_blob) pdp_dev_free(p->exns_blob);
-    if (p->exns_cubes) pdp_dev_free(p->exns_cubes);
-    if (p->exms_blob) pdp_dev_free(p->exms_blob);
-    if (p->exms_cubes) pdp_dev_free(p->exms_cubes);
+    for (pdp_exact_cubes *s : {&p->exs, &p->exns, &p->exms}) {
+        if (s->blob) pdp_dev_free(s->blob);
+        if (s->cubes) pdp_dev_free(s->cubes);
+    }
     if (p->exr_blob) pdp_dev_free(p->exr_blob);
     if (p->ws_side_stream) { (void)hipStreamDestroy(p->ws_side_stream); for (int i = 0; i < 2; ++i) (void)hipEventDestroy(p->ws_side_ev[i]); }
     if (p->res_side_stream) { (void)hipStreamDestroy(p->res_side_stream); for (int i = 0; i < 2; ++i) (void)hipEventDestroy(p->res_side_ev[i]); }
