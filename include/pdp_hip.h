@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -434,6 +434,48 @@ int pdp_exact_min_unsat(pdp_problem *p, const float *hint, int64_t budget, int8_
 int pdp_exact_count(pdp_problem *p, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work, int64_t *leaves,
                     void *stream);
 
+/* The exact solution mass of a soft prediction: Z(p) = the sum over the models x of the instance of prod_v (x_v ? p_v : 1 - p_v), the
+ * probability that rounding every variable independently with the predicted probability gives a model (plain Python, normative:
+ * tests/exact_mass_model.py).  pdp_exact_count's search with a weight per literal.  weights [V] (device float32, the
+ * prediction's own dtype): p_v = (double)weights[v]; the positive literal weighs p_v, the negative one 1.0 - p_v, computed in double
+ * wherever it is used; an unassigned variable contributes the factor 1.  Outputs per instance: status = 1, the search is complete and
+ * mass [B] = Z, or -1, the budget ran out, mass covers the part of the tree visited so far and open_mass [B] the part not yet visited,
+ * or -2, the instance has more than 1023 variables, or -3, one of its weights is NaN or outside [0, 1]; -2 and -3 are not searched and
+ * every other output of the instance is 0; never 0: an unsatisfiable instance is status 1 with mass 0.  true_mass [V] = the part of
+ * mass with the variable true; work [B] and leaves [B] (each may be NULL) as pdp_exact_count's.  All new arithmetic is IEEE double
+ * add, subtract and multiply, in this order:
+ *   State.  pdp_exact_count's (Z in the place of count), plus mass = 1.0, the product of the weights of everything on the trail, and
+ *      pre[level], mass before the level's decision was applied.
+ *   Assigning a pass's pending set.  The new trail entries (in variable order) are taken 64 consecutive ones at a time; a chunk's
+ *      weights, 1.0 in the lanes without an entry, are multiplied by the xor butterfly 32, 16, 8, 4, 2, 1 (x = x * x[lane ^ o]; a
+ *      multiplication commutes, so every lane ends with the same bits); then mass = mass * chunk, chunks in ascending order.
+ *   Zero mass.  Once the pending set is assigned and multiplied in (also in a pass that assigned nothing), mass == 0.0 makes the state
+ *      a conflict: no leaf is credited, and backtracking runs as after a conflict.  Weights are at most 1, so a prefix of mass 0 stays
+ *      0: the rule, underflow included, changes no bit of mass, true_mass or open_mass; it only lowers work (and leaves of mass 0).
+ *   Leaf.  Z = Z + mass, leaves + 1, then as after a conflict.
+ *   Decision.  The variable is pdp_exact_count's.  pre[level] = mass, snap[level] = Z; the first polarity is the heavier literal (true
+ *      if p_v > 0.5, false if p_v < 0.5, pdp_exact_count's rule at exactly 0.5); then mass = mass * (the decided literal's weight).
+ *   Flip.  snap[level] = Z, mass = pre[level] * (the other literal's weight).  If that is 0.0 the flipped state is a conflict at once,
+ *      before any pass: backtracking goes on with this level (a subtree without mass is pruned for free, so a 0 / 1 prediction costs
+ *      one descent).
+ *   Crediting.  pdp_exact_count's rule with d = Z - snap[level], the end flush included.
+ *   End.  true_mass[v] = T[v] + (Z - T[v] - F[v]) * p_v.  open_mass = 0.0 at status 1.  At status -1 the budget check fired before a
+ *      pass, so the current node is unresolved: sequentially, for the levels 1 .. level in ascending order, a level whose decision is
+ *      not yet flipped adds pre[level] * (the untried literal's weight); then open_mass = open_mass + mass.
+ * The passes, the budget check before every pass (budget <= 0: PDP_EXACT_DEFAULT_BUDGET), work < budget + 3 * (edges of the instance)
+ * and leaves are pdp_exact_count's.  Consequences: the true Z lies in [mass, mass + open_mass] up to rounding; mass never falls as the
+ * budget rises; with all weights 0.5 the search is pdp_exact_count's state for state -- mass * 2^n == count, true_mass * 2^n ==
+ * true_count, work and leaves are equal; with 0 / 1 weights mass is 1.0 if that assignment is a model and 0.0 if not, and leaves <= 1.
+ * Every output is a function of the instance, its weights and the budget alone: mass, Z, snap and pre are uniform over the wave, T[u]
+ * and F[u] are updated by the one lane that holds u's trail slot, and there is no atomic and no reduction of doubles across lanes other
+ * than the stated butterfly; the default and the fast build give the same bits.
+ * NULL weights or outputs (other than work and leaves) -> PDP_ERR_INVALID before any launch; R != 1 -> PDP_ERR_UNSUPPORTED.  Same stream
+ * rules; routing and working arrays are pdp_exact_solve's, shared with it; the LDS slab is pdp_exact_solve's plus 40 n + 16 bytes of
+ * the kernel's own for snap, pre, T, F and the weights as doubles (at most 40 936 bytes), in HBM on the HBM route, in a block that only
+ * this call uses, T being true_mass itself. */
+int pdp_exact_mass(pdp_problem *p, const float *weights, int64_t budget, int8_t *status, double *mass, double *true_mass,
+                   double *open_mass, int64_t *work, int64_t *leaves, void *stream);
+
 /* pdp_exact_solve_hinted with the search of every instance spread over 2^depth[b] waves (plain Python, normative:
  * tests/exact_split_model.py).  The deciding search is a deterministic depth-first tree; a cube is a prefix of it: cube
  * `index` of the 2^depth cubes of an instance is that search, without its check pass, where the decision of every level L <= depth is
@@ -578,7 +620,7 @@ int pdp_exact_min_unsat_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *c
                                     int32_t *cube_improvements, void *stream);
 
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split and pdp_exact_min_unsat_split (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split and pdp_exact_min_unsat_split (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

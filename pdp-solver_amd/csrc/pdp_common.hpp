@@ -157,6 +157,9 @@ struct pdp_problem {
     int ext_ready, ext_nbig; size_t ext_lds_bytes; char *ext_blob;
     // counting complete solver (pdp_exact.hip::exn_prepare): ex_prepare's routing; the slab bytes of its own layout and the HBM route's F and snap
     int exn_ready; size_t exn_lds_bytes; char *exn_blob;
+    // weighted counting complete solver (pdp_exact.hip::exz_prepare): ex_prepare's routing; the slab bytes of its own layout and the HBM
+    // route's F, snap, pre and weights, a block of its own so that a count and a mass call on one handle never meet
+    int exz_ready; size_t exz_lds_bytes; char *exz_blob;
     // the split calls of the complete solver, one pdp_exact_cubes each: exs the deciding one (pdp_exact.hip::exs_launch; records: work,
     // model rows, status), exns the counting one (exns_launch, on exn_prepare's routing and slab; records: count, work, leaves,
     // true_count rows, status), exms the optimising one (exms_launch; records: work, cost, improvements, model rows, status)
@@ -164,7 +167,7 @@ struct pdp_problem {
     // k-th models of the counting search (pdp_exact.hip::exr_launch): ex_prepare's routing and slab; the rows' byte offsets [B+1] and the
     // validation words of the last call, one block allocated on first use
     char *exr_blob;
-    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_min, k_exact_count, k_exact_learn, k_exact_check, k_exact_trim, k_exact_split, k_exact_count_split, k_exact_min_split or k_exact_models on this problem (0: none yet)
+    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_min, k_exact_count, k_exact_learn, k_exact_check, k_exact_trim, k_exact_split, k_exact_count_split, k_exact_min_split, k_exact_models or k_exact_mass on this problem (0: none yet)
     uint32_t *team_ws;          // barrier counters and reduction mailboxes of the workgroup teams (k_sp_solve<NT, true>)
     hipStream_t res_side_stream; hipEvent_t res_side_ev[2];   // the big instances' launches overlap the LDS-resident kernel on a stream of their own
     float *nws[4]; size_t nws_floats[4];             // neural workspaces (grow on demand)

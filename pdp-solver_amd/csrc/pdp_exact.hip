@@ -32,6 +32,7 @@
 // same way; its cubes share nothing at all, and a second kernel adds their counts up in cube order.  pdp_exact_models_at (last) walks
 // the counting search's leaves with a cursor over given ranks and writes the models of those ranks, one wave per instance again.
 // pdp_exact_min_unsat_split (after it) cuts the branch and bound into cubes that share ub[b], the best cost any of them has found.
+// pdp_exact_mass (the last kernel) is the counting search under a product prior: a weight per literal, a two-sided bracket at the budget.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -189,7 +190,8 @@ __device__ __forceinline__ unsigned long long ex_max64(unsigned long long x)
 constexpr uint32_t EX_HINT_SHIFT = 8;            // bits 8-9 of pend[v]: the hint code of v (0 none, 1 true, 2 false); bits 0-1 are the unit bits
 
 // ---- the blocks every DPLL search below is built from, each written once ---------------------------------------------------------------
-// ex_search (deciding), ex_search_min (optimising), ex_search_count (counting) and ex_search_rank (k-th model) share them; the learning
+// ex_search (deciding), ex_search_min (optimising), ex_search_count (counting), ex_search_rank (k-th model) and ex_search_mass (weighted
+// counting) share them; the learning
 // search, the checker and the trimmer further down keep state layouts and passes of their own.
 
 // What one lane met in a unit-propagation pass over its clauses.
@@ -3366,6 +3368,279 @@ int exms_launch(pdp_problem *p, const float *hint, const int8_t *depth, int64_t 
     return PDP_OK;
 }
 
+// ---- pdp_exact_mass: the exact solution mass of a soft prediction, the counting search under a product prior ---------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_mass_model.py).  ex_search_count's passes, backtracking
+// and crediting (ExnCredit on the running sum Z) with a weight per literal: `mass` is the product of the weights of the trail, uniform
+// over the wave; pre[level] is its value before the level's decision, so a flip restores it with one multiplication.  The first polarity
+// of a decision comes from the hint code in bits 8-9 of pend[v] (1: p > 0.5, 2: p < 0.5, 0: the count's rule), which is why the shared
+// blocks run in their HINT forms here.  On the LDS route snap, pre, T, F and the weights as doubles follow ex_lds_layout's slab (40 n + 16
+// bytes); on the HBM route T is the instance's slice of true_mass and the rest a block of this call's own on the handle (exz_blob).
+struct ExzLds { size_t snap, pre, T, F, w, bytes; };
+
+// ex_lds_layout's slab (a multiple of 16 bytes), then the doubles
+__host__ __device__ inline ExzLds exz_lds_layout(int n, int m, int e)
+{
+    ExzLds L;
+    size_t o = ex_lds_layout(n, m, e).bytes;
+    L.snap = o; o += 8 * ((size_t)n + 1);
+    L.pre = o;  o += 8 * ((size_t)n + 1);
+    L.T = o;    o += 8 * (size_t)n;
+    L.F = o;    o += 8 * (size_t)n;
+    L.w = o;    o += 8 * (size_t)n;
+    L.bytes = (o + 15) & ~(size_t)15;
+    return L;
+}
+
+struct ExzParams {
+    const int32_t *order;       // as ExParams
+    int nbig, B;
+    uint32_t *next;
+    int64_t budget;
+    const float *weights;       // [V] the prediction
+    int8_t *status; double *mass; double *true_mass; double *open_mass; int64_t *work; int64_t *leaves;
+    ExHbm h;
+    double *h_F, *h_w;          // [V]   (HBM route; its T is true_mass)
+    double *h_snap, *h_pre;     // [V+B] (instance b at v0 + b: n+1 entries)
+};
+
+// the count's accumulators, plus pre [n+1] and the weights as doubles [n]
+struct ExzAcc { ExnAcc a; double *pre, *w; };
+
+__device__ __forceinline__ ExzAcc exz_bind_hbm(const ExzParams &xp, const Inst &I)
+{
+    ExzAcc A;
+    A.a = exn_bind_hbm(xp.true_mass, xp.h_F, xp.h_snap, I);
+    A.pre = xp.h_pre + I.v0 + I.b; A.w = xp.h_w + I.v0;
+    return A;
+}
+
+__device__ __forceinline__ ExzAcc exz_bind_lds(unsigned char *slab, const Inst &I)
+{
+    const ExzLds N = exz_lds_layout(I.n, I.m, I.e);
+    ExzAcc A;
+    A.a.T = (double *)(slab + N.T); A.a.F = (double *)(slab + N.F); A.a.snap = (double *)(slab + N.snap);
+    A.pre = (double *)(slab + N.pre); A.w = (double *)(slab + N.w);
+    return A;
+}
+
+// the weight of variable v's literal that the value x (1 true, 2 false) makes true
+__device__ __forceinline__ double exz_omega(const ExzAcc &A, int v, uint32_t x)
+{
+    const double p = A.w[v];
+    return x == 1u ? p : 1.0 - p;
+}
+
+// The product of the weights of trail[from .. tlen), 64 consecutive entries at a time: lanes without an entry hold 1.0, the xor butterfly
+// leaves the same bits in every lane (a multiplication commutes), and the chunks are multiplied into `mass` in ascending order.
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ double exz_extend(const ExInst<LitT, PtrT> &X, const ExzAcc &A, int from, int tlen, double mass)
+{
+    for (int base = from; base < tlen; base += EX_NT) {
+        const int i = base + (int)threadIdx.x;
+        double x = 1.0;
+        if (i < tlen) { const int u = X.trail[i]; x = exz_omega(A, u, X.val[u]); }
+        for (int o = 32; o > 0; o >>= 1) x = x * __shfl_xor(x, o);
+        mass = mass * x;
+    }
+    return mass;
+}
+
+// The mass of the part of the tree not yet visited when the budget check fires: the untried halves of the open levels, oldest first,
+// then the current node.  Every lane runs the same sequential sum on the same addresses; it runs once per search, behind the loop.
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ double exz_open(const ExInst<LitT, PtrT> &X, const ExzAcc &A, int level, double mass)
+{
+    double open = 0.0;
+    for (int l = 1; l <= level; ++l) {
+        const uint32_t d = X.dvar[l];
+        if (d & 0x80000000u) continue;
+        const int v = (int)d;
+        open = open + A.pre[l] * exz_omega(A, v, 3u - X.val[v]);
+    }
+    return open + mass;
+}
+
+// The weighted counting search of one instance by the calling wave.  Returns 1 (complete) or -1 (budget spent); T and F hold every
+// level's credit, *z_out the mass of the leaves met and *open_out the mass not yet visited (0.0 at 1).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_mass(const ExInst<LitT, PtrT> &X, const ExzAcc &A, int64_t budget, int64_t *work_out, double *z_out, double *open_out,
+                              int64_t *leaves_out)
+{
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0;
+    int64_t work = 0, leaves = 0;
+    double Z = 0.0, mass = 1.0;
+    int result = -1;
+    ExnCredit credit{A.a, Z, 0.0};
+    for (;;) {
+        if (work >= budget) break;
+        const ExPass P = ex_propagate(X);
+        work += ex_sum(P.reads);
+        bool any_conflict = __ballot(P.conflict) != 0ull;
+        const bool any_unit = __ballot(P.unit) != 0ull;
+        if (any_unit) {
+            ex_sync<HBM>();
+            const int from = tlen;
+            const bool both = ex_assign_pending<HBM, true>(X, tlen);
+            any_conflict = any_conflict || both;
+            mass = exz_extend(X, A, from, tlen, mass);
+        }
+        any_conflict = any_conflict || mass == 0.0;                 // a prefix without mass has no leaf that counts
+        int wmin = INF;
+        if (!any_conflict) {
+            if (any_unit) continue;
+            wmin = ex_min(P.wmin);
+            if (wmin == INF) {
+                // a leaf: every clause has a true literal and the unassigned variables contribute a factor 1; then as after a conflict
+                Z = Z + mass;
+                ++leaves;
+                any_conflict = true;
+            }
+        }
+        if (any_conflict) {
+            // a flip to a literal of weight 0 is a conflict at once, without a pass: the level is undone by the next round
+            bool resumed;
+            do {
+                resumed = ex_backtrack<HBM>(X, level, tlen, credit);
+                if (!resumed) break;
+                const int v = (int)(X.dvar[level] & 0x7fffffffu);   // the flipped decision: behind ex_backtrack's last barrier
+                mass = A.pre[level] * exz_omega(A, v, X.val[v]);
+            } while (mass == 0.0);
+            if (!resumed) { result = 1; break; }
+            continue;
+        }
+        const unsigned long long best = ex_branch<HBM, EX_PHASE_HINT>(X, wmin, work);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        // pre of the level ex_decide opens: nothing reads it before the barriers of ex_decide
+        if (threadIdx.x == 0) A.pre[level + 1] = mass;
+        ex_decide<HBM, false>(X, ExCube<false>{}, best, level, tlen, credit);
+        mass = mass * exz_omega(A, (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull)), (best & 1ull) ? 1u : 2u);
+    }
+    *open_out = result == 1 ? 0.0 : exz_open(X, A, level, mass);
+    // the end: every open level is flushed, the newest first, as in ex_search_count
+    for (; level >= 0; --level) {
+        const int from = level > 0 ? X.mark[level] : 0;
+        exn_credit(X, A.a, from, tlen, Z - A.a.snap[level]);
+        tlen = from;
+    }
+    *work_out = work; *z_out = Z; *leaves_out = leaves;
+    return result;
+}
+
+// copy the instance's literals in clause order and its weights as doubles, clear the state, search, write the results
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_mass(const ExzParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExzAcc A)
+{
+    const int lane = (int)threadIdx.x;
+    ex_fill<HBM>(I, X);
+    for (int v = lane; v < I.n; v += EX_NT) {
+        const float h = xp.weights[I.v0 + v];
+        const uint32_t code = h > 0.5f ? 1u : (h < 0.5f ? 2u : 0u);
+        X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        A.a.T[v] = 0.0; A.a.F[v] = 0.0; A.w[v] = (double)h;
+    }
+    if (lane == 0) A.a.snap[0] = 0.0;
+    ex_sync<HBM>();
+    int64_t work = 0, leaves = 0;
+    double Z = 0.0, open = 0.0;
+    const int st = ex_search_mass<HBM>(X, A, xp.budget, &work, &Z, &open, &leaves);
+    ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
+    for (int v = lane; v < I.n; v += EX_NT) {
+        const double t = A.a.T[v];
+        xp.true_mass[I.v0 + v] = t + (Z - t - A.a.F[v]) * A.w[v];
+    }
+    if (lane == 0) {
+        xp.status[I.b] = (int8_t)st;
+        xp.mass[I.b] = Z;
+        xp.open_mass[I.b] = open;
+        if (xp.work) xp.work[I.b] = work;
+        if (xp.leaves) xp.leaves[I.b] = leaves;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_mass(PView pv, ExzParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        // not searched: more than 1023 variables (-2, as the count), or a weight that is NaN or outside [0, 1] (-3), decided for the
+        // whole wave by a ballot before anything is bound
+        int refused = I.n > EXN_MAX_N ? -2 : 0;
+        if (!refused) {
+            int bad = 0;
+            for (int v = (int)threadIdx.x; v < I.n; v += EX_NT) { const float h = xp.weights[I.v0 + v]; bad |= !(h >= 0.0f && h <= 1.0f); }
+            if (__ballot(bad) != 0ull) refused = -3;
+        }
+        if (refused) {
+            // as k_exact_count's arm: it ends in the barrier every arm of the loop ends in and falls through to the end of the loop
+            // body, so the wave is whole again before the shuffle that hands out the next instance
+            for (int v = (int)threadIdx.x; v < I.n; v += EX_NT) xp.true_mass[I.v0 + v] = 0.0;
+            if (threadIdx.x == 0) {
+                xp.status[I.b] = (int8_t)refused;
+                xp.mass[I.b] = 0.0;
+                xp.open_mass[I.b] = 0.0;
+                if (xp.work) xp.work[I.b] = 0;
+                if (xp.leaves) xp.leaves[I.b] = 0;
+            }
+            ex_sync<false>();
+        } else if (i < xp.nbig) {
+            ex_solve_mass<true>(xp, I, ex_bind_hbm(xp.h, I), exz_bind_hbm(xp, I));
+        } else {
+            ex_solve_mass<false>(xp, I, ex_bind_lds(ex_slab, I), exz_bind_lds(ex_slab, I));
+        }
+    }
+}
+
+// ex_prepare's routing and order, plus what the mass kernel needs of its own: the largest slab of its layout over the LDS-routed
+// instances it may search (n <= 1023), and F [V] | w [V] | snap [V+B] | pre [V+B] for the HBM route.  Once per problem.
+int exz_prepare(pdp_problem *p)
+{
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    if (p->exz_ready) return PDP_OK;
+    const size_t B = p->B, V = p->V;
+    std::vector<int32_t> v0(B + 1), f0(B + 1), e0(B + 1);
+    PDP_HIP_CHECK(hipMemcpy(v0.data(), p->inst_v0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(f0.data(), p->inst_f0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    PDP_HIP_CHECK(hipMemcpy(e0.data(), p->inst_e0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    size_t lds = 0;
+    for (size_t b = 0; b < B; ++b) {
+        const int n = v0[b + 1] - v0[b], m = f0[b + 1] - f0[b], e = e0[b + 1] - e0[b];
+        if (n <= EXN_MAX_N && ex_fits_lds(n, m, e)) lds = std::max(lds, exz_lds_layout(n, m, e).bytes);
+    }
+    p->exz_lds_bytes = lds;
+    p->exz_blob = nullptr;
+    if (p->ex_nbig > 0) {
+        const int st_ = pdp_dev_alloc((void **)&p->exz_blob, (2 * V * 8 + 2 * (V + B) * 8 + 15) & ~(size_t)15);
+        if (st_ != PDP_OK) return st_;
+    }
+    p->exz_ready = 1;
+    return PDP_OK;
+}
+
+int exz_launch(pdp_problem *p, const float *weights, int64_t budget, int8_t *status, double *mass, double *true_mass, double *open_mass,
+               int64_t *work, int64_t *leaves, void *stream)
+{
+    { const int st_ = exz_prepare(p); if (st_ != PDP_OK) return st_; }
+    ExzParams xp;
+    xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
+    xp.budget = ex_budget(budget);
+    xp.weights = weights;
+    xp.status = status; xp.mass = mass; xp.true_mass = true_mass; xp.open_mass = open_mass; xp.work = work; xp.leaves = leaves;
+    xp.h = ex_hbm(p);
+    const size_t V = p->V, B = p->B;
+    double *blk = (double *)p->exz_blob;
+    xp.h_F = blk ? blk : nullptr;
+    xp.h_w = blk ? blk + V : nullptr;
+    xp.h_snap = blk ? blk + 2 * V : nullptr;
+    xp.h_pre = blk ? blk + 2 * V + (V + B) : nullptr;
+    return ex_launch_persistent(p, k_exact_mass, xp, (int64_t)p->B, p->exz_lds_bytes, ST(stream));
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -3408,6 +3683,17 @@ extern "C" int pdp_exact_count(pdp_problem *p, int64_t budget, int8_t *status, d
         return PDP_ERR_UNSUPPORTED;
     }
     return exn_launch(p, budget, status, count, true_count, work, leaves, stream);
+}
+
+extern "C" int pdp_exact_mass(pdp_problem *p, const float *weights, int64_t budget, int8_t *status, double *mass, double *true_mass,
+                              double *open_mass, int64_t *work, int64_t *leaves, void *stream)
+{
+    PDP_REQUIRE(p && weights && status && mass && true_mass && open_mass, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_mass: a replicated problem (R = %d) is not supported; weigh the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exz_launch(p, weights, budget, status, mass, true_mass, open_mass, work, leaves, stream);
 }
 
 extern "C" int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work,

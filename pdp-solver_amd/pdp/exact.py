@@ -23,7 +23,9 @@ others; a proved cost is the same minimum, which minimiser comes back depends on
 count into the models themselves: the counting search meets its satisfying cubes in a fixed order, so "count before the cube + offset inside it" numbers every model once, and
 a rank becomes a model by walking that order with a cursor (pdp_exact_models_at) -- ``enumerate_models`` lists the first
 models of an instance, ``sample_models`` draws uniformly from all of them (uniform ranks below the exact count): what PDP's own solution
-is to be compared with, and a supervised target the marginals alone do not give.
+is to be compared with, and a supervised target the marginals alone do not give.  ``solution_mass`` weighs instead of counting: the
+probability that rounding every variable independently with a soft prediction gives a model, the posterior under that product prior,
+and, where the budget ran out, the mass of the part of the tree not visited (pdp_exact_mass).
 """
 
 import numpy as np
@@ -570,6 +572,57 @@ def count_models(items, budget=0, device=None, max_edges=MAX_EDGES, split=None, 
                 marginals[i] = tc[off:off + n] / co[j]
             off += n
     return (status, count, marginals, work, used) if depths else (status, count, marginals, work)
+
+
+def solution_mass(items, weights, budget=0, device=None, max_edges=MAX_EDGES):
+    """The exact solution mass of soft predictions for loader items (pdp_exact_mass): with ``weights`` (per instance an
+    array of n_i probabilities of the variables being true, taken as float32) rounded independently, how likely the result is a model.
+    Returns numpy (status int8 [N]: 1 mass is that probability, -1 the budget ran out and it lies in [mass, mass + open_mass], -2 more
+    than 1023 variables, -3 a weight is NaN or outside [0, 1], neither searched; mass float64 [N]; posterior: per instance a float64
+    array of n_i values, P(variable true | the draw is a model) over the part of the tree visited, or None where mass is 0; open_mass
+    float64 [N]; work int64 [N])."""
+    native.require_gpu()
+    device = torch.device('cuda:0') if device is None else torch.device(device)
+    N = len(items)
+    if len(weights) != N:
+        raise ValueError("weights must hold one array per item: %d items, %d arrays" % (N, len(weights)))
+    weights = [np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1)) for w in weights]
+    for i, (it, w) in enumerate(zip(items, weights)):
+        if w.size != int(it[0]):
+            raise ValueError("weights[%d] must have %d values (one per variable), got %d" % (i, int(it[0]), w.size))
+    status = np.ones(N, dtype=np.int8)
+    mass = np.zeros(N, dtype=np.float64)
+    open_mass = np.zeros(N, dtype=np.float64)
+    work = np.zeros(N, dtype=np.int64)
+    posterior = [None] * N
+    for seg in _segments(items, max_edges):
+        part = [items[i] for i in seg]
+        if sum(int(it[2].shape[1]) for it in part) == 0:
+            # no literal anywhere (and no problem to build: the layout needs an edge): without a clause every draw is a model and the
+            # posterior is the prior, with an (empty) clause none is
+            for i, it in zip(seg, part):
+                w = weights[i]
+                if int(it[0]) > COUNT_MAX_N:
+                    status[i] = -2
+                elif not bool(((w >= 0) & (w <= 1)).all()):
+                    status[i] = -3
+                elif int(it[1]) == 0:
+                    mass[i] = 1.0
+                    posterior[i] = w.astype(np.float64)
+            continue
+        with torch.cuda.device(device):
+            prob = _problem(part, device)
+            wt = torch.from_numpy(np.concatenate([weights[i] for i in seg])).to(device)
+            st, ma, tm, op, wk = [t.cpu().numpy() for t in prob.exact_mass(wt, budget)]
+        del prob
+        off = 0
+        for j, (i, it) in enumerate(zip(seg, part)):
+            n = int(it[0])
+            status[i], mass[i], open_mass[i], work[i] = st[j], ma[j], op[j], wk[j]
+            if ma[j] > 0:
+                posterior[i] = tm[off:off + n] / ma[j]
+            off += n
+    return status, mass, posterior, open_mass, work
 
 
 def count_is_exact(status, count):

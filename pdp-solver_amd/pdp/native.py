@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_solve_learn_proof', 'pdp_exact_check', 'pdp_exact_trim', 'pdp_exact_last_grid', 'pdp_exact_solve_learn_assume',
     'pdp_exact_min_unsat', 'pdp_exact_count', 'pdp_exact_solve_split', 'pdp_exact_split_cubes',
     'pdp_exact_count_split', 'pdp_exact_count_split_cubes', 'pdp_exact_models_at',
-    'pdp_exact_min_unsat_split', 'pdp_exact_min_unsat_split_cubes',
+    'pdp_exact_min_unsat_split', 'pdp_exact_min_unsat_split_cubes', 'pdp_exact_mass',
 ]
 
 
@@ -572,6 +572,31 @@ class Problem(object):
                                     _stream()))
         return (status, count, true_count, work, leaves) if stats else (status, count, true_count, work)
 
+    def exact_mass(self, weights, budget=0, stats=False):
+        """The exact solution mass of a soft prediction (pdp_exact_mass): with ``weights`` (float32, V elements, contiguous, on the
+        problem's device) as independent probabilities of the variables being true, (status int8 [B]: 1 the search is complete and mass
+        is the probability that such a draw is a model, -1 the budget ran out and that probability lies in [mass, mass + open_mass], -2
+        more than 1023 variables, -3 a weight of the instance is NaN or outside [0, 1], neither searched; mass float64 [B]; true_mass
+        float64 [V]: the part of mass with the variable true, so true_mass / mass is the posterior; open_mass float64 [B]: the mass of
+        the part of the tree not yet visited, 0 at status 1; work int64 [B]), plus leaves int64 [B] with ``stats``.  An unsatisfiable
+        instance is status 1 with mass 0.  ``budget`` as in exact_solve.  Asynchronous on the current stream."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads (0: the library default), got %r" % (budget,))
+        if not torch.is_tensor(weights):
+            raise NativeError("weights must be a float32 tensor of %d elements on %s, got %s" % (self.V, self.device, type(weights).__name__))
+        if weights.device != self.device:
+            raise NativeError("weights must live on %s, got %s" % (self.device, weights.device))
+        weights = ptr(weights, torch.float32, self.V, 'weights')
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        mass = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        true_mass = torch.empty(self.V, dtype=torch.float64, device=self.device)
+        open_mass = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        leaves = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_mass(self._h, weights, C.c_int64(int(budget)), ptr(status), ptr(mass), ptr(true_mass), ptr(open_mass), ptr(work),
+                                   ptr(leaves), _stream()))
+        return (status, mass, true_mass, open_mass, work, leaves) if stats else (status, mass, true_mass, open_mass, work)
+
     def exact_count_split(self, budget=0, depth=None, stats=False):
         """exact_count with the search of instance b spread over 2^depth[b] waves (pdp_exact_count_split): (status, count, true_count, work)
         as exact_count's -- count and true_count equal its bit for bit while count <= 2^53 and no cube runs out of ``budget``, which applies
@@ -800,7 +825,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split and exact_min_unsat_split (their cube kernels), exact_min_unsat, exact_count, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split and exact_min_unsat_split (their cube kernels), exact_min_unsat, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

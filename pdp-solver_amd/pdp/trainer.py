@@ -131,7 +131,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         if hasattr(self, '_run_stats'):
             self._run_stats[0] += len(rows); self._run_stats[1] += sum(r['solved'] for r in rows)
             self._run_stats[2] += sum(r['unsat_clauses'] for r in rows)
-        return "".join(str(r).replace("'", '"') + "\n" for r in rows)
+        # a None (solution_mass_log2 at mass 0; model_count_log2 would hold one at a count of 0) is written as JSON's null
+        return "".join(str(r).replace("'", '"').replace(': None', ': null') + "\n" for r in rows)
 
     def _post_process_predictions(self, model, prediction, graph_map, batch_variable_map, batch_function_map,
                                   edge_feature, graph_feat, label, misc_data):
@@ -169,7 +170,14 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         "count_split_depth" after "count_work".  With config['complete_sample'] (K >= 1, with complete_count) every row whose count is proved and
         exact (at most 2^53, above 0) gains "samples", K models in the format of "solution" drawn uniformly with replacement from ALL its
         models (exact.sample_models: uniform ranks below the count, then pdp_exact_models_at; the seed is config['random_seed'], the stream
-        that of the row's position among the forward's satisfiable rows), and "sample_ranks", the ranks drawn; every other row is unchanged."""
+        that of the row's position among the forward's satisfiable rows), and "sample_ranks", the ranks drawn; every other row is unchanged.
+        With config['complete_mass'] (independent of complete_count) every row whose "complete" is 1 gains "solution_mass" (pdp_exact_mass
+        within the same budget, the weights being the row's slice of the soft prediction that also serves as hints: the probability that
+        rounding every variable independently with it gives a model), "solution_mass_log2" (None at 0), "solution_mass_open" (the mass
+        of the part of the tree not visited: the true value lies in [solution_mass, solution_mass + solution_mass_open]),
+        "solution_mass_proved" (1 / 0), "posterior" (per variable, P(true | the draw is a model); left out where the mass is 0) and
+        "mass_work"; a row of more than 1023 variables or with a prediction outside [0, 1] stays as it is.  After Walk-SAT the prediction
+        is 0/1, so the mass is 1 or 0 and costs one descent."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -284,6 +292,28 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                             rows[i]['sample_ranks'] = [int(r) for r in sranks[k]]
                     if hasattr(self, '_sample_stats'):
                         self._sample_stats[0] += sum(s is not None for s in samples); self._sample_stats[1] += len(sat_rows)
+        if self._config.get('complete_mass'):
+            # the satisfiable rows, once more, as one batch of their own: how much of the soft prediction's own mass lies on models
+            from pdp import exact
+            sat_rows = [i for i in range(len(rows)) if status[i] == 1]
+            if sat_rows:
+                items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
+                pred = hint.cpu().numpy()
+                st, mass, posterior, open_mass, zwork = exact.solution_mass([items[i] for i in sat_rows], [pred[offs[i]:offs[i + 1]] for i in sat_rows],
+                                                                            budget=budget, device=hint.device)
+                for k, i in enumerate(sat_rows):
+                    if st[k] in (-2, -3):
+                        continue                # more than 1023 variables, or a prediction that is not a probability: the row stays as it is
+                    row = rows[i]
+                    row['solution_mass'] = float(mass[k])
+                    row['solution_mass_log2'] = float(np.log2(mass[k])) if mass[k] > 0 else None
+                    row['solution_mass_open'] = float(open_mass[k])
+                    row['solution_mass_proved'] = int(st[k] == 1)
+                    if mass[k] > 0:
+                        row['posterior'] = posterior[k].tolist()
+                    row['mass_work'] = int(zwork[k])
+                if hasattr(self, '_mass_stats'):
+                    self._mass_stats[0] += int((st == 1).sum()); self._mass_stats[1] += len(sat_rows)
         if hasattr(self, '_complete_stats'):
             for k, s in enumerate((1, 0, -1)):
                 self._complete_stats[k] += int((status == s).sum())

@@ -28,7 +28,13 @@ spreads that branch and bound over 2^N waves per row that share the best cost fo
 then the rows left unproved once more from the cost reached): "min_unsat" and "min_unsat_proved" mean the same, "min_unsat_work" is summed
 over the cubes, and "min_unsat_split_depth" appears on the rows searched at a depth above 0; ``--complete-sample K`` (with ``--complete-count``) gives every row
 whose count is proved and exact "samples", K models in the format of "solution" drawn uniformly from all its models (pdp_exact_models_at at
-uniform ranks below the count, seeded by ``-s``), and "sample_ranks", the ranks drawn; every other row is unchanged.
+uniform ranks below the count, seeded by ``-s``), and "sample_ranks", the ranks drawn; every other row is unchanged;
+``--complete-mass`` (with ``--complete``, independent of ``--complete-count``) gives every satisfiable row "solution_mass", the probability
+that rounding every variable independently with the model's soft prediction gives a model of the instance (pdp_exact_mass),
+"solution_mass_log2", "solution_mass_open" (the mass of the part of the tree not visited within the budget: the true value lies in
+[solution_mass, solution_mass + solution_mass_open]), "solution_mass_proved" (1 / 0), "posterior" (per variable, P(true | the draw is a
+model); left out where the mass is 0) and "mass_work".  After Walk-SAT (``-w`` above 0) the prediction is 0/1, the mass is 1 or 0 and
+costs one descent: the flag is meant for runs whose prediction is soft (``-w 0``).
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -79,6 +85,7 @@ def run(config, logger, output):
     solver._min_unsat_stats = [0, 0]                    # optima proved, rows asked (this rank's units)
     solver._count_stats = [0, 0]                        # counts completed, rows asked (this rank's units)
     solver._sample_stats = [0, 0]                       # rows sampled, rows asked (this rank's units)
+    solver._mass_stats = [0, 0]                         # solution masses proved, rows asked (this rank's units)
     say("Starting the prediction phase...")
     sink, owned = _open_output(output)
     try:
@@ -92,7 +99,8 @@ def run(config, logger, output):
         proved = "; minimum unsatisfied clauses proved for %d of %d" % tuple(solver._min_unsat_stats) if config.get('complete_min_unsat') else ""
         counted = "; models counted for %d of %d" % tuple(solver._count_stats) if config.get('complete_count') else ""
         sampled = "; sampled %d of %d" % tuple(solver._sample_stats) if config.get('complete_sample') else ""
-        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s%s%s" % (tuple(solver._complete_stats) + (proved, counted, sampled)))
+        massed = "; solution mass for %d of %d" % tuple(solver._mass_stats) if config.get('complete_mass') else ""
+        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s%s%s%s" % (tuple(solver._complete_stats) + (proved, counted, sampled, massed)))
     return solver
 
 
@@ -160,6 +168,12 @@ def main(argv=None):
                         'exact (at most 2^53) gains "samples", K models in the format of "solution" drawn uniformly, with replacement, from all its '
                         'models (pdp_exact_models_at at uniform ranks below the count; the seed is -s), and "sample_ranks", the ranks drawn',
                         type=int, default=None, metavar='K')
+    parser.add_argument('--complete-mass', dest='complete_mass', help='With --complete: every satisfiable row gains "solution_mass", the probability '
+                        'that rounding every variable independently with the soft prediction gives a model (pdp_exact_mass, --complete-budget '
+                        'reads), "solution_mass_log2", "solution_mass_open" (the mass not visited: the true value lies in [solution_mass, '
+                        'solution_mass + solution_mass_open]), "solution_mass_proved" (0: the budget ran out), "posterior" (per variable, '
+                        'P(true | the draw is a model)) and "mass_work"; after Walk-SAT (-w above 0) the prediction is 0/1 and the mass 1 or 0: '
+                        'meant for -w 0', action='store_true')
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -176,6 +190,8 @@ def main(argv=None):
         parser.error("--complete-min-unsat bounds the rows --complete leaves unsatisfied: give --complete as well")
     if args['complete_count'] and not args['complete']:
         parser.error("--complete-count counts the models of the rows --complete satisfies: give --complete as well")
+    if args['complete_mass'] and not args['complete']:
+        parser.error("--complete-mass weighs the models of the rows --complete satisfies: give --complete as well")
     if args['complete_split'] is not None:
         if not args['complete']:
             parser.error("--complete-split spreads the search of --complete: give --complete as well")

@@ -73,7 +73,15 @@ Rank rows (pdp_exact_models_at; never part of the default): ``ra`` = the batch o
 pdp_exact_models_at with one and with 1 000 uniformly drawn ranks per instance (exact.sample_ranks, sorted), one timed call each after a
 call with a budget of one read that does the one-time preparation: kernel time (the call's validation kernels and its one synchronisation
 included), total work against the count's, leaves, and the bytes of models written; every rank answered and the first row of every
-instance checked by pdp_cnf_eval."""
+instance checked by pdp_cnf_eval.
+
+Mass rows (pdp_exact_mass; never part of the default): ``za`` = the batch of row ``ca``: pdp_exact_count next to pdp_exact_mass with all
+weights 0.5, kernel time of each after a call with a budget of one read; equal status, work and leaves and mass * 2^n == count asserted.
+PDP_MASS_ONLY=count / mass times that one call alone (a fresh process per measurement of the alternating comparison).  ``zp`` = the same
+batch with the soft prediction of a T=100 p-d-p forward (-w 0, philox) as weights: how many instances are refused (-3), kernel time, work
+against the count's, the distribution of log2(mass), and the mean |prediction - posterior| next to marginal_gap.  ``zd`` = the batch of
+row ``cd`` at 2^28 reads per instance, with weights 0.5 and with the forward's prediction: how many brackets close, and the median and
+p99 of open_mass on those that do not."""
 import io
 import json
 import logging
@@ -385,10 +393,10 @@ def _timed(p, hints):
     return ev[0].elapsed_time(ev[1]), st.cpu().numpy(), wk.cpu().numpy()
 
 
-def _pdp_forward(items):
+def _pdp_forward(items, local_search=100):
     "the p-d-p forwards over the items as one loader batch, per segment: (prediction float32 [V], graph_map, variable map, function map, edge feature)"
     from pdp.trainer import SatFactorGraphTrainer
-    cfg = dict(model_type='p-d-p', model_name='exact-time', verbose=False, local_search_iteration=100, epsilon=0.5, tolerance=0.02,
+    cfg = dict(model_type='p-d-p', model_name='exact-time', verbose=False, local_search_iteration=local_search, epsilon=0.5, tolerance=0.02,
                t_max=100, pi=0.01, decimation_probability=0.5, rng='philox', random_seed=0, hidden_dim=3, test_batch_limit=40000000,
                batch_size=len(items), test_recurrence_num=100)
     tr = SatFactorGraphTrainer(cfg, use_cuda=True, logger=logging.getLogger('exact-time'))
@@ -848,9 +856,99 @@ def run_rank(key):
               flush=True)
 
 
+MASS_ROWS = ('za', 'zp', 'zd')
+ZD_BUDGET = 1 << 28
+
+
+def _soft_prediction(items, pick):
+    "the T=100 -w 0 philox p-d-p forward's prediction on all ``items``, cut down to the instances ``pick``: float32 [their variables]"
+    pred = np.concatenate([g[0].cpu().numpy() for g in _pdp_forward(items, local_search=0)]).astype(np.float32)
+    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in items])])
+    assert pred.size == voff[-1], "the forward's variables are not the items'"
+    return np.concatenate([pred[voff[i]:voff[i + 1]] for i in pick])
+
+
+def run_mass(key):
+    """the satisfiable instances of row a (za, zp) or d (zd) as a batch of their own: pdp_exact_mass next to pdp_exact_count.  Every timed
+    call follows a call with a budget of one read, which does the one-time preparation.  PDP_MASS_ONLY=count / mass (za) times that one
+    call alone: a fresh process per measurement of the alternating comparison."""
+    from pdp import exact
+    title, make = ROWS['d' if key == 'zd' else 'a']
+    items = make()
+    status = exact.solve_items(items)[0]
+    pick = np.nonzero(status == 1)[0]
+    sub = [items[i] for i in pick]
+    b = dataset.to_torch(dataset.collate_segment(sub), torch.device('cuda:0'))
+    q = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(sub))
+    soff = np.concatenate([[0], np.cumsum([int(it[0]) for it in sub])])
+    half = torch.full((q.V,), 0.5, dtype=torch.float32, device=q.device)
+    budget = ZD_BUDGET if key == 'zd' else 0
+    head = "(%s) the %d instances of %s that the deciding search answers 1" % (key, len(sub), title)
+
+    def count():
+        q.exact_count(1)
+        ms, out = _event_ms(lambda: q.exact_count(budget, stats=True))
+        return ms, [t.cpu().numpy() for t in out]
+
+    def mass(w):
+        q.exact_mass(w, 1)
+        ms, out = _event_ms(lambda: q.exact_mass(w, budget, stats=True))
+        return ms, [t.cpu().numpy() for t in out]
+
+    if key == 'za':
+        only = os.environ.get('PDP_MASS_ONLY')
+        if only:
+            ms, out = count() if only == 'count' else mass(half)
+            print("%s, %s alone: kernel %.2f ms  work total %d" % (head, 'pdp_exact_count' if only == 'count' else 'pdp_exact_mass at weights 0.5', ms,
+                                                                 int(out[3 if only == 'count' else 4].sum())), flush=True)
+            return
+        ms0, c = count()
+        ms1, z = mass(half)
+        assert np.array_equal(c[3], z[4]) and np.array_equal(c[4], z[5]) and np.array_equal(c[0], z[0]), "weights 0.5: not the count's search"
+        assert np.array_equal(c[1], z[1] * 2.0 ** np.diff(soff)), "weights 0.5: mass * 2^n is not the count"
+        print("%s: pdp_exact_count kernel %.2f ms, pdp_exact_mass at weights 0.5 kernel %.2f ms (ratio %.3f); work equal, total %d; "
+              "mass * 2^n == count on all" % (head, ms0, ms1, ms1 / ms0, int(z[4].sum())), flush=True)
+        return
+    w = _soft_prediction(items, pick)
+    bad = np.array([not bool(((w[soff[k]:soff[k + 1]] >= 0) & (w[soff[k]:soff[k + 1]] <= 1)).all()) for k in range(len(sub))])
+    wt = torch.from_numpy(w).to(q.device)
+    if key == 'zp':
+        ms0, c = count()
+        ms1, z = mass(wt)
+        st, ma, tm, op, wk, lv = z
+        assert np.array_equal(st == -3, bad), "status -3 is not exactly the predictions outside [0, 1]"
+        ok, some = st == 1, ma > 0
+        lg = np.log2(ma[some])
+        post_gap = np.array([np.mean(np.abs(w[soff[k]:soff[k + 1]] - tm[soff[k]:soff[k + 1]] / ma[k])) if some[k] else np.nan for k in range(len(sub))])
+        unif_gap = np.array([np.mean(np.abs(w[soff[k]:soff[k + 1]] - c[2][soff[k]:soff[k + 1]] / c[1][k])) if c[1][k] > 0 and not bad[k] else np.nan
+                             for k in range(len(sub))])
+        print("%s, weights = p-d-p forward T=100 -w 0 philox: refused (-3, NaN or outside [0, 1]) %d  complete %d  at the budget %d  with "
+              "mass 0: %d;  kernel %.2f ms (pdp_exact_count %.2f ms)  work total %d against the count's %d on the instances searched (ratio %.3f)"
+              % (head, int(bad.sum()), int(ok.sum()), int((st == -1).sum()), int((ok & ~some).sum()), ms1, ms0, int(wk.sum()), int(c[3][~bad].sum()),
+                 float(wk.sum()) / max(1.0, float(c[3][~bad].sum()))), flush=True)
+        if some.any():
+            print("    log2(mass) over the %d instances with mass: min %.2f  %s;  mean |prediction - posterior| %.4f next to marginal_gap "
+                  "(mean |prediction - uniform marginal|) %.4f on the same instances;  soft entries (strictly between 0 and 1) %.3f of the prediction"
+                  % (int(some.sum()), float(lg.min()), _q(lg), float(np.nanmean(post_gap[some])), float(np.nanmean(unif_gap[some])),
+                     float(np.mean((w > 0) & (w < 1)))), flush=True)
+        return
+    for name, weights in (('weights 0.5', half), ('the forward\'s prediction (T=100 -w 0 philox)', wt)):
+        ms, z = mass(weights)
+        st, ma, tm, op, wk, lv = z
+        opened = op[st == -1]
+        print("%s, budget 2^28, %s: kernel %.2f ms  refused %d  brackets closed (status 1) %d  open %d%s" %
+              (head, name, ms, int((st == -3).sum()), int((st == 1).sum()), int((st == -1).sum()),
+               ";  open_mass over the open ones: median %.4g  p99 %.4g;  mass + open_mass <= 1e-6 on %d, mass > 0 on %d of them"
+               % (float(np.median(opened)), float(np.percentile(opened, 99)), int(((ma + op)[st == -1] <= 1e-6).sum()), int((ma[st == -1] > 0).sum()))
+               if opened.size else ""), flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
+        if k in MASS_ROWS:
+            run_mass(k)
+            continue
         if k in RANK_ROWS:
             run_rank(k)
             continue
