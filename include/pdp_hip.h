@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass, pdp_exact_mass_split, pdp_exact_mass_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -476,6 +476,53 @@ int pdp_exact_count(pdp_problem *p, int64_t budget, int8_t *status, double *coun
 int pdp_exact_mass(pdp_problem *p, const float *weights, int64_t budget, int8_t *status, double *mass, double *true_mass,
                    double *open_mass, int64_t *work, int64_t *leaves, void *stream);
 
+/* pdp_exact_mass with the search of every instance spread over 2^depth[b] waves (plain Python, normative:
+ * tests/exact_mass_split_model.py).  Cube `index` of the 2^depth cubes of an instance is pdp_exact_mass's search with the
+ * decision of every level L <= depth pinned as in pdp_exact_count_split (bit (index >> (depth - L)) & 1: 0 the polarity the mass search
+ * tries first -- the heavier literal, pdp_exact_count's rule at exactly 0.5 --, 1 the other; the level counts as already flipped).
+ * pre[L] = mass and snap[L] = Z as at any decision, then mass = mass * (the pinned literal's weight).
+ *   A pinned decision of mass 0.  If that product is 0.0 the state is a conflict at once, without a pass and without a budget check
+ *      (pdp_exact_mass's flip rule: a pinned "other" polarity is a flip); every open level is pinned then, so the cube ends.
+ *   A leaf inside the prefix.  A state without an open clause met with L < depth levels open is reached by every cube that shares those
+ *      levels' bits; the cube with index & ((1 << (depth - L)) - 1) == 0 adds mass to Z and 1 to leaves, the others add nothing; either
+ *      way the cube backtracks as after a conflict (pdp_exact_count_split's rule).
+ *   Open mass.  At cube status -1 the levels not yet flipped add pre[level] * (the untried literal's weight) as in pdp_exact_mass; a
+ *      pinned level counts as flipped and adds nothing, its sibling cube owns that half.  The cubes that share a prefix make the same
+ *      reads up to a node inside it and run out at the same check, so the current node's mass is added only by the cube that owns the
+ *      node: level >= depth, or index & ((1 << (depth - level)) - 1) == 0.
+ *   The budget is per cube: own reads >= budget before every pass (budget <= 0: PDP_EXACT_DEFAULT_BUDGET).  The end flush and
+ *      true_mass_c[v] = T[v] + (Z_c - T[v] - F[v]) * p_v are pdp_exact_mass's, per cube.
+ *   The instance's outputs are sums over its cubes in ASCENDING index, sequentially in double: mass = mass + mass_c, open_mass =
+ *   open_mass + open_c, true_mass[v] = true_mass[v] + true_mass_c[v]; work and leaves are integer sums; status 1 if every cube's is 1,
+ *   else -1, and then Z lies in [mass, mass + open_mass] up to rounding.  Where every product and sum is exact (weights that are small
+ *   dyadic fractions) mass, true_mass and leaves equal pdp_exact_mass's bit for bit at every depth; elsewhere they are the correctly
+ *   rounded results of this order and may differ from the plain call's in the last bits.  depth 0 gives pdp_exact_mass's six outputs
+ *   exactly.  With all weights 0.5 the cubes are pdp_exact_count_split's, record for record.  work >= pdp_exact_mass's (prefixes are
+ *   replayed) and work < cubes * (budget + 3 * edges of the instance).
+ *   depth [B] (device int8; NULL: all 0) in 0 .. 16; at most 2^22 cubes per call; the per-cube rows below at most 2^31 bytes; any of them
+ *   violated -> PDP_ERR_INVALID, the message names the instance.  An instance on the HBM route and an instance of more than 1023
+ *   variables (status -2, one record -2 / 0 / 0 / 0 / 0) have one cube.  An instance with a weight that is NaN or outside [0, 1] keeps
+ *   its depth: status -3, every other output 0, and each of its cubes leaves the record -3 / 0 / 0 / 0 / 0.  depth_used [B] (int8, may
+ *   be NULL) = the depth each instance was searched at.  work and leaves may be NULL.
+ * One wave takes one cube at a time from one counter and runs it to its own end; no word is shared between two cubes and no wave waits
+ * for another.  A cube of an instance with depth_used > 0 leaves its record and, unless its mass is 0.0, its row of true_mass_c in
+ * [cubes][n_max] doubles on the handle; a second kernel sums records and rows per instance in cube order, one lane per variable.  No
+ * double goes through an atomic or, other than pdp_exact_mass's stated butterfly, a reduction across lanes: every output and every
+ * record is a function of the instance, its weights, the depth and the budget alone; the default and the fast build give the same bits.
+ * NULL weights or outputs (other than work, leaves and depth_used) -> PDP_ERR_INVALID before any launch; R != 1 -> PDP_ERR_UNSUPPORTED.
+ * Routing, slab and working arrays are pdp_exact_mass's, shared with it; records and rows are a block of this call's own, so a
+ * pdp_exact_count_split call on the same problem does not disturb them.  The call synchronises the stream once (the cube count sizes
+ * its records and its grid); the kernels that follow are asynchronous on it. */
+int pdp_exact_mass_split(pdp_problem *p, const float *weights, const int8_t *depth, int64_t budget, int8_t *status, double *mass,
+                         double *true_mass, double *open_mass, int64_t *work, int64_t *leaves, int8_t *depth_used, void *stream);
+
+/* The per-cube records of the last pdp_exact_mass_split call on the problem that succeeded (PDP_ERR_INVALID before the first, and after
+ * a call that was refused): cube_off [B+1] (int64), cube_status [cubes] (1 / -1, -2: more than 1023 variables, -3: a bad weight),
+ * cube_mass and cube_open [cubes] (double), cube_work and cube_leaves [cubes], cubes = cube_off[B] = the sum of 2^depth_used.  Device to
+ * device, asynchronous on the stream. */
+int pdp_exact_mass_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, double *cube_mass, double *cube_open,
+                               int64_t *cube_work, int64_t *cube_leaves, void *stream);
+
 /* pdp_exact_solve_hinted with the search of every instance spread over 2^depth[b] waves (plain Python, normative:
  * tests/exact_split_model.py).  The deciding search is a deterministic depth-first tree; a cube is a prefix of it: cube
  * `index` of the 2^depth cubes of an instance is that search, without its check pass, where the decision of every level L <= depth is
@@ -620,7 +667,7 @@ int pdp_exact_min_unsat_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *c
                                     int32_t *cube_improvements, void *stream);
 
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split and pdp_exact_min_unsat_split (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split and pdp_exact_mass_split (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

@@ -32,7 +32,8 @@
 // same way; its cubes share nothing at all, and a second kernel adds their counts up in cube order.  pdp_exact_models_at (last) walks
 // the counting search's leaves with a cursor over given ranks and writes the models of those ranks, one wave per instance again.
 // pdp_exact_min_unsat_split (after it) cuts the branch and bound into cubes that share ub[b], the best cost any of them has found.
-// pdp_exact_mass (the last kernel) is the counting search under a product prior: a weight per literal, a two-sided bracket at the budget.
+// pdp_exact_mass is the counting search under a product prior: a weight per literal, a two-sided bracket at the budget;
+// pdp_exact_mass_split (the last kernels) cuts it into cubes as the count's split does, and its cubes share nothing either.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -3406,7 +3407,8 @@ struct ExzParams {
 // the count's accumulators, plus pre [n+1] and the weights as doubles [n]
 struct ExzAcc { ExnAcc a; double *pre, *w; };
 
-__device__ __forceinline__ ExzAcc exz_bind_hbm(const ExzParams &xp, const Inst &I)
+template <typename Params>
+__device__ __forceinline__ ExzAcc exz_bind_hbm(const Params &xp, const Inst &I)
 {
     ExzAcc A;
     A.a = exn_bind_hbm(xp.true_mass, xp.h_F, xp.h_snap, I);
@@ -3447,8 +3449,10 @@ __device__ __forceinline__ double exz_extend(const ExInst<LitT, PtrT> &X, const 
 
 // The mass of the part of the tree not yet visited when the budget check fires: the untried halves of the open levels, oldest first,
 // then the current node.  Every lane runs the same sequential sum on the same addresses; it runs once per search, behind the loop.
-template <typename LitT, typename PtrT>
-__device__ __forceinline__ double exz_open(const ExInst<LitT, PtrT> &X, const ExzAcc &A, int level, double mass)
+// SPLIT: a pinned level carries the flipped bit, so its other half is left to the sibling cube; the current node is reached after the
+// same reads by every cube that shares the open levels' bits and is added by the one that owns it (ex_owns_leaf).
+template <bool SPLIT, typename LitT, typename PtrT>
+__device__ __forceinline__ double exz_open(const ExInst<LitT, PtrT> &X, const ExzAcc &A, const ExCube<SPLIT> &Q, int level, double mass)
 {
     double open = 0.0;
     for (int l = 1; l <= level; ++l) {
@@ -3457,14 +3461,34 @@ __device__ __forceinline__ double exz_open(const ExInst<LitT, PtrT> &X, const Ex
         const int v = (int)d;
         open = open + A.pre[l] * exz_omega(A, v, 3u - X.val[v]);
     }
+    if constexpr (SPLIT) {
+        if (!ex_owns_leaf(Q, level)) return open;
+    }
     return open + mass;
 }
 
-// The weighted counting search of one instance by the calling wave.  Returns 1 (complete) or -1 (budget spent); T and F hold every
-// level's credit, *z_out the mass of the leaves met and *open_out the mass not yet visited (0.0 at 1).
+// Backtracking of the weighted search: ex_backtrack, then the mass of the flipped decision from pre.  A flip onto a literal of weight 0
+// is a conflict at once, without a pass: the level is undone by the next round.  Returns false when no level is left.
 template <bool HBM, typename LitT, typename PtrT>
-__device__ int ex_search_mass(const ExInst<LitT, PtrT> &X, const ExzAcc &A, int64_t budget, int64_t *work_out, double *z_out, double *open_out,
-                              int64_t *leaves_out)
+__device__ __forceinline__ bool exz_backtrack(const ExInst<LitT, PtrT> &X, const ExzAcc &A, int &level, int &tlen, ExnCredit &credit, double &mass)
+{
+    bool resumed;
+    do {
+        resumed = ex_backtrack<HBM>(X, level, tlen, credit);
+        if (!resumed) break;
+        const int v = (int)(X.dvar[level] & 0x7fffffffu);           // the flipped decision: behind ex_backtrack's last barrier
+        mass = A.pre[level] * exz_omega(A, v, X.val[v]);
+    } while (mass == 0.0);
+    return resumed;
+}
+
+// The weighted counting search of one instance, or of one cube of it, by the calling wave.  Returns 1 (complete) or -1 (budget spent); T
+// and F hold every level's credit, *z_out the mass of the leaves met and *open_out the mass not yet visited (0.0 at 1).  SPLIT: a leaf
+// met with fewer than `depth` levels open counts only in the cube that owns it, as in ex_search_count; a pinned decision onto a literal
+// of weight 0 is a flip onto it, a conflict at once without a pass (every open level is pinned then, so that ends the cube).
+template <bool HBM, bool SPLIT, typename LitT, typename PtrT>
+__device__ int ex_search_mass(const ExInst<LitT, PtrT> &X, const ExzAcc &A, int64_t budget, const ExCube<SPLIT> &Q, int64_t *work_out,
+                              double *z_out, double *open_out, int64_t *leaves_out)
 {
     constexpr int INF = 0x7fffffff;
     int level = 0, tlen = 0;
@@ -3492,31 +3516,35 @@ __device__ int ex_search_mass(const ExInst<LitT, PtrT> &X, const ExzAcc &A, int6
             wmin = ex_min(P.wmin);
             if (wmin == INF) {
                 // a leaf: every clause has a true literal and the unassigned variables contribute a factor 1; then as after a conflict
-                Z = Z + mass;
-                ++leaves;
+                bool mine = true;
+                if constexpr (SPLIT) mine = ex_owns_leaf(Q, level);
+                if (mine) {
+                    Z = Z + mass;
+                    ++leaves;
+                }
                 any_conflict = true;
             }
         }
         if (any_conflict) {
-            // a flip to a literal of weight 0 is a conflict at once, without a pass: the level is undone by the next round
-            bool resumed;
-            do {
-                resumed = ex_backtrack<HBM>(X, level, tlen, credit);
-                if (!resumed) break;
-                const int v = (int)(X.dvar[level] & 0x7fffffffu);   // the flipped decision: behind ex_backtrack's last barrier
-                mass = A.pre[level] * exz_omega(A, v, X.val[v]);
-            } while (mass == 0.0);
-            if (!resumed) { result = 1; break; }
+            if (!exz_backtrack<HBM>(X, A, level, tlen, credit, mass)) { result = 1; break; }
             continue;
         }
         const unsigned long long best = ex_branch<HBM, EX_PHASE_HINT>(X, wmin, work);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
         // pre of the level ex_decide opens: nothing reads it before the barriers of ex_decide
         if (threadIdx.x == 0) A.pre[level + 1] = mass;
-        ex_decide<HBM, false>(X, ExCube<false>{}, best, level, tlen, credit);
-        mass = mass * exz_omega(A, (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull)), (best & 1ull) ? 1u : 2u);
+        ex_decide<HBM, SPLIT>(X, Q, best, level, tlen, credit);
+        const int dv = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+        if constexpr (SPLIT) {
+            mass = mass * exz_omega(A, dv, X.val[dv]);              // the pinned polarity: behind ex_decide's last barrier
+            if (level <= Q.depth && mass == 0.0) {                  // wave-uniform
+                if (!exz_backtrack<HBM>(X, A, level, tlen, credit, mass)) { result = 1; break; }
+            }
+        } else {
+            mass = mass * exz_omega(A, dv, (best & 1ull) ? 1u : 2u);
+        }
     }
-    *open_out = result == 1 ? 0.0 : exz_open(X, A, level, mass);
+    *open_out = result == 1 ? 0.0 : exz_open<SPLIT>(X, A, Q, level, mass);
     // the end: every open level is flushed, the newest first, as in ex_search_count
     for (; level >= 0; --level) {
         const int from = level > 0 ? X.mark[level] : 0;
@@ -3543,7 +3571,7 @@ __device__ void ex_solve_mass(const ExzParams &xp, const Inst &I, ExInst<LitT, P
     ex_sync<HBM>();
     int64_t work = 0, leaves = 0;
     double Z = 0.0, open = 0.0;
-    const int st = ex_search_mass<HBM>(X, A, xp.budget, &work, &Z, &open, &leaves);
+    const int st = ex_search_mass<HBM, false>(X, A, xp.budget, ExCube<false>{}, &work, &Z, &open, &leaves);
     ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
     for (int v = lane; v < I.n; v += EX_NT) {
         const double t = A.a.T[v];
@@ -3641,6 +3669,230 @@ int exz_launch(pdp_problem *p, const float *weights, int64_t budget, int8_t *sta
     return ex_launch_persistent(p, k_exact_mass, xp, (int64_t)p->B, p->exz_lds_bytes, ST(stream));
 }
 
+// ---- pdp_exact_mass_split: one instance's solution mass spread over 2^depth cubes, one wave per cube -----------------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_mass_split_model.py).  A cube is ex_search_mass<HBM, true>:
+// the weighted search with the decisions of levels 1..depth pinned as in pdp_exact_count_split, a leaf met inside the prefix credited to
+// the cube that owns it, and the node the budget fires at added to the open mass of the cube that owns it.  Every cube runs to its own
+// end: no word is shared between two waves.  The state, the slab (exz_lds_layout), the routing and the HBM arrays are k_exact_mass's.
+// Three launches on one stream, as the count's: k_exact_split_setup (it does not read the weights), the cubes (every cube leaves a
+// record, and where its instance has more than one cube and its mass is not 0.0, its row of n per-variable masses), the finish (per
+// instance of depth > 0: the records and rows summed in ascending cube order).  An instance at depth 0 has one cube, which writes the
+// instance's outputs itself exactly as k_exact_mass does.  No double goes through an atomic or, past exz_extend's butterfly, a reduction
+// across lanes.
+struct ExzsParams {
+    int B;
+    uint32_t total;             // cubes of the call
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;             // per cube
+    const float *weights;       // [V] the prediction
+    const int8_t *du;           // [B] depth used
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    int8_t *cube_status;        // [total] 1 / -1, -2: n > 1023, -3: a weight of the instance is NaN or outside [0, 1]
+    double *cube_mass;          // [total]
+    double *cube_open;          // [total]
+    int64_t *cube_work;         // [total]
+    int64_t *cube_leaves;       // [total]
+    double *rows;               // [total][n_max] true_mass of every cube of an instance with depth_used > 0 whose mass is not 0.0
+    int n_max;
+    int8_t *status; double *mass; double *true_mass; double *open_mass; int64_t *work; int64_t *leaves;     // the instance's outputs
+    ExHbm h;
+    double *h_F, *h_w, *h_snap, *h_pre;         // as ExzParams
+};
+
+// cube q = (instance I.b, index): copy the instance and its weights, clear the state, search; then the cube's record, and its
+// per-variable masses: the instance's slice of true_mass and the instance's other outputs when this is its one cube (depth 0), the
+// cube's own row otherwise, skipped when the mass is 0.0 (every entry is then +0.0, and the finish kernel skips the row as well).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_mass_split(const ExzsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExzAcc A, uint32_t q, int depth, int index)
+{
+    const int lane = (int)threadIdx.x;
+    ex_fill<HBM>(I, X);
+    for (int v = lane; v < I.n; v += EX_NT) {
+        const float h = xp.weights[I.v0 + v];
+        const uint32_t code = h > 0.5f ? 1u : (h < 0.5f ? 2u : 0u);
+        X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        A.a.T[v] = 0.0; A.a.F[v] = 0.0; A.w[v] = (double)h;
+    }
+    if (lane == 0) A.a.snap[0] = 0.0;
+    ex_sync<HBM>();
+    int64_t work = 0, leaves = 0;
+    double Z = 0.0, open = 0.0;
+    const int st = ex_search_mass<HBM, true>(X, A, xp.budget, ExCube<true>{depth, index, 0, nullptr, 0}, &work, &Z, &open, &leaves);
+    ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
+    if (depth == 0 || Z != 0.0) {
+        double *out = depth == 0 ? xp.true_mass + I.v0 : xp.rows + (size_t)q * (size_t)xp.n_max;
+        for (int v = lane; v < I.n; v += EX_NT) {
+            const double t = A.a.T[v];
+            out[v] = t + (Z - t - A.a.F[v]) * A.w[v];
+        }
+    }
+    if (lane == 0) {
+        xp.cube_status[q] = (int8_t)st;
+        xp.cube_mass[q] = Z;
+        xp.cube_open[q] = open;
+        xp.cube_work[q] = work;
+        xp.cube_leaves[q] = leaves;
+        if (depth == 0) {
+            xp.status[I.b] = (int8_t)st;
+            xp.mass[I.b] = Z;
+            xp.open_mass[I.b] = open;
+            if (xp.work) xp.work[I.b] = work;
+            if (xp.leaves) xp.leaves[I.b] = leaves;
+        }
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_mass_split(PView pv, ExzsParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= xp.total) break;
+        const int lo = exs_instance(xp.cube_off, xp.B, q);
+        const Inst I = load_inst(pv, lo);
+        const int depth = (int)xp.du[lo], index = (int)((int64_t)q - xp.cube_off[lo]);
+        // not searched, as in k_exact_mass: -2 (the setup gave such an instance depth 0) or -3, decided for the whole wave by a ballot
+        // before anything is bound; every cube of a -3 instance finds the same
+        int refused = I.n > EXN_MAX_N ? -2 : 0;
+        if (!refused) {
+            int bad = 0;
+            for (int v = (int)threadIdx.x; v < I.n; v += EX_NT) { const float h = xp.weights[I.v0 + v]; bad |= !(h >= 0.0f && h <= 1.0f); }
+            if (__ballot(bad) != 0ull) refused = -3;
+        }
+        // every arm ends in the barrier every arm ends in and falls through to the end of the loop body (see k_exact_count)
+        if (refused) {
+            // the record, and at depth 0 the instance's outputs; at a depth above 0 the finish kernel writes them from the records
+            if (depth == 0)
+                for (int v = (int)threadIdx.x; v < I.n; v += EX_NT) xp.true_mass[I.v0 + v] = 0.0;
+            if (threadIdx.x == 0) {
+                xp.cube_status[q] = (int8_t)refused; xp.cube_mass[q] = 0.0; xp.cube_open[q] = 0.0; xp.cube_work[q] = 0; xp.cube_leaves[q] = 0;
+                if (depth == 0) {
+                    xp.status[I.b] = (int8_t)refused;
+                    xp.mass[I.b] = 0.0;
+                    xp.open_mass[I.b] = 0.0;
+                    if (xp.work) xp.work[I.b] = 0;
+                    if (xp.leaves) xp.leaves[I.b] = 0;
+                }
+            }
+            ex_sync<false>();
+        } else if (xp.route[lo]) {
+            ex_solve_mass_split<true>(xp, I, ex_bind_hbm(xp.h, I), exz_bind_hbm(xp, I), q, 0, 0);
+        } else {
+            ex_solve_mass_split<false>(xp, I, ex_bind_lds(ex_slab, I), exz_bind_lds(ex_slab, I), q, depth, index);
+        }
+    }
+}
+
+// The outputs of every instance with depth_used > 0 from its cubes' records and rows, one wave per instance, as
+// k_exact_count_split_finish: mass and open_mass of 64 cubes at a time are staged in LDS and every lane adds them up in cube order;
+// true_mass[v] by the lane that holds v, over the rows of the cubes whose mass is not 0.0.  work and leaves are integer sums; status is
+// -3 where the cubes found a bad weight (all of them did), else 1 when every cube's is.
+__global__ void __launch_bounds__(EX_NT) k_exact_mass_split_finish(PView pv, ExzsParams xp)
+{
+    __shared__ double s_mass[EX_NT], s_open[EX_NT];
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        if (xp.du[b] == 0) continue;                                // wave-uniform, before any barrier of the body
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        double mass = 0.0, open_mass = 0.0;
+        int64_t w = 0, lv = 0;
+        int open = 0;
+        for (int64_t base = 0; base < nc; base += EX_NT) {
+            const int64_t j = base + lane;
+            const bool in = j < nc;
+            s_mass[lane] = in ? xp.cube_mass[c0 + j] : 0.0;
+            s_open[lane] = in ? xp.cube_open[c0 + j] : 0.0;
+            if (in) { w += xp.cube_work[c0 + j]; lv += xp.cube_leaves[c0 + j]; open |= xp.cube_status[c0 + j] != 1; }
+            __syncthreads();
+            const int lim = (int)(nc - base < EX_NT ? nc - base : EX_NT);
+            for (int t = 0; t < lim; ++t) { mass = mass + s_mass[t]; open_mass = open_mass + s_open[t]; }
+            __syncthreads();
+        }
+        w = exs_sum64(w);
+        lv = exs_sum64(lv);
+        const bool any_open = __ballot(open) != 0ull;
+        const bool bad_weight = xp.cube_status[c0] == (int8_t)-3;   // one address for the whole wave
+        for (int vb = 0; vb < n; vb += EX_NT) {
+            const int v = vb + lane;
+            double acc = 0.0;
+            for (int64_t base = 0; base < nc; base += EX_NT) {
+                const int64_t j = base + lane;
+                s_mass[lane] = j < nc ? xp.cube_mass[c0 + j] : 0.0;
+                __syncthreads();
+                const int lim = (int)(nc - base < EX_NT ? nc - base : EX_NT);
+                for (int t = 0; t < lim; t += EXNS_ROWS_IN_FLIGHT) {
+                    double r[EXNS_ROWS_IN_FLIGHT];
+#pragma unroll
+                    for (int u = 0; u < EXNS_ROWS_IN_FLIGHT; ++u) {
+                        const bool take = t + u < lim && s_mass[t + u] != 0.0 && v < n;
+                        r[u] = take ? xp.rows[(size_t)(c0 + base + t + u) * (size_t)xp.n_max + (size_t)v] : 0.0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < EXNS_ROWS_IN_FLIGHT; ++u)
+                        if (t + u < lim && s_mass[t + u] != 0.0) acc = acc + r[u];
+                }
+                __syncthreads();
+            }
+            if (v < n) xp.true_mass[v0 + v] = acc;
+        }
+        if (lane == 0) {
+            xp.status[b] = (int8_t)(bad_weight ? -3 : (any_open ? -1 : 1));
+            xp.mass[b] = mass;
+            xp.open_mass[b] = open_mass;
+            if (xp.work) xp.work[b] = w;
+            if (xp.leaves) xp.leaves[b] = lv;
+        }
+    }
+}
+
+int exzs_launch(pdp_problem *p, const float *weights, const int8_t *depth, int64_t budget, int8_t *status, double *mass, double *true_mass,
+                double *open_mass, int64_t *work, int64_t *leaves, int8_t *depth_used, void *stream)
+{
+    { const int st_ = exz_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t B = p->B, V = p->V;
+    ExsFixed F;
+    int64_t info[EXS_INFO];
+    {
+        const int st_ = exs_setup(p, p->exzs, "pdp_exact_mass_split", depth, depth_used, EXN_MAX_N, 8, EXNS_MAX_ROW_BYTES, st, F, info);
+        if (st_ != PDP_OK) return st_;
+    }
+    const size_t total = (size_t)info[2], nmax = (size_t)info[3];
+    // per-cube records: mass [total] | open [total] | work [total] | leaves [total] | rows [total][n_max] | status [total]
+    { const int st_ = exs_records(p->exzs, total * 32 + total * nmax * 8 + total); if (st_ != PDP_OK) return st_; }
+    ExzsParams xp;
+    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
+    xp.budget = ex_budget(budget);
+    xp.weights = weights;
+    xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off;
+    xp.cube_mass = (double *)p->exzs.cubes;
+    xp.cube_open = (double *)(p->exzs.cubes + total * 8);
+    xp.cube_work = (int64_t *)(p->exzs.cubes + total * 16);
+    xp.cube_leaves = (int64_t *)(p->exzs.cubes + total * 24);
+    xp.rows = (double *)(p->exzs.cubes + total * 32);
+    xp.cube_status = (int8_t *)(p->exzs.cubes + total * 32 + total * nmax * 8);
+    xp.n_max = (int)nmax;
+    xp.status = status; xp.mass = mass; xp.true_mass = true_mass; xp.open_mass = open_mass; xp.work = work; xp.leaves = leaves;
+    xp.h = ex_hbm(p);
+    double *blk = (double *)p->exz_blob;
+    xp.h_F = blk ? blk : nullptr;
+    xp.h_w = blk ? blk + V : nullptr;
+    xp.h_snap = blk ? blk + 2 * V : nullptr;
+    xp.h_pre = blk ? blk + 2 * V + (V + B) : nullptr;
+    { const int st_ = ex_launch_persistent(p, k_exact_mass_split, xp, (int64_t)total, p->exz_lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_mass_split_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    p->exzs.total = (int64_t)total;
+    p->exzs.status_off = total * 32 + total * nmax * 8;
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -3694,6 +3946,33 @@ extern "C" int pdp_exact_mass(pdp_problem *p, const float *weights, int64_t budg
         return PDP_ERR_UNSUPPORTED;
     }
     return exz_launch(p, weights, budget, status, mass, true_mass, open_mass, work, leaves, stream);
+}
+
+extern "C" int pdp_exact_mass_split(pdp_problem *p, const float *weights, const int8_t *depth, int64_t budget, int8_t *status, double *mass,
+                                    double *true_mass, double *open_mass, int64_t *work, int64_t *leaves, int8_t *depth_used, void *stream)
+{
+    PDP_REQUIRE(p && weights && status && mass && true_mass && open_mass, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_mass_split: a replicated problem (R = %d) is not supported; weigh the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exzs_launch(p, weights, depth, budget, status, mass, true_mass, open_mass, work, leaves, depth_used, stream);
+}
+
+extern "C" int pdp_exact_mass_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, double *cube_mass, double *cube_open,
+                                          int64_t *cube_work, int64_t *cube_leaves, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && cube_status && cube_mass && cube_open && cube_work && cube_leaves, "NULL argument");
+    PDP_REQUIRE(p->exzs.total > 0, "pdp_exact_mass_split_cubes: no pdp_exact_mass_split call on this problem yet");
+    const size_t B = p->B, total = (size_t)p->exzs.total;
+    const ExsFixed F = exs_fixed(p, p->exzs);
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_mass, p->exzs.cubes, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_open, p->exzs.cubes + total * 8, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exzs.cubes + total * 16, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, p->exzs.cubes + total * 24, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exzs.cubes + p->exzs.status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
+    return PDP_OK;
 }
 
 extern "C" int pdp_exact_solve_learn(pdp_problem *p, const float *hint, int64_t budget, int64_t arena, int8_t *status, float *model, int64_t *work,

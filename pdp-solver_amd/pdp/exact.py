@@ -26,6 +26,9 @@ models of an instance, ``sample_models`` draws uniformly from all of them (unifo
 is to be compared with, and a supervised target the marginals alone do not give.  ``solution_mass`` weighs instead of counting: the
 probability that rounding every variable independently with a soft prediction gives a model, the posterior under that product prior,
 and, where the budget ran out, the mass of the part of the tree not visited (pdp_exact_mass).
+``solution_mass(split=)`` spreads that search over 2^depth waves as well (pdp_exact_mass_split): cube masses and open
+masses add, the budget applies per cube, so a bracket is tightened by 2^depth times the reads.  ``mass_logit_gradient`` is the exact
+gradient of -ln(mass) in the logits of the prediction, from the posterior.
 """
 
 import numpy as np
@@ -49,6 +52,9 @@ AUTO_COUNT_STAGE1_BUDGET = 1 << 26
 # min_unsat(split='auto'): the reads per instance of the plain first branch and bound.  Chosen from the sweep in profiles/exact_time.txt
 # (tools/exact_time.py xsweep)
 AUTO_MIN_STAGE1_BUDGET = 1 << 26
+# solution_mass(split='auto'): the reads per instance of the plain first mass.  The count's value: the tree at weights 0.5 is the count's
+# (tools/exact_time.py zssweep sweeps it)
+AUTO_MASS_STAGE1_BUDGET = 1 << 26
 
 
 def raw_item(n, clauses, label=-1.0, name=""):
@@ -574,13 +580,70 @@ def count_models(items, budget=0, device=None, max_edges=MAX_EDGES, split=None, 
     return (status, count, marginals, work, used) if depths else (status, count, marginals, work)
 
 
-def solution_mass(items, weights, budget=0, device=None, max_edges=MAX_EDGES):
+def mass_split(prob, part, weights, budget, split, device):
+    """The split solution mass of one problem (``part``: its loader items, or a callable that returns them; ``weights``: the float32
+    tensor of the problem's V weights on its device): numpy (status, mass, true_mass, open_mass, work, depth_used).  ``split`` an int: one
+    pdp_exact_mass_split call at that depth.  'auto': a plain exact_mass with AUTO_MASS_STAGE1_BUDGET reads per instance (``budget`` if
+    that is smaller), then the instances that ran out are weighed again from the start -- a partial search cannot be resumed, so the first
+    stage's outputs are discarded -- as one split call on a problem of their own at auto_depth, with ``budget`` per cube; work is the sum
+    of the two stages."""
+    if split != 'auto':
+        st, ma, tm, op, wk, _, du = prob.exact_mass_split(weights, budget, depth=split, stats=True)[:7]
+        return st.cpu().numpy(), ma.cpu().numpy(), tm.cpu().numpy(), op.cpu().numpy(), wk.cpu().numpy(), du.cpu().numpy()
+    stage1 = min(budget, AUTO_MASS_STAGE1_BUDGET) if budget > 0 else AUTO_MASS_STAGE1_BUDGET
+    st, ma, tm, op, wk = [t.cpu().numpy() for t in prob.exact_mass(weights, stage1)]
+    du = np.zeros(len(st), dtype=np.int8)
+    again = [int(j) for j in np.nonzero(st == -1)[0]]
+    if again:
+        part = part() if callable(part) else part
+        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+        sub = _problem([part[j] for j in again], device)
+        w2 = torch.cat([weights[voff[j]:voff[j + 1]] for j in again]).contiguous()
+        r = [t.cpu().numpy() for t in sub.exact_mass_split(w2, budget, depth=auto_depth(len(again), device), stats=True)[:7]]
+        del sub
+        off = 0
+        for k, j in enumerate(again):
+            n = int(voff[j + 1] - voff[j])
+            st[j], ma[j], op[j], du[j] = r[0][k], r[1][k], r[3][k], r[6][k]
+            wk[j] += r[4][k]
+            tm[voff[j]:voff[j + 1]] = r[2][off:off + n]
+            off += n
+    return st, ma, tm, op, wk, du
+
+
+def mass_logit_gradient(weights, posterior):
+    """The gradient of -ln(mass) in the logits of a prediction, per instance ``weights - posterior`` (float64; zeros where the posterior is
+    None, i.e. the mass is 0 and the loss has no finite gradient).  Z is multilinear in p, so dZ/dp_v = Z1 - Z0 (the masses with v fixed
+    true / false, its own weight left out), and with p_v = sigmoid(logit_v): d(-ln Z)/d logit_v = -p_v (1 - p_v)(Z1 - Z0) / Z = p_v -
+    p_v Z1 / Z = p_v - posterior_v.  With a posterior of status 1 this is the exact gradient of the likelihood loss; at status -1 it is
+    the gradient of the lower bound's loss (the mass of the part of the tree visited)."""
+    if len(weights) != len(posterior):
+        raise ValueError("weights and posterior must hold one array per instance: %d and %d" % (len(weights), len(posterior)))
+    out = []
+    for i, (w, q) in enumerate(zip(weights, posterior)):
+        w = np.asarray(w, dtype=np.float32).reshape(-1).astype(np.float64)
+        if q is None:
+            out.append(np.zeros(w.size, dtype=np.float64))
+            continue
+        q = np.asarray(q, dtype=np.float64).reshape(-1)
+        if q.size != w.size:
+            raise ValueError("posterior[%d] must have %d values (one per variable), got %d" % (i, w.size, q.size))
+        out.append(w - q)
+    return out
+
+
+def solution_mass(items, weights, budget=0, device=None, max_edges=MAX_EDGES, split=None, depths=False):
     """The exact solution mass of soft predictions for loader items (pdp_exact_mass): with ``weights`` (per instance an
     array of n_i probabilities of the variables being true, taken as float32) rounded independently, how likely the result is a model.
     Returns numpy (status int8 [N]: 1 mass is that probability, -1 the budget ran out and it lies in [mass, mass + open_mass], -2 more
     than 1023 variables, -3 a weight is NaN or outside [0, 1], neither searched; mass float64 [N]; posterior: per instance a float64
     array of n_i values, P(variable true | the draw is a model) over the part of the tree visited, or None where mass is 0; open_mass
-    float64 [N]; work int64 [N])."""
+    float64 [N]; work int64 [N]).
+    ``split``: the search of every instance spread over 2^split waves (pdp_exact_mass_split; an int from 0 to 16), or
+    'auto': see mass_split.  ``budget`` then applies to every cube and work is the sum over the cubes; mass and posterior are those of
+    the call without ``split`` up to the last bits (bit for bit where every product is exact).  ``depths``: also return depth_used int8
+    [N]."""
+    split = _check_split(split)
     native.require_gpu()
     device = torch.device('cuda:0') if device is None else torch.device(device)
     N = len(items)
@@ -594,6 +657,7 @@ def solution_mass(items, weights, budget=0, device=None, max_edges=MAX_EDGES):
     mass = np.zeros(N, dtype=np.float64)
     open_mass = np.zeros(N, dtype=np.float64)
     work = np.zeros(N, dtype=np.int64)
+    used = np.zeros(N, dtype=np.int8)
     posterior = [None] * N
     for seg in _segments(items, max_edges):
         part = [items[i] for i in seg]
@@ -613,16 +677,20 @@ def solution_mass(items, weights, budget=0, device=None, max_edges=MAX_EDGES):
         with torch.cuda.device(device):
             prob = _problem(part, device)
             wt = torch.from_numpy(np.concatenate([weights[i] for i in seg])).to(device)
-            st, ma, tm, op, wk = [t.cpu().numpy() for t in prob.exact_mass(wt, budget)]
+            if split is None:
+                st, ma, tm, op, wk = [t.cpu().numpy() for t in prob.exact_mass(wt, budget)]
+                du = np.zeros(len(part), dtype=np.int8)
+            else:
+                st, ma, tm, op, wk, du = mass_split(prob, part, wt, budget, split, device)
         del prob
         off = 0
         for j, (i, it) in enumerate(zip(seg, part)):
             n = int(it[0])
-            status[i], mass[i], open_mass[i], work[i] = st[j], ma[j], op[j], wk[j]
+            status[i], mass[i], open_mass[i], work[i], used[i] = st[j], ma[j], op[j], wk[j], du[j]
             if ma[j] > 0:
                 posterior[i] = tm[off:off + n] / ma[j]
             off += n
-    return status, mass, posterior, open_mass, work
+    return (status, mass, posterior, open_mass, work, used) if depths else (status, mass, posterior, open_mass, work)
 
 
 def count_is_exact(status, count):

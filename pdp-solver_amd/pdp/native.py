@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_min_unsat', 'pdp_exact_count', 'pdp_exact_solve_split', 'pdp_exact_split_cubes',
     'pdp_exact_count_split', 'pdp_exact_count_split_cubes', 'pdp_exact_models_at',
     'pdp_exact_min_unsat_split', 'pdp_exact_min_unsat_split_cubes', 'pdp_exact_mass',
+    'pdp_exact_mass_split', 'pdp_exact_mass_split_cubes',
 ]
 
 
@@ -638,6 +639,57 @@ class Problem(object):
                                                 _stream()))
         return status, count, true_count, work, leaves, depth_used, cube_off, cube_status, cube_count, cube_work, cube_leaves
 
+    def exact_mass_split(self, weights, budget=0, depth=None, stats=False):
+        """exact_mass with the search of instance b spread over 2^depth[b] waves (pdp_exact_mass_split): (status, mass, true_mass,
+        open_mass, work) as exact_mass's.  ``budget`` applies to every cube; at status -1 the probability lies in [mass, mass + open_mass];
+        work is the sum over the cubes.  With weights whose products are exact (small dyadic fractions) mass and true_mass equal
+        exact_mass's bit for bit, elsewhere to the last bits.  ``weights`` as exact_mass's; ``depth``: an int, or an int8 tensor of B
+        elements on the problem's device, values 0 .. 16, at most 2^22 cubes and 2^31 bytes of per-cube rows per call; None: 0.
+        ``stats``: also leaves int64 [B], depth_used int8 [B] (0 for an instance on the HBM route or of more than 1023 variables),
+        cube_off int64 [B+1], cube_status int8 [cubes], cube_mass and cube_open float64 [cubes], cube_work and cube_leaves int64 [cubes].
+        Everything is a function of the instances, the weights, the depths and the budget.  Synchronises the current stream once, then
+        asynchronous on it (``stats`` synchronises again)."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads (0: the library default), got %r" % (budget,))
+        if not torch.is_tensor(weights):
+            raise NativeError("weights must be a float32 tensor of %d elements on %s, got %s" % (self.V, self.device, type(weights).__name__))
+        if weights.device != self.device:
+            raise NativeError("weights must live on %s, got %s" % (self.device, weights.device))
+        weights = ptr(weights, torch.float32, self.V, 'weights')
+        if depth is None:
+            depth = 0
+        if torch.is_tensor(depth):
+            if depth.dtype != torch.int8 or depth.numel() != self.B or depth.device != self.device:
+                raise ValueError("depth must be an int or an int8 tensor of %d elements (one per instance) on %s, got %s of %d on %s"
+                                 % (self.B, self.device, depth.dtype, depth.numel(), depth.device))
+            depth = depth.reshape(-1).contiguous()
+        elif isinstance(depth, bool) or not isinstance(depth, numbers.Integral) or not -128 <= depth <= 127:
+            raise ValueError("depth must be an int or an int8 tensor of %d elements (one per instance), got %r" % (self.B, depth))
+        else:
+            depth = torch.full((self.B,), int(depth), dtype=torch.int8, device=self.device)
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        mass = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        true_mass = torch.empty(self.V, dtype=torch.float64, device=self.device)
+        open_mass = torch.empty(self.B, dtype=torch.float64, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        leaves = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        depth_used = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        check(lib().pdp_exact_mass_split(self._h, weights, ptr(depth), C.c_int64(int(budget)), ptr(status), ptr(mass), ptr(true_mass),
+                                         ptr(open_mass), ptr(work), ptr(leaves), ptr(depth_used), _stream()))
+        if not stats:
+            return status, mass, true_mass, open_mass, work
+        cubes = int(torch.bitwise_left_shift(torch.ones_like(depth_used, dtype=torch.int64), depth_used.to(torch.int64)).sum().item())
+        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=self.device)
+        cube_status = torch.empty(cubes, dtype=torch.int8, device=self.device)
+        cube_mass = torch.empty(cubes, dtype=torch.float64, device=self.device)
+        cube_open = torch.empty(cubes, dtype=torch.float64, device=self.device)
+        cube_work = torch.empty(cubes, dtype=torch.int64, device=self.device)
+        cube_leaves = torch.empty(cubes, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_mass_split_cubes(self._h, ptr(cube_off), ptr(cube_status), ptr(cube_mass), ptr(cube_open), ptr(cube_work),
+                                               ptr(cube_leaves), _stream()))
+        return (status, mass, true_mass, open_mass, work, leaves, depth_used, cube_off, cube_status, cube_mass, cube_open, cube_work,
+                cube_leaves)
+
     def exact_models_at(self, ranks, rank_off, budget=0, stats=False):
         """The models of given ranks in exact_count's own order (pdp_exact_models_at): (status int8 [B]: 1 every rank of the instance is
         answered, -1 the budget ran out first, -2 more than 1023 variables, not searched; count_seen float64 [B]: the count when the search
@@ -825,7 +877,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split and exact_min_unsat_split (their cube kernels), exact_min_unsat, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split and exact_mass_split (their cube kernels), exact_min_unsat, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

@@ -177,7 +177,9 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         of the part of the tree not visited: the true value lies in [solution_mass, solution_mass + solution_mass_open]),
         "solution_mass_proved" (1 / 0), "posterior" (per variable, P(true | the draw is a model); left out where the mass is 0) and
         "mass_work"; a row of more than 1023 variables or with a prediction outside [0, 1] stays as it is.  After Walk-SAT the prediction
-        is 0/1, so the mass is 1 or 0 and costs one descent."""
+        is 0/1, so the mass is 1 or 0 and costs one descent.  With config['complete_mass_split'] (a depth 0..16, or -1: exact.mass_split's
+        'auto') that search runs with every row spread over 2^depth waves (pdp_exact_mass_split): the budget applies per cube, "mass_work" is
+        the sum over the cubes, and a row weighed at a depth above 0 gains "mass_split_depth" after "mass_work"."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -299,8 +301,12 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             if sat_rows:
                 items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
                 pred = hint.cpu().numpy()
-                st, mass, posterior, open_mass, zwork = exact.solution_mass([items[i] for i in sat_rows], [pred[offs[i]:offs[i + 1]] for i in sat_rows],
-                                                                            budget=budget, device=hint.device)
+                # config['complete_mass_split']: the search of every row spread over 2^depth waves (pdp_exact_mass_split); -1: auto
+                zsplit = self._config.get('complete_mass_split')
+                zsplit = None if zsplit is None else ('auto' if int(zsplit) < 0 else int(zsplit))
+                st, mass, posterior, open_mass, zwork, zdepth = exact.solution_mass([items[i] for i in sat_rows],
+                                                                                    [pred[offs[i]:offs[i + 1]] for i in sat_rows], budget=budget,
+                                                                                    device=hint.device, split=zsplit, depths=True)
                 for k, i in enumerate(sat_rows):
                     if st[k] in (-2, -3):
                         continue                # more than 1023 variables, or a prediction that is not a probability: the row stays as it is
@@ -312,6 +318,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                     if mass[k] > 0:
                         row['posterior'] = posterior[k].tolist()
                     row['mass_work'] = int(zwork[k])
+                    if zdepth[k] > 0:
+                        row['mass_split_depth'] = int(zdepth[k])
                 if hasattr(self, '_mass_stats'):
                     self._mass_stats[0] += int((st == 1).sum()); self._mass_stats[1] += len(sat_rows)
         if hasattr(self, '_complete_stats'):

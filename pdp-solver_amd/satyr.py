@@ -34,7 +34,10 @@ that rounding every variable independently with the model's soft prediction give
 "solution_mass_log2", "solution_mass_open" (the mass of the part of the tree not visited within the budget: the true value lies in
 [solution_mass, solution_mass + solution_mass_open]), "solution_mass_proved" (1 / 0), "posterior" (per variable, P(true | the draw is a
 model); left out where the mass is 0) and "mass_work".  After Walk-SAT (``-w`` above 0) the prediction is 0/1, the mass is 1 or 0 and
-costs one descent: the flag is meant for runs whose prediction is soft (``-w 0``).
+costs one descent: the flag is meant for runs whose prediction is soft (``-w 0``); ``--complete-mass-split N`` (with ``--complete-mass``)
+spreads that search over 2^N waves per row (pdp_exact_mass_split; -1: a plain first stage, then the rows that ran out once more at a depth
+chosen from their number): the budget applies per cube, so a bracket is tightened by 2^N times the reads, "mass_work" is summed over the
+cubes, and "mass_split_depth" appears on the rows weighed at a depth above 0.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -174,6 +177,10 @@ def main(argv=None):
                         'solution_mass + solution_mass_open]), "solution_mass_proved" (0: the budget ran out), "posterior" (per variable, '
                         'P(true | the draw is a model)) and "mass_work"; after Walk-SAT (-w above 0) the prediction is 0/1 and the mass 1 or 0: '
                         'meant for -w 0', action='store_true')
+    parser.add_argument('--complete-mass-split', dest='complete_mass_split', help='With --complete --complete-mass: spread the weighted search of '
+                        'every satisfiable row over 2^N waves (pdp_exact_mass_split), N from 0 to 16, or -1: a plain first stage, then the rows '
+                        'that ran out of its reads once more at a depth that fills the GPU; the budget applies per cube, "mass_work" is summed '
+                        'over the cubes, "mass_split_depth" on the rows weighed at a depth above 0', type=int, default=None)
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -204,6 +211,11 @@ def main(argv=None):
             parser.error("--complete-count-split spreads the count of --complete-count: give --complete-count as well")
         if not -1 <= args['complete_count_split'] <= 16:
             parser.error("--complete-count-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows that ran out")
+    if args['complete_mass_split'] is not None:
+        if not args['complete_mass']:
+            parser.error("--complete-mass-split spreads the search of --complete-mass: give --complete-mass as well")
+        if not -1 <= args['complete_mass_split'] <= 16:
+            parser.error("--complete-mass-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows that ran out")
     if args['complete_min_unsat_split'] is not None:
         if not args['complete_min_unsat']:
             parser.error("--complete-min-unsat-split spreads the search of --complete-min-unsat: give --complete-min-unsat as well")

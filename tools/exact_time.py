@@ -81,7 +81,16 @@ PDP_MASS_ONLY=count / mass times that one call alone (a fresh process per measur
 batch with the soft prediction of a T=100 p-d-p forward (-w 0, philox) as weights: how many instances are refused (-3), kernel time, work
 against the count's, the distribution of log2(mass), and the mean |prediction - posterior| next to marginal_gap.  ``zd`` = the batch of
 row ``cd`` at 2^28 reads per instance, with weights 0.5 and with the forward's prediction: how many brackets close, and the median and
-p99 of open_mass on those that do not."""
+p99 of open_mass on those that do not.
+
+Split mass rows (pdp_exact_mass_split; never part of the default): ``zsa`` / ``zsb`` = the 1 / 8 instances of row ``ca`` with the largest plain
+work at weights 0.5 as a batch of their own: kernel time of pdp_exact_mass and of the split call at depths 4 / 8 / 12 on the same problem
+(each after an untimed call with a budget of one read), with mass * 2^n == count and mass, true_mass and leaves equal to the plain call's
+asserted.  ``zsauto`` = the whole batch of row ``ca`` at weights 0.5: host wall time of exact.solution_mass(split='auto'), status equal and
+mass and posterior within the derived bounds of the plain call asserted; PDP_MASS_ONLY=plain / auto times that one call alone (a fresh
+process per measurement of the alternating comparison).  ``zssweep`` = the same over AUTO_MASS_STAGE1_BUDGET = 2^20 / 2^22 / 2^24 / 2^26.
+``zsd`` = the batch of row ``cd`` at weights 0.5 and 2^28 reads per stage-1 instance and per cube: how many of the plain call's open
+brackets close, the median open_mass of the rest, and whether any bracket is wider than the plain call's."""
 import io
 import json
 import logging
@@ -943,9 +952,109 @@ def run_mass(key):
                if opened.size else ""), flush=True)
 
 
+MASS_SPLIT_ROWS = ('zsa', 'zsb', 'zsauto', 'zssweep', 'zsd')
+
+
+def _mass_close(got, plain, items, what):
+    """status equal; mass and posterior of ``got`` (a split call) within the derived bounds of ``plain``'s: both lie within their own bound
+    of the exact value, the split sum with one rounding more per cube (tests/exact_mass_model.py's bounds; leaves is not returned here:
+    every leaf costs a pass that reads a literal of every clause, so leaves <= reads / clauses; at most 2^16 cubes)"""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import exact_mass_model as zm
+    assert np.array_equal(got[0], plain[0]), what + ": status differs"
+    for j, it in enumerate(items):
+        n, z, k = int(it[0]), float(plain[1][j]), int(plain[4][j]) // max(1, int(it[1])) + (1 << 16)
+        assert abs(got[1][j] - z) <= 2 * zm.mass_bound(n, k, z), what + ": mass of instance %d outside the bound" % j
+        assert (got[2][j] is None) == (plain[2][j] is None), what + ": posterior of instance %d" % j
+        if z > 0:
+            assert (np.abs(got[2][j] - plain[2][j]) * z <= 4 * zm.true_mass_bound(n, k, z)).all(), what + ": posterior of instance %d outside the bound" % j
+
+
+def run_mass_split(key):
+    """zsa / zsb: the 1 / 8 instances of row ca with the largest plain work at weights 0.5, pdp_exact_mass next to pdp_exact_mass_split at
+    depths 4 / 8 / 12.  zsauto: row ca whole at weights 0.5, host wall time of exact.solution_mass and of solution_mass(split='auto');
+    PDP_MASS_ONLY=plain / auto times that one call alone (a fresh process per measurement of the alternating comparison; 'plain' uses
+    nothing that this call added, so the same file measures an older tree).  zssweep: the same over AUTO_MASS_STAGE1_BUDGET = 2^20 .. 2^26.
+    zsd: row cd at 2^28 reads per stage-1 instance and per cube: how many open brackets close, and how wide the others stay."""
+    from pdp import exact
+    title, sub = _satisfiable_of('d' if key == 'zsd' else 'a')
+    half = [np.full(int(it[0]), 0.5, dtype=np.float32) for it in sub]
+    if key == 'zsd':
+        exact.solution_mass(sub[:8], half[:8], budget=1, split=1)
+        ms0, plain = _wall(lambda: exact.solution_mass(sub, half, budget=ZD_BUDGET))
+        ms, got = _wall(lambda: exact.solution_mass(sub, half, budget=ZD_BUDGET, split='auto', depths=True))
+        was = plain[0] == -1
+        still = was & (got[0] == -1)
+        wider = int((got[3][was] > plain[3][was] * (1 + 1e-12)).sum())         # against the plain call at 2^28, narrower than stage 1's at 2^26
+        lower = int((got[1][was] < plain[1][was] * (1 - 1e-12)).sum())
+        print("(zsd) the %d instances of %s that the deciding search answers 1, weights 0.5, budget 2^28 reads per instance / per cube: plain "
+              "solution_mass wall %.0f ms, closed %d, open %d, median open_mass %.4g;  split='auto' (stage 1 budget %d) wall %.0f ms, closed %d, "
+              "open %d: of the plain open brackets %d close, median open_mass of the rest %.4g (p99 %.4g);  brackets wider after stage 2 than "
+              "the plain call's: %d, with a lower mass: %d;  depths %s  reads %d (plain %d)"
+              % (len(sub), title, ms0, int((plain[0] == 1).sum()), int(was.sum()), float(np.median(plain[3][was])) if was.any() else 0.0,
+                 min(ZD_BUDGET, exact.AUTO_MASS_STAGE1_BUDGET), ms, int((got[0] == 1).sum()), int((got[0] == -1).sum()),
+                 int((was & (got[0] == 1)).sum()), float(np.median(got[3][still])) if still.any() else 0.0,
+                 float(np.percentile(got[3][still], 99)) if still.any() else 0.0, wider, lower, sorted(set(got[5].tolist())), int(got[4].sum()),
+                 int(plain[4].sum())), flush=True)
+        return
+    if key in ('zsauto', 'zssweep'):
+        only = os.environ.get('PDP_MASS_ONLY')
+        if only == 'plain':
+            exact.solution_mass(sub[:8], half[:8], budget=1)                         # the context, the library and the kernel are loaded
+            ms, out = _wall(lambda: exact.solution_mass(sub, half))
+            print("(zsauto, plain alone) the %d satisfiable instances of %s, weights 0.5: solution_mass wall %.1f ms  complete %d  reads %d  "
+                  "mass sum %.17g" % (len(sub), title, ms, int((out[0] == 1).sum()), int(out[4].sum()), float(out[1].sum())), flush=True)
+            return
+        exact.solution_mass(sub[:8], half[:8], budget=1, split=1)                    # the context, the library and both kernels are loaded
+        plain = None
+        for stage1 in ((1 << 20, 1 << 22, 1 << 24, 1 << 26) if key == 'zssweep' else (exact.AUTO_MASS_STAGE1_BUDGET,)):
+            exact.AUTO_MASS_STAGE1_BUDGET = stage1
+            ms, out = _wall(lambda: exact.solution_mass(sub, half, split='auto', depths=True))
+            if plain is None:
+                plain = exact.solution_mass(sub, half)
+            _mass_close(out, plain, sub, "split='auto'")
+            print("(%s%s) the %d satisfiable instances of %s, weights 0.5: solution_mass(split='auto') stage 1 budget 2^%d: wall %.1f ms  weighed "
+                  "again %d at depth %s  reads %d (plain %d);  status equal, mass and posterior within the derived bounds of the plain "
+                  "solution_mass on all %d, bit-equal mass on %d  mass sum %.17g"
+                  % (key, ', auto alone' if only else '', len(sub), title, stage1.bit_length() - 1, ms, int((out[5] > 0).sum()),
+                     sorted(set(out[5][out[5] > 0].tolist())), int(out[4].sum()), int(plain[4].sum()), len(sub), int((out[1] == plain[1]).sum()),
+                     float(out[1].sum())), flush=True)
+        return
+    work = exact.solution_mass(sub, half)[4]
+    top = np.argsort(-work, kind='stable')[:1 if key == 'zsa' else 8]
+    part = [sub[i] for i in top]
+    b = dataset.to_torch(dataset.collate_segment(part), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(part))
+    w = torch.full((p.V,), 0.5, dtype=torch.float32, device=p.device)
+    scale = 2.0 ** np.array([int(it[0]) for it in part], dtype=np.float64)
+    p.exact_mass(w, 1)                                                               # the one-time preparation is not timed
+    p.exact_mass_split(w, 1, depth=1)
+    count = p.exact_count(stats=True)[1].cpu().numpy()
+    torch.cuda.synchronize()
+    ms0, out = _event_ms(lambda: p.exact_mass(w, stats=True))
+    st0, ma0, tm0, op0, wk0, lv0 = [t.cpu().numpy() for t in out]
+    assert np.array_equal(ma0 * scale, count), "weights 0.5: mass * 2^n is not the count"
+    print("(%s) the %d instances of row ca (%s, satisfiable) with the largest mass_work at weights 0.5: pdp_exact_mass kernel %.2f ms  complete %d  "
+          "work %s  total %d  leaves total %d  log2(mass) max %.1f" % (key, len(part), title, ms0, int((st0 == 1).sum()), _q(wk0), int(wk0.sum()),
+                                                                       int(lv0.sum()), float(np.log2(ma0.max()))), flush=True)
+    for depth in SPLIT_DEPTHS:
+        ms, out = _event_ms(lambda: p.exact_mass_split(w, depth=depth, stats=True))
+        st, ma, tm, op, wk, lv, du, off, cst, cma, cop, cwk, clv = [t.cpu().numpy() for t in out]
+        assert np.array_equal(st, st0) and np.array_equal(lv, lv0) and not op.any(), "the split mass differs"
+        assert np.array_equal(ma * scale, count) and np.array_equal(ma, ma0) and np.array_equal(tm, tm0), "weights 0.5: mass * 2^n is not the count"
+        share = max(float(cwk[off[j]:off[j + 1]].max()) / max(1.0, float(wk0[j])) for j in range(len(st)))
+        print("    split depth %2d: kernel %.2f ms (%.3f of pdp_exact_mass)  cubes %d  without mass %d  reads %d (%.3f of the plain mass's)  "
+              "largest cube's share of its instance's plain work %.4f  grid %d;  mass * 2^n == count, mass, true_mass and leaves equal"
+              % (depth, ms, ms / ms0, cst.size, int((cma == 0).sum()), int(wk.sum()), float(wk.sum()) / float(wk0.sum()), share, p.exact_last_grid()),
+              flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
+        if k in MASS_SPLIT_ROWS:
+            run_mass_split(k)
+            continue
         if k in MASS_ROWS:
             run_mass(k)
             continue
