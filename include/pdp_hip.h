@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass, pdp_exact_mass_split, pdp_exact_mass_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass, pdp_exact_mass_split, pdp_exact_mass_split_cubes, pdp_exact_nearest and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -405,6 +405,47 @@ int pdp_exact_solve_learn_assume(pdp_problem *p, const float *hint, const int8_t
 int pdp_exact_min_unsat(pdp_problem *p, const float *hint, int64_t budget, int8_t *status, int32_t *cost, float *model,
                         int64_t *work, int32_t *improvements, void *stream);
 
+/* The model of every instance that is nearest to a hint, by depth-first branch and bound over pdp_exact_solve_hinted's passes with the
+ * cost on the variables and every clause hard (plain Python, normative: tests/exact_nearest_model.py).  hint [V] (may be
+ * NULL) is the point the distance is measured from: h > 0.5 true, every other value false, NaN included; NULL = all false.  penalty [V]
+ * (device int32, may be NULL = all 1) is what a variable costs where the model differs from the hint, an integer in [0, 2^20]:
+ * cost(x) = the sum of penalty[v] over the variables with x[v] != hint bit of v, a 64-bit integer; all 1 gives the Hamming distance.
+ * Outputs per instance: status = 1, cost is the minimum over the models and model attains it; 0, the instance has no model (cost -1, model
+ * all 0); -1, the budget ran out: cost and model are the best model met so far (an upper bound), or -1 and all 0 if none was met; -3, a
+ * penalty of the instance is outside [0, 2^20]: it is not searched and cost, model, work and improvements are 0.  cost [B] (int64);
+ * model [V] = a complete 0 / 1 assignment wherever cost >= 0; work [B] (may be NULL) = clause-literal reads; improvements [B] (may be NULL)
+ * = how often a better model was met.  The search of one instance:
+ *   Check pass.  It always runs, before the first budget check, and is pdp_exact_solve_hinted's: every clause is read up to and including
+ *      its first literal that is true under the hint (the whole clause if there is none), counted into work.  Every clause has one: status
+ *      1, cost 0, model = the hint, improvements 0.  Otherwise the search starts from the empty assignment with ub = infinity, dist = 0.
+ *   A pass is pdp_exact_solve's: the conflict flag, the unit requests, wmin over the open clauses that are no units.  The pending set is
+ *      assigned as there, and dist grows by penalty[v] for every unit assigned against the hint.
+ *   After the pass, in this order:
+ *      1. a conflict, a variable asked for in both polarities, or dist >= ub: prune.
+ *      2. else units were assigned: next pass.
+ *      3. else no open clause: a leaf with dist < ub.  ub = dist, improvements + 1, model = the current assignment with every unassigned
+ *         variable at its hint value (these cost nothing); ub == 0 ends the search with status 1, otherwise prune.
+ *      4. else branch: pdp_exact_solve's variable (most occurrences in the open clauses of width wmin, ties to the lower index), first
+ *         polarity the hint's, which costs nothing.
+ *   Prune is pdp_exact_solve's chronological backtracking.  Undoing a level takes what its variables had added off dist; flipping a
+ *      decision adds the variable's penalty, and if dist >= ub then, the flipped state is pruned at once, before any pass, and backtracking
+ *      goes on with this level.  Running out of levels ends the search: status 1 and cost = ub if a model was met, status 0 otherwise.
+ * The budget is checked before every pass (budget <= 0: PDP_EXACT_DEFAULT_BUDGET) and work < budget + 3 * (edges of the instance) holds.
+ * dist, ub and every sum are 64-bit integers, uniform over the wave; every reduction is an integer sum, an OR, a minimum or a maximum of
+ * unique keys: all five outputs are a function of the instance, its hint, its penalties and the budget alone.
+ *   N1  a hint that is a model: status 1, cost 0, model = hint, improvements 0, work = pdp_exact_solve_hinted's with that hint.
+ *   N2  run to its end, status is pdp_exact_solve's; model satisfies every clause and cost is the penalty sum of model != hint.
+ *   N4  the visited tree is a pruned subtree of pdp_exact_count's (the variable choice does not depend on the polarity order):
+ *       work <= pdp_exact_count's work + (edges of the instance) wherever the count completes; the extra term is the check pass.
+ *   N6  multiplying every penalty by an integer c > 0 (within 2^20) multiplies cost by c and changes no other output.
+ * The bound is dist and nothing stronger: an open clause all of whose remaining literals disagree with the hint is not charged before a
+ * pass makes it a unit, so with an uninformative hint the tree is about the count's.  There is no limit on n.
+ * R != 1 -> PDP_ERR_UNSUPPORTED; NULL status, cost or model -> PDP_ERR_INVALID.  Same stream rules; routing, LDS slab and working arrays
+ * are pdp_exact_solve's, shared with it: the penalty lives in bits 10-31 of the word that holds the hint code, and dist is restored from
+ * the trail. */
+int pdp_exact_nearest(pdp_problem *p, const float *hint, const int32_t *penalty, int64_t budget, int8_t *status, int64_t *cost,
+                      float *model, int64_t *work, int32_t *improvements, void *stream);
+
 /* Exact model counts and per-variable counts of every instance: pdp_exact_solve's search (no hints) that does not stop at the first
  * assignment under which no clause is open (plain Python, normative: tests/exact_count_model.py).  Outputs per instance:
  * status = 1, the search is complete and count [B] is the number of models, or -1, the budget ran out and count covers the part of the
@@ -667,7 +708,7 @@ int pdp_exact_min_unsat_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *c
                                     int32_t *cube_improvements, void *stream);
 
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split and pdp_exact_mass_split (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split and pdp_exact_mass_split (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

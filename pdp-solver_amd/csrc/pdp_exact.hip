@@ -34,6 +34,7 @@
 // pdp_exact_min_unsat_split (after it) cuts the branch and bound into cubes that share ub[b], the best cost any of them has found.
 // pdp_exact_mass is the counting search under a product prior: a weight per literal, a two-sided bracket at the budget;
 // pdp_exact_mass_split (the last kernels) cuts it into cubes as the count's split does, and its cubes share nothing either.
+// pdp_exact_nearest (behind pdp_exact_min_unsat) is the branch and bound with the cost on the variables: the model nearest to a hint.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -829,6 +830,231 @@ int exm_launch(pdp_problem *p, const float *hint, int64_t budget, int8_t *status
     xp.status = status; xp.cost = cost; xp.model = model; xp.work = work; xp.improvements = improvements; xp.hint = hint;
     xp.h = ex_hbm(p);
     return ex_launch_persistent(p, k_exact_min, xp, (int64_t)p->B, p->ex_lds_bytes, ST(stream));
+}
+
+// ---- pdp_exact_nearest: the model nearest to a hint by depth-first branch and bound over ex_search's passes ------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_nearest_model.py).  The cost is on the variables and every
+// clause is hard: ex_search_near is ex_search's loop from the same blocks with `dist`, the penalty sum of the assigned variables that
+// differ from the hint, pruned against `ub`, the cost of the best model met.  The state is ex_search's, array for array: the hint code
+// lives in bits 8-9 of pend[v] and the penalty in bits 10-31 next to it (ex_assign_pending<.., true> and ex_pick leave them alone), the
+// incumbent in the output model in HBM, and dist is at all times the sum over the trail of exd_cost -- a first decision takes the hint's
+// value and costs nothing, its flip costs the penalty -- so an undo subtracts the wave sum over the entries it clears and no per-level
+// array is kept.  The slab, the routing, the launch LDS size and the HBM arrays are therefore k_exact's, from ex_prepare.
+constexpr uint32_t EXD_PEN_SHIFT = 10;          // bits 10-31 of pend[v]: the penalty of v
+constexpr int32_t EXD_MAX_PENALTY = 1 << 20;
+constexpr int64_t EXD_INF = 0x7fffffffffffffffll;               // ub before the first model
+
+struct ExdParams {
+    const int32_t *order;       // as ExParams
+    int nbig, B;
+    uint32_t *next;
+    int64_t budget;
+    int8_t *status; int64_t *cost; float *model; int64_t *work; int32_t *improvements;
+    ExHbm h;
+    const float *hint;          // [V] the point the distance is measured from (NULL: all false)
+    const int32_t *penalty;     // [V] (NULL: all 1)
+};
+
+__device__ __forceinline__ int64_t ex_sum64(int64_t x)
+{
+    for (int o = 32; o > 0; o >>= 1) x += (int64_t)__shfl_xor((long long)x, o);
+    return x;
+}
+
+// what the assigned variable u adds to dist: its penalty where its value is not the hint's
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ int64_t exd_cost(const ExInst<LitT, PtrT> &X, int u)
+{
+    const uint32_t word = X.pend[u];
+    return X.val[u] != ((word >> EX_HINT_SHIFT) & 3u) ? (int64_t)(word >> EXD_PEN_SHIFT) : (int64_t)0;
+}
+
+// this lane's share of dist over trail[from .. tlen), in chunks of 64; the caller takes the wave sum
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ int64_t exd_span(const ExInst<LitT, PtrT> &X, int from, int tlen)
+{
+    int64_t s = 0;
+    for (int i = from + (int)threadIdx.x; i < tlen; i += EX_NT) s += exd_cost(X, X.trail[i]);
+    return s;
+}
+
+// ex_backtrack's hook of the nearest-model search: what the entries an undo clears had added to dist, a share per lane, read by the
+// lane that clears the entry before it does
+struct ExdCredit {
+    int64_t undone;
+    __device__ __forceinline__ void load(int) {}
+    template <typename LitT, typename PtrT>
+    __device__ __forceinline__ void undo(const ExInst<LitT, PtrT> &X, int from, int tlen) { undone += exd_span(X, from, tlen); }
+    __device__ __forceinline__ void open(int) const {}
+};
+
+// Backtracking of the nearest-model search: ex_backtrack, dist lowered by what was undone and raised by the flipped decision's penalty.
+// A flip that reaches ub is pruned at once, without a pass: the level is undone by the next round (as exz_backtrack does on a literal
+// of weight 0).  Returns false when no level is left.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ __forceinline__ bool exd_backtrack(const ExInst<LitT, PtrT> &X, int &level, int &tlen, int64_t &dist, int64_t ub)
+{
+    bool resumed;
+    do {
+        ExdCredit credit{0};
+        resumed = ex_backtrack<HBM>(X, level, tlen, credit);
+        dist -= ex_sum64(credit.undone);
+        if (!resumed) break;
+        const int v = (int)(X.dvar[level] & 0x7fffffffu);           // the flipped decision: behind ex_backtrack's last barrier
+        dist += (int64_t)(X.pend[v] >> EXD_PEN_SHIFT);
+    } while (dist >= ub);
+    return resumed;
+}
+
+// The nearest-model search of one instance by the calling wave.  pend[v] carries the hint's code (1 true, 2 false: never 0) and the
+// penalty; `model` points at the instance's slice of the output.  The check pass (ex_search's, over the hint) always runs, before the
+// first budget check.  Returns 1 (*cost_out is the minimum and model attains it), 0 (no model: *cost_out = -1, model all 0) or -1
+// (budget spent: *cost_out and model are the best met, or -1 and all 0).  dist, ub and every sum are 64-bit integers, uniform over the wave.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_near(const ExInst<LitT, PtrT> &X, int64_t budget, float *model, int64_t *work_out, int64_t *cost_out, int *improved_out)
+{
+    const int lane = (int)threadIdx.x;
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0, improved = 0;
+    int64_t work = 0, dist = 0, ub = EXD_INF;
+    int result = -1;
+    ExNoCredit none;
+    {
+        for (int v = lane; v < X.n; v += EX_NT) X.val[v] = (uint8_t)((X.pend[v] >> EX_HINT_SHIFT) & 3u);
+        ex_sync<HBM>();
+        int reads = 0, open = 0;
+        for (int c = lane; c < X.m; c += EX_NT) {
+            const int a = (int)X.cptr[c], z = (int)X.cptr[c + 1];
+            int sat = 0, k = a;
+            for (; k < z; ++k) {
+                const uint32_t L = X.lit[k];
+                if (X.val[L >> 1] == 1u + (L & 1u)) { sat = 1; ++k; break; }
+            }
+            reads += k - a;
+            open |= !sat;
+        }
+        work += ex_sum(reads);
+        if (__ballot(open) == 0ull) {
+            for (int v = lane; v < X.n; v += EX_NT) model[v] = X.val[v] == 1 ? 1.0f : 0.0f;
+            *work_out = work; *cost_out = 0; *improved_out = 0;
+            return 1;
+        }
+        ex_sync<HBM>();                                             // every lane has read val before it is cleared
+        for (int v = lane; v < X.n; v += EX_NT) { X.val[v] = 0; model[v] = 0.0f; }
+        ex_sync<HBM>();
+    }
+    for (;;) {
+        if (work >= budget) break;
+        const ExPass P = ex_propagate(X);
+        work += ex_sum(P.reads);
+        bool prune = __ballot(P.conflict) != 0ull;
+        const bool any_unit = __ballot(P.unit) != 0ull;
+        if (any_unit) {
+            ex_sync<HBM>();
+            const int from = tlen;
+            const bool both = ex_assign_pending<HBM, true>(X, tlen);
+            prune = prune || both;
+            dist += ex_sum64(exd_span(X, from, tlen));              // the units assigned against the hint
+        }
+        prune = prune || dist >= ub;
+        int wmin = INF;
+        if (!prune) {
+            if (any_unit) continue;
+            wmin = ex_min(P.wmin);
+            if (wmin == INF) {
+                // a leaf below ub: the new incumbent; an unassigned variable takes the hint's value, which costs nothing
+                ub = dist;
+                ++improved;
+                for (int v = lane; v < X.n; v += EX_NT) {
+                    const uint32_t x = X.val[v];
+                    model[v] = (x ? x : ((X.pend[v] >> EX_HINT_SHIFT) & 3u)) == 1u ? 1.0f : 0.0f;
+                }
+                if (ub == 0) { result = 1; break; }
+                prune = true;
+            }
+        }
+        if (prune) {
+            // out of levels: ub is the minimum, or there is no model
+            if (!exd_backtrack<HBM>(X, level, tlen, dist, ub)) { result = ub == EXD_INF ? 0 : 1; break; }
+            continue;
+        }
+        const unsigned long long best = ex_branch<HBM, EX_PHASE_INCUMBENT>(X, wmin, work);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        ex_decide<HBM, false>(X, ExCube<false>{}, best, level, tlen, none);
+    }
+    *work_out = work; *cost_out = ub == EXD_INF ? (int64_t)-1 : ub; *improved_out = improved;
+    return result;
+}
+
+// copy the instance (ex_fill), clear the state (pend starts as the hint's codes and the penalties), search, write the results
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_near(const ExdParams &xp, const Inst &I, ExInst<LitT, PtrT> X)
+{
+    const int lane = (int)threadIdx.x;
+    ex_fill<HBM>(I, X);
+    for (int v = lane; v < I.n; v += EX_NT) {
+        const uint32_t code = (xp.hint && xp.hint[I.v0 + v] > 0.5f) ? 1u : 2u;          // NaN compares false
+        const uint32_t q = xp.penalty ? (uint32_t)xp.penalty[I.v0 + v] : 1u;
+        X.val[v] = 0; X.pend[v] = (q << EXD_PEN_SHIFT) | (code << EX_HINT_SHIFT); X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+    }
+    ex_sync<HBM>();
+    int64_t work = 0, cost = 0;
+    int improved = 0;
+    const int st = ex_search_near<HBM>(X, xp.budget, xp.model + I.v0, &work, &cost, &improved);
+    if (lane == 0) {
+        xp.status[I.b] = (int8_t)st;
+        xp.cost[I.b] = cost;
+        if (xp.work) xp.work[I.b] = work;
+        if (xp.improvements) xp.improvements[I.b] = improved;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next instance
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_nearest(PView pv, ExdParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        int i = 0;
+        if (threadIdx.x == 0) i = (int)atomicAdd(xp.next, 1u);
+        i = __shfl(i, 0);
+        if (i >= xp.B) break;
+        const Inst I = load_inst(pv, xp.order[i]);
+        // not searched: a penalty outside [0, 2^20] (-3), decided for the whole wave by a ballot before anything is bound
+        int bad = 0;
+        if (xp.penalty) {
+            for (int v = (int)threadIdx.x; v < I.n; v += EX_NT) { const int32_t q = xp.penalty[I.v0 + v]; bad |= q < 0 || q > EXD_MAX_PENALTY; }
+        }
+        if (__ballot(bad) != 0ull) {
+            // as k_exact_count's arm: it ends in the barrier every arm of the loop ends in and falls through to the end of the loop
+            // body, so the wave is whole again before the shuffle that hands out the next instance
+            for (int v = (int)threadIdx.x; v < I.n; v += EX_NT) xp.model[I.v0 + v] = 0.0f;
+            if (threadIdx.x == 0) {
+                xp.status[I.b] = (int8_t)-3;
+                xp.cost[I.b] = 0;
+                if (xp.work) xp.work[I.b] = 0;
+                if (xp.improvements) xp.improvements[I.b] = 0;
+            }
+            ex_sync<false>();
+        } else if (i < xp.nbig) {
+            ex_solve_near<true>(xp, I, ex_bind_hbm(xp.h, I));
+        } else {
+            ex_solve_near<false>(xp, I, ex_bind_lds(ex_slab, I));
+        }
+    }
+}
+
+// routing, order, slab size and working arrays are ex_prepare's, shared with pdp_exact_solve: this search adds no array of its own
+int exd_launch(pdp_problem *p, const float *hint, const int32_t *penalty, int64_t budget, int8_t *status, int64_t *cost, float *model,
+               int64_t *work, int32_t *improvements, void *stream)
+{
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    ExdParams xp;
+    xp.order = p->ex_order; xp.nbig = p->ex_nbig; xp.B = p->B; xp.next = p->ex_next;
+    xp.budget = ex_budget(budget);
+    xp.status = status; xp.cost = cost; xp.model = model; xp.work = work; xp.improvements = improvements;
+    xp.hint = hint; xp.penalty = penalty;
+    xp.h = ex_hbm(p);
+    return ex_launch_persistent(p, k_exact_nearest, xp, (int64_t)p->B, p->ex_lds_bytes, ST(stream));
 }
 
 // ---- pdp_exact_count: exact model counts and per-variable counts by the same passes, without stopping at the first model ---------------
@@ -3924,6 +4150,17 @@ extern "C" int pdp_exact_min_unsat(pdp_problem *p, const float *hint, int64_t bu
         return PDP_ERR_UNSUPPORTED;
     }
     return exm_launch(p, hint, budget, status, cost, model, work, improvements, stream);
+}
+
+extern "C" int pdp_exact_nearest(pdp_problem *p, const float *hint, const int32_t *penalty, int64_t budget, int8_t *status, int64_t *cost,
+                                 float *model, int64_t *work, int32_t *improvements, void *stream)
+{
+    PDP_REQUIRE(p && status && cost && model, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_nearest: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exd_launch(p, hint, penalty, budget, status, cost, model, work, improvements, stream);
 }
 
 extern "C" int pdp_exact_count(pdp_problem *p, int64_t budget, int8_t *status, double *count, double *true_count, int64_t *work, int64_t *leaves,

@@ -28,7 +28,10 @@ probability that rounding every variable independently with a soft prediction gi
 and, where the budget ran out, the mass of the part of the tree not visited (pdp_exact_mass).
 ``solution_mass(split=)`` spreads that search over 2^depth waves as well (pdp_exact_mass_split): cube masses and open
 masses add, the budget applies per cube, so a bracket is tightened by 2^depth times the reads.  ``mass_logit_gradient`` is the exact
-gradient of -ln(mass) in the logits of the prediction, from the posterior.
+gradient of -ln(mass) in the logits of the prediction, from the posterior.  ``nearest_model`` measures an assignment instead: the model
+with the fewest variables (or the least sum of per-variable penalties) different from it, by branch and bound with every clause hard
+(pdp_exact_nearest) -- how far PDP's assignment was from a solution, and which one; ``map_penalties`` turns a soft
+prediction into the hint and penalties under which that model is the most probable one.
 """
 
 import numpy as np
@@ -501,6 +504,90 @@ def min_unsat(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, spl
             models[i] = model[off:off + n].copy()
             off += n
     return (status, cost, models, work, used) if depths else (status, cost, models, work)
+
+
+MAX_PENALTY = 1 << 20        # pdp_exact_nearest: a penalty is an integer in [0, MAX_PENALTY]
+
+
+def map_penalties(weights, scale=1024):
+    """(hints float32, penalties int32) of a soft prediction ``weights`` (probabilities of the variables being true, any shape) for
+    nearest_model: hint = p > 0.5 and penalty = min(2^20, round(scale * |log p - log(1 - p)|)), computed in float64, with p = 0 or 1
+    giving 2^20.  With these the nearest model is the model of highest probability under the product prior, up to the quantisation.
+    NaN or a value outside [0, 1] raises."""
+    p = np.asarray(weights, dtype=np.float64)
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("weights must be probabilities in [0, 1] without NaN")
+    if not scale > 0:
+        raise ValueError("scale must be positive, got %r" % (scale,))
+    with np.errstate(divide='ignore'):
+        gap = np.abs(np.log(p) - np.log1p(-p))
+    pen = np.where(np.isfinite(gap), np.minimum(np.rint(scale * np.where(np.isfinite(gap), gap, 0.0)), MAX_PENALTY), MAX_PENALTY)
+    return (p > 0.5).astype(np.float32), pen.astype(np.int32)
+
+
+def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges=MAX_EDGES):
+    """The model of every loader item (as solve_items takes them) nearest to its hint, by branch and bound (pdp_exact_nearest; DESIGN.md
+    §9.15).  Returns numpy (status int8 [N]: 1 cost is the minimum over the models, 0 the instance has no model, -1 the budget ran out and
+    cost is that of the best model met, -1 if none was, -3 a penalty of the instance is outside [0, 2^20]; cost int64 [N]: the penalties
+    of the variables where the model differs from the thresholded hint, summed; models: per instance a float32 0/1 array of n_i values,
+    all 0 where cost is not >= 0 or status is -3; work int64 [N]).
+    ``hints``: per instance an array of n_i values or None (> 0.5 true, every other value false, NaN included; None: all false), or None
+    for all.  ``penalties``: per instance an integer array of n_i values or None (all 1), or None for all: the Hamming distance."""
+    native.require_gpu()
+    for name, per in (('hints', hints), ('penalties', penalties)):
+        if per is None:
+            continue
+        if len(per) != len(items):
+            raise ValueError("%s: one entry per instance (%d), got %d" % (name, len(items), len(per)))
+        for it, h in zip(items, per):
+            if h is not None and np.asarray(h).size != int(it[0]):
+                raise ValueError("%s: instance %r has %d variables, its %s %d values" % (name, it[5], int(it[0]), name, np.asarray(h).size))
+    if penalties is not None:
+        for it, q in zip(items, penalties):
+            if q is not None and not np.issubdtype(np.asarray(q).dtype, np.integer):
+                raise ValueError("penalties: instance %r has penalties of type %s, not integers" % (it[5], np.asarray(q).dtype))
+    device = torch.device('cuda:0') if device is None else torch.device(device)
+    N = len(items)
+    status = np.ones(N, dtype=np.int8)
+    cost = np.zeros(N, dtype=np.int64)
+    work = np.zeros(N, dtype=np.int64)
+    models = [None] * N
+    for seg in _segments(items, max_edges):
+        part = [items[i] for i in seg]
+        flat = [np.zeros(int(it[0]), dtype=np.float32) if hints is None or hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
+                for i, it in zip(seg, part)]
+        pens = None
+        if penalties is not None:
+            pens = [np.ones(int(it[0]), dtype=np.int64) if penalties[i] is None else np.asarray(penalties[i]).astype(np.int64).reshape(-1)
+                    for i, it in zip(seg, part)]
+        if sum(int(it[2].shape[1]) for it in part) == 0:
+            # no literal anywhere (and no problem to build: the layout needs an edge): without a clause the hint itself is the nearest
+            # model, with an (empty) clause there is none
+            for j, (i, it, h) in enumerate(zip(seg, part, flat)):
+                if pens is not None and ((pens[j] < 0) | (pens[j] > MAX_PENALTY)).any():
+                    status[i], models[i] = -3, np.zeros(int(it[0]), dtype=np.float32)
+                elif int(it[1]) > 0:
+                    status[i], cost[i], models[i] = 0, -1, np.zeros(int(it[0]), dtype=np.float32)
+                else:
+                    models[i] = (h > 0.5).astype(np.float32)
+            continue
+        with torch.cuda.device(device):
+            prob = _problem(part, device)
+            hint = torch.from_numpy(np.concatenate(flat)).to(device)
+            pen = None
+            if pens is not None:
+                # a value that does not fit int32 is out of range either way: -1 stands for it
+                allp = np.concatenate(pens)
+                pen = torch.from_numpy(np.where((allp < 0) | (allp > MAX_PENALTY), -1, allp).astype(np.int32)).to(device)
+            st, co, model, wk = [t.cpu().numpy() for t in prob.exact_nearest(hint, pen, budget)]
+        del prob
+        off = 0
+        for j, (i, it) in enumerate(zip(seg, part)):
+            n = int(it[0])
+            status[i], cost[i], work[i] = st[j], co[j], wk[j]
+            models[i] = model[off:off + n].copy()
+            off += n
+    return status, cost, models, work
 
 
 def count_split(prob, part, budget, split, device):

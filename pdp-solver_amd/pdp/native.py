@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_min_unsat', 'pdp_exact_count', 'pdp_exact_solve_split', 'pdp_exact_split_cubes',
     'pdp_exact_count_split', 'pdp_exact_count_split_cubes', 'pdp_exact_models_at',
     'pdp_exact_min_unsat_split', 'pdp_exact_min_unsat_split_cubes', 'pdp_exact_mass',
-    'pdp_exact_mass_split', 'pdp_exact_mass_split_cubes',
+    'pdp_exact_mass_split', 'pdp_exact_mass_split_cubes', 'pdp_exact_nearest',
 ]
 
 
@@ -507,6 +507,38 @@ class Problem(object):
                                         ptr(model), ptr(work), ptr(improvements), _stream()))
         return (status, cost, model, work, improvements) if stats else (status, cost, model, work)
 
+    def exact_nearest(self, hints=None, penalties=None, budget=0, stats=False):
+        """The model of every instance nearest to ``hints`` (pdp_exact_nearest): (status int8 [B]: 1 cost is the minimum over the models
+        and model attains it, 0 the instance has no model, -1 the budget ran out and cost / model are the best model met so far, cost -1
+        and model all 0 if none was, -3 a penalty of the instance is outside [0, 2^20] and it was not searched; cost int64 [B]: the sum of
+        the penalties of the variables where model differs from the thresholded hints; model float32 [V]; work int64 [B]), plus
+        improvements int32 [B] with ``stats``: how often a better model was met.  ``hints`` (float32, V elements, on the problem's
+        device): > 0.5 true and every other value false, NaN included; None: all false.  ``penalties`` (int32, V elements, on the
+        problem's device): what a variable costs where it differs; None: all 1, the Hamming distance.  ``budget`` as in exact_solve.
+        Asynchronous on the current stream."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads (0: the library default), got %r" % (budget,))
+        for name, t, dtype in (('hints', hints, torch.float32), ('penalties', penalties, torch.int32)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != dtype or t.numel() != self.V:
+                raise ValueError("%s must be a %s tensor of %d elements (one per variable), got %s"
+                                 % (name, dtype, self.V, '%s of %d' % (t.dtype, t.numel()) if torch.is_tensor(t) else type(t).__name__))
+            if t.device != self.device:
+                raise ValueError("%s must live on %s, got %s" % (name, self.device, t.device))
+        if hints is not None:
+            hints = hints.reshape(-1).contiguous()
+        if penalties is not None:
+            penalties = penalties.reshape(-1).contiguous()
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        cost = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        model = torch.empty(self.V, dtype=torch.float32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        improvements = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        check(lib().pdp_exact_nearest(self._h, ptr(hints, torch.float32, self.V, 'hints'), ptr(penalties, torch.int32, self.V, 'penalties'),
+                                      C.c_int64(int(budget)), ptr(status), ptr(cost), ptr(model), ptr(work), ptr(improvements), _stream()))
+        return (status, cost, model, work, improvements) if stats else (status, cost, model, work)
+
     def exact_min_unsat_split(self, budget=0, hints=None, depth=None, stats=False):
         """exact_min_unsat(hints) with the search of instance b spread over 2^depth[b] waves that share the best cost found so far
         (pdp_exact_min_unsat_split): (status, cost, model, work) as exact_min_unsat's.  With a ``budget`` -- it applies to every cube -- that
@@ -877,7 +909,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split and exact_mass_split (their cube kernels), exact_min_unsat, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split and exact_mass_split (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

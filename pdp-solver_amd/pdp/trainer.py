@@ -179,7 +179,12 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         "mass_work"; a row of more than 1023 variables or with a prediction outside [0, 1] stays as it is.  After Walk-SAT the prediction
         is 0/1, so the mass is 1 or 0 and costs one descent.  With config['complete_mass_split'] (a depth 0..16, or -1: exact.mass_split's
         'auto') that search runs with every row spread over 2^depth waves (pdp_exact_mass_split): the budget applies per cube, "mass_work" is
-        the sum over the cubes, and a row weighed at a depth above 0 gains "mass_split_depth" after "mass_work"."""
+        the sum over the cubes, and a row weighed at a depth above 0 gains "mass_split_depth" after "mass_work".  With
+        config['complete_nearest'] every row whose "complete" is 1 gains "nearest" (pdp_exact_nearest within the same budget from the
+        same slice of the prediction, all penalties 1: the fewest variables in which a model differs from PDP's assignment; left out
+        where no model was met within the budget), "nearest_proved" (1: that is the minimum over all models, 0: an upper bound or
+        nothing), "nearest_solution" (that model, in the format of "solution") and "nearest_work"; a row PDP solved costs one check pass
+        and gets "nearest" 0."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -322,6 +327,23 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                         row['mass_split_depth'] = int(zdepth[k])
                 if hasattr(self, '_mass_stats'):
                     self._mass_stats[0] += int((st == 1).sum()); self._mass_stats[1] += len(sat_rows)
+        if self._config.get('complete_nearest'):
+            # the satisfiable rows, once more, as one batch of their own: how far PDP's assignment was from a model, and from which one
+            from pdp import exact
+            sat_rows = [i for i in range(len(rows)) if status[i] == 1]
+            if sat_rows:
+                items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
+                pred = hint.cpu().numpy()
+                st, cost, models, nwork = exact.nearest_model([items[i] for i in sat_rows], [pred[offs[i]:offs[i + 1]] for i in sat_rows],
+                                                              budget=budget, device=hint.device)
+                for k, i in enumerate(sat_rows):
+                    row = rows[i]
+                    if cost[k] >= 0:
+                        row['nearest'] = int(cost[k])
+                    row['nearest_proved'] = int(st[k] == 1)
+                    row['nearest_solution'], row['nearest_work'] = models[k].astype(int).tolist(), int(nwork[k])
+                if hasattr(self, '_nearest_stats'):
+                    self._nearest_stats[0] += int((st == 1).sum()); self._nearest_stats[1] += len(sat_rows)
         if hasattr(self, '_complete_stats'):
             for k, s in enumerate((1, 0, -1)):
                 self._complete_stats[k] += int((status == s).sum())

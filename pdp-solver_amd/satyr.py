@@ -37,7 +37,10 @@ model); left out where the mass is 0) and "mass_work".  After Walk-SAT (``-w`` a
 costs one descent: the flag is meant for runs whose prediction is soft (``-w 0``); ``--complete-mass-split N`` (with ``--complete-mass``)
 spreads that search over 2^N waves per row (pdp_exact_mass_split; -1: a plain first stage, then the rows that ran out once more at a depth
 chosen from their number): the budget applies per cube, so a bracket is tightened by 2^N times the reads, "mass_work" is summed over the
-cubes, and "mass_split_depth" appears on the rows weighed at a depth above 0.
+cubes, and "mass_split_depth" appears on the rows weighed at a depth above 0; ``--complete-nearest`` (with ``--complete``) gives every
+satisfiable row "nearest", the fewest variables in which a model of the instance differs from the model's own assignment
+(pdp_exact_nearest, branch and bound from that assignment; left out where no model was met within the budget), "nearest_proved" (1 / 0: the
+budget ran out and it is an upper bound), "nearest_solution" (that model) and "nearest_work"; a row PDP solved gets "nearest" 0.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -89,6 +92,7 @@ def run(config, logger, output):
     solver._count_stats = [0, 0]                        # counts completed, rows asked (this rank's units)
     solver._sample_stats = [0, 0]                       # rows sampled, rows asked (this rank's units)
     solver._mass_stats = [0, 0]                         # solution masses proved, rows asked (this rank's units)
+    solver._nearest_stats = [0, 0]                      # nearest models proved, rows asked (this rank's units)
     say("Starting the prediction phase...")
     sink, owned = _open_output(output)
     try:
@@ -103,7 +107,9 @@ def run(config, logger, output):
         counted = "; models counted for %d of %d" % tuple(solver._count_stats) if config.get('complete_count') else ""
         sampled = "; sampled %d of %d" % tuple(solver._sample_stats) if config.get('complete_sample') else ""
         massed = "; solution mass for %d of %d" % tuple(solver._mass_stats) if config.get('complete_mass') else ""
-        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s%s%s%s" % (tuple(solver._complete_stats) + (proved, counted, sampled, massed)))
+        neared = "; nearest model proved for %d of %d" % tuple(solver._nearest_stats) if config.get('complete_nearest') else ""
+        say("complete search: satisfiable %d, unsatisfiable %d, undecided %d%s%s%s%s%s"
+            % (tuple(solver._complete_stats) + (proved, counted, sampled, massed, neared)))
     return solver
 
 
@@ -181,6 +187,10 @@ def main(argv=None):
                         'every satisfiable row over 2^N waves (pdp_exact_mass_split), N from 0 to 16, or -1: a plain first stage, then the rows '
                         'that ran out of its reads once more at a depth that fills the GPU; the budget applies per cube, "mass_work" is summed '
                         'over the cubes, "mass_split_depth" on the rows weighed at a depth above 0', type=int, default=None)
+    parser.add_argument('--complete-nearest', dest='complete_nearest', help='With --complete: every satisfiable row gains "nearest", the fewest '
+                        'variables in which a model of the instance differs from the model\'s assignment (pdp_exact_nearest, branch and bound from '
+                        'that assignment, --complete-budget reads; left out where no model was met), "nearest_proved" (0: the budget ran out, an '
+                        'upper bound), "nearest_solution" and "nearest_work"; a row PDP solved gets "nearest" 0', action='store_true')
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -199,6 +209,8 @@ def main(argv=None):
         parser.error("--complete-count counts the models of the rows --complete satisfies: give --complete as well")
     if args['complete_mass'] and not args['complete']:
         parser.error("--complete-mass weighs the models of the rows --complete satisfies: give --complete as well")
+    if args['complete_nearest'] and not args['complete']:
+        parser.error("--complete-nearest measures the rows --complete satisfies: give --complete as well")
     if args['complete_split'] is not None:
         if not args['complete']:
             parser.error("--complete-split spreads the search of --complete: give --complete as well")

@@ -83,6 +83,12 @@ against the count's, the distribution of log2(mass), and the mean |prediction - 
 row ``cd`` at 2^28 reads per instance, with weights 0.5 and with the forward's prediction: how many brackets close, and the median and
 p99 of open_mass on those that do not.
 
+Nearest rows (pdp_exact_nearest; never part of the default): ``na`` / ``nd`` = the batches of rows ``ca`` / ``cd`` (``nd`` at 2^28 reads per
+instance for both searches), the hint being the assignment of one T=100 p-d-p forward (-w 100, philox) as in row ``ha``, all penalties 1:
+pdp_exact_count next to pdp_exact_nearest on the same problem, one timed call each after a call with a budget of one read; kernel time,
+reads against the count's (work <= the count's + edges asserted on every complete count), how many rows are proved, end at the budget
+with an upper bound or with nothing found, the distribution of the distance, and the unsat_clauses of PDP's assignment next to it.
+
 Split mass rows (pdp_exact_mass_split; never part of the default): ``zsa`` / ``zsb`` = the 1 / 8 instances of row ``ca`` with the largest plain
 work at weights 0.5 as a batch of their own: kernel time of pdp_exact_mass and of the split call at depths 4 / 8 / 12 on the same problem
 (each after an untimed call with a budget of one read), with mass * 2^n == count and mass, true_mass and leaves equal to the plain call's
@@ -952,6 +958,66 @@ def run_mass(key):
                if opened.size else ""), flush=True)
 
 
+NEAREST_ROWS = ('na', 'nd')
+ND_BUDGET = 1 << 28
+
+
+def run_nearest(key):
+    """the satisfiable instances of row a (na) or d (nd, 2^28 reads per instance) as a batch of their own, the hint the assignment of one
+    T=100 -w 100 p-d-p forward as in row ha: pdp_exact_nearest next to pdp_exact_count on the same problem.  Every timed call follows a
+    call with a budget of one read, which does the one-time preparation."""
+    from pdp import exact
+    title, make = ROWS[key[1:]]
+    items = make()
+    pred = np.concatenate([g[0].cpu().numpy() for g in _pdp_forward(items)]).astype(np.float32)
+    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in items])])
+    assert pred.size == voff[-1], "the forward's variables are not the items'"
+    status = exact.solve_items(items)[0]
+    pick = np.nonzero(status == 1)[0]
+    sub = [items[i] for i in pick]
+    b = dataset.to_torch(dataset.collate_segment(sub), torch.device('cuda:0'))
+    q = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(sub))
+    hint = torch.from_numpy(np.concatenate([pred[voff[i]:voff[i + 1]] for i in pick])).to(q.device)
+    soff = np.concatenate([[0], np.cumsum([int(it[0]) for it in sub])])
+    edges = np.array([int(it[2].shape[1]) for it in sub], dtype=np.int64)
+    budget = ND_BUDGET if key == 'nd' else 0
+    unsat = q.cnf_eval(hint.contiguous())[1].cpu().numpy().reshape(-1).astype(np.int64)
+    q.exact_count(1)
+    ms0, c = _event_ms(lambda: q.exact_count(budget, stats=True))
+    cst, _, _, cwk, _ = [t.cpu().numpy() for t in c]
+    q.exact_nearest(hint, None, 1)
+    ms1, z = _event_ms(lambda: q.exact_nearest(hint, None, budget, stats=True))
+    st, cost, model, wk, imp = [t.cpu().numpy() for t in z]
+    counted = cst == 1
+    assert (wk[counted] <= cwk[counted] + edges[counted]).all(), "N4: more reads than the count's plus the check pass"
+    assert (st != 0).all() and (st != -3).all(), "a satisfiable instance without a model, or refused"
+    found = cost >= 0
+    h = hint.cpu().numpy() > 0.5
+    ham = np.array([int(((model[soff[k]:soff[k + 1]] > 0.5) != h[soff[k]:soff[k + 1]]).sum()) for k in range(len(sub))])
+    assert (q.cnf_eval(z[2].contiguous())[0].cpu().numpy().reshape(-1)[found] == 1).all(), "a model returned leaves a clause unsatisfied"
+    assert (ham[found] == cost[found]).all(), "cost is not the Hamming distance of the model returned"
+    assert ((cost == 0) == (unsat == 0))[found].all(), "distance 0 is not exactly the rows PDP solved"
+    proved, upper, nothing = st == 1, (st == -1) & found, (st == -1) & ~found
+    far = found & (cost > 0)
+    print("(%s) the %d instances of %s that the deciding search answers 1, hints = p-d-p forward T=100 -w 100 philox (PDP solved %d), budget %s: "
+          "pdp_exact_nearest kernel %.2f ms (pdp_exact_count %.2f ms, ratio %.3f)  proved %d  upper bound %d  nothing found %d (the count: "
+          "complete %d, at the budget %d)  work %s  total %d against the count's %d (ratio %.3f; over the %d rows both finish: %.3f)  "
+          "improvements %s  N4 holds on the %d complete counts"
+          % (key, len(sub), title, int((unsat == 0).sum()), '2^28' if budget else '2^32', ms1, ms0, ms1 / ms0, int(proved.sum()), int(upper.sum()),
+             int(nothing.sum()), int(counted.sum()), int((cst == -1).sum()), _q(wk), int(wk.sum()), int(cwk.sum()), float(wk.sum()) / max(1.0, float(cwk.sum())),
+             int((counted & proved).sum()), float(wk[counted & proved].sum()) / max(1.0, float(cwk[counted & proved].sum())), _q(imp), int(counted.sum())),
+          flush=True)
+    if found.any():
+        print("    nearest over the %d rows with a model: %s  histogram by fives: %s;  over the proved alone: %s"
+              % (int(found.sum()), _q(cost[found]), '  '.join('%d-%d: %d' % (5 * v, 5 * v + 4, k) for v, k in enumerate(np.bincount(cost[found] // 5)) if k),
+                 _q(cost[proved]) if proved.any() else "-"), flush=True)
+    if far.any():
+        print("    unsat_clauses of PDP's assignment next to its distance, over the %d rows with a distance above 0: unsat_clauses %s;  "
+              "unsat_clauses / nearest %s;  rows with fewer broken clauses than wrong variables %d, as many %d, more %d"
+              % (int(far.sum()), _q(unsat[far]), _q(unsat[far] / cost[far]), int((unsat[far] < cost[far]).sum()), int((unsat[far] == cost[far]).sum()),
+                 int((unsat[far] > cost[far]).sum())), flush=True)
+
+
 MASS_SPLIT_ROWS = ('zsa', 'zsb', 'zsauto', 'zssweep', 'zsd')
 
 
@@ -1052,6 +1118,9 @@ def run_mass_split(key):
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
+        if k in NEAREST_ROWS:
+            run_nearest(k)
+            continue
         if k in MASS_SPLIT_ROWS:
             run_mass_split(k)
             continue
