@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass, pdp_exact_mass_split, pdp_exact_mass_split_cubes, pdp_exact_nearest and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass, pdp_exact_mass_split, pdp_exact_mass_split_cubes, pdp_exact_nearest, pdp_exact_nearest_split, pdp_exact_nearest_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -707,8 +707,64 @@ int pdp_exact_min_unsat_split(pdp_problem *p, const float *hint, const int8_t *d
 int pdp_exact_min_unsat_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int32_t *cube_cost, int64_t *cube_work,
                                     int32_t *cube_improvements, void *stream);
 
+/* pdp_exact_nearest with the search of every instance spread over 2^depth[b] waves that share one 64-bit word, the cost of the best
+ * model found so far (plain Python, normative: tests/exact_nearest_split_model.py).  Same passes, same bound, same
+ * branching rule, penalties and thresholding as pdp_exact_nearest; same cubes as pdp_exact_solve_split: cube `index` of the 2^depth
+ * cubes of an instance is that search where the decision of every level L <= depth is pinned -- the hint's polarity if bit
+ * (index >> (depth - L)) & 1 is 0, else the other one -- and the level counts as already flipped, so backtracking pops through it and
+ * ends the cube.  A pinned decision against the hint adds its penalty to dist at once; if dist >= live then, the cube ends before any pass.
+ *   Check.  Once per instance, in a kernel of its own before the cubes.  A penalty outside [0, 2^20]: status -3, nothing is searched,
+ *      every other output is 0 (start_cost -1).  Otherwise pdp_exact_nearest's check pass over the thresholded hint, its reads to chk:
+ *      a model -> ub[b] = 0, status 1, cost 0, model = the hint, first = -1, no cube is searched (cube status 1, work 0); else ub[b] =
+ *      infinity and model = 0.  With start != NULL it is thresholded like the hint and checked by one more such pass on every such
+ *      instance, its reads added to chk: where it satisfies every clause, start_cost[b] = its penalty distance from the hint, computed
+ *      by the kernel, and where that is below ub[b] it becomes ub[b] and the start model goes to model; where it does not, it is ignored
+ *      and start_cost[b] = -1.  (A caller without a start model for some instance passes any assignment there.)
+ *   One bound.  live is the cube's view of ub[b]: its own accepted cost at once, the other cubes' at the next re-read.  A conflict, a
+ *      variable asked for twice or dist >= live prunes, at every level; a flip whose penalty brings dist to live is pruned before any
+ *      pass.  The units are always forced and the branching variable does not depend on the bound, so all cubes agree on one prefix
+ *      tree whatever the timing, and partition it.
+ *   A prefix that ends early.  A prune while level < depth ends the cube.  A leaf met while level < depth belongs to the one cube with
+ *      index & ((1 << (depth - level)) - 1) == 0; every other cube that reaches it ends there with nothing credited.
+ *   Improvement.  A leaf (not pruned, no unit, no open clause) does one device-scope 64-bit atomic minimum on ub[b] with dist and is
+ *      accepted iff the old value was above dist.  On acceptance the cube writes its assignment (an unassigned variable at its hint
+ *      value) to its own row, records dist as its cube_cost and one improvement more, and goes on with live = dist; otherwise live =
+ *      the old value.  Either way it prunes.
+ *   Budget.  Per cube, before every pass, in this order: live = min(live, the value of ub[b] loaded at the previous check); live == 0
+ *      ends the cube as exhausted; chk[b] + own reads >= budget ends it with status -1 (budget <= 0: PDP_EXACT_DEFAULT_BUDGET); one lane
+ *      issues the next relaxed device-scope load.  The first load happens before the cube copies the instance.  So
+ *      work < chk + cubes * (budget + 3 * edges of the instance).  No wave waits for another.
+ *   Finish (one wave per instance, sums in int64 and cube order).  cost = ub[b], -1 while it is infinite.  first [B] (int32, may be
+ *      NULL) = the lowest cube whose cube_cost == cost, -1 if none: model stays what the check wrote; else model = that cube's row.
+ *      status -1 if any cube ran out of budget, else 1 if cost >= 0, else 0.  work = chk + the cubes' work.  improvements = the cubes'
+ *      accepted ones.
+ * Promised.  At depth 0 without a start model: pdp_exact_nearest's five outputs bit for bit under every budget.  At any depth with a
+ * budget that no cube exhausts: status and cost are pdp_exact_nearest's, model satisfies every clause at penalty distance cost from the
+ * hint, and cube_cost[first] == cost or first == -1 with cost 0 or start_cost; depth_used as requested (0 for an instance on the HBM
+ * route).  At any budget: cost is -1 or an upper bound that model attains, cost <= start_cost where a start model was accepted, a
+ * status -1 cost never rises with the budget, and the work bound.  With one wave (PDP_EXACT_GRID=1) the cubes run in ascending order,
+ * each to its end, and every output and record is the model's sequential().  NOT promised with more than one wave, because they depend
+ * on which cube lowers ub[b] first: which minimiser model is, first, work, improvements, the cube records, and the status of a cube
+ * that ends near its budget.
+ *   hint [V] (device; NULL: all false) and penalty [V] (device int32; NULL: all 1) as pdp_exact_nearest.  start [V] (device float; NULL:
+ *   none).  depth [B] (device int8; NULL: all 0) in 0 .. 16; at most 2^22 cubes per call; either violated -> PDP_ERR_INVALID, the
+ *   message names the instance, before any search is launched.  cost [B] int64.  work, improvements, first, depth_used [B] (int8) and
+ *   start_cost [B] (int64) may be NULL.
+ * R != 1 -> PDP_ERR_UNSUPPORTED.  Routing and working arrays are pdp_exact_solve's, shared with it.  The call synchronises the stream once
+ * (the cube count sizes its records and its grid); the kernels that follow are asynchronous on it. */
+int pdp_exact_nearest_split(pdp_problem *p, const float *hint, const int32_t *penalty, const float *start, const int8_t *depth,
+                            int64_t budget, int8_t *status, int64_t *cost, float *model, int64_t *work, int32_t *improvements,
+                            int32_t *first, int8_t *depth_used, int64_t *start_cost, void *stream);
+
+/* The per-cube records of the last pdp_exact_nearest_split call on the problem that succeeded (PDP_ERR_INVALID before the first and
+ * after a refused one): cube_off [B+1] (int64), cube_status [cubes] (1 exhausted / -1 budget spent), cube_cost [cubes] (int64: the cube's
+ * last accepted cost, -1: it accepted none), cube_work [cubes] (int64) and cube_improvements [cubes] (int32), cubes = cube_off[B] = the
+ * sum of 2^depth_used.  Device to device, asynchronous on the stream. */
+int pdp_exact_nearest_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int64_t *cube_cost, int64_t *cube_work,
+                                  int32_t *cube_improvements, void *stream);
+
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split and pdp_exact_mass_split (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split, pdp_exact_nearest_split and pdp_exact_mass_split (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

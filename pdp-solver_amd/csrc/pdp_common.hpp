@@ -163,8 +163,10 @@ struct pdp_problem {
     // the split calls of the complete solver, one pdp_exact_cubes each: exs the deciding one (pdp_exact.hip::exs_launch; records: work,
     // model rows, status), exns the counting one (exns_launch, on exn_prepare's routing and slab; records: count, work, leaves,
     // true_count rows, status), exms the optimising one (exms_launch; records: work, cost, improvements, model rows, status), exzs the
-    // weighing one (exzs_launch, on exz_prepare's routing and slab; records: mass, open mass, work, leaves, true_mass rows, status)
-    pdp_exact_cubes exs, exns, exms, exzs;
+    // weighing one (exzs_launch, on exz_prepare's routing and slab; records: mass, open mass, work, leaves, true_mass rows, status),
+    // exds the nearest-model one (exds_launch; ub and start_cost of every instance, then the records: work, cost, improvements, model
+    // rows, status)
+    pdp_exact_cubes exs, exns, exms, exzs, exds;
     // k-th models of the counting search (pdp_exact.hip::exr_launch): ex_prepare's routing and slab; the rows' byte offsets [B+1] and the
     // validation words of the last call, one block allocated on first use
     char *exr_blob;

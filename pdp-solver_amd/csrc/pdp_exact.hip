@@ -35,6 +35,7 @@
 // pdp_exact_mass is the counting search under a product prior: a weight per literal, a two-sided bracket at the budget;
 // pdp_exact_mass_split (the last kernels) cuts it into cubes as the count's split does, and its cubes share nothing either.
 // pdp_exact_nearest (behind pdp_exact_min_unsat) is the branch and bound with the cost on the variables: the model nearest to a hint.
+// pdp_exact_nearest_split (behind pdp_exact_min_unsat_split) cuts it into cubes that share the 64-bit ub[b]; a start model seeds it.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -906,20 +907,63 @@ __device__ __forceinline__ bool exd_backtrack(const ExInst<LitT, PtrT> &X, int &
     return resumed;
 }
 
-// The nearest-model search of one instance by the calling wave.  pend[v] carries the hint's code (1 true, 2 false: never 0) and the
-// penalty; `model` points at the instance's slice of the output.  The check pass (ex_search's, over the hint) always runs, before the
+constexpr int64_t EXDS_NO_COST = -1;            // cube_cost of pdp_exact_nearest_split: the cube accepted no improvement
+
+// What a cube of pdp_exact_nearest_split knows: ExCube's prefix (its 32-bit word unused) and the 64-bit word its instance's cubes share,
+// ub[b] -- a cost passes 2^32 -- with its value when the cube was picked up.  A plain call has no cube.
+template <bool SPLIT> struct ExCubeNear {};
+template <> struct ExCubeNear<true> { ExCube<true> q; int64_t *word; int64_t seen; };
+
+__device__ __forceinline__ int64_t ex_shared_load64(const int64_t *word)
+{
+    return __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the assignment in val as a cube's new incumbent, an unassigned variable at its hint value: floats into `model`, or one bit per
+// variable into `row` where model is NULL (a cube of an instance that has several); every lane runs every chunk, so the ballots are whole
+template <typename LitT, typename PtrT>
+__device__ __forceinline__ void exd_store_incumbent(const ExInst<LitT, PtrT> &X, float *model, uint32_t *row)
+{
+    const int lane = (int)threadIdx.x;
+    for (int base = 0; base < X.n; base += EX_NT) {
+        const int v = base + lane;
+        bool one = false;
+        if (v < X.n) { const uint32_t x = X.val[v]; one = (x ? x : ((X.pend[v] >> EX_HINT_SHIFT) & 3u)) == 1u; }
+        const unsigned long long mask = __ballot(one);
+        if (model) {
+            if (v < X.n) model[v] = one ? 1.0f : 0.0f;
+        } else if (lane == 0) {
+            row[base >> 5] = (uint32_t)mask;
+            if (base + 32 < X.n) row[(base >> 5) + 1] = (uint32_t)(mask >> 32);
+        }
+    }
+}
+
+// The nearest-model search of one instance, or of one cube of it, by the calling wave.  pend[v] carries the hint's code (1 true, 2
+// false: never 0) and the penalty.
+// Plain: `model` points at the instance's slice of the output.  The check pass (ex_search's, over the hint) always runs, before the
 // first budget check.  Returns 1 (*cost_out is the minimum and model attains it), 0 (no model: *cost_out = -1, model all 0) or -1
 // (budget spent: *cost_out and model are the best met, or -1 and all 0).  dist, ub and every sum are 64-bit integers, uniform over the wave.
-template <bool HBM, typename LitT, typename PtrT>
-__device__ int ex_search_near(const ExInst<LitT, PtrT> &X, int64_t budget, float *model, int64_t *work_out, int64_t *cost_out, int *improved_out)
+// SPLIT: the check has run once per instance in k_exact_near_split_check.  `ub` is the cube's view of the shared ub[b]: it comes in as
+// the value loaded before the instance was copied (not 0), is lowered by one 64-bit atomic minimum per leaf the cube owns, and is re-read
+// by lane 0 at the budget checks, one pass ahead of its use.  It is the only bound: the units are always forced and ex_branch does not
+// read it, so the decisions of the pinned levels depend on the instance and its hint alone.  A pinned decision against the hint adds its
+// penalty to dist at once and ends the cube where that reaches ub (every open level is pinned).  An accepted leaf writes the assignment
+// to `model` (depth 0) or bit-packed to `row` (model NULL).  Returns 1 (the cube is exhausted, or some cube has reached cost 0) or -1
+// (budget spent); *cost_out = the cube's last accepted cost (EXDS_NO_COST: none).
+template <bool HBM, bool SPLIT, typename LitT, typename PtrT>
+__device__ int ex_search_near(const ExInst<LitT, PtrT> &X, int64_t budget, const ExCubeNear<SPLIT> &Q, float *model,
+                              [[maybe_unused]] uint32_t *row, int64_t *work_out, int64_t *cost_out, int *improved_out)
 {
     const int lane = (int)threadIdx.x;
     constexpr int INF = 0x7fffffff;
     int level = 0, tlen = 0, improved = 0;
     int64_t work = 0, dist = 0, ub = EXD_INF;
+    [[maybe_unused]] int64_t accepted = EXDS_NO_COST, seen = 0;
+    if constexpr (SPLIT) { ub = Q.seen; seen = Q.seen; }
     int result = -1;
     ExNoCredit none;
-    {
+    if constexpr (!SPLIT) {
         for (int v = lane; v < X.n; v += EX_NT) X.val[v] = (uint8_t)((X.pend[v] >> EX_HINT_SHIFT) & 3u);
         ex_sync<HBM>();
         int reads = 0, open = 0;
@@ -944,7 +988,15 @@ __device__ int ex_search_near(const ExInst<LitT, PtrT> &X, int64_t budget, float
         ex_sync<HBM>();
     }
     for (;;) {
-        if (work >= budget) break;
+        if constexpr (SPLIT) {
+            seen = (int64_t)__shfl((long long)seen, 0);
+            ub = seen < ub ? seen : ub;
+            if (ub == 0) { result = 1; break; }                     // some cube has met the hint's own cost
+            if (Q.q.spent + work >= budget) break;
+            if (lane == 0) seen = ex_shared_load64(Q.word);         // used at the next check: its latency lies behind the pass
+        } else {
+            if (work >= budget) break;
+        }
         const ExPass P = ex_propagate(X);
         work += ex_sum(P.reads);
         bool prune = __ballot(P.conflict) != 0ull;
@@ -963,26 +1015,54 @@ __device__ int ex_search_near(const ExInst<LitT, PtrT> &X, int64_t budget, float
             wmin = ex_min(P.wmin);
             if (wmin == INF) {
                 // a leaf below ub: the new incumbent; an unassigned variable takes the hint's value, which costs nothing
-                ub = dist;
-                ++improved;
-                for (int v = lane; v < X.n; v += EX_NT) {
-                    const uint32_t x = X.val[v];
-                    model[v] = (x ? x : ((X.pend[v] >> EX_HINT_SHIFT) & 3u)) == 1u ? 1.0f : 0.0f;
+                if constexpr (SPLIT) {
+                    // the cubes that do not own the leaf end (every open level is pinned) with nothing credited
+                    if (ex_owns_leaf(Q.q, level)) {
+                        int64_t old = 0;
+                        if (lane == 0) old = __hip_atomic_fetch_min(Q.word, dist, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        old = (int64_t)__shfl((long long)old, 0);
+                        if (old > dist) {
+                            exd_store_incumbent(X, model, row);
+                            accepted = dist;
+                            ++improved;
+                            ub = dist;
+                        } else {
+                            ub = old;                               // another cube was there first
+                        }
+                    }
+                } else {
+                    ub = dist;
+                    ++improved;
+                    for (int v = lane; v < X.n; v += EX_NT) {
+                        const uint32_t x = X.val[v];
+                        model[v] = (x ? x : ((X.pend[v] >> EX_HINT_SHIFT) & 3u)) == 1u ? 1.0f : 0.0f;
+                    }
+                    if (ub == 0) { result = 1; break; }
                 }
-                if (ub == 0) { result = 1; break; }
                 prune = true;
             }
         }
         if (prune) {
-            // out of levels: ub is the minimum, or there is no model
-            if (!exd_backtrack<HBM>(X, level, tlen, dist, ub)) { result = ub == EXD_INF ? 0 : 1; break; }
+            // out of levels: ub is the minimum, or there is no model / the cube is exhausted
+            if (!exd_backtrack<HBM>(X, level, tlen, dist, ub)) { result = (!SPLIT && ub == EXD_INF) ? 0 : 1; break; }
             continue;
         }
         const unsigned long long best = ex_branch<HBM, EX_PHASE_INCUMBENT>(X, wmin, work);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        ex_decide<HBM, false>(X, ExCube<false>{}, best, level, tlen, none);
+        if constexpr (SPLIT) {
+            ex_decide<HBM, true>(X, Q.q, best, level, tlen, none);
+            if (level <= Q.q.depth && ((Q.q.index >> (Q.q.depth - level)) & 1) != 0) {
+                // pinned against the hint: its penalty counts at once, and a cube that starts at ub has nothing to find
+                const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+                dist += (int64_t)(X.pend[v] >> EXD_PEN_SHIFT);
+                if (dist >= ub) { result = 1; break; }
+            }
+        } else {
+            ex_decide<HBM, false>(X, ExCube<false>{}, best, level, tlen, none);
+        }
     }
-    *work_out = work; *cost_out = ub == EXD_INF ? (int64_t)-1 : ub; *improved_out = improved;
+    if constexpr (SPLIT) ub = accepted; else ub = ub == EXD_INF ? (int64_t)-1 : ub;
+    *work_out = work; *cost_out = ub; *improved_out = improved;
     return result;
 }
 
@@ -1000,7 +1080,7 @@ __device__ void ex_solve_near(const ExdParams &xp, const Inst &I, ExInst<LitT, P
     ex_sync<HBM>();
     int64_t work = 0, cost = 0;
     int improved = 0;
-    const int st = ex_search_near<HBM>(X, xp.budget, xp.model + I.v0, &work, &cost, &improved);
+    const int st = ex_search_near<HBM, false>(X, xp.budget, ExCubeNear<false>{}, xp.model + I.v0, nullptr, &work, &cost, &improved);
     if (lane == 0) {
         xp.status[I.b] = (int8_t)st;
         xp.cost[I.b] = cost;
@@ -3595,6 +3675,235 @@ int exms_launch(pdp_problem *p, const float *hint, const int8_t *depth, int64_t 
     return PDP_OK;
 }
 
+// ---- pdp_exact_nearest_split: one instance's nearest-model search spread over 2^depth cubes, one wave per cube --------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_nearest_split_model.py).  A cube is
+// ex_search_near<HBM, true>: the branch and bound with the decisions of levels 1..depth pinned as in pdp_exact_solve_split.  The state,
+// the slab, the routing and the occupancy by LDS are k_exact's.  Four launches on one stream: k_exact_split_setup (depth_used, route,
+// cube_off), the check (once per instance: the penalties' range, the thresholded hint and, where given, the start model; reads into
+// chk[b], the first bound into ub[b], what stays when no cube accepts anything into model), the cubes (one counter hands out cube ids:
+// instance order, ascending index), the finish.
+// The only word two waves share is ub[b], the cost of the best model any cube of instance b has found, 64 bits wide: lowered by one
+// atomic minimum per owned leaf, read by lane 0 at the budget checks with a relaxed agent-scope load, one pass ahead of its use.  No wave
+// waits for another.  One bound suffices where pdp_exact_min_unsat_split needs two: every clause is hard, so no rule of the search but
+// the prune reads the bound, and the cubes partition one prefix tree whatever the timing.  Every condition of the search is uniform over
+// the wave, and both arms of ex_solve_near_split end in its one barrier.
+struct ExdsParams {
+    int B;
+    uint32_t total;             // cubes of the call
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;
+    const float *hint;          // [V] the point the distance is measured from (NULL: all false)
+    const int32_t *penalty;     // [V] (NULL: all 1)
+    const int8_t *du;           // [B] depth used
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    const int64_t *chk;         // [B] reads of the check (-1: a penalty is out of range, nothing is searched)
+    int64_t *ub;                // [B] the shared best cost (EXD_INF: no model yet)
+    const int64_t *start_cost;  // [B] the accepted start model's distance (-1: none)
+    int8_t *cube_status;        // [total] 1 exhausted / -1 budget spent
+    int64_t *cube_work;         // [total]
+    int64_t *cube_cost;         // [total] the cube's last accepted cost (EXDS_NO_COST: none)
+    int32_t *cube_imp;          // [total] improvements the cube had accepted
+    uint32_t *rows;             // [total][words] bit-packed assignment of the cube's last accepted cost (instances of depth > 0)
+    int words;
+    float *model;               // [V] written by the check; by the cube of a depth-0 instance, by the finish kernel elsewhere
+    ExHbm h;
+};
+
+// One check pass straight from the problem's arrays: every clause up to its first literal true under the thresholded x (NULL: all
+// false; NaN compares false).  This lane's reads are added to `reads`; returns whether one of its clauses has no true literal.
+__device__ __forceinline__ int exds_check_pass(const Inst &I, const float *x, int &reads)
+{
+    int open = 0;
+    for (int c = (int)threadIdx.x; c < I.m; c += EX_NT) {
+        const int a = I.f_ptr[c], z = I.f_ptr[c + 1];
+        int sat = 0, k = a;
+        for (; k < z; ++k) {
+            const int ed = I.f_edges[k];
+            const bool t = x && x[I.v0 + I.e_var[ed]] > 0.5f;
+            if (t != (I.sgn[ed] < 0)) { sat = 1; ++k; break; }
+        }
+        reads += k - a;
+        open |= !sat;
+    }
+    return open;
+}
+
+// The check of pdp_exact_nearest_split, once per instance.  A penalty outside [0, 2^20]: chk = -1, ub = 0 (no cube starts), model 0.
+// Otherwise pdp_exact_nearest's check pass over the hint (a model: ub = 0, model = the hint; else ub = EXD_INF, model 0), then, where a
+// start model is given, one more such pass over it: where it satisfies every clause, start_cost = its penalty distance from the hint,
+// computed here, and where that is below ub it becomes ub and the start the model; elsewhere start_cost = -1 and it is ignored.
+__global__ void __launch_bounds__(EX_NT) k_exact_near_split_check(PView pv, const float *hint, const int32_t *penalty, const float *start,
+                                                                  int64_t *chk, int64_t *ub, int64_t *start_cost, float *model)
+{
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const Inst I = load_inst(pv, b);
+        int bad = 0;
+        if (penalty) for (int v = lane; v < I.n; v += EX_NT) { const int32_t q = penalty[I.v0 + v]; bad |= q < 0 || q > EXD_MAX_PENALTY; }
+        if (__ballot(bad) != 0ull) {
+            for (int v = lane; v < I.n; v += EX_NT) model[I.v0 + v] = 0.0f;
+            if (lane == 0) { chk[b] = -1; ub[b] = 0; start_cost[b] = -1; }
+            continue;
+        }
+        int reads = 0;
+        const bool accept = __ballot(exds_check_pass(I, hint, reads)) == 0ull;
+        int64_t bound = accept ? (int64_t)0 : EXD_INF, sc = -1;
+        bool take = false;
+        if (start) {
+            if (__ballot(exds_check_pass(I, start, reads)) == 0ull) {
+                int64_t d = 0;
+                for (int v = lane; v < I.n; v += EX_NT) {
+                    const bool h = hint && hint[I.v0 + v] > 0.5f, s = start[I.v0 + v] > 0.5f;
+                    if (h != s) d += penalty ? (int64_t)penalty[I.v0 + v] : (int64_t)1;
+                }
+                sc = ex_sum64(d);
+                take = sc < bound;
+                if (take) bound = sc;
+            }
+        }
+        for (int v = lane; v < I.n; v += EX_NT) {
+            const float *from = take ? start : (accept ? hint : nullptr);
+            model[I.v0 + v] = (from && from[I.v0 + v] > 0.5f) ? 1.0f : 0.0f;
+        }
+        reads = ex_sum(reads);
+        if (lane == 0) { chk[b] = reads; ub[b] = bound; start_cost[b] = sc; }
+    }
+}
+
+// cube q = (instance I.b, index): load ub[b]; unless it is 0 already, copy the instance (ex_fill), clear the state (pend starts as the
+// hint's codes and the penalties) and search; then the cube's record.  Both arms end in the record and the barrier below.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_near_split(const ExdsParams &xp, const Inst &I, ExInst<LitT, PtrT> X, uint32_t q, int depth, int index)
+{
+    const int lane = (int)threadIdx.x;
+    int64_t live = 0;
+    if (lane == 0) live = ex_shared_load64(xp.ub + I.b);
+    live = (int64_t)__shfl((long long)live, 0);
+    int st = 1, improved = 0;
+    int64_t work = 0, cost = EXDS_NO_COST;
+    if (live != 0) {
+        ex_fill<HBM>(I, X);
+        for (int v = lane; v < I.n; v += EX_NT) {
+            const uint32_t code = (xp.hint && xp.hint[I.v0 + v] > 0.5f) ? 1u : 2u;          // NaN compares false
+            const uint32_t w = xp.penalty ? (uint32_t)xp.penalty[I.v0 + v] : 1u;
+            X.val[v] = 0; X.pend[v] = (w << EXD_PEN_SHIFT) | (code << EX_HINT_SHIFT); X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        }
+        ex_sync<HBM>();
+        st = ex_search_near<HBM, true>(X, xp.budget, ExCubeNear<true>{ExCube<true>{depth, index, xp.chk[I.b], nullptr, 0}, xp.ub + I.b, live},
+                                       depth == 0 ? xp.model + I.v0 : (float *)nullptr, xp.rows + (size_t)q * (size_t)xp.words, &work, &cost,
+                                       &improved);
+    }
+    if (lane == 0) {
+        xp.cube_status[q] = (int8_t)st;
+        xp.cube_work[q] = work;
+        xp.cube_cost[q] = cost;
+        xp.cube_imp[q] = improved;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_near_split(PView pv, ExdsParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= xp.total) break;
+        const int lo = exs_instance(xp.cube_off, xp.B, q);
+        const Inst I = load_inst(pv, lo);
+        const int depth = (int)xp.du[lo], index = (int)((int64_t)q - xp.cube_off[lo]);
+        if (xp.route[lo]) ex_solve_near_split<true>(xp, I, ex_bind_hbm(xp.h, I), q, depth, index);
+        else ex_solve_near_split<false>(xp, I, ex_bind_lds(ex_slab, I), q, depth, index);
+    }
+}
+
+// The instance's answer from its cubes' records, one wave per instance: cost = ub[b] (-1: still EXD_INF); first = the lowest cube whose
+// last accepted cost is that (-1: none, what the check wrote stays in model); the model of cube `first` expanded from its row (a depth-0
+// instance's single cube wrote its slice itself); status -1 when a cube ran out of budget, else 1 with a cost, else 0; work and
+// improvements summed in int64 in cube order.  chk[b] < 0: status -3 and every other output 0.
+__global__ void __launch_bounds__(EX_NT) k_exact_near_split_finish(PView pv, ExdsParams xp, int8_t *status, int64_t *cost, int64_t *work,
+                                                                   int32_t *improvements, int32_t *first, int64_t *start_cost)
+{
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        const int64_t best = xp.ub[b], reads = xp.chk[b];
+        const int depth = (int)xp.du[b];
+        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        int64_t sum = 0, imp = 0;
+        int open = 0, at = EXS_NONE;
+        for (int64_t j = lane; j < nc; j += EX_NT) {
+            sum += xp.cube_work[c0 + j];
+            imp += xp.cube_imp[c0 + j];
+            open |= xp.cube_status[c0 + j] != 1;
+            if (at == EXS_NONE && xp.cube_cost[c0 + j] == best) at = (int)j;
+        }
+        sum = exs_sum64(sum);
+        imp = exs_sum64(imp);
+        at = ex_min(at);
+        const bool all_done = __ballot(open) == 0ull, bad = reads < 0;
+        if (depth > 0 && at != EXS_NONE) {
+            const uint32_t *row = xp.rows + (size_t)(c0 + at) * (size_t)xp.words;
+            for (int v = lane; v < n; v += EX_NT) xp.model[v0 + v] = ((row[v >> 5] >> (v & 31)) & 1u) ? 1.0f : 0.0f;
+        }
+        if (lane == 0) {
+            status[b] = (int8_t)(bad ? -3 : (!all_done ? -1 : (best != EXD_INF ? 1 : 0)));
+            cost[b] = best == EXD_INF ? (int64_t)-1 : best;
+            if (work) work[b] = bad ? (int64_t)0 : reads + sum;
+            if (improvements) improvements[b] = (int32_t)imp;
+            if (first) first[b] = at == EXS_NONE ? -1 : at;
+            if (start_cost) start_cost[b] = xp.start_cost[b];
+        }
+    }
+}
+
+int exds_launch(pdp_problem *p, const float *hint, const int32_t *penalty, const float *start, const int8_t *depth, int64_t budget, int8_t *status,
+                int64_t *cost, float *model, int64_t *work, int32_t *improvements, int32_t *first, int8_t *depth_used, int64_t *start_cost,
+                void *stream)
+{
+    { const int st_ = ex_prepare(p); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    const size_t B = p->B;
+    ExsFixed F;
+    int64_t info[EXS_INFO];
+    {
+        const int st_ = exs_setup(p, p->exds, "pdp_exact_nearest_split", depth, depth_used, 0x7fffffff, 0, 0, st, F, info);
+        if (st_ != PDP_OK) return st_;
+    }
+    const size_t total = (size_t)info[2], words = ((size_t)info[3] + 31) / 32;
+    // the two 64-bit words per instance, then the per-cube records:
+    // ub [B] | start_cost [B] | work [total] | cost [total] | improvements [total] | rows [total][words] | status [total]
+    const size_t head = B * 16;
+    { const int st_ = exs_records(p->exds, head + total * 20 + total * words * 4 + total); if (st_ != PDP_OK) return st_; }
+    ExdsParams xp;
+    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
+    xp.budget = ex_budget(budget);
+    xp.hint = hint; xp.penalty = penalty; xp.du = F.du; xp.route = F.route; xp.cube_off = F.cube_off; xp.chk = F.chk;
+    xp.ub = (int64_t *)p->exds.cubes;
+    xp.start_cost = (int64_t *)(p->exds.cubes + B * 8);
+    xp.cube_work = (int64_t *)(p->exds.cubes + head);
+    xp.cube_cost = (int64_t *)(p->exds.cubes + head + total * 8);
+    xp.cube_imp = (int32_t *)(p->exds.cubes + head + total * 16);
+    xp.rows = (uint32_t *)(p->exds.cubes + head + total * 20);
+    xp.cube_status = (int8_t *)(p->exds.cubes + head + total * 20 + total * words * 4);
+    xp.words = (int)words;
+    xp.model = model;
+    xp.h = ex_hbm(p);
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_near_split_check, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), hint, penalty, start, F.chk, xp.ub,
+                       (int64_t *)(p->exds.cubes + B * 8), model);
+    PDP_LAUNCH_CHECK();
+    { const int st_ = ex_launch_persistent(p, k_exact_near_split, xp, (int64_t)total, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    hipLaunchKernelGGL(k_exact_near_split_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp, status, cost, work, improvements,
+                       first, start_cost);
+    PDP_LAUNCH_CHECK();
+    p->exds.total = (int64_t)total;
+    p->exds.status_off = head + total * 20 + total * words * 4;
+    return PDP_OK;
+}
+
 // ---- pdp_exact_mass: the exact solution mass of a soft prediction, the counting search under a product prior ---------------------------
 // (specification: include/pdp_hip.h; plain Python: tests/exact_mass_model.py).  ex_search_count's passes, backtracking
 // and crediting (ExnCredit on the running sum Z) with a weight per literal: `mass` is the product of the weights of the trail, uniform
@@ -4347,6 +4656,33 @@ extern "C" int pdp_exact_min_unsat_split_cubes(pdp_problem *p, int64_t *cube_off
     PDP_HIP_CHECK(hipMemcpyAsync(cube_cost, p->exms.cubes + total * 8, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
     PDP_HIP_CHECK(hipMemcpyAsync(cube_improvements, p->exms.cubes + total * 12, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
     PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exms.cubes + p->exms.status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
+    return PDP_OK;
+}
+
+extern "C" int pdp_exact_nearest_split(pdp_problem *p, const float *hint, const int32_t *penalty, const float *start, const int8_t *depth,
+                                       int64_t budget, int8_t *status, int64_t *cost, float *model, int64_t *work, int32_t *improvements,
+                                       int32_t *first, int8_t *depth_used, int64_t *start_cost, void *stream)
+{
+    PDP_REQUIRE(p && status && cost && model, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_nearest_split: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exds_launch(p, hint, penalty, start, depth, budget, status, cost, model, work, improvements, first, depth_used, start_cost, stream);
+}
+
+extern "C" int pdp_exact_nearest_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, int64_t *cube_cost, int64_t *cube_work,
+                                             int32_t *cube_improvements, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && cube_status && cube_cost && cube_work && cube_improvements, "NULL argument");
+    PDP_REQUIRE(p->exds.total > 0, "pdp_exact_nearest_split_cubes: no pdp_exact_nearest_split call on this problem yet");
+    const size_t B = p->B, total = (size_t)p->exds.total, head = B * 16;
+    const ExsFixed F = exs_fixed(p, p->exds);
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_off, F.cube_off, (B + 1) * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_work, p->exds.cubes + head, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_cost, p->exds.cubes + head + total * 8, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_improvements, p->exds.cubes + head + total * 16, total * 4, hipMemcpyDeviceToDevice, ST(stream)));
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exds.cubes + p->exds.status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
     return PDP_OK;
 }
 

@@ -31,7 +31,9 @@ masses add, the budget applies per cube, so a bracket is tightened by 2^depth ti
 gradient of -ln(mass) in the logits of the prediction, from the posterior.  ``nearest_model`` measures an assignment instead: the model
 with the fewest variables (or the least sum of per-variable penalties) different from it, by branch and bound with every clause hard
 (pdp_exact_nearest) -- how far PDP's assignment was from a solution, and which one; ``map_penalties`` turns a soft
-prediction into the hint and penalties under which that model is the most probable one.
+prediction into the hint and penalties under which that model is the most probable one.  ``nearest_model(split=N)`` spreads that
+search over 2^N waves per instance that share the best cost found, and ``start`` gives it models the caller already has to start below
+(pdp_exact_nearest_split).
 """
 
 import numpy as np
@@ -58,6 +60,10 @@ AUTO_MIN_STAGE1_BUDGET = 1 << 26
 # solution_mass(split='auto'): the reads per instance of the plain first mass.  The count's value: the tree at weights 0.5 is the count's
 # (tools/exact_time.py zssweep sweeps it)
 AUTO_MASS_STAGE1_BUDGET = 1 << 26
+# nearest_model(split='auto'): the reads per instance of the plain first search.  Chosen from the sweep in profiles/exact_time.txt
+# (tools/exact_time.py nssweep: the fastest of 2^18 / 2^22 / 2^26 on row nd; on row na, whose instances finish near 2^22 reads, it makes
+# 'auto' 2.0 times the plain call where 2^26 is free: DESIGN.md §9.16 weighs the two)
+AUTO_NEAREST_STAGE1_BUDGET = 1 << 22
 
 
 def raw_item(n, clauses, label=-1.0, name=""):
@@ -525,16 +531,60 @@ def map_penalties(weights, scale=1024):
     return (p > 0.5).astype(np.float32), pen.astype(np.int32)
 
 
-def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges=MAX_EDGES):
+def nearest_split(prob, part, budget, hint, pen, start, split, device):
+    """The split nearest-model search of one problem (``part``: its loader items, or a callable that returns them; ``hint``, ``pen``,
+    ``start``: tensors of V values, the last two or None): numpy (status, cost, model, work, depth_used, start_cost).  ``split`` an int: one
+    pdp_exact_nearest_split call at that depth.  'auto': a plain exact_nearest with AUTO_NEAREST_STAGE1_BUDGET reads per instance
+    (``budget`` if that is smaller), then the instances whose optimum is not proved go through one split call on a problem of their own at
+    auto_depth, with ``budget`` per cube.  The hint is the point the distance is measured from and stays; the models of the first stage are
+    the start models of that call -- an incumbent carries over, so the second stage starts below the first stage's cost (where the first
+    stage met no model, the caller's start model is passed on instead); work is the sum of the two stages."""
+    if split != 'auto':
+        r = prob.exact_nearest_split(hint, pen, start, depth=split, budget=budget, stats=True)
+        st, co, model, wk, du, sc = r[0], r[1], r[2], r[3], r[6], r[7]
+        return st.cpu().numpy(), co.cpu().numpy(), model.cpu().numpy(), wk.cpu().numpy(), du.cpu().numpy(), sc.cpu().numpy()
+    stage1 = min(budget, AUTO_NEAREST_STAGE1_BUDGET) if budget > 0 else AUTO_NEAREST_STAGE1_BUDGET
+    st, co, model, wk = [t.cpu().numpy() for t in prob.exact_nearest(hint, pen, stage1)]
+    du = np.zeros(len(st), dtype=np.int8)
+    sc = np.full(len(st), -1, dtype=np.int64)
+    again = [int(j) for j in np.nonzero(st == -1)[0]]
+    if again:
+        part = part() if callable(part) else part
+        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+        sub = _problem([part[j] for j in again], device)
+        cut = lambda t: None if t is None else torch.cat([t[int(voff[j]):int(voff[j + 1])] for j in again])
+        given = None if start is None else start.cpu().numpy()
+        start2 = np.concatenate([model[voff[j]:voff[j + 1]] if co[j] >= 0 or given is None else given[voff[j]:voff[j + 1]] for j in again])
+        r = [t.cpu().numpy() for t in sub.exact_nearest_split(cut(hint), cut(pen), torch.from_numpy(start2.astype(np.float32)).to(device),
+                                                              depth=auto_depth(len(again), device), budget=budget, stats=True)[:8]]
+        del sub
+        off = 0
+        for k, j in enumerate(again):
+            n = int(voff[j + 1] - voff[j])
+            st[j], co[j], du[j], sc[j] = r[0][k], r[1][k], r[6][k], r[7][k]
+            wk[j] += r[3][k]
+            model[voff[j]:voff[j + 1]] = r[2][off:off + n]
+            off += n
+    return st, co, model, wk, du, sc
+
+
+def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges=MAX_EDGES, split=None, start=None, depths=False):
     """The model of every loader item (as solve_items takes them) nearest to its hint, by branch and bound (pdp_exact_nearest; DESIGN.md
     §9.15).  Returns numpy (status int8 [N]: 1 cost is the minimum over the models, 0 the instance has no model, -1 the budget ran out and
     cost is that of the best model met, -1 if none was, -3 a penalty of the instance is outside [0, 2^20]; cost int64 [N]: the penalties
     of the variables where the model differs from the thresholded hint, summed; models: per instance a float32 0/1 array of n_i values,
     all 0 where cost is not >= 0 or status is -3; work int64 [N]).
     ``hints``: per instance an array of n_i values or None (> 0.5 true, every other value false, NaN included; None: all false), or None
-    for all.  ``penalties``: per instance an integer array of n_i values or None (all 1), or None for all: the Hamming distance."""
+    for all.  ``penalties``: per instance an integer array of n_i values or None (all 1), or None for all: the Hamming distance.
+    ``split``: the search of every instance spread over 2^split waves that share the best cost found (pdp_exact_nearest_split; DESIGN.md
+    §9.16; an int from 0 to 16), or 'auto': see nearest_split.  ``budget`` then applies to every cube.  A proved cost is the same minimum;
+    which minimiser the model is and work depend on the timing of the cubes.  ``start``: per instance a model the caller already has
+    (an array of n_i values, thresholded like a hint) or None, or None for all; the search of that instance starts below its distance,
+    computed and checked on the GPU, and an array that is not a model is ignored.  Giving one turns on the split call (at depth 0 without
+    ``split``).  ``depths``: also return depth_used int8 [N].  Without ``split`` and ``start`` the call is pdp_exact_nearest's."""
+    split = _check_split(split)
     native.require_gpu()
-    for name, per in (('hints', hints), ('penalties', penalties)):
+    for name, per in (('hints', hints), ('penalties', penalties), ('start', start)):
         if per is None:
             continue
         if len(per) != len(items):
@@ -551,11 +601,16 @@ def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges
     status = np.ones(N, dtype=np.int8)
     cost = np.zeros(N, dtype=np.int64)
     work = np.zeros(N, dtype=np.int64)
+    used = np.zeros(N, dtype=np.int8)
     models = [None] * N
     for seg in _segments(items, max_edges):
         part = [items[i] for i in seg]
         flat = [np.zeros(int(it[0]), dtype=np.float32) if hints is None or hints[i] is None else np.asarray(hints[i], dtype=np.float32).reshape(-1)
                 for i, it in zip(seg, part)]
+        # an instance without a start model passes its hint: the check pass has just rejected it, so it is ignored
+        begin = None
+        if start is not None:
+            begin = [h if start[i] is None else np.asarray(start[i], dtype=np.float32).reshape(-1) for i, h in zip(seg, flat)]
         pens = None
         if penalties is not None:
             pens = [np.ones(int(it[0]), dtype=np.int64) if penalties[i] is None else np.asarray(penalties[i]).astype(np.int64).reshape(-1)
@@ -579,15 +634,20 @@ def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges
                 # a value that does not fit int32 is out of range either way: -1 stands for it
                 allp = np.concatenate(pens)
                 pen = torch.from_numpy(np.where((allp < 0) | (allp > MAX_PENALTY), -1, allp).astype(np.int32)).to(device)
-            st, co, model, wk = [t.cpu().numpy() for t in prob.exact_nearest(hint, pen, budget)]
+            if split is None and start is None:
+                st, co, model, wk = [t.cpu().numpy() for t in prob.exact_nearest(hint, pen, budget)]
+                du = np.zeros(len(part), dtype=np.int8)
+            else:
+                first = None if begin is None else torch.from_numpy(np.concatenate(begin)).to(device)
+                st, co, model, wk, du, _ = nearest_split(prob, part, budget, hint, pen, first, 0 if split is None else split, device)
         del prob
         off = 0
         for j, (i, it) in enumerate(zip(seg, part)):
             n = int(it[0])
-            status[i], cost[i], work[i] = st[j], co[j], wk[j]
+            status[i], cost[i], work[i], used[i] = st[j], co[j], wk[j], du[j]
             models[i] = model[off:off + n].copy()
             off += n
-    return status, cost, models, work
+    return (status, cost, models, work, used) if depths else (status, cost, models, work)
 
 
 def count_split(prob, part, budget, split, device):

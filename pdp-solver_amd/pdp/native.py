@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_count_split', 'pdp_exact_count_split_cubes', 'pdp_exact_models_at',
     'pdp_exact_min_unsat_split', 'pdp_exact_min_unsat_split_cubes', 'pdp_exact_mass',
     'pdp_exact_mass_split', 'pdp_exact_mass_split_cubes', 'pdp_exact_nearest',
+    'pdp_exact_nearest_split', 'pdp_exact_nearest_split_cubes',
 ]
 
 
@@ -587,6 +588,73 @@ class Problem(object):
                                                     ptr(cube_improvements), _stream()))
         return status, cost, model, work, improvements, first, depth_used, cube_off, cube_status, cube_cost, cube_work, cube_improvements
 
+    def exact_nearest_split(self, hints=None, penalties=None, start=None, depth=None, budget=0, stats=False):
+        """exact_nearest(hints, penalties) with the search of instance b spread over 2^depth[b] waves that share the cost of the best model
+        found so far (pdp_exact_nearest_split): (status, cost, model, work) as exact_nearest's.  With a ``budget`` -- it applies to every
+        cube -- that no cube exhausts, status and cost are exact_nearest's and model attains cost; at any budget cost is -1 or an upper
+        bound that model attains; at depth 0 without ``start`` all outputs are exact_nearest's bit for bit.  ``start`` (float32, V elements,
+        on the problem's device; None: none): a model of every instance the caller already has, thresholded like the hints; the kernel
+        checks it and computes its distance itself, the search starts below that distance, and where it is not a model it is ignored.
+        Above depth 0, which minimiser model is, work, and the ``stats`` other than depth_used, start_cost and cube_off depend on which cube
+        lowers the shared cost first, unless one wave runs all cubes (PDP_EXACT_GRID=1).  ``depth``: an int, or an int8 tensor of B elements
+        on the problem's device, values 0 .. 16, at most 2^22 cubes per call; None: 0.  ``stats``: also improvements int32 [B], first int32
+        [B] (the lowest cube that holds the cost, -1: the hints or the start model do, or nothing does), depth_used int8 [B] (0 for an
+        instance on the HBM route), start_cost int64 [B] (the distance of the start model, -1: none or not a model), cube_off int64 [B+1],
+        cube_status int8 [cubes] (1 exhausted / -1 budget spent), cube_cost int64 [cubes] (the cube's last accepted cost, -1: none),
+        cube_work int64 [cubes] and cube_improvements int32 [cubes].  Synchronises the current stream once, then asynchronous on it
+        (``stats`` synchronises again)."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads (0: the library default), got %r" % (budget,))
+        for name, t, dtype in (('hints', hints, torch.float32), ('penalties', penalties, torch.int32), ('start', start, torch.float32)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != dtype or t.numel() != self.V:
+                raise ValueError("%s must be a %s tensor of %d elements (one per variable), got %s"
+                                 % (name, dtype, self.V, '%s of %d' % (t.dtype, t.numel()) if torch.is_tensor(t) else type(t).__name__))
+            if t.device != self.device:
+                raise ValueError("%s must live on %s, got %s" % (name, self.device, t.device))
+        if hints is not None:
+            hints = hints.reshape(-1).contiguous()
+        if penalties is not None:
+            penalties = penalties.reshape(-1).contiguous()
+        if start is not None:
+            start = start.reshape(-1).contiguous()
+        if depth is None:
+            depth = 0
+        if torch.is_tensor(depth):
+            if depth.dtype != torch.int8 or depth.numel() != self.B or depth.device != self.device:
+                raise ValueError("depth must be an int or an int8 tensor of %d elements (one per instance) on %s, got %s of %d on %s"
+                                 % (self.B, self.device, depth.dtype, depth.numel(), depth.device))
+            depth = depth.reshape(-1).contiguous()
+        elif isinstance(depth, bool) or not isinstance(depth, numbers.Integral) or not -128 <= depth <= 127:
+            raise ValueError("depth must be an int or an int8 tensor of %d elements (one per instance), got %r" % (self.B, depth))
+        else:
+            depth = torch.full((self.B,), int(depth), dtype=torch.int8, device=self.device)
+        status = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        cost = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        model = torch.empty(self.V, dtype=torch.float32, device=self.device)
+        work = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        improvements = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        first = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        depth_used = torch.empty(self.B, dtype=torch.int8, device=self.device)
+        start_cost = torch.empty(self.B, dtype=torch.int64, device=self.device)
+        check(lib().pdp_exact_nearest_split(self._h, ptr(hints, torch.float32, self.V, 'hints'), ptr(penalties, torch.int32, self.V, 'penalties'),
+                                            ptr(start, torch.float32, self.V, 'start'), ptr(depth), C.c_int64(int(budget)), ptr(status),
+                                            ptr(cost), ptr(model), ptr(work), ptr(improvements), ptr(first), ptr(depth_used), ptr(start_cost),
+                                            _stream()))
+        if not stats:
+            return status, cost, model, work
+        cubes = int(torch.bitwise_left_shift(torch.ones_like(depth_used, dtype=torch.int64), depth_used.to(torch.int64)).sum().item())
+        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=self.device)
+        cube_status = torch.empty(cubes, dtype=torch.int8, device=self.device)
+        cube_cost = torch.empty(cubes, dtype=torch.int64, device=self.device)
+        cube_work = torch.empty(cubes, dtype=torch.int64, device=self.device)
+        cube_improvements = torch.empty(cubes, dtype=torch.int32, device=self.device)
+        check(lib().pdp_exact_nearest_split_cubes(self._h, ptr(cube_off), ptr(cube_status), ptr(cube_cost), ptr(cube_work),
+                                                  ptr(cube_improvements), _stream()))
+        return (status, cost, model, work, improvements, first, depth_used, start_cost, cube_off, cube_status, cube_cost, cube_work,
+                cube_improvements)
+
     def exact_count(self, budget=0, stats=False):
         """Exact model counts and per-variable counts of every instance (pdp_exact_count): (status int8 [B]: 1 the search is complete and
         count is the number of models, -1 the budget ran out and count covers the part of the tree visited so far, a lower bound, -2 the
@@ -909,7 +977,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split and exact_mass_split (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split, exact_nearest_split and exact_mass_split (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

@@ -184,7 +184,11 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         same slice of the prediction, all penalties 1: the fewest variables in which a model differs from PDP's assignment; left out
         where no model was met within the budget), "nearest_proved" (1: that is the minimum over all models, 0: an upper bound or
         nothing), "nearest_solution" (that model, in the format of "solution") and "nearest_work"; a row PDP solved costs one check pass
-        and gets "nearest" 0."""
+        and gets "nearest" 0.  With config['complete_nearest_split'] (a depth 0..16, or -1: exact.nearest_split's 'auto') that search runs
+        with every row spread over 2^depth waves that share the best cost found (pdp_exact_nearest_split), from the complete search's model
+        as its start model: "nearest", "nearest_proved" and "nearest_solution" mean the same, which nearest model comes back and
+        "nearest_work" (the sum over the cubes) depend on the timing of the cubes, and a row searched at a depth above 0 gains
+        "nearest_split_depth" after "nearest_work"."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -334,14 +338,21 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             if sat_rows:
                 items = exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows))
                 pred = hint.cpu().numpy()
-                st, cost, models, nwork = exact.nearest_model([items[i] for i in sat_rows], [pred[offs[i]:offs[i + 1]] for i in sat_rows],
-                                                              budget=budget, device=hint.device)
+                # config['complete_nearest_split']: the search of every row spread over 2^depth waves (pdp_exact_nearest_split); -1: auto.
+                # The model the complete search has just found is the start model: the cubes look below its distance only.
+                nsplit = self._config.get('complete_nearest_split')
+                nsplit = None if nsplit is None else ('auto' if int(nsplit) < 0 else int(nsplit))
+                begin = None if nsplit is None else [np.asarray(rows[i]['solution'], dtype=np.float32) for i in sat_rows]
+                st, cost, models, nwork, ndepth = exact.nearest_model([items[i] for i in sat_rows], [pred[offs[i]:offs[i + 1]] for i in sat_rows],
+                                                                      budget=budget, device=hint.device, split=nsplit, start=begin, depths=True)
                 for k, i in enumerate(sat_rows):
                     row = rows[i]
                     if cost[k] >= 0:
                         row['nearest'] = int(cost[k])
                     row['nearest_proved'] = int(st[k] == 1)
                     row['nearest_solution'], row['nearest_work'] = models[k].astype(int).tolist(), int(nwork[k])
+                    if ndepth[k] > 0:
+                        row['nearest_split_depth'] = int(ndepth[k])
                 if hasattr(self, '_nearest_stats'):
                     self._nearest_stats[0] += int((st == 1).sum()); self._nearest_stats[1] += len(sat_rows)
         if hasattr(self, '_complete_stats'):

@@ -40,7 +40,10 @@ chosen from their number): the budget applies per cube, so a bracket is tightene
 cubes, and "mass_split_depth" appears on the rows weighed at a depth above 0; ``--complete-nearest`` (with ``--complete``) gives every
 satisfiable row "nearest", the fewest variables in which a model of the instance differs from the model's own assignment
 (pdp_exact_nearest, branch and bound from that assignment; left out where no model was met within the budget), "nearest_proved" (1 / 0: the
-budget ran out and it is an upper bound), "nearest_solution" (that model) and "nearest_work"; a row PDP solved gets "nearest" 0.
+budget ran out and it is an upper bound), "nearest_solution" (that model) and "nearest_work"; a row PDP solved gets "nearest" 0; ``--complete-nearest-split N`` (with
+``--complete-nearest``) spreads that branch and bound over 2^N waves per row that share the best cost found (pdp_exact_nearest_split; -1: a
+plain first stage, then the rows left unproved once more at a depth chosen from their number, starting below the cost they hold): the
+budget applies per cube, "nearest_work" is summed over the cubes, and "nearest_split_depth" appears on the rows searched at a depth above 0.
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -191,6 +194,13 @@ def main(argv=None):
                         'variables in which a model of the instance differs from the model\'s assignment (pdp_exact_nearest, branch and bound from '
                         'that assignment, --complete-budget reads; left out where no model was met), "nearest_proved" (0: the budget ran out, an '
                         'upper bound), "nearest_solution" and "nearest_work"; a row PDP solved gets "nearest" 0', action='store_true')
+    parser.add_argument('--complete-nearest-split', dest='complete_nearest_split', help='With --complete --complete-nearest: spread the branch '
+                        'and bound of every satisfiable row over 2^N waves that share the best cost found (pdp_exact_nearest_split), N from 0 to '
+                        '16, or -1: a plain first stage, then the rows left unproved once more at a depth that fills the GPU, starting below the '
+                        'cost of the model they hold; the budget applies per cube, "nearest_work" is summed over the cubes, '
+                        '"nearest_split_depth" on the rows searched at a depth above 0.  The model --complete found is always the start model of '
+                        'that search, so N = 0 is not the call without the flag: the start model is checked first and its reads are part of '
+                        '"nearest_work"', type=int, default=None)
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -233,6 +243,11 @@ def main(argv=None):
             parser.error("--complete-min-unsat-split spreads the search of --complete-min-unsat: give --complete-min-unsat as well")
         if not -1 <= args['complete_min_unsat_split'] <= 16:
             parser.error("--complete-min-unsat-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows left unproved")
+    if args['complete_nearest_split'] is not None:
+        if not args['complete_nearest']:
+            parser.error("--complete-nearest-split spreads the search of --complete-nearest: give --complete-nearest as well")
+        if not -1 <= args['complete_nearest_split'] <= 16:
+            parser.error("--complete-nearest-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows left unproved")
     if args['complete_sample'] is not None:
         if not args['complete_count']:
             parser.error("--complete-sample draws from the models --complete-count counts: give --complete-count as well")

@@ -89,6 +89,12 @@ pdp_exact_count next to pdp_exact_nearest on the same problem, one timed call ea
 reads against the count's (work <= the count's + edges asserted on every complete count), how many rows are proved, end at the budget
 with an upper bound or with nothing found, the distribution of the distance, and the unsat_clauses of PDP's assignment next to it.
 
+Split nearest rows (pdp_exact_nearest_split; never part of the default): ``nsa`` / ``nsb`` = the first / all of the instances row ``nd``
+leaves at an upper bound as a batch of their own, 2^28 reads per instance and per cube: kernel time of pdp_exact_nearest and of the split
+call at depths 4 / 8 / 12 (``nsb`` also with the plain call's models as start models), proved counts, reads, the largest cube's share and
+the cubes that accepted nothing; equal costs wherever both prove are asserted.  ``nsauto`` / ``nsd`` = rows ``na`` / ``nd`` whole, host
+wall time of exact.nearest_model against nearest_model(split='auto'); ``nssweep`` = row ``nd`` over AUTO_NEAREST_STAGE1_BUDGET.
+
 Split mass rows (pdp_exact_mass_split; never part of the default): ``zsa`` / ``zsb`` = the 1 / 8 instances of row ``ca`` with the largest plain
 work at weights 0.5 as a batch of their own: kernel time of pdp_exact_mass and of the split call at depths 4 / 8 / 12 on the same problem
 (each after an untimed call with a budget of one read), with mass * 2^n == count and mass, true_mass and leaves equal to the plain call's
@@ -1115,9 +1121,105 @@ def run_mass_split(key):
               flush=True)
 
 
+NEAREST_SPLIT_ROWS = ('nsa', 'nsb', 'nsauto', 'nssweep', 'nsd')
+
+
+def _nearest_batch(key):
+    "rows na / nd: (title, the instances of row ``key`` that the deciding search answers 1, their slices of the p-d-p forward's assignment)"
+    from pdp import exact
+    title, make = ROWS[key]
+    items = make()
+    pred = np.concatenate([g[0].cpu().numpy() for g in _pdp_forward(items)]).astype(np.float32)
+    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in items])])
+    assert pred.size == voff[-1], "the forward's variables are not the items'"
+    pick = np.nonzero(exact.solve_items(items)[0] == 1)[0]
+    return title, [items[i] for i in pick], [pred[voff[i]:voff[i + 1]] for i in pick]
+
+
+def _nearest_problem(sub, hints):
+    b = dataset.to_torch(dataset.collate_segment(sub), torch.device('cuda:0'))
+    p = native.Problem(b['graph_map'], b['batch_variable_map'], b['batch_function_map'], b['edge_feature'], batch_size=len(sub))
+    return p, torch.from_numpy(np.concatenate(hints)).to(p.device)
+
+
+def run_nearest_split(key):
+    """nsa / nsb: the first / all of the instances row nd leaves at an upper bound, as a batch of their own at 2^28 reads per instance and
+    per cube: pdp_exact_nearest next to pdp_exact_nearest_split at depths 4 / 8 / 12 (PDP_NS_DEPTHS=4,8 picks others), nsb also with the
+    plain call's models as start models; wherever both prove, the costs are asserted equal, and every model is checked by pdp_cnf_eval.
+    PDP_NS_ONLY=plain times the plain call alone and uses nothing that this call added, so the same file measures an older tree (a fresh
+    process per measurement of the alternating comparison); PDP_NS_CACHE=<path> keeps the batch and its hints for those processes.  nsauto / nsd: rows na / nd whole, host wall time of exact.nearest_model and of
+    nearest_model(split='auto').  nssweep: the same on row nd over AUTO_NEAREST_STAGE1_BUDGET = 2^18 / 2^22 / 2^26."""
+    from pdp import exact
+    if key in ('nsa', 'nsb'):
+        import pickle
+        cache = os.environ.get('PDP_NS_CACHE')
+        if cache and os.path.exists(cache):
+            with open(cache, 'rb') as f:
+                title, part, ph = pickle.load(f)
+        else:
+            title, sub, hints = _nearest_batch('d')
+            p, hint = _nearest_problem(sub, hints)
+            st = p.exact_nearest(hint, None, ND_BUDGET)[0].cpu().numpy()
+            left = np.nonzero(st == -1)[0]
+            del p
+            part, ph = [sub[i] for i in left], [hints[i] for i in left]
+            if cache:
+                with open(cache, 'wb') as f:
+                    pickle.dump((title, part, ph), f)
+        if key == 'nsa':
+            part, ph = part[:1], ph[:1]
+        q, h = _nearest_problem(part, ph)
+        q.exact_nearest(h, None, 1)                                                      # the one-time preparation is not timed
+        ms0, out = _event_ms(lambda: q.exact_nearest(h, None, ND_BUDGET, stats=True))
+        st0, co0, mo0, wk0, _ = [t.cpu().numpy() for t in out]
+        print("(%s) the %d instances of row nd (%s) left at an upper bound, 2^28 reads per instance: pdp_exact_nearest kernel %.2f ms  proved %d  "
+              "upper bound %d  nothing found %d  reads %d  cost sum over the rows with a model %d"
+              % (key, len(part), title, ms0, int((st0 == 1).sum()), int(((st0 == -1) & (co0 >= 0)).sum()), int(((st0 == -1) & (co0 < 0)).sum()),
+                 int(wk0.sum()), int(co0[co0 >= 0].sum())), flush=True)
+        if os.environ.get('PDP_NS_ONLY') == 'plain':
+            return
+        q.exact_nearest_split(h, depth=1, budget=1)
+        depths = [int(d) for d in os.environ.get('PDP_NS_DEPTHS', '4,8,12').split(',')]
+        for begin in ((None,) if key == 'nsa' else (None, out[2])):
+            for depth in depths:
+                ms, r = _event_ms(lambda: q.exact_nearest_split(h, None, begin, depth=depth, budget=ND_BUDGET, stats=True))
+                st, co, mo, wk, imp, first, du, sc, off, cst, cco, cwk, cim = [t.cpu().numpy() for t in r]
+                both = (st == 1) & (st0 == 1)
+                assert np.array_equal(co[both], co0[both]), "a proved cost differs from the plain call's"
+                found = co >= 0
+                assert (q.cnf_eval(r[2].contiguous())[0].cpu().numpy().reshape(-1)[found] == 1).all(), "a model returned leaves a clause unsatisfied"
+                share = max(float(cwk[off[j]:off[j + 1]].max()) / max(1.0, float(wk0[j])) for j in range(len(st)))
+                print("    split depth %2d%s: kernel %.2f ms (%.3f of pdp_exact_nearest)  proved %d  upper bound %d  nothing found %d  cubes %d  "
+                      "that accepted nothing %d  at the budget %d  reads %d (%.3f of the plain call's)  largest cube's share of its instance's "
+                      "plain work %.4f  cost sum over the rows with a model %d  lower than the plain call's on %d rows  grid %d"
+                      % (depth, '' if begin is None else ', start = the plain models', ms, ms / ms0, int((st == 1).sum()),
+                         int(((st == -1) & found).sum()), int(((st == -1) & ~found).sum()), cst.size, int((cim == 0).sum()), int((cst == -1).sum()),
+                         int(wk.sum()), float(wk.sum()) / float(wk0.sum()), share, int(co[found].sum()), int((found & ((co0 < 0) | (co < co0))).sum()),
+                         q.exact_last_grid()), flush=True)
+        return
+    title, sub, hints = _nearest_batch('a' if key == 'nsauto' else 'd')
+    budget = 0 if key == 'nsauto' else ND_BUDGET
+    exact.nearest_model(sub[:8], hints[:8], budget=1, split=1)                           # the context, the library and both kernels are loaded
+    ms0, plain = _wall(lambda: exact.nearest_model(sub, hints, budget=budget))
+    print("(%s) the %d satisfiable instances of %s, hints = p-d-p forward, budget %s: nearest_model wall %.1f ms  proved %d  reads %d"
+          % (key, len(sub), title, '2^28' if budget else '2^32', ms0, int((plain[0] == 1).sum()), int(plain[3].sum())), flush=True)
+    for stage1 in ((1 << 18, 1 << 22, 1 << 26) if key == 'nssweep' else (exact.AUTO_NEAREST_STAGE1_BUDGET,)):
+        exact.AUTO_NEAREST_STAGE1_BUDGET = stage1
+        ms, got = _wall(lambda: exact.nearest_model(sub, hints, budget=budget, split='auto', depths=True))
+        both = (plain[0] == 1) & (got[0] == 1)
+        assert np.array_equal(got[1][both], plain[1][both]), "a proved cost differs from the plain call's"
+        assert ((got[1] >= 0) | (plain[1] < 0)).all(), "split='auto' lost a model the plain call holds"
+        print("    nearest_model(split='auto') stage 1 budget 2^%d: wall %.1f ms (%.3f of the plain call)  proved %d  searched again %d at depth %s  "
+              "reads %d" % (stage1.bit_length() - 1, ms, ms / ms0, int((got[0] == 1).sum()), int((got[4] > 0).sum()),
+                            sorted(set(got[4][got[4] > 0].tolist())), int(got[3].sum())), flush=True)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
+        if k in NEAREST_SPLIT_ROWS:
+            run_nearest_split(k)
+            continue
         if k in NEAREST_ROWS:
             run_nearest(k)
             continue
