@@ -25,7 +25,7 @@ extern "C" {
 /* 2 (round 5): pdp_train_gru_backward's scratch contract and the training entry points added in round 4; a coupled multi-process forward
  * (pdp_problem_set_exchange) reports PDP_ERR_SPECULATION on EVERY part when one part cannot take the resident loops.
  * pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn, pdp_exact_learn_reductions, pdp_exact_solve_learn_proof, pdp_exact_check,
- * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass, pdp_exact_mass_split, pdp_exact_mass_split_cubes, pdp_exact_nearest, pdp_exact_nearest_split, pdp_exact_nearest_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
+ * pdp_exact_trim, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_count, pdp_exact_solve_split, pdp_exact_split_cubes, pdp_exact_count_split, pdp_exact_count_split_cubes, pdp_exact_count_frontier_words, pdp_exact_count_round, pdp_exact_count_expand, pdp_exact_models_at, pdp_exact_min_unsat_split, pdp_exact_min_unsat_split_cubes, pdp_exact_mass, pdp_exact_mass_split, pdp_exact_mass_split_cubes, pdp_exact_nearest, pdp_exact_nearest_split, pdp_exact_nearest_split_cubes and pdp_exact_last_grid are additions that change no existing entry point or structure, so the version stays 3. */
 #define PDP_ABI_VERSION 3
 
 enum {
@@ -630,6 +630,61 @@ int pdp_exact_count_split(pdp_problem *p, const int8_t *depth, int64_t budget, i
 int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cube_status, double *cube_count, int64_t *cube_work,
                                 int64_t *cube_leaves, void *stream);
 
+/* pdp_exact_count as a sequence of short launches ("rounds") that can be stopped, continued and re-cut between launches (plain Python,
+ * normative: tests/exact_count_rounds_model.py).  The state of the depth-first search at a budget stop is two bits per
+ * decision level: the polarity the level is on, and whether its other polarity is still owed.
+ *   Cube.  A cube belongs to one instance and has a path of len levels, 0 <= len <= n.  Level L is bit (L - 1) % 32 of word (L - 1) / 32
+ *   of the cube's rows in bits and closed [cubes][words]: (bit, closed) = (0, 0) the polarity the search tries first, the other one
+ *   still owed; (0, 1) the first polarity, nothing owed; (1, 1) the other polarity, nothing owed; (1, 0) is refused.  Bits of levels
+ *   beyond len are not read.  The root cube has len 0.  pdp_exact_count_split's cube (depth, index) is the path of depth closed levels
+ *   with the bits of index.
+ *   Search of a cube.  pdp_exact_count's search with plen = len: a decision that opens level L <= plen takes the polarity its bit asks
+ *   for (0: the search's own first polarity, 1: the other) and carries the flipped mark iff closed; levels above plen are free.  When
+ *   backtracking flips an open level L, plen = min(plen, L): the path beyond a flipped level no longer applies.  A leaf met at a level
+ *   < plen is counted iff every path bit of levels level+1 .. plen is 0; either way the search goes on as after a conflict.  snap, the
+ *   crediting, the end flush of every open level and true_count_c[v] = T[v] + (count_c - T[v] - F[v]) * 0.5 are pdp_exact_count's.
+ *   Budget of a round (reads per cube; budget <= 0: PDP_EXACT_ROUND_BUDGET).  It is tested only where a node begins -- before the first
+ *   pass of the cube, of a decision and of a flip -- never between the passes of one propagation.  Reads count against it from the first
+ *   node that begins with level >= plen: the replay of the path is free against the budget, but counted in work (cube_replay).  reads
+ *   since then >= budget stops the cube with status -1, so every round finishes at least one node beyond its checkpoint, and a cube's
+ *   work is at most its replay plus the budget plus one node.
+ *   Checkpoint of a stopped cube (len_out, bits_out, closed_out, the same shapes as the inputs and distinct from them): len_out = the open
+ *   levels; bit = 1 iff the level is on its other polarity (a path bit, or flipped in this round); closed = its flipped mark.  A cube
+ *   that ends (status 1) leaves len_out 0 and a row of zeros.
+ *   Accumulation.  Per instance, in ascending cube order: count[b] = count[b] + count_c and true_count[v] = true_count[v] +
+ *   true_count_c[v], sequentially in double, INTO the caller's running totals (in/out; zero them before the first round); work[b] and
+ *   leaves[b] take integer sums.  No double goes through an atomic or a reduction across lanes.  While the total is <= 2^53 everything is
+ *   an exact integer, and a count that runs until its frontier is empty equals pdp_exact_count's count, true_count and leaves bit for bit,
+ *   for any budgets and any re-cutting; above, it is the correctly rounded result of this order.
+ * pdp_exact_count_frontier_words: *words_host = the words of a path row, max(1, ceil(n_max / 32)) over the instances of at most 1023
+ * variables.
+ * pdp_exact_count_round: cube_off [B+1] (device int64; instance b owns cubes cube_off[b] .. cube_off[b+1]; cube_off[B] == cubes), len
+ * [cubes] (int32), bits / closed [cubes][words].  cube_status [cubes] = 1 / -1.  cube_count (double), cube_work, cube_leaves and
+ * cube_replay (int64) [cubes] may be NULL.  A check kernel runs BEFORE anything is searched, and a malformed frontier returns
+ * PDP_ERR_INVALID with nothing written, the message naming the cube or instance: cube_off not starting at 0, not monotone or not ending
+ * at cubes; len outside 0 .. n; a (1, 0) pair among a path's levels; a cube on an instance of more than 1023 variables (such an instance
+ * has no cube; its status is the caller's to keep); more than one cube on an instance of the HBM route (its working arrays are per
+ * instance); more than 2^22 cubes, or per-cube rows (cubes x n_max doubles, on the handle) past 2^31 bytes.  One wave takes one cube at a
+ * time from one counter; no wave waits for, or reads a word of, another.  The call synchronises the stream once (the check's verdict).
+ * pdp_exact_count_expand: from a round's inputs cube_off and outputs cube_status, len_out, bits_out, closed_out, the next frontier.
+ * Every stopped cube, in cube order, becomes up to `give` (>= 0) children followed by its remainder: the child of level L is the path of
+ * levels 1 .. L-1 with their bits, all closed, followed by (1, 1); children are made for the shallowest min(give, open levels) open
+ * levels, in ascending L; the remainder is the checkpoint with those levels closed.  A cube of status 1 leaves nothing.  An instance on
+ * the HBM route is never expanded: its one cube is resumed as it is.  The same check runs first (PDP_ERR_INVALID, nothing written); a new
+ * frontier of more than `capacity` cubes (the rows of len_new, bits_new and closed_new) or more than 2^22 is refused the same way.
+ * *cubes_new_host = the new cube count = cube_off_new[B].  The call synchronises the stream once.
+ * Every output of both calls is a function of the instances, the frontier, the budget and give alone.  R != 1 -> PDP_ERR_UNSUPPORTED.
+ * Routing, slab and working arrays are pdp_exact_count's, plus T [V] of the HBM route. */
+#define PDP_EXACT_ROUND_BUDGET (((int64_t)1) << 18)
+int pdp_exact_count_frontier_words(pdp_problem *p, int32_t *words_host);
+int pdp_exact_count_round(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int32_t *len, const uint32_t *bits,
+                          const uint32_t *closed, int64_t budget, double *count, double *true_count, int64_t *work, int64_t *leaves,
+                          int8_t *cube_status, int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out, double *cube_count,
+                          int64_t *cube_work, int64_t *cube_leaves, int64_t *cube_replay, void *stream);
+int pdp_exact_count_expand(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int8_t *cube_status, const int32_t *len,
+                           const uint32_t *bits, const uint32_t *closed, int32_t give, int64_t capacity, int64_t *cube_off_new,
+                           int32_t *len_new, uint32_t *bits_new, uint32_t *closed_new, int64_t *cubes_new_host, void *stream);
+
 /* The models of given ranks in pdp_exact_count's own order (plain Python, normative: tests/exact_rank_model.py).  The
  * counting search meets its leaves in a fixed depth-first order and a leaf with f unassigned variables stands for 2^f models, so "count
  * before the leaf + offset inside it" numbers every model of an instance exactly once.  Instance b asks for K_b = rank_off[b+1] -
@@ -764,7 +819,7 @@ int pdp_exact_nearest_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cub
                                   int32_t *cube_improvements, void *stream);
 
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split, pdp_exact_nearest_split and pdp_exact_mass_split (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split, pdp_exact_nearest_split, pdp_exact_mass_split and pdp_exact_count_round (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

@@ -36,6 +36,8 @@
 // pdp_exact_mass_split (the last kernels) cuts it into cubes as the count's split does, and its cubes share nothing either.
 // pdp_exact_nearest (behind pdp_exact_min_unsat) is the branch and bound with the cost on the variables: the model nearest to a hint.
 // pdp_exact_nearest_split (behind pdp_exact_min_unsat_split) cuts it into cubes that share the 64-bit ub[b]; a start model seeds it.
+// pdp_exact_count_round / pdp_exact_count_expand (the very last kernels) run the count as a sequence of launches over a frontier of path
+// cubes, two bits per decision level, that is checkpointed at a budget stop and cut again between two launches; its cubes share nothing.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -4428,6 +4430,566 @@ int exzs_launch(pdp_problem *p, const float *weights, const int8_t *depth, int64
     return PDP_OK;
 }
 
+// ---- pdp_exact_count_round / pdp_exact_count_expand: a count as a sequence of rounds over a frontier of path cubes ---------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_count_rounds_model.py).  A cube is a path of two bits per
+// decision level; ex_search_count_path is the counting search from the shared blocks with a decision, a leaf rule and a budget of its
+// own.  A round is three launches on one stream: the check (one workgroup; nothing is searched on a malformed frontier), the cubes (one
+// counter hands out cube ids, one wave per cube; every cube leaves a record, its checkpoint and, unless its count is 0.0, its row of
+// per-variable counts), the accumulation (per instance: records and rows added to the caller's running totals in ascending cube
+// order, sequentially).  The state, the slab (exn_lds_layout), the routing and the HBM arrays are k_exact_count's; the HBM route's T is an
+// array of this call's own, because true_count holds the running total here.  An expansion is the check, a scan by one workgroup (the
+// first new cube of every old one) and the rows written by one wave per old cube.  No wave waits for, or reads a word of, another.
+constexpr int EXQ_NT = 1024;                    // the check and the scan: one workgroup each
+constexpr int EXQ_INFO = 8;                     // words of the check (EXQ_BAD_*) and of the scan (EXQ_TOTAL)
+enum { EXQ_BAD_OFF = 0, EXQ_BAD_WIDE, EXQ_BAD_HBM, EXQ_BAD_LEN, EXQ_BAD_PAIR, EXQ_TOTAL };
+
+// What a cube of a round knows: its path (rows of `words` words, level L at bit (L - 1) % 32 of word (L - 1) / 32) and its length.
+struct ExPath { const uint32_t *bits, *closed; int len; };
+
+__device__ __forceinline__ uint32_t exq_bit(const uint32_t *row, int L) { return (row[(L - 1) >> 5] >> ((L - 1) & 31)) & 1u; }
+
+// the bits of word w that belong to levels 1 .. len
+__device__ __forceinline__ uint32_t exq_mask(int len, int w)
+{
+    const int rest = len - 32 * w;
+    return rest <= 0 ? 0u : (rest >= 32 ? ~0u : (1u << rest) - 1u);
+}
+
+// a leaf met at a level < plen is counted iff every path bit of levels level+1 .. plen is 0 (wave-uniform)
+__device__ __forceinline__ bool exq_owns_leaf(const ExPath &Q, int level, int plen)
+{
+    uint32_t any = 0u;
+    for (int w = level >> 5; 32 * w < plen; ++w) any |= Q.bits[w] & exq_mask(plen, w) & ~exq_mask(level, w);
+    return any == 0u;
+}
+
+// The decision push of a path cube: ex_decide where a level L <= plen takes the polarity its path bit asks for (0: the key's, 1: the
+// other) and is recorded as already flipped iff the path has it closed.
+template <bool HBM, typename LitT, typename PtrT, typename Credit>
+__device__ __forceinline__ void exq_decide(const ExInst<LitT, PtrT> &X, const ExPath &Q, int plen, unsigned long long best, int &level,
+                                           int &tlen, const Credit &credit)
+{
+    const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+    ++level;
+    bool pos = (best & 1ull) != 0ull;
+    uint32_t d = (uint32_t)v;
+    if (level <= plen) {
+        pos = pos != (exq_bit(Q.bits, level) != 0u);
+        d |= exq_bit(Q.closed, level) << 31;
+    }
+    ex_sync<HBM>();
+    if (threadIdx.x == 0) { X.mark[level] = tlen; X.dvar[level] = d; X.val[v] = pos ? 1 : 2; X.trail[tlen] = v; credit.open(level); }
+    ++tlen;
+    ex_sync<HBM>();
+}
+
+// The counting search of one path cube by the calling wave.  Returns 1 (the cube is exhausted) or -1 (budget spent: levels 1 .. *level_out
+// are open, *plen_out of them still as the path has them).  The budget is tested only where a node begins (`fresh`), on the reads made
+// since the first node that began with level >= plen (`base`; -1: still replaying).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_count_path(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int64_t budget, const ExPath &Q, int *level_out,
+                                    int *plen_out, int64_t *work_out, int64_t *replay_out, double *count_out, int64_t *leaves_out)
+{
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0, plen = Q.len;
+    int64_t work = 0, leaves = 0, base = -1;
+    double count = 0.0;
+    int result = -1;
+    bool fresh = true;
+    ExnCredit credit{A, count, 0.0};
+    for (;;) {
+        if (fresh) {
+            if (base < 0 && level >= plen) base = work;
+            if (base >= 0 && work - base >= budget) break;
+            fresh = false;
+        }
+        const ExPass P = ex_propagate(X);
+        work += ex_sum(P.reads);
+        bool any_conflict = __ballot(P.conflict) != 0ull;
+        const bool any_unit = __ballot(P.unit) != 0ull;
+        if (any_unit) {
+            ex_sync<HBM>();
+            const bool both = ex_assign_pending<HBM, false>(X, tlen);
+            any_conflict = any_conflict || both;
+        }
+        int wmin = INF;
+        if (!any_conflict) {
+            if (any_unit) continue;
+            wmin = ex_min(P.wmin);
+            if (wmin == INF) {
+                // a leaf: every clause has a true literal and the unassigned variables are free; then as after a conflict
+                if (level >= plen || exq_owns_leaf(Q, level, plen)) {
+                    count = count + ldexp(1.0, X.n - tlen);
+                    ++leaves;
+                }
+                any_conflict = true;
+            }
+        }
+        if (any_conflict) {
+            if (!ex_backtrack<HBM>(X, level, tlen, credit)) { result = 1; break; }
+            plen = level < plen ? level : plen;                     // `level` was flipped: the path beyond it no longer applies
+            fresh = true;
+            continue;
+        }
+        const unsigned long long best = ex_branch<HBM, EX_PHASE_COUNT>(X, wmin, work);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        exq_decide<HBM>(X, Q, plen, best, level, tlen, credit);
+        fresh = true;
+    }
+    *level_out = result == 1 ? 0 : level; *plen_out = plen;
+    // the end flush of ex_search_count; dvar keeps the levels' marks for the checkpoint
+    for (; level >= 0; --level) {
+        const int from = level > 0 ? X.mark[level] : 0;
+        exn_credit(X, A, from, tlen, count - A.snap[level]);
+        tlen = from;
+    }
+    *work_out = work; *replay_out = base < 0 ? work : base; *count_out = count; *leaves_out = leaves;
+    return result;
+}
+
+struct ExqParams {
+    int B;
+    uint32_t total;             // cubes of the round
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;             // per cube, past its replay
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    const int32_t *len;         // [total]
+    const uint32_t *bits, *closed;      // [total][words]
+    int words;
+    int8_t *cube_status;        // [total] 1 / -1
+    int32_t *len_out; uint32_t *bits_out, *closed_out;      // the checkpoints, shaped as the inputs
+    double *cube_count;         // [total]
+    int64_t *cube_work, *cube_leaves, *cube_replay;         // [total]
+    double *rows;               // [total][n_max] true_count of every cube whose count is not 0.0
+    int n_max;
+    double *count, *true_count; int64_t *work, *leaves;     // the running totals (in/out)
+    ExHbm h;
+    double *h_T, *h_F, *h_snap; // the HBM route's accumulators: T [V] of this call's own, F and snap as ExnParams
+};
+
+// cube q of instance I.b: copy the instance (ex_fill), clear the state, search along the path; then the cube's record, its row of
+// per-variable counts unless its count is 0.0, and its checkpoint: one lane per level, the row's words from ballots, written by lane 0
+// with plain stores.  A level is closed iff it carries the flipped mark; it is on its other polarity iff its path bit says so (levels
+// 1 .. plen are still as the path has them) or it was flipped in this round (marked, and not closed by the path).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_count_path(const ExqParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExnAcc A, uint32_t q)
+{
+    const int lane = (int)threadIdx.x;
+    ex_fill<HBM>(I, X);
+    for (int v = lane; v < I.n; v += EX_NT) {
+        X.val[v] = 0; X.pend[v] = 0u; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+        A.T[v] = 0.0; A.F[v] = 0.0;
+    }
+    if (lane == 0) A.snap[0] = 0.0;
+    ex_sync<HBM>();
+    const size_t row = (size_t)q * (size_t)xp.words;
+    const ExPath Q{xp.bits + row, xp.closed + row, xp.len[q]};
+    int64_t work = 0, replay = 0, leaves = 0;
+    double count = 0.0;
+    int level = 0, plen = 0;
+    const int st = ex_search_count_path<HBM>(X, A, xp.budget, Q, &level, &plen, &work, &replay, &count, &leaves);
+    ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
+    if (count != 0.0) {
+        double *out = xp.rows + (size_t)q * (size_t)xp.n_max;
+        for (int v = lane; v < I.n; v += EX_NT) {
+            const double t = A.T[v];
+            out[v] = t + (count - t - A.F[v]) * 0.5;
+        }
+    }
+    for (int w = 0; w < xp.words; w += 2) {
+        const int L = 32 * w + lane + 1;
+        const uint32_t mark = L <= level ? X.dvar[L] >> 31 : 0u;
+        const bool path = L <= plen && L <= level;
+        const uint32_t pb = path ? exq_bit(Q.bits, L) : 0u, pc = path ? exq_bit(Q.closed, L) : 0u;
+        const unsigned long long bb = __ballot((pb | (mark & (pc ^ 1u))) != 0u), cc = __ballot(mark != 0u);
+        if (lane == 0) {
+            xp.bits_out[row + w] = (uint32_t)bb; xp.closed_out[row + w] = (uint32_t)cc;
+            if (w + 1 < xp.words) { xp.bits_out[row + w + 1] = (uint32_t)(bb >> 32); xp.closed_out[row + w + 1] = (uint32_t)(cc >> 32); }
+        }
+    }
+    if (lane == 0) {
+        xp.cube_status[q] = (int8_t)st;
+        xp.len_out[q] = level;
+        xp.cube_count[q] = count;
+        xp.cube_work[q] = work;
+        xp.cube_leaves[q] = leaves;
+        xp.cube_replay[q] = replay;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_count_round(PView pv, ExqParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= xp.total) break;
+        const int lo = exs_instance(xp.cube_off, xp.B, q);
+        const Inst I = load_inst(pv, lo);
+        // the check has passed: every cube's instance has at most 1023 variables.  Both arms end in the barrier of ex_solve_count_path
+        // and fall through to the end of the loop body (see k_exact_count)
+        if (xp.route[lo]) {
+            ExnAcc A;
+            A.T = xp.h_T + I.v0; A.F = xp.h_F + I.v0; A.snap = xp.h_snap + I.v0 + I.b;
+            ex_solve_count_path<true>(xp, I, ex_bind_hbm(xp.h, I), A, q);
+        } else {
+            ex_solve_count_path<false>(xp, I, ex_bind_lds(ex_slab, I), exn_bind_lds(ex_slab, I), q);
+        }
+    }
+}
+
+// The running totals of every instance take its cubes' records and rows, one wave per instance: k_exact_count_split_finish's order
+// (the counts of 64 cubes at a time staged in LDS and added by every lane in the same order; true_count[v] by the lane that holds v,
+// over the rows of the cubes whose count is not 0.0), starting from the caller's values instead of 0.
+__global__ void __launch_bounds__(EX_NT) k_exact_count_round_accumulate(PView pv, ExqParams xp)
+{
+    __shared__ double s_count[EX_NT];
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        if (nc == 0) continue;                                      // wave-uniform, before any barrier of the body
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        double count = xp.count[b];
+        int64_t w = 0, lv = 0;
+        for (int64_t base = 0; base < nc; base += EX_NT) {
+            const int64_t j = base + lane;
+            const bool in = j < nc;
+            s_count[lane] = in ? xp.cube_count[c0 + j] : 0.0;
+            if (in) { w += xp.cube_work[c0 + j]; lv += xp.cube_leaves[c0 + j]; }
+            __syncthreads();
+            const int lim = (int)(nc - base < EX_NT ? nc - base : EX_NT);
+            for (int t = 0; t < lim; ++t) count = count + s_count[t];
+            __syncthreads();
+        }
+        w = exs_sum64(w);
+        lv = exs_sum64(lv);
+        for (int vb = 0; vb < n; vb += EX_NT) {
+            const int v = vb + lane;
+            double acc = v < n ? xp.true_count[v0 + v] : 0.0;
+            for (int64_t base = 0; base < nc; base += EX_NT) {
+                const int64_t j = base + lane;
+                s_count[lane] = j < nc ? xp.cube_count[c0 + j] : 0.0;
+                __syncthreads();
+                const int lim = (int)(nc - base < EX_NT ? nc - base : EX_NT);
+                for (int t = 0; t < lim; t += EXNS_ROWS_IN_FLIGHT) {
+                    double r[EXNS_ROWS_IN_FLIGHT];
+#pragma unroll
+                    for (int u = 0; u < EXNS_ROWS_IN_FLIGHT; ++u) {
+                        const bool take = t + u < lim && s_count[t + u] != 0.0 && v < n;
+                        r[u] = take ? xp.rows[(size_t)(c0 + base + t + u) * (size_t)xp.n_max + (size_t)v] : 0.0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < EXNS_ROWS_IN_FLIGHT; ++u)
+                        if (t + u < lim && s_count[t + u] != 0.0) acc = acc + r[u];
+                }
+                __syncthreads();
+            }
+            if (v < n) xp.true_count[v0 + v] = acc;
+        }
+        if (lane == 0) {
+            xp.count[b] = count;
+            xp.work[b] += w;
+            xp.leaves[b] += lv;
+        }
+    }
+}
+
+// The check of a frontier, by one workgroup, before anything reads it: info[EXQ_BAD_*] = the lowest offender of each kind (EXS_NONE:
+// none).  OFF (an instance): cube_off does not start at 0, falls, or does not end at `cubes`; the cubes are looked at only when it is
+// sound, so the bisection and every row index below stay in bounds.  WIDE (a cube): its instance has more than 1023 variables.  HBM (an
+// instance): more than one cube on the HBM route.  LEN (a cube): len outside 0 .. n.  PAIR (a cube): a level on its other polarity that
+// is not closed.
+__global__ void __launch_bounds__(EXQ_NT) k_exact_count_round_check(PView pv, const uint8_t *route, const int64_t *cube_off, int64_t cubes,
+                                                                    const int32_t *len, const uint32_t *bits, const uint32_t *closed, int words,
+                                                                    int64_t *info)
+{
+    __shared__ int bad[EXQ_TOTAL];
+    const int t = (int)threadIdx.x, B = pv.B;
+    if (t < EXQ_TOTAL) bad[t] = EXS_NONE;
+    __syncthreads();
+    for (int b = t; b < B; b += EXQ_NT) {
+        const int64_t a = cube_off[b], z = cube_off[b + 1];
+        if (z < a || (b == 0 && a != 0) || (b == B - 1 && z != cubes)) atomicMin(&bad[EXQ_BAD_OFF], b);
+    }
+    __syncthreads();
+    if (bad[EXQ_BAD_OFF] == EXS_NONE) {                             // uniform over the workgroup
+        for (int b = t; b < B; b += EXQ_NT) {
+            const int64_t a = cube_off[b], nc = cube_off[b + 1] - a;
+            if (nc > 0 && pv.inst_v0[b + 1] - pv.inst_v0[b] > EXN_MAX_N) atomicMin(&bad[EXQ_BAD_WIDE], (int)a);
+            if (nc > 1 && route[b]) atomicMin(&bad[EXQ_BAD_HBM], b);
+        }
+        for (int64_t c = t; c < cubes; c += EXQ_NT) {
+            const int b = exs_instance(cube_off, B, (uint32_t)c);
+            const int n = pv.inst_v0[b + 1] - pv.inst_v0[b], L = len[c];
+            if (n > EXN_MAX_N) continue;                            // reported above; the rows are `words` wide for n <= 1023 only
+            if (L < 0 || L > n) { atomicMin(&bad[EXQ_BAD_LEN], (int)c); continue; }
+            uint32_t pair = 0u;
+            for (int w = 0; 32 * w < L; ++w) pair |= bits[c * words + w] & ~closed[c * words + w] & exq_mask(L, w);
+            if (pair) atomicMin(&bad[EXQ_BAD_PAIR], (int)c);
+        }
+    }
+    __syncthreads();
+    if (t < EXQ_TOTAL) info[t] = bad[t];
+}
+
+// The scan of an expansion, by one workgroup; it returns at once unless the check before it found nothing.  Old cube c becomes
+// dst[c + 1] - dst[c] new ones: none unless it stopped, else 1 + min(give, its open levels), give = 0 on the HBM route.  new_off[b] =
+// dst[cube_off[b]]; info[EXQ_TOTAL] = the new cube count.
+__global__ void __launch_bounds__(EXQ_NT) k_exact_count_expand_scan(PView pv, const uint8_t *route, const int64_t *cube_off, int64_t cubes,
+                                                                    const int8_t *cube_status, const int32_t *len, const uint32_t *closed,
+                                                                    int words, int give, int64_t *dst, int64_t *new_off, int64_t *info)
+{
+    __shared__ int64_t s[EXQ_NT];
+    const int t = (int)threadIdx.x, B = pv.B;
+    bool sound = true;
+    for (int k = 0; k < EXQ_TOTAL; ++k) sound = sound && info[k] == EXS_NONE;
+    if (!sound) return;                                             // uniform: every thread reads the same words
+    int64_t running = 0;
+    for (int64_t base = 0; base < cubes; base += EXQ_NT) {
+        const int64_t c = base + t;
+        int64_t x = 0;
+        if (c < cubes && cube_status[c] == -1) {
+            const int b = exs_instance(cube_off, B, (uint32_t)c);
+            const int L = len[c];
+            int open = 0;
+            for (int w = 0; 32 * w < L; ++w) open += __popc(~closed[c * words + w] & exq_mask(L, w));
+            const int g = route[b] ? 0 : give;
+            x = 1 + (open < g ? open : g);
+        }
+        s[t] = x;
+        __syncthreads();
+        for (int o = 1; o < EXQ_NT; o <<= 1) {
+            const int64_t y = t >= o ? s[t - o] : 0;
+            __syncthreads();
+            s[t] += y;
+            __syncthreads();
+        }
+        if (c < cubes) dst[c] = running + s[t] - x;
+        running += s[EXQ_NT - 1];
+        __syncthreads();
+    }
+    if (t == 0) dst[cubes] = running;
+    __syncthreads();
+    for (int b = t; b <= B; b += EXQ_NT) new_off[b] = dst[cube_off[b]];
+    if (t == 0) info[EXQ_TOTAL] = running;
+}
+
+// The rows of an expansion, one wave per old cube that stopped, lane w on word w of its row.  Child j gives away the j-th open level L
+// (ascending): levels 1 .. L-1 with their bits, all closed, then (1, 1).  The remainder is the checkpoint with the given levels closed.
+__global__ void __launch_bounds__(EX_NT) k_exact_count_expand_write(int64_t cubes, const int32_t *len, const uint32_t *bits, const uint32_t *closed,
+                                                                    int words, const int64_t *dst, int32_t *len_new, uint32_t *bits_new,
+                                                                    uint32_t *closed_new)
+{
+    const int lane = (int)threadIdx.x;
+    for (int64_t c = (int64_t)blockIdx.x; c < cubes; c += (int64_t)gridDim.x) {
+        const int64_t at = dst[c];
+        const int made = (int)(dst[c + 1] - at);
+        if (made == 0) continue;                                    // wave-uniform
+        const int g = made - 1, L = len[c];
+        const bool mine = lane < words;
+        const uint32_t m = exq_mask(L, lane);
+        const uint32_t cb = mine ? bits[c * words + lane] & m : 0u, cc = mine ? closed[c * words + lane] & m : 0u;
+        const uint32_t open = mine ? ~cc & m : 0u;
+        const int pop = __popc(open);
+        int before = pop;                                           // open levels in the words below this lane's
+        for (int o = 1; o < EX_NT; o <<= 1) { const int y = __shfl_up(before, o); if (lane >= o) before += y; }
+        before -= pop;
+        for (int j = 0; j < g; ++j) {
+            const int k = j - before;                               // the k-th open level of this word is the j-th of the row
+            const bool has = k >= 0 && k < pop;
+            uint32_t o = open;
+            for (int i = 0; has && i < k; ++i) o &= o - 1u;
+            const int at_bit = has ? 32 * lane + (__ffs((int)o) - 1) : 0;
+            const unsigned long long who = __ballot(has);
+            const int L0 = __shfl(at_bit, __ffsll((long long)who) - 1);        // the level's index from 0; exactly one lane has it
+            const int w0 = L0 >> 5;
+            const uint32_t one = 1u << (L0 & 31);
+            if (mine) {
+                const size_t r = (size_t)(at + j) * (size_t)words + (size_t)lane;
+                bits_new[r] = lane < w0 ? cb : (lane == w0 ? (cb & (one - 1u)) | one : 0u);
+                closed_new[r] = lane < w0 ? ~0u : (lane == w0 ? (one - 1u) | one : 0u);
+            }
+            if (lane == 0) len_new[at + j] = L0 + 1;
+        }
+        int k = g - before;                                         // this word's open levels among the g given away
+        k = k < 0 ? 0 : (k > pop ? pop : k);
+        uint32_t given = 0u, o = open;
+        for (int i = 0; i < k; ++i) { given |= o & (0u - o); o &= o - 1u; }
+        if (mine) {
+            const size_t r = (size_t)(at + g) * (size_t)words + (size_t)lane;
+            bits_new[r] = cb;
+            closed_new[r] = cc | given;
+        }
+        if (lane == 0) len_new[at + g] = L;
+    }
+}
+
+// exn_prepare's routing and slab, plus what the rounds need of their own: n_max over the instances that are searched, the route bytes
+// (ex_prepare's HBM list, per instance) and T [V] for the HBM route.  One block: info [EXQ_INFO] | T [V] | route [B].  Once per problem.
+int exq_prepare(pdp_problem *p)
+{
+    { const int st_ = exn_prepare(p); if (st_ != PDP_OK) return st_; }
+    if (p->exq_ready) return PDP_OK;
+    const size_t B = p->B, V = p->ex_nbig > 0 ? (size_t)p->V : 0;
+    std::vector<int32_t> v0(B + 1), big((size_t)p->ex_nbig);
+    PDP_HIP_CHECK(hipMemcpy(v0.data(), p->inst_v0, (B + 1) * 4, hipMemcpyDeviceToHost));
+    if (!big.empty()) PDP_HIP_CHECK(hipMemcpy(big.data(), p->ex_order, big.size() * 4, hipMemcpyDeviceToHost));
+    int nmax = 0;
+    for (size_t b = 0; b < B; ++b) { const int n = v0[b + 1] - v0[b]; if (n <= EXN_MAX_N) nmax = std::max(nmax, n); }
+    std::vector<uint8_t> route(B, 0);
+    for (int32_t b : big) route[(size_t)b] = 1;
+    { const int st_ = pdp_dev_alloc((void **)&p->exq.blob, (EXQ_INFO * 8 + V * 8 + B + 15) & ~(size_t)15); if (st_ != PDP_OK) return st_; }
+    PDP_HIP_CHECK(hipMemcpy(p->exq.blob + EXQ_INFO * 8 + V * 8, route.data(), B, hipMemcpyHostToDevice));
+    p->exq_nmax = nmax;
+    p->exq_ready = 1;
+    return PDP_OK;
+}
+
+inline int exq_words(const pdp_problem *p) { return std::max(1, (p->exq_nmax + 31) / 32); }
+inline int64_t *exq_info(const pdp_problem *p) { return (int64_t *)p->exq.blob; }
+inline const uint8_t *exq_route(const pdp_problem *p) { return (const uint8_t *)(p->exq.blob + EXQ_INFO * 8 + (p->ex_nbig > 0 ? (size_t)p->V * 8 : 0)); }
+
+// what the host can refuse before a kernel looks at the frontier
+int exq_sizes(const pdp_problem *p, const char *name, int64_t cubes)
+{
+    if (cubes < 0 || cubes > EXS_MAX_CUBES) {
+        pdp_set_error("%s: %lld cubes; a frontier holds 0 .. 2^22", name, (long long)cubes);
+        return PDP_ERR_INVALID;
+    }
+    if (cubes * (int64_t)p->exq_nmax * 8 > EXNS_MAX_ROW_BYTES) {
+        pdp_set_error("%s: the per-cube rows (%lld cubes x %d variables x 8 bytes) pass 2^31 bytes; split the batch", name, (long long)cubes,
+                      p->exq_nmax);
+        return PDP_ERR_INVALID;
+    }
+    return PDP_OK;
+}
+
+void exq_check_launch(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int32_t *len, const uint32_t *bits, const uint32_t *closed,
+                      hipStream_t st)
+{
+    hipLaunchKernelGGL(k_exact_count_round_check, dim3(1), dim3(EXQ_NT), 0, st, make_view(p), exq_route(p), cube_off, cubes, len, bits, closed,
+                       exq_words(p), exq_info(p));
+}
+
+// the check's verdict, in the order of its kinds
+int exq_verdict(const char *name, const int64_t info[EXQ_INFO])
+{
+    if (info[EXQ_BAD_OFF] != EXS_NONE) {
+        pdp_set_error("%s: cube_off must start at 0, never fall and end at the cube count (instance %lld)", name, (long long)info[EXQ_BAD_OFF]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[EXQ_BAD_WIDE] != EXS_NONE) {
+        pdp_set_error("%s: cube %lld is on an instance of more than %d variables, which is not searched", name, (long long)info[EXQ_BAD_WIDE],
+                      EXN_MAX_N);
+        return PDP_ERR_INVALID;
+    }
+    if (info[EXQ_BAD_HBM] != EXS_NONE) {
+        pdp_set_error("%s: instance %lld is on the HBM route (per-instance working arrays) and has more than one cube", name,
+                      (long long)info[EXQ_BAD_HBM]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[EXQ_BAD_LEN] != EXS_NONE) {
+        pdp_set_error("%s: the length of cube %lld is not in 0 .. the variables of its instance", name, (long long)info[EXQ_BAD_LEN]);
+        return PDP_ERR_INVALID;
+    }
+    if (info[EXQ_BAD_PAIR] != EXS_NONE) {
+        pdp_set_error("%s: cube %lld has a level on its other polarity that is not closed (the pair (1, 0))", name, (long long)info[EXQ_BAD_PAIR]);
+        return PDP_ERR_INVALID;
+    }
+    return PDP_OK;
+}
+
+int exq_round(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int32_t *len, const uint32_t *bits, const uint32_t *closed,
+              int64_t budget, double *count, double *true_count, int64_t *work, int64_t *leaves, int8_t *cube_status, int32_t *len_out,
+              uint32_t *bits_out, uint32_t *closed_out, double *cube_count, int64_t *cube_work, int64_t *cube_leaves, int64_t *cube_replay,
+              void *stream)
+{
+    const char *name = "pdp_exact_count_round";
+    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
+    { const int st_ = exq_sizes(p, name, cubes); if (st_ != PDP_OK) return st_; }
+    const hipStream_t st = ST(stream);
+    int64_t info[EXQ_INFO];
+    exq_check_launch(p, cube_off, cubes, len, bits, closed, st);
+    PDP_LAUNCH_CHECK();
+    PDP_HIP_CHECK(hipMemcpyAsync(info, exq_info(p), EXQ_INFO * 8, hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));
+    { const int st_ = exq_verdict(name, info); if (st_ != PDP_OK) return st_; }
+    if (cubes == 0) return PDP_OK;
+    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax, B = p->B;
+    // per-cube records: count [total] | work [total] | leaves [total] | replay [total] | rows [total][n_max] | status [total]
+    { const int st_ = exs_records(p->exq, total * 32 + total * nmax * 8 + total); if (st_ != PDP_OK) return st_; }
+    ExqParams xp;
+    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_ROUND_BUDGET;
+    xp.route = exq_route(p); xp.cube_off = cube_off; xp.len = len; xp.bits = bits; xp.closed = closed; xp.words = exq_words(p);
+    xp.cube_status = cube_status; xp.len_out = len_out; xp.bits_out = bits_out; xp.closed_out = closed_out;
+    xp.cube_count = (double *)p->exq.cubes;
+    xp.cube_work = (int64_t *)(p->exq.cubes + total * 8);
+    xp.cube_leaves = (int64_t *)(p->exq.cubes + total * 16);
+    xp.cube_replay = (int64_t *)(p->exq.cubes + total * 24);
+    xp.rows = (double *)(p->exq.cubes + total * 32);
+    xp.n_max = (int)nmax;
+    xp.count = count; xp.true_count = true_count; xp.work = work; xp.leaves = leaves;
+    xp.h = ex_hbm(p);
+    xp.h_T = p->ex_nbig > 0 ? (double *)(p->exq.blob + EXQ_INFO * 8) : nullptr;
+    xp.h_F = p->exn_blob ? (double *)p->exn_blob : nullptr;
+    xp.h_snap = p->exn_blob ? (double *)(p->exn_blob + (size_t)p->V * 8) : nullptr;
+    { const int st_ = ex_launch_persistent(p, k_exact_count_round, xp, (int64_t)total, p->exn_lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_count_round_accumulate, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    if (cube_count) PDP_HIP_CHECK(hipMemcpyAsync(cube_count, xp.cube_count, total * 8, hipMemcpyDeviceToDevice, st));
+    if (cube_work) PDP_HIP_CHECK(hipMemcpyAsync(cube_work, xp.cube_work, total * 8, hipMemcpyDeviceToDevice, st));
+    if (cube_leaves) PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, xp.cube_leaves, total * 8, hipMemcpyDeviceToDevice, st));
+    if (cube_replay) PDP_HIP_CHECK(hipMemcpyAsync(cube_replay, xp.cube_replay, total * 8, hipMemcpyDeviceToDevice, st));
+    return PDP_OK;
+}
+
+int exq_expand(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int8_t *cube_status, const int32_t *len, const uint32_t *bits,
+               const uint32_t *closed, int32_t give, int64_t capacity, int64_t *cube_off_new, int32_t *len_new, uint32_t *bits_new,
+               uint32_t *closed_new, int64_t *cubes_new_host, void *stream)
+{
+    const char *name = "pdp_exact_count_expand";
+    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
+    { const int st_ = exq_sizes(p, name, cubes); if (st_ != PDP_OK) return st_; }
+    if (give < 0 || capacity < 0) {
+        pdp_set_error("%s: give (%d) and capacity (%lld) must not be negative", name, (int)give, (long long)capacity);
+        return PDP_ERR_INVALID;
+    }
+    const hipStream_t st = ST(stream);
+    const size_t total = (size_t)cubes, B = p->B;
+    // the scan: dst [total + 1] | new_off [B + 1]
+    { const int st_ = exs_records(p->exq, (total + 1) * 8 + (B + 1) * 8); if (st_ != PDP_OK) return st_; }
+    int64_t *dst = (int64_t *)p->exq.cubes, *new_off = dst + total + 1;
+    int64_t info[EXQ_INFO];
+    exq_check_launch(p, cube_off, cubes, len, bits, closed, st);
+    PDP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_exact_count_expand_scan, dim3(1), dim3(EXQ_NT), 0, st, make_view(p), exq_route(p), cube_off, cubes, cube_status, len,
+                       closed, exq_words(p), (int)give, dst, new_off, exq_info(p));
+    PDP_LAUNCH_CHECK();
+    PDP_HIP_CHECK(hipMemcpyAsync(info, exq_info(p), EXQ_INFO * 8, hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));
+    { const int st_ = exq_verdict(name, info); if (st_ != PDP_OK) return st_; }
+    const int64_t made = info[EXQ_TOTAL];
+    if (made > EXS_MAX_CUBES || made > capacity) {
+        pdp_set_error("%s: the new frontier has %lld cubes, more than %s; lower give", name, (long long)made,
+                      made > EXS_MAX_CUBES ? "2^22" : "the capacity of the output rows");
+        return PDP_ERR_INVALID;
+    }
+    PDP_HIP_CHECK(hipMemcpyAsync(cube_off_new, new_off, (B + 1) * 8, hipMemcpyDeviceToDevice, st));
+    if (cubes > 0 && made > 0) {
+        const int64_t grid = std::min<int64_t>(cubes, (int64_t)pdp_device_cus() * 16);
+        hipLaunchKernelGGL(k_exact_count_expand_write, dim3((unsigned)grid), dim3(EX_NT), 0, st, cubes, len, bits, closed, exq_words(p), dst,
+                           len_new, bits_new, closed_new);
+        PDP_LAUNCH_CHECK();
+    }
+    *cubes_new_host = made;
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -4631,6 +5193,49 @@ extern "C" int pdp_exact_count_split_cubes(pdp_problem *p, int64_t *cube_off, in
     PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, p->exns.cubes + total * 16, total * 8, hipMemcpyDeviceToDevice, ST(stream)));
     PDP_HIP_CHECK(hipMemcpyAsync(cube_status, p->exns.cubes + p->exns.status_off, total, hipMemcpyDeviceToDevice, ST(stream)));
     return PDP_OK;
+}
+
+extern "C" int pdp_exact_count_frontier_words(pdp_problem *p, int32_t *words_host)
+{
+    PDP_REQUIRE(p && words_host, "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_count_frontier_words: a replicated problem (R = %d) is not supported; count on the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
+    *words_host = (int32_t)exq_words(p);
+    return PDP_OK;
+}
+
+extern "C" int pdp_exact_count_round(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int32_t *len, const uint32_t *bits,
+                                     const uint32_t *closed, int64_t budget, double *count, double *true_count, int64_t *work, int64_t *leaves,
+                                     int8_t *cube_status, int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out, double *cube_count,
+                                     int64_t *cube_work, int64_t *cube_leaves, int64_t *cube_replay, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && count && true_count && work && leaves, "NULL argument");
+    PDP_REQUIRE(cubes <= 0 || (len && bits && closed && cube_status && len_out && bits_out && closed_out), "NULL argument");
+    PDP_REQUIRE(cubes <= 0 || (bits_out != bits && closed_out != closed && len_out != len), "pdp_exact_count_round: the checkpoints must not alias the frontier");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_count_round: a replicated problem (R = %d) is not supported; count on the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exq_round(p, cube_off, cubes, len, bits, closed, budget, count, true_count, work, leaves, cube_status, len_out, bits_out, closed_out,
+                     cube_count, cube_work, cube_leaves, cube_replay, stream);
+}
+
+extern "C" int pdp_exact_count_expand(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int8_t *cube_status, const int32_t *len,
+                                      const uint32_t *bits, const uint32_t *closed, int32_t give, int64_t capacity, int64_t *cube_off_new,
+                                      int32_t *len_new, uint32_t *bits_new, uint32_t *closed_new, int64_t *cubes_new_host, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && cube_off_new && cubes_new_host, "NULL argument");
+    PDP_REQUIRE(cubes <= 0 || (cube_status && len && bits && closed), "NULL argument");
+    PDP_REQUIRE(capacity <= 0 || (len_new && bits_new && closed_new), "NULL argument");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_count_expand: a replicated problem (R = %d) is not supported; count on the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exq_expand(p, cube_off, cubes, cube_status, len, bits, closed, give, capacity, cube_off_new, len_new, bits_new, closed_new,
+                      cubes_new_host, stream);
 }
 
 extern "C" int pdp_exact_min_unsat_split(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, int32_t *cost,

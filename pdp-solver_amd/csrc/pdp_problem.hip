@@ -348,7 +348,7 @@ extern "C" int pdp_problem_destroy(pdp_problem *p)
     if (p->ext_blob) pdp_dev_free(p->ext_blob);
     if (p->exn_blob) pdp_dev_free(p->exn_blob);
     if (p->exz_blob) pdp_dev_free(p->exz_blob);
-    for (pdp_exact_cubes *s : {&p->exs, &p->exns, &p->exms, &p->exzs, &p->exds}) {
+    for (pdp_exact_cubes *s : {&p->exs, &p->exns, &p->exms, &p->exzs, &p->exds, &p->exq}) {
         if (s->blob) pdp_dev_free(s->blob);
         if (s->cubes) pdp_dev_free(s->cubes);
     }

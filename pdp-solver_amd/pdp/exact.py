@@ -54,6 +54,14 @@ AUTO_CUBES_PER_WAVE = 16
 # count_models(split='auto'): the reads per instance of the plain first count.  Chosen from the sweep in profiles/exact_time.txt
 # (tools/exact_time.py cssweep)
 AUTO_COUNT_STAGE1_BUDGET = 1 << 26
+# count_models(split='rounds'): the reads per cube and round (the library's default, PDP_EXACT_ROUND_BUDGET) and the most levels a stopped
+# cube gives away in one expansion.  Chosen from the sweep in profiles/exact_time.txt (tools/exact_time.py crsweep): on
+# row ca 2^18 is the fastest of 2^16 .. 2^24 at every cap of 4 and above, and the caps 4 / 8 / 16 differ by less than their spread.
+# ROUNDS_WAVES_PER_SIMD is k_exact_count_round's occupancy by registers (resources)
+ROUND_BUDGET = 1 << 18
+ROUNDS_MAX_GIVE = 8
+ROUNDS_WAVES_PER_SIMD = 3
+DEFAULT_BUDGET = 1 << 32     # PDP_EXACT_DEFAULT_BUDGET
 # min_unsat(split='auto'): the reads per instance of the plain first branch and bound.  Chosen from the sweep in profiles/exact_time.txt
 # (tools/exact_time.py xsweep)
 AUTO_MIN_STAGE1_BUDGET = 1 << 26
@@ -678,7 +686,45 @@ def count_split(prob, part, budget, split, device):
     return st, co, tc, wk, du
 
 
-def count_models(items, budget=0, device=None, max_edges=MAX_EDGES, split=None, depths=False):
+def rounds_give(open_cubes, device):
+    """split='rounds': the levels every stopped cube gives away so that ``open_cubes`` of them become AUTO_CUBES_PER_WAVE cubes per resident
+    wave of k_exact_count_round -- the smallest g with open_cubes * (1 + g) >= that target, 0 once the frontier fills the GPU -- capped
+    by ROUNDS_MAX_GIVE and by the 2^22 cubes of a frontier"""
+    waves = torch.cuda.get_device_properties(device).multi_processor_count * 4 * ROUNDS_WAVES_PER_SIMD
+    target = AUTO_CUBES_PER_WAVE * waves
+    open_cubes = max(1, int(open_cubes))
+    give = -(-target // open_cubes) - 1
+    return max(0, min(give, ROUNDS_MAX_GIVE, native.COUNT_ROUNDS_MAX_CUBES // open_cubes - 1))
+
+
+def count_rounds(prob, part, budget, round_budget, give, rounds, device):
+    """The count of one problem in rounds (Problem.exact_count_round; ``part`` is not read: a state is continued, nothing is counted
+    twice): numpy (status, count, true_count, work, rounds_used int32).  Every round runs every open cube for ``round_budget`` reads past
+    its replay (None or 0: ROUND_BUDGET) and cuts the frontier it leaves again, ``give`` levels per stopped cube (None: rounds_give of the
+    open cubes, every round).  ``budget`` is the total of reads per instance over all rounds and cubes (0: the library's default budget):
+    an instance whose work has reached it is not scheduled again and ends with status -1 and a lower bound.  ``rounds``: at most so many
+    rounds (None: until no cube is open); instances that are still open then end with status -1 as well."""
+    total = budget if budget > 0 else DEFAULT_BUDGET
+    state = prob.exact_count_begin()
+    ended = torch.zeros(prob.B, dtype=torch.bool, device=state.status.device)
+    done = 0
+    while state.cubes and (rounds is None or done < rounds):
+        prob.exact_count_round(state, round_budget or ROUND_BUDGET, rounds_give(state.cubes, device) if give is None else give)
+        done += 1
+        per = state.cube_off[1:] - state.cube_off[:-1]
+        spent = (state.work >= total) & (per > 0)
+        if bool(spent.any()):
+            # out of reads: the instance's cubes leave the frontier, its totals stay as the lower bound they are
+            keep = ~torch.repeat_interleave(spent, per)
+            ended |= spent
+            state.len, state.bits, state.closed = state.len[keep], state.bits[keep], state.closed[keep]
+            state.cube_off = torch.cat([state.cube_off[:1], torch.cumsum(torch.where(spent, torch.zeros_like(per), per), 0)])
+    status = torch.where(ended, torch.full_like(state.status, -1), state.status)
+    return (status.cpu().numpy(), state.count.cpu().numpy(), state.true_count.cpu().numpy(), state.work.cpu().numpy(),
+            state.rounds.cpu().numpy())
+
+
+def count_models(items, budget=0, device=None, max_edges=MAX_EDGES, split=None, depths=False, round_budget=None, rounds=None):
     """Exact model counts of loader items (as solve_items takes them) by the counting search (pdp_exact_count).  Returns numpy (status int8
     [N]: 1 count is the number of models, -1 the budget ran out and it is a lower bound, -2 the instance has more than 1023 variables and
     was not searched; count float64 [N], over all n_i variables of an instance, unused ones included; marginals: per instance a float64
@@ -686,15 +732,26 @@ def count_models(items, budget=0, device=None, max_edges=MAX_EDGES, split=None, 
     count_is_exact says where count is an integer without rounding.
     ``split``: the count of every instance spread over 2^split waves (pdp_exact_count_split; an int from 0 to 16), or 'auto': see
     count_split.  Status, count and marginals are those of the call without ``split`` while count <= 2^53 and no cube runs out of
-    ``budget``, which then applies to every cube; work is the sum over the cubes.  ``depths``: also return depth_used int8 [N]."""
-    split = _check_split(split)
+    ``budget``, which then applies to every cube; work is the sum over the cubes.  ``depths``: also return depth_used int8 [N].
+    ``split='rounds'``: see count_rounds -- the count in rounds of ``round_budget`` reads per cube, at most ``rounds`` of them, the open
+    part of every tree cut again between two rounds to fill the GPU.  ``budget`` is then the total of reads per instance; status, count
+    and marginals are those of the plain call while count <= 2^53 and the total is not reached; ``depths``: the rounds used, int32 [N]."""
+    by_rounds = isinstance(split, str) and split == 'rounds'
+    if not by_rounds:
+        split = _check_split(split)
+        if round_budget is not None or rounds is not None:
+            raise ValueError("round_budget and rounds belong to split='rounds'")
+    else:
+        for name, x in (('round_budget', round_budget), ('rounds', rounds)):
+            if x is not None and (isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1):
+                raise ValueError("%s must be None or a positive integer, got %r" % (name, x))
     native.require_gpu()
     device = torch.device('cuda:0') if device is None else torch.device(device)
     N = len(items)
     status = np.ones(N, dtype=np.int8)
     count = np.zeros(N, dtype=np.float64)
     work = np.zeros(N, dtype=np.int64)
-    used = np.zeros(N, dtype=np.int8)
+    used = np.zeros(N, dtype=np.int32 if by_rounds else np.int8)
     marginals = [None] * N
     for seg in _segments(items, max_edges):
         part = [items[i] for i in seg]
@@ -714,6 +771,8 @@ def count_models(items, budget=0, device=None, max_edges=MAX_EDGES, split=None, 
             if split is None:
                 st, co, tc, wk = [t.cpu().numpy() for t in prob.exact_count(budget)]
                 du = np.zeros(len(part), dtype=np.int8)
+            elif by_rounds:
+                st, co, tc, wk, du = count_rounds(prob, part, budget, round_budget, None, rounds, device)
             else:
                 st, co, tc, wk, du = count_split(prob, part, budget, split, device)
         del prob

@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_min_unsat_split', 'pdp_exact_min_unsat_split_cubes', 'pdp_exact_mass',
     'pdp_exact_mass_split', 'pdp_exact_mass_split_cubes', 'pdp_exact_nearest',
     'pdp_exact_nearest_split', 'pdp_exact_nearest_split_cubes',
+    'pdp_exact_count_frontier_words', 'pdp_exact_count_round', 'pdp_exact_count_expand',
 ]
 
 
@@ -236,6 +237,50 @@ class Decimator(object):
                 self._h = None
         except Exception:
             pass
+
+
+COUNT_ROUNDS_MAX_N = 1023           # pdp_exact_count_round searches instances of up to this many variables, as pdp_exact_count
+COUNT_ROUNDS_MAX_CUBES = 1 << 22    # cubes of one frontier
+
+
+class CountState(object):
+    """A resumable count (Problem.exact_count_begin / exact_count_round): plain tensors, so it can be saved, moved with cpu() / to() and
+    continued on another Problem built from the same items.  The frontier: cube_off int64 [B+1], len int32 [cubes], bits and closed int32
+    [cubes, words] (two bits per decision level, include/pdp_hip.h).  The running totals: count float64 [B], true_count float64 [V],
+    work and leaves int64 [B].  status int8 [B]: 1 complete, -1 cubes are open (count is a lower bound), -2 not searched; rounds int32
+    [B]: the rounds the instance had a cube in."""
+    FIELDS = ('cube_off', 'len', 'bits', 'closed', 'count', 'true_count', 'work', 'leaves', 'status', 'rounds')
+
+    @property
+    def cubes(self):
+        return int(self.len.numel())
+
+    def to(self, device):
+        "a copy on ``device``"
+        s = CountState()
+        for f in self.FIELDS:
+            setattr(s, f, getattr(self, f).to(device).clone())
+        return s
+
+    def cpu(self):
+        return self.to('cpu')
+
+    def validate(self, problem):
+        "what the library cannot see from raw pointers: devices, dtypes and shapes (the frontier's contents are checked on the GPU)"
+        kinds = {'cube_off': torch.int64, 'len': torch.int32, 'bits': torch.int32, 'closed': torch.int32, 'count': torch.float64,
+                 'true_count': torch.float64, 'work': torch.int64, 'leaves': torch.int64, 'status': torch.int8, 'rounds': torch.int32}
+        cubes = int(self.len.numel())
+        sizes = {'cube_off': (problem.B + 1,), 'len': (cubes,), 'count': (problem.B,), 'true_count': (problem.V,), 'work': (problem.B,),
+                 'leaves': (problem.B,), 'status': (problem.B,), 'rounds': (problem.B,)}
+        words = C.c_int32()
+        check(lib().pdp_exact_count_frontier_words(problem._h, C.byref(words)))
+        sizes['bits'] = sizes['closed'] = (cubes, words.value)
+        for f in self.FIELDS:
+            t = getattr(self, f)
+            if not torch.is_tensor(t) or t.device != problem.device or t.dtype != kinds[f] or tuple(t.shape) != sizes[f] or not t.is_contiguous():
+                raise NativeError("state.%s must be a contiguous %s tensor of shape %s on %s" % (f, kinds[f], sizes[f], problem.device))
+        if cubes > COUNT_ROUNDS_MAX_CUBES:
+            raise NativeError("state holds %d cubes; a frontier holds at most 2^22" % cubes)
 
 
 class Problem(object):
@@ -739,6 +784,77 @@ class Problem(object):
                                                 _stream()))
         return status, count, true_count, work, leaves, depth_used, cube_off, cube_status, cube_count, cube_work, cube_leaves
 
+    def exact_count_begin(self):
+        """The state of a resumable count (pdp_exact_count_round): the root frontier -- one cube of length 0 per instance of at most 1023
+        variables -- zeroed totals, and status -1 (open), or -2 where the instance is not searched.  See CountState."""
+        words = C.c_int32()
+        check(lib().pdp_exact_count_frontier_words(self._h, C.byref(words)))
+        dev = self.device
+        n = torch.bincount(self.export_graph()[1].to(torch.int64), minlength=self.B)[:self.B]
+        wide = n > COUNT_ROUNDS_MAX_N
+        cube_off = torch.zeros(self.B + 1, dtype=torch.int64, device=dev)
+        cube_off[1:] = torch.cumsum((~wide).to(torch.int64), 0)
+        cubes = int(cube_off[-1].item())
+        s = CountState()
+        s.cube_off = cube_off
+        s.len = torch.zeros(cubes, dtype=torch.int32, device=dev)
+        s.bits = torch.zeros(cubes, words.value, dtype=torch.int32, device=dev)
+        s.closed = torch.zeros(cubes, words.value, dtype=torch.int32, device=dev)
+        s.count = torch.zeros(self.B, dtype=torch.float64, device=dev)
+        s.true_count = torch.zeros(self.V, dtype=torch.float64, device=dev)
+        s.work = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        s.leaves = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        s.rounds = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        s.status = torch.where(wide, -2, -1).to(torch.int8)
+        return s
+
+    def exact_count_round(self, state, budget=0, give=0, stats=False):
+        """One round of a resumable count (pdp_exact_count_round, then pdp_exact_count_expand): every open cube of ``state`` runs for
+        ``budget`` clause-literal reads past the replay of its path (0: the library default, 2^18), the totals of the state take what it
+        counted, and the frontier becomes the checkpoints of the cubes that stopped, each cut into up to ``give`` children and a remainder.
+        Advances ``state`` in place and returns the number of open cubes; 0: the count is complete, and while count <= 2^53 the totals equal
+        exact_count's bit for bit, whatever the budgets and gives of the rounds were.  ``stats``: also the round's per-cube records
+        (cube_off int64 [B+1] of the frontier that ran, cube_status int8 [cubes] 1 / -1, cube_count float64, cube_work, cube_leaves and
+        cube_replay int64 [cubes], and the checkpoints len_out int32 [cubes], bits_out and closed_out int32 [cubes, words]).  The state
+        may come from another Problem of the same items.  A malformed state raises before anything is searched or written.  More than
+        2^22 cubes after the expansion raises; lower ``give``.  Synchronises the current stream twice."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads per cube (0: the library default), got %r" % (budget,))
+        if isinstance(give, bool) or not isinstance(give, numbers.Integral) or not 0 <= give <= COUNT_ROUNDS_MAX_N:
+            raise ValueError("give must be an integer from 0 to %d, got %r" % (COUNT_ROUNDS_MAX_N, give))
+        if not isinstance(state, CountState):
+            raise ValueError("state must come from exact_count_begin, got %s" % type(state).__name__)
+        state.validate(self)
+        dev = self.device
+        cubes, words = int(state.len.numel()), int(state.bits.size(1))
+        cube_status = torch.empty(cubes, dtype=torch.int8, device=dev)
+        len_out = torch.empty(cubes, dtype=torch.int32, device=dev)
+        bits_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        closed_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        rec = [torch.empty(cubes, dtype=torch.float64 if k == 0 else torch.int64, device=dev) if stats else None for k in range(4)]
+        check(lib().pdp_exact_count_round(self._h, ptr(state.cube_off), C.c_int64(cubes), ptr(state.len), ptr(state.bits), ptr(state.closed),
+                                          C.c_int64(int(budget)), ptr(state.count), ptr(state.true_count), ptr(state.work), ptr(state.leaves),
+                                          ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out), ptr(rec[0]), ptr(rec[1]),
+                                          ptr(rec[2]), ptr(rec[3]), _stream()))
+        capacity = min(cubes * (1 + int(give)), COUNT_ROUNDS_MAX_CUBES)
+        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=dev)
+        len_new = torch.empty(capacity, dtype=torch.int32, device=dev)
+        bits_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
+        closed_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
+        made = C.c_int64()
+        ran = state.cube_off
+        check(lib().pdp_exact_count_expand(self._h, ptr(ran), C.c_int64(cubes), ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out),
+                                           C.c_int32(int(give)), C.c_int64(capacity), ptr(cube_off), ptr(len_new), ptr(bits_new),
+                                           ptr(closed_new), C.byref(made), _stream()))
+        made = int(made.value)
+        state.rounds += (ran[1:] > ran[:-1]).to(torch.int32)
+        state.cube_off, state.len, state.bits, state.closed = cube_off, len_new[:made], bits_new[:made], closed_new[:made]
+        open_ = cube_off[1:] > cube_off[:-1]
+        state.status = torch.where(state.status == -2, state.status, torch.where(open_, -1, 1).to(torch.int8))
+        if not stats:
+            return made
+        return made, (ran, cube_status, rec[0], rec[1], rec[2], rec[3], len_out, bits_out, closed_out)
+
     def exact_mass_split(self, weights, budget=0, depth=None, stats=False):
         """exact_mass with the search of instance b spread over 2^depth[b] waves (pdp_exact_mass_split): (status, mass, true_mass,
         open_mass, work) as exact_mass's.  ``budget`` applies to every cube; at status -1 the probability lies in [mass, mass + open_mass];
@@ -977,7 +1093,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split, exact_nearest_split and exact_mass_split (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split, exact_nearest_split, exact_mass_split and exact_count_round (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

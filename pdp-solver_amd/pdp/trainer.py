@@ -167,7 +167,9 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         counted, and an instance of more than 1023 variables keeps its row as it is.  With config['complete_count_split'] (a depth 0..16, or
         -1: exact.count_split's 'auto') that count runs with every instance spread over 2^depth waves (pdp_exact_count_split): the same
         counts and marginals while no budget runs out, "count_work" is the sum over the cubes, and a row counted at a depth above 0 gains
-        "count_split_depth" after "count_work".  With config['complete_sample'] (K >= 1, with complete_count) every row whose count is proved and
+        "count_split_depth" after "count_work".  With config['complete_count_rounds'] (log2 of the reads per cube and round, or -1: the
+        default) the count runs in rounds instead (exact.count_rounds, pdp_exact_count_round): the budget is the total per row over all
+        rounds, and every counted row gains "count_rounds" after "count_work".  With config['complete_sample'] (K >= 1, with complete_count) every row whose count is proved and
         exact (at most 2^53, above 0) gains "samples", K models in the format of "solution" drawn uniformly with replacement from ALL its
         models (exact.sample_models: uniform ranks below the count, then pdp_exact_models_at; the seed is config['random_seed'], the stream
         that of the row's position among the forward's satisfiable rows), and "sample_ranks", the ranks drawn; every other row is unchanged.
@@ -274,8 +276,16 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                 # config['complete_count_split']: the count of every row spread over 2^depth waves (pdp_exact_count_split); -1: auto
                 csplit = self._config.get('complete_count_split')
                 csplit = None if csplit is None else ('auto' if int(csplit) < 0 else int(csplit))
-                st, count, marginals, cwork, cdepth = exact.count_models([items[i] for i in sat_rows], budget=budget, device=hint.device,
-                                                                         split=csplit, depths=True)
+                # config['complete_count_rounds']: the count in rounds of 2^N reads per cube (pdp_exact_count_round); -1: the default
+                crounds = self._config.get('complete_count_rounds')
+                if crounds is not None:
+                    st, count, marginals, cwork, cdepth = exact.count_models(
+                        [items[i] for i in sat_rows], budget=budget, device=hint.device, split='rounds',
+                        round_budget=None if int(crounds) < 0 else 1 << int(crounds), depths=True)
+                    cdepth, crounds = np.zeros(len(sat_rows), dtype=np.int8), cdepth
+                else:
+                    st, count, marginals, cwork, cdepth = exact.count_models([items[i] for i in sat_rows], budget=budget, device=hint.device,
+                                                                             split=csplit, depths=True)
                 exact_int = exact.count_is_exact(st, count)
                 for k, i in enumerate(sat_rows):
                     if st[k] == -2:
@@ -290,6 +300,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                     row['count_work'] = int(cwork[k])
                     if cdepth[k] > 0:
                         row['count_split_depth'] = int(cdepth[k])
+                    if crounds is not None:
+                        row['count_rounds'] = int(crounds[k])
                 if hasattr(self, '_count_stats'):
                     self._count_stats[0] += int((st == 1).sum()); self._count_stats[1] += len(sat_rows)
                 if self._config.get('complete_sample'):

@@ -23,7 +23,10 @@ search of every instance over 2^N waves (pdp_exact_solve_split; -1: a plain firs
 undecided instances): the same "complete" and solution, "work" summed over the cubes, and "split_depth" on the rows searched at a depth
 above 0; ``--complete-count-split N`` (with ``--complete-count``) does the same for the count (pdp_exact_count_split; -1: a plain first count,
 then the instances that ran out once more at a depth chosen from their number): the same counts and marginals, "count_work" summed over
-the cubes, and "count_split_depth" on the rows counted at a depth above 0; ``--complete-min-unsat-split N`` (with ``--complete-min-unsat``)
+the cubes, and "count_split_depth" on the rows counted at a depth above 0; ``--complete-count-rounds N`` (with ``--complete-count``, not
+with ``--complete-count-split``) counts in rounds of 2^N reads per cube (pdp_exact_count_round; -1: the default) and cuts the open part of
+every tree again between two rounds: the same counts and marginals, ``--complete-budget`` as the total per row, "count_work" summed over
+rounds and cubes, and "count_rounds" on every counted row; ``--complete-min-unsat-split N`` (with ``--complete-min-unsat``)
 spreads that branch and bound over 2^N waves per row that share the best cost found (pdp_exact_min_unsat_split; -1: a plain first stage,
 then the rows left unproved once more from the cost reached): "min_unsat" and "min_unsat_proved" mean the same, "min_unsat_work" is summed
 over the cubes, and "min_unsat_split_depth" appears on the rows searched at a depth above 0; ``--complete-sample K`` (with ``--complete-count``) gives every row
@@ -171,6 +174,11 @@ def main(argv=None):
                         'satisfiable row over 2^N waves (pdp_exact_count_split), N from 0 to 16, or -1: a plain first count, then the rows that ran '
                         'out of its reads once more at a depth that fills the GPU; the same counts and marginals, "count_work" summed over the cubes, '
                         '"count_split_depth" on the rows counted at a depth above 0', type=int, default=None)
+    parser.add_argument('--complete-count-rounds', dest='complete_count_rounds', help='With --complete --complete-count: count in rounds of 2^N '
+                        'reads per cube (pdp_exact_count_round), N from 0 to 40, or -1 for the default; between two rounds the open part of '
+                        'every search tree is cut again to fill the GPU, and --complete-budget is the total of reads per row over all rounds; the '
+                        'same counts and marginals, "count_work" summed over the rounds and cubes, "count_rounds" on every counted row; not '
+                        'with --complete-count-split', type=int, default=None)
     parser.add_argument('--complete-min-unsat-split', dest='complete_min_unsat_split', help='With --complete --complete-min-unsat: spread the branch '
                         'and bound of every row over 2^N waves that share the best cost found (pdp_exact_min_unsat_split), N from 0 to 16, or -1: a '
                         'plain first stage, then the rows whose optimum is not proved once more, from the cost reached, at a depth that fills the '
@@ -233,6 +241,13 @@ def main(argv=None):
             parser.error("--complete-count-split spreads the count of --complete-count: give --complete-count as well")
         if not -1 <= args['complete_count_split'] <= 16:
             parser.error("--complete-count-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows that ran out")
+    if args['complete_count_rounds'] is not None:
+        if not args['complete_count']:
+            parser.error("--complete-count-rounds counts the models of --complete-count in rounds: give --complete-count as well")
+        if args['complete_count_split'] is not None:
+            parser.error("--complete-count-rounds cuts the search between its rounds: give it without --complete-count-split")
+        if not -1 <= args['complete_count_rounds'] <= 40:
+            parser.error("--complete-count-rounds takes log2 of the reads per cube and round, from 0 to 40, or -1 for the default")
     if args['complete_mass_split'] is not None:
         if not args['complete_mass']:
             parser.error("--complete-mass-split spreads the search of --complete-mass: give --complete-mass as well")

@@ -60,6 +60,13 @@ count_models(split='auto') on row ``ca`` over AUTO_COUNT_STAGE1_BUDGET = 2^20 / 
 budget of PDP_CSD_BUDGET reads per stage-1 instance and per cube (default and cap 2^28), one timed call: how many instances end with a
 complete count, next to the plain count under the same budget per instance.
 
+Rounds count rows (pdp_exact_count_round; never part of the default): ``cra`` / ``crb`` = the 1 / 8 instances of row ``ca`` with the largest plain
+count_work, ``crauto`` = row ``ca`` whole: host wall time of count_models plain, split=12, split='auto' and split='rounds' on the same items,
+counts and marginals asserted equal, the reads against the plain count's and the rounds used; PDP_COUNT_ONLY=plain / auto / split:<depth> /
+rounds times that one call alone (a fresh process per measurement of an alternating comparison).  ``crsweep`` = count_models(split='rounds')
+on row ``ca`` over round budgets 2^16 .. 2^24 and ROUNDS_MAX_GIVE = 1 / 4 / 8 / 16.  ``crd`` = row ``cd`` with PDP_CSD_BUDGET reads per
+instance in all (default and cap 2^28): complete counts and lower bounds next to the plain count under the same budget.
+
 Split minimum rows (pdp_exact_min_unsat_split; never part of the default): ``xsa`` / ``xsb`` = the 1 / 8 instances of row ``xa`` with the largest
 plain work as a batch of their own, same incumbents: kernel time of pdp_exact_min_unsat and of the split call at depths 4 / 8 / 12 on the
 same problem (each after an untimed call with a budget of one read), proved counts, costs, the reads against the plain call's, the
@@ -743,6 +750,69 @@ def run_count_split(key):
               flush=True)
 
 
+COUNT_ROUNDS_ROWS = ('cra', 'crb', 'crauto', 'crsweep', 'crd')
+
+
+def _rounds_line(tag, ms, out, plain_work):
+    print("    %s: wall %.1f ms  complete %d  lower bounds %d  reads %d (%.3f of the plain count's)  rounds (split: depth) max %d"
+          % (tag, ms, int((out[0] == 1).sum()), int((out[0] == -1).sum()), int(out[3].sum()), float(out[3].sum()) / max(1.0, float(plain_work)),
+             int(out[4].max()) if len(out[4]) else 0), flush=True)
+
+
+def run_count_rounds(key):
+    """cra / crb / crauto: host wall time of count_models(split='rounds') next to split=12 and split='auto' on the same items, equal
+    counts asserted; PDP_COUNT_ONLY=plain / auto / split:<depth> / rounds times that one call alone (a fresh process per measurement of
+    an alternating comparison).  crsweep: the round budget and the give cap.  crd: row cd at 2^28 total reads per instance."""
+    from pdp import exact
+    only = os.environ.get('PDP_COUNT_ONLY')
+    if key == 'crd':
+        budget = min(CSD_MAX_BUDGET, int(os.environ.get('PDP_CSD_BUDGET', CSD_MAX_BUDGET)))
+        title, sub = _satisfiable_of('d')
+        exact.count_models(sub[:8], budget=1, split='rounds')
+        ms0, plain = _wall(lambda: exact.count_models(sub, budget=budget))
+        ms, got = _wall(lambda: exact.count_models(sub, budget=budget, split='rounds', depths=True))
+        both = (plain[0] == 1) & (got[0] == 1)
+        assert np.array_equal(plain[1][both], got[1][both]), "a complete count differs"
+        print("(crd) the %d instances of %s that the deciding search answers 1, %d reads per instance in all: plain count_models wall %.0f ms, "
+              "complete counts %d, lower bounds %d;  split='rounds' wall %.0f ms, complete counts %d, lower bounds %d, of the plain lower bounds %d "
+              "become complete, of the plain complete counts %d become lower bounds;  rounds max %d  reads %d (plain %d)"
+              % (len(sub), title, budget, ms0, int((plain[0] == 1).sum()), int((plain[0] == -1).sum()), ms, int((got[0] == 1).sum()),
+                 int((got[0] == -1).sum()), int(((plain[0] == -1) & (got[0] == 1)).sum()), int(((plain[0] == 1) & (got[0] == -1)).sum()),
+                 int(got[4].max()), int(got[3].sum()), int(plain[3].sum())), flush=True)
+        return
+    title, sub = _satisfiable_of('a')
+    exact.count_models(sub[:8], budget=1, split=1)                                   # the context, the library and the kernels are loaded
+    exact.count_models(sub[:8], budget=1, split='rounds')
+    if key in ('cra', 'crb'):
+        work = exact.count_models(sub)[3]
+        sub = [sub[i] for i in np.argsort(-work, kind='stable')[:1 if key == 'cra' else 8]]
+    if only:
+        call = {'plain': lambda: exact.count_models(sub), 'auto': lambda: exact.count_models(sub, split='auto'),
+                'rounds': lambda: exact.count_models(sub, split='rounds')}.get(only)
+        if call is None:
+            depth = int(only.split(':')[1])
+            call = lambda: exact.count_models(sub, split=depth)                      # noqa: E731
+        ms, out = _wall(call)
+        print("(%s, %s alone) %d instances of %s: count_models wall %.1f ms  complete %d  reads %d"
+              % (key, only, len(sub), title, ms, int((out[0] == 1).sum()), int(out[3].sum())), flush=True)
+        return
+    ms0, plain = _wall(lambda: exact.count_models(sub))
+    print("(%s) %d satisfiable instances of %s: plain count_models wall %.1f ms  reads %d" % (key, len(sub), title, ms0, int(plain[3].sum())),
+          flush=True)
+    if key == 'crsweep':
+        for cap in (1, 4, 8, 16):
+            exact.ROUNDS_MAX_GIVE = cap
+            for lg in (16, 18, 20, 22, 24):
+                ms, out = _wall(lambda: exact.count_models(sub, split='rounds', round_budget=1 << lg, depths=True))
+                _same_counts(out, plain, "split='rounds'")
+                _rounds_line("give cap %2d, round budget 2^%d" % (cap, lg), ms, out, plain[3].sum())
+        return
+    for tag, kw in (("split=12", dict(split=12)), ("split='auto'", dict(split='auto')), ("split='rounds'", dict(split='rounds'))):
+        ms, out = _wall(lambda: exact.count_models(sub, depths=True, **kw))
+        _same_counts(out, plain, tag)
+        _rounds_line(tag, ms, out, plain[3].sum())
+
+
 MIN_SPLIT_ROWS = ('xsa', 'xsb', 'xsauto', 'xsweep')
 
 
@@ -1234,6 +1304,9 @@ if __name__ == '__main__':
             continue
         if k in COUNT_SPLIT_ROWS:
             run_count_split(k)
+            continue
+        if k in COUNT_ROUNDS_ROWS:
+            run_count_rounds(k)
             continue
         if k in MIN_SPLIT_ROWS:
             run_min_split(k)
