@@ -15,6 +15,16 @@
  * path uses, denormal inputs and outputs handled exactly (the reference relies on
  * log(1e-40) = -92.1034 and exp(-92.1034) = 1e-40).
  *
+ * Every figure below is exhaustive, not sampled: tools/math_checksums.py --accuracy runs the host build over all 2^32 inputs against
+ * float64, and tests/test_math_sweep_gpu.py does the same on the device, where every output bit must also be the host's
+ * (tests/golden/math_checksums.npz).  Errors in ulp of the correctly rounded result, the worst input in parentheses:
+ *   pdp_expf         1.0103 ulp on [-104, 88.72], denormal results included (-5.87788, 0xc0bc17a1)
+ *   pdp_logf         0.8265 ulp on every positive finite x, denormals included (1.41364, 0x3fb4f239)
+ *   pdp_logsigmoidf  2.9313 ulp on every finite x (3.4502, 0x405cd015)
+ *   pdp_sigmoidf     2.4807 ulp on [-87, FLT_MAX] (-16.6357, 0xc18515ec); 8.93e-8 absolute on every finite x
+ *   pdp_tanhf        2.8284 ulp on every finite x, denormals included (+-0.175405, 0x3e339d62); 8.93e-8 absolute
+ *   pdp_tanhf_abs    1.192e-7 absolute on every finite x (0.000172496, 0x3934e004); no relative accuracy near 0, by design
+ *
  * NaN semantics follow torch: max/min propagate NaN (torch.max(x, eps)), sign(NaN) = 0.
  */
 #ifndef PDP_MATH_H
@@ -156,20 +166,38 @@ PDP_HD float pdp_logf(float x)
 }
 
 /* ---- lean variants for hot loops --------------------------------------------------------------
- * Same results as the general functions on their stated domain (checked bit for bit by the tests);
+ * Same results as the general functions on their stated domain, bit for bit on EVERY input of it
+ * (tests/test_math_sweep_gpu.py::test_lean_forms_equal_the_general_forms_on_every_input);
  * they only drop selects for inputs the caller rules out. */
 /* torch.max(a, c) / torch.min(a, c) for a constant c that is not NaN: NaN in a propagates */
 PDP_HD float pdp_max_c(float a, float c) { return (a < c) ? c : a; }
 PDP_HD float pdp_min_c(float a, float c) { return (a > c) ? c : a; }
 
-/* p * 2^n, correctly rounded also into the denormal range (|n| <= 160) */
+/* p * 2^n, correctly rounded also into the denormal range.  Every caller on its domain has p in [0.25, 4] and |n| <= 160: there the host's
+ * first product is exact and its second rounds once.  Off the callers' domains (pdp_expf_fin_le30 above 88.7, say) the host takes ldexpf,
+ * which is what v_ldexp_f32 computes for any p and n: host and device agree on every input, not only on the stated domains. */
 PDP_HD float pdp_scale2(float p, int n)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_ldexpf(p, n);                          /* v_ldexp_f32: one correctly rounded instruction */
 #else
-    const int n1 = n >> 1, n2 = n - n1;
-    return (p * pdp_pow2i(n1)) * pdp_pow2i(n2);
+    if (p >= 0.25f && p <= 4.0f && n >= -160 && n <= 160) {
+        const int n1 = n >> 1, n2 = n - n1;
+        return (p * pdp_pow2i(n1)) * pdp_pow2i(n2);
+    }
+    return ldexpf(p, n);
+#endif
+}
+
+/* (int)f the way v_cvt_i32_f32 converts: saturating, NaN -> 0.  In C an out-of-range conversion is undefined and x86 returns INT_MIN;
+ * only a function whose argument is not clamped needs this (pdp_expf_fin_le30 off its domain). */
+PDP_HD int pdp_f2i(float f)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)f;
+#else
+    if (f > -2147483648.0f && f < 2147483648.0f) return (int)f;
+    return (f != f) ? 0 : ((f > 0.0f) ? 2147483647 : (-2147483647 - 1));
 #endif
 }
 
@@ -235,8 +263,8 @@ PDP_HD float pdp_logf_pos(float x)
  * On gfx950 a v_cmp + v_cndmask pair costs about four FMAs (the compare result travels through an SGPR pair), so the
  * per-edge code avoids selects: clamps are v_max_f32, mantissa / exponent come from v_frexp_*, the "m < sqrt(1/2)"
  * decision is integer arithmetic on the bit pattern, and a NaN argument is re-injected at the end as x - x (exactly 0
- * for finite x).  Same results as the general functions on the stated domains (tests/test_hip_ops.py,
- * tests/test_oracle_golden.py). */
+ * for finite x).  Same results as the general functions on every input of the stated domains, and the device's v_frexp / v_ldexp /
+ * v_max forms give the host's bits on all 2^32 inputs (tests/test_math_sweep_gpu.py). */
 PDP_HD float pdp_fmaxf(float a, float b)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -307,7 +335,7 @@ PDP_HD float pdp_expf_fin_le30(float x)
     p = fmaf(p, r, 5.0000001201e-1f);
     p = fmaf(p, z, r);
     p = p + 1.0f;
-    return pdp_scale2(p, (int)nf) + (x - x);
+    return pdp_scale2(p, pdp_f2i(nf)) + (x - x);
 }
 /* safe_exp with the lean pieces (valid for every input: the clamp bounds the argument) */
 PDP_HD float pdp_safe_exp_fast(float x) { return pdp_expf_le30(pdp_min_c(x, 30.0f)); }
@@ -347,8 +375,8 @@ PDP_HD float pdp_expf_fin_hi(float x, float hi)
 PDP_HD float pdp_expf_fin(float x) { return pdp_expf_fin_hi(x, 89.0f); }
 
 /* torch F.logsigmoid(x) = min(x, 0) - log1p(exp(-|x|)).  With t = e^-|x| in (0, 1]: log1p(t) = t * P(t), P the degree-8 polynomial
- * fitted to log1p(t) / t at Chebyshev nodes of [0, 1] (truncation 3e-8 relative; with fp32 Horner rounding < 3 ulp over the whole range,
- * tests/test_oracle_golden.py checks it against log1p in double).  For tiny t the product is t itself.  No log, no exponent extraction:
+ * fitted to log1p(t) / t at Chebyshev nodes of [0, 1] (truncation 3e-8 relative; with fp32 Horner rounding < 3 ulp over the whole range:
+ * 2.9313 ulp at 3.4502 is the worst of all finite inputs, tests/test_math_sweep_gpu.py checks every one against log1p in double).  For tiny t the product is t itself.  No log, no exponent extraction:
  * 27 instead of 50 VALU instructions per element on gfx950, which matters because f32 MFMA and VALU time add up on a SIMD. */
 PDP_HD float pdp_logsigmoidf(float x)
 {
@@ -395,7 +423,8 @@ PDP_HD float pdp_rcp_ge1(float d)
 }
 
 /* torch.sigmoid(x) = 1 / (1 + exp(-x)).  The exponent is clamped at 87 so that the denominator stays in the range of pdp_rcp_ge1: for
- * x < -87 the result is 1.6e-38 where torch's decays on to 0 through the denormals -- a difference of at most 1.6e-38. */
+ * x < -87 the result is 1.6e-38 where torch's decays on to 0 through the denormals -- a difference of at most 1.6e-38.  On [-87, FLT_MAX]
+ * at most 2.4807 ulp (at -16.6357), 8.93e-8 absolute: exhaustive, the test bounds are 2.5 ulp and 1.5e-7. */
 PDP_HD float pdp_sigmoidf(float x)
 {
 #ifdef PDP_FAST_DEVICE
@@ -405,7 +434,9 @@ PDP_HD float pdp_sigmoidf(float x)
 }
 
 /* tanh(x) = em / (em + 2), em = e^{2|x|} - 1 without cancellation: with 2|x| = n ln2 + r the polynomial part q = e^r - 1 is
- * the exact answer for n == 0.  |x| is clamped at 10 (tanh(10) rounds to 1). */
+ * the exact answer for n == 0.  |x| is clamped at 10 (tanh(10) rounds to 1).  At most 2.8284 ulp (at +-0.175405) and 8.93e-8 absolute over
+ * every finite x, denormals included: exhaustive, the test bounds are 3 ulp and 2e-7.  Odd bit for bit: the sign is applied last, so
+ * tanh(-0) = -0 like torch.tanh (the NaN re-injection x - x is +0 and would turn a -0 into +0 if it came after the sign). */
 PDP_HD float pdp_tanhf(float x)
 {
 #ifdef PDP_FAST_DEVICE
@@ -414,7 +445,7 @@ PDP_HD float pdp_tanhf(float x)
         const float a = pdp_fminf(pdp_abs(x), 10.0f);
         const float r = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(2.88539008177792681f * a) + 1.0f);
         const float v = 1.0f - (r + r);
-        return pdp_bits2f(pdp_f2bits(v) | (pdp_f2bits(x) & 0x80000000u)) + (x - x);
+        return pdp_bits2f(pdp_f2bits(v + (x - x)) | (pdp_f2bits(x) & 0x80000000u));     /* sign last: a zero result keeps x's sign */
     }
 #endif
     const float a = pdp_fminf(pdp_abs(x), 10.0f);
@@ -435,10 +466,11 @@ PDP_HD float pdp_tanhf(float x)
     const float big = pdp_scale2(q + 1.0f, n) - 1.0f;
     const float em = (n == 0) ? q : big;
     const float v = em / (em + 2.0f);
-    return pdp_bits2f(pdp_f2bits(v) | (pdp_f2bits(x) & 0x80000000u)) + (x - x);
+    return pdp_bits2f(pdp_f2bits(v + (x - x)) | (pdp_f2bits(x) & 0x80000000u));     /* sign last: a zero result keeps x's sign */
 }
 
-/* GRU candidate gate: tanh(x) = sign(x) (1 - 2 / (e^{2|x|} + 1)), |x| clamped at 10 (tanh(10) rounds to 1).  Absolute error < 1.2e-7 (half an ulp of 1 from the
+/* GRU candidate gate: tanh(x) = sign(x) (1 - 2 / (e^{2|x|} + 1)), |x| clamped at 10 (tanh(10) rounds to 1).  Absolute error < 1.2e-7 (1.192e-7 at 0.000172496 is
+ * the worst of all finite inputs; half an ulp of 1 from the
  * division and from the subtraction each, plus a quarter of the exponential's relative error); near 0 the RELATIVE error is not that of a
  * cancellation-free form, which the GRU does not need: the value only enters h' = (h - n) z + n.  32 instead of 45 VALU instructions on gfx950
  * (no expm1 reconstruction, no n == 0 select). */
@@ -449,14 +481,14 @@ PDP_HD float pdp_tanhf_abs(float x)
         const float a = pdp_fminf(pdp_abs(x), 10.0f);
         const float r = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(2.88539008177792681f * a) + 1.0f);
         const float v = 1.0f - (r + r);
-        return pdp_bits2f(pdp_f2bits(v) | (pdp_f2bits(x) & 0x80000000u)) + (x - x);
+        return pdp_bits2f(pdp_f2bits(v + (x - x)) | (pdp_f2bits(x) & 0x80000000u));     /* sign last: a zero result keeps x's sign */
     }
 #endif
     const float a = pdp_fminf(pdp_abs(x), 10.0f);
     const float t = pdp_expf_fin(a + a);
     const float r = pdp_rcp_ge1(t + 1.0f);                  /* t + 1 in [2, e^20 + 1] */
     const float v = 1.0f - (r + r);
-    return pdp_bits2f(pdp_f2bits(v) | (pdp_f2bits(x) & 0x80000000u)) + (x - x);
+    return pdp_bits2f(pdp_f2bits(v + (x - x)) | (pdp_f2bits(x) & 0x80000000u));     /* sign last: a zero result keeps x's sign */
 }
 
 /* ---- the reference's clamped forms ------------------------------------------------------- */
