@@ -685,6 +685,36 @@ int pdp_exact_count_expand(pdp_problem *p, const int64_t *cube_off, int64_t cube
                            const uint32_t *bits, const uint32_t *closed, int32_t give, int64_t capacity, int64_t *cube_off_new,
                            int32_t *len_new, uint32_t *bits_new, uint32_t *closed_new, int64_t *cubes_new_host, void *stream);
 
+/* pdp_exact_solve_hinted as a sequence of rounds over the same frontier (plain Python, normative: tests/exact_solve_rounds_model.py;
+ * DESIGN.md 9.18).  The frontier (cube_off, len, bits, closed, the pairs, pdp_exact_count_frontier_words), its check and the checkpoints
+ * are pdp_exact_count_round's, and the next frontier comes from pdp_exact_count_expand, called as it is with this call's cube_status.
+ *   Search of a cube.  pdp_exact_solve_hinted's search without its check pass, with plen = len: a decision that opens level L <= plen takes
+ *   the polarity its bit asks for (0: the polarity the search would try first, the hint's where the variable has one; 1: the other) and
+ *   carries the flipped mark iff closed.  When backtracking flips an open level L, plen = min(plen, L).  A state without an open clause
+ *   answers 1 with that assignment wherever it is met, also at a level < plen: every cube that reaches it holds the same model.  Out of
+ *   levels answers 0.  hint [V] may be NULL (no hints).
+ *   Budget of a round (reads per cube; budget <= 0: PDP_EXACT_SOLVE_ROUND_BUDGET) and checkpoint: pdp_exact_count_round's, word for word.
+ *   A cube of status 0 or 1 leaves len_out 0 and a row of zeros.
+ *   Outcome, per instance that has a cube.  first[b] = the lowest cube of the instance, counted from cube_off[b], that answered 1 (-1:
+ *   none).  If there is one: status[b] = 1, model (its slice of [V]) = that cube's, and the instance's stopped cubes get cube_status -2
+ *   ("dropped"), so that the expansion leaves nothing of them; their checkpoints stay as written.  Else status[b] = 0 if no cube
+ *   stopped, else -1.  work[b] (in/out) takes the integer sum of its cubes' work.  An instance without a cube is not touched in status,
+ *   model, work or first.  cube_status [cubes] = 1 / 0 / -1 / -2; cube_work and cube_replay [cubes] may be NULL.
+ * No word is shared between two cubes: a cube of a satisfiable instance runs out its round even if a sibling has a model already, so
+ * every output, record and frontier word is a function of the instances, the hints, the frontier and the budget alone.  With one cube per
+ * instance throughout (give 0) status and model are pdp_exact_solve_hinted's bit for bit wherever that call's check pass does not accept
+ * the hints, and the sum of cube_work - cube_replay over the rounds is its work less the check pass's reads; with more, which model comes
+ * back is not promised.  One wave takes one cube at a time from one counter; a cube that answered 1 leaves its model as a row of bytes in
+ * [cubes][n_max] on the handle; a second kernel writes the outcome, one wave per instance.  The refusals are pdp_exact_count_round's
+ * (PDP_ERR_INVALID naming the cube or instance, before anything is searched or written), with model rows past 2^31 bytes in place of its
+ * rows of doubles.  R != 1 -> PDP_ERR_UNSUPPORTED.  Routing, slab and working arrays are pdp_exact_solve's.  The call synchronises the
+ * stream once (the check's verdict). */
+#define PDP_EXACT_SOLVE_ROUND_BUDGET (((int64_t)1) << 18)
+int pdp_exact_solve_round(pdp_problem *p, const float *hint, const int64_t *cube_off, int64_t cubes, const int32_t *len,
+                          const uint32_t *bits, const uint32_t *closed, int64_t budget, int8_t *status, float *model, int64_t *work,
+                          int32_t *first, int8_t *cube_status, int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out,
+                          int64_t *cube_work, int64_t *cube_replay, void *stream);
+
 /* The models of given ranks in pdp_exact_count's own order (plain Python, normative: tests/exact_rank_model.py).  The
  * counting search meets its leaves in a fixed depth-first order and a leaf with f unassigned variables stands for 2^f models, so "count
  * before the leaf + offset inside it" numbers every model of an instance exactly once.  Instance b asks for K_b = rank_off[b+1] -
@@ -819,7 +849,7 @@ int pdp_exact_nearest_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cub
                                   int32_t *cube_improvements, void *stream);
 
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split, pdp_exact_nearest_split, pdp_exact_mass_split and pdp_exact_count_round (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split, pdp_exact_nearest_split, pdp_exact_mass_split, pdp_exact_count_round and pdp_exact_solve_round (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

@@ -169,7 +169,9 @@ struct pdp_problem {
     pdp_exact_cubes exs, exns, exms, exzs, exds;
     // resumable counts (pdp_exact.hip::exq_prepare, on exn_prepare's routing and slab): exq.blob = the check's words, the HBM route's T [V]
     // and the route bytes [B]; exq.cubes = a round's per-cube records (count, work, leaves, replay, true_count rows, status) or an
-    // expansion's scan (first new cube of every old one, the new cube_off); exq_nmax = the most variables of a searched instance
+    // expansion's scan (first new cube of every old one, the new cube_off); exq_nmax = the most variables of a searched instance.
+    // pdp_exact_solve_round (exv_round) uses the same check words, route bytes and exq_nmax, and exq.cubes for its own records (work,
+    // replay, model rows of bytes)
     pdp_exact_cubes exq; int exq_ready, exq_nmax;
     // k-th models of the counting search (pdp_exact.hip::exr_launch): ex_prepare's routing and slab; the rows' byte offsets [B+1] and the
     // validation words of the last call, one block allocated on first use

@@ -36,8 +36,9 @@
 // pdp_exact_mass_split (the last kernels) cuts it into cubes as the count's split does, and its cubes share nothing either.
 // pdp_exact_nearest (behind pdp_exact_min_unsat) is the branch and bound with the cost on the variables: the model nearest to a hint.
 // pdp_exact_nearest_split (behind pdp_exact_min_unsat_split) cuts it into cubes that share the 64-bit ub[b]; a start model seeds it.
-// pdp_exact_count_round / pdp_exact_count_expand (the very last kernels) run the count as a sequence of launches over a frontier of path
+// pdp_exact_count_round / pdp_exact_count_expand (near the end) run the count as a sequence of launches over a frontier of path
 // cubes, two bits per decision level, that is checkpointed at a budget stop and cut again between two launches; its cubes share nothing.
+// pdp_exact_solve_round (the very last kernels) runs the hinted deciding search over the same frontier, with the same check and expansion.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -4990,6 +4991,224 @@ int exq_expand(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int
     return PDP_OK;
 }
 
+// ---- pdp_exact_solve_round: the deciding search as a sequence of rounds over the same frontier ------------------------------------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_solve_rounds_model.py).  The frontier, its check kernel and
+// the expansion are the count's, called as they are.  ex_search_path is pdp_exact_solve_hinted's search without its check pass, from the
+// shared blocks, with exq_decide's decision and the round budget of ex_search_count_path; a state without an open clause answers 1
+// wherever it is met.  A round is three launches on one stream: the check, the cubes (one counter hands out cube ids, one wave per
+// cube; every cube leaves its record, its checkpoint and, where it answered 1, its model as a row of bytes), the finish (one wave per
+// instance that has a cube: the lowest cube that answered 1 gives the model, the stopped cubes of such an instance become -2 so that the
+// expansion leaves nothing of them).  The state, the slab (ex_lds_layout), the routing and the HBM arrays are k_exact's.  No cube reads a
+// word of another: a cube of a satisfiable instance runs out its round even if a sibling has a model already.
+constexpr int64_t EXV_MAX_ROW_BYTES = (int64_t)1 << 31;
+
+// The deciding search of one path cube by the calling wave.  Returns 1 (val holds a model), 0 (the cube has none) or -1 (budget spent:
+// levels 1 .. *level_out are open, *plen_out of them still as the path has them).  The budget is ex_search_count_path's: tested only where
+// a node begins (`fresh`), on the reads made since the first node that began with level >= plen (`base`; -1: still replaying).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_path(const ExInst<LitT, PtrT> &X, int64_t budget, const ExPath &Q, int *level_out, int *plen_out, int64_t *work_out,
+                              int64_t *replay_out)
+{
+    int level = 0, tlen = 0, plen = Q.len;
+    int64_t work = 0, base = -1;
+    int result = -1;
+    bool fresh = true;
+    ExNoCredit none;
+    for (;;) {
+        if (fresh) {
+            if (base < 0 && level >= plen) base = work;
+            if (base >= 0 && work - base >= budget) break;
+            fresh = false;
+        }
+        const ExPass P = ex_propagate(X);
+        work += ex_sum(P.reads);
+        bool any_conflict = __ballot(P.conflict) != 0ull;
+        const bool any_unit = __ballot(P.unit) != 0ull;
+        if (any_unit) {
+            ex_sync<HBM>();
+            const bool both = ex_assign_pending<HBM, true>(X, tlen);
+            any_conflict = any_conflict || both;
+        }
+        if (any_conflict) {
+            if (!ex_backtrack<HBM>(X, level, tlen, none)) { result = 0; break; }
+            plen = level < plen ? level : plen;                     // `level` was flipped: the path beyond it no longer applies
+            fresh = true;
+            continue;
+        }
+        if (any_unit) continue;
+        const int wmin = ex_min(P.wmin);
+        if (wmin == 0x7fffffff) { result = 1; break; }              // no open clause: a model, inside the path too
+        const unsigned long long best = ex_branch<HBM, EX_PHASE_HINT>(X, wmin, work);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        exq_decide<HBM>(X, Q, plen, best, level, tlen, none);
+        fresh = true;
+    }
+    *level_out = result == -1 ? level : 0; *plen_out = plen;
+    *work_out = work; *replay_out = base < 0 ? work : base;
+    return result;
+}
+
+struct ExvParams {
+    int B;
+    uint32_t total;             // cubes of the round
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;             // per cube, past its replay
+    const float *hint;          // [V] phase hints (NULL: none)
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    const int32_t *len;         // [total]
+    const uint32_t *bits, *closed;      // [total][words]
+    int words;
+    int8_t *cube_status;        // [total] 1 / 0 / -1; the finish kernel turns the -1 of an answered instance into -2
+    int32_t *len_out; uint32_t *bits_out, *closed_out;      // the checkpoints, shaped as the inputs
+    int64_t *cube_work, *cube_replay;   // [total]
+    uint8_t *rows;              // [total][n_max] the assignment of every cube that answered 1
+    int n_max;
+    int8_t *status; float *model; int64_t *work; int32_t *first;    // per instance (status and work in/out)
+    ExHbm h;
+};
+
+// cube q of instance I.b: copy the instance (ex_fill), clear the state (pend starts as the hint codes), search along the path; then the
+// cube's record, its model row where it answered 1, and its checkpoint by ex_solve_count_path's ballots.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_path(const ExvParams &xp, const Inst &I, ExInst<LitT, PtrT> X, uint32_t q)
+{
+    const int lane = (int)threadIdx.x;
+    ex_fill<HBM>(I, X);
+    for (int v = lane; v < I.n; v += EX_NT) {
+        uint32_t code = 0u;
+        if (xp.hint) { const float h = xp.hint[I.v0 + v]; code = h != h ? 0u : (h > 0.5f ? 1u : 2u); }
+        X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+    }
+    ex_sync<HBM>();
+    const size_t row = (size_t)q * (size_t)xp.words;
+    const ExPath Q{xp.bits + row, xp.closed + row, xp.len[q]};
+    int64_t work = 0, replay = 0;
+    int level = 0, plen = 0;
+    const int st = ex_search_path<HBM>(X, xp.budget, Q, &level, &plen, &work, &replay);
+    if (st == 1) {
+        uint8_t *out = xp.rows + (size_t)q * (size_t)xp.n_max;
+        for (int v = lane; v < I.n; v += EX_NT) out[v] = X.val[v] == 1 ? 1 : 0;
+    }
+    for (int w = 0; w < xp.words; w += 2) {
+        const int L = 32 * w + lane + 1;
+        const uint32_t mark = L <= level ? X.dvar[L] >> 31 : 0u;
+        const bool path = L <= plen && L <= level;
+        const uint32_t pb = path ? exq_bit(Q.bits, L) : 0u, pc = path ? exq_bit(Q.closed, L) : 0u;
+        const unsigned long long bb = __ballot((pb | (mark & (pc ^ 1u))) != 0u), cc = __ballot(mark != 0u);
+        if (lane == 0) {
+            xp.bits_out[row + w] = (uint32_t)bb; xp.closed_out[row + w] = (uint32_t)cc;
+            if (w + 1 < xp.words) { xp.bits_out[row + w + 1] = (uint32_t)(bb >> 32); xp.closed_out[row + w + 1] = (uint32_t)(cc >> 32); }
+        }
+    }
+    if (lane == 0) {
+        xp.cube_status[q] = (int8_t)st;
+        xp.len_out[q] = level;
+        xp.cube_work[q] = work;
+        xp.cube_replay[q] = replay;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_solve_round(PView pv, ExvParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= xp.total) break;
+        const int lo = exs_instance(xp.cube_off, xp.B, q);
+        const Inst I = load_inst(pv, lo);
+        // the check has passed: every cube's instance has at most 1023 variables.  Both arms end in the barrier of ex_solve_path and fall
+        // through to the end of the loop body (see k_exact_count)
+        if (xp.route[lo]) ex_solve_path<true>(xp, I, ex_bind_hbm(xp.h, I), q);
+        else ex_solve_path<false>(xp, I, ex_bind_lds(ex_slab, I), q);
+    }
+}
+
+// The outcome of every instance that has a cube, one wave per instance: first = the lowest cube, counted from the instance's own first
+// one, that answered 1; then status 1, the model from that cube's row (one lane per variable) and the instance's stopped cubes rewritten to
+// -2; else status 0 when no cube stopped, else -1.  work[b] takes the cubes' work as an int64 wave sum.
+__global__ void __launch_bounds__(EX_NT) k_exact_solve_round_finish(PView pv, ExvParams xp)
+{
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        if (nc == 0) continue;                                      // wave-uniform
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        int64_t w = 0;
+        int at = EXS_NONE, open = 0;
+        for (int64_t j = lane; j < nc; j += EX_NT) {
+            const int st = (int)xp.cube_status[c0 + j];
+            w += xp.cube_work[c0 + j];
+            if (st == 1 && at == EXS_NONE) at = (int)j;
+            open |= st == -1;
+        }
+        w = exs_sum64(w);
+        at = ex_min(at);
+        const bool found = at != EXS_NONE, stopped = __ballot(open) != 0ull;
+        if (found) {
+            const uint8_t *row = xp.rows + (size_t)(c0 + at) * (size_t)xp.n_max;
+            for (int v = lane; v < n; v += EX_NT) xp.model[v0 + v] = row[v] ? 1.0f : 0.0f;
+            for (int64_t j = lane; j < nc; j += EX_NT)
+                if (xp.cube_status[c0 + j] == -1) xp.cube_status[c0 + j] = -2;
+        }
+        if (lane == 0) {
+            xp.status[b] = (int8_t)(found ? 1 : (stopped ? -1 : 0));
+            xp.first[b] = found ? at : -1;
+            xp.work[b] += w;
+        }
+    }
+}
+
+int exv_round(pdp_problem *p, const float *hint, const int64_t *cube_off, int64_t cubes, const int32_t *len, const uint32_t *bits,
+              const uint32_t *closed, int64_t budget, int8_t *status, float *model, int64_t *work, int32_t *first, int8_t *cube_status,
+              int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out, int64_t *cube_work, int64_t *cube_replay, void *stream)
+{
+    const char *name = "pdp_exact_solve_round";
+    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
+    if (cubes < 0 || cubes > EXS_MAX_CUBES) {
+        pdp_set_error("%s: %lld cubes; a frontier holds 0 .. 2^22", name, (long long)cubes);
+        return PDP_ERR_INVALID;
+    }
+    if (cubes * (int64_t)p->exq_nmax > EXV_MAX_ROW_BYTES) {
+        pdp_set_error("%s: the per-cube model rows (%lld cubes x %d variables) pass 2^31 bytes; split the batch", name, (long long)cubes,
+                      p->exq_nmax);
+        return PDP_ERR_INVALID;
+    }
+    const hipStream_t st = ST(stream);
+    int64_t info[EXQ_INFO];
+    exq_check_launch(p, cube_off, cubes, len, bits, closed, st);
+    PDP_LAUNCH_CHECK();
+    PDP_HIP_CHECK(hipMemcpyAsync(info, exq_info(p), EXQ_INFO * 8, hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));
+    { const int st_ = exq_verdict(name, info); if (st_ != PDP_OK) return st_; }
+    if (cubes == 0) return PDP_OK;
+    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax, B = p->B;
+    // per-cube records: work [total] | replay [total] | model rows [total][n_max]
+    { const int st_ = exs_records(p->exq, total * 16 + total * nmax); if (st_ != PDP_OK) return st_; }
+    ExvParams xp;
+    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_SOLVE_ROUND_BUDGET;
+    xp.hint = hint;
+    xp.route = exq_route(p); xp.cube_off = cube_off; xp.len = len; xp.bits = bits; xp.closed = closed; xp.words = exq_words(p);
+    xp.cube_status = cube_status; xp.len_out = len_out; xp.bits_out = bits_out; xp.closed_out = closed_out;
+    xp.cube_work = (int64_t *)p->exq.cubes;
+    xp.cube_replay = (int64_t *)(p->exq.cubes + total * 8);
+    xp.rows = (uint8_t *)(p->exq.cubes + total * 16);
+    xp.n_max = (int)nmax;
+    xp.status = status; xp.model = model; xp.work = work; xp.first = first;
+    xp.h = ex_hbm(p);
+    { const int st_ = ex_launch_persistent(p, k_exact_solve_round, xp, (int64_t)total, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_solve_round_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    if (cube_work) PDP_HIP_CHECK(hipMemcpyAsync(cube_work, xp.cube_work, total * 8, hipMemcpyDeviceToDevice, st));
+    if (cube_replay) PDP_HIP_CHECK(hipMemcpyAsync(cube_replay, xp.cube_replay, total * 8, hipMemcpyDeviceToDevice, st));
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -5236,6 +5455,22 @@ extern "C" int pdp_exact_count_expand(pdp_problem *p, const int64_t *cube_off, i
     }
     return exq_expand(p, cube_off, cubes, cube_status, len, bits, closed, give, capacity, cube_off_new, len_new, bits_new, closed_new,
                       cubes_new_host, stream);
+}
+
+extern "C" int pdp_exact_solve_round(pdp_problem *p, const float *hint, const int64_t *cube_off, int64_t cubes, const int32_t *len,
+                                     const uint32_t *bits, const uint32_t *closed, int64_t budget, int8_t *status, float *model, int64_t *work,
+                                     int32_t *first, int8_t *cube_status, int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out,
+                                     int64_t *cube_work, int64_t *cube_replay, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && status && model && work && first, "NULL argument");
+    PDP_REQUIRE(cubes <= 0 || (len && bits && closed && cube_status && len_out && bits_out && closed_out), "NULL argument");
+    PDP_REQUIRE(cubes <= 0 || (bits_out != bits && closed_out != closed && len_out != len), "pdp_exact_solve_round: the checkpoints must not alias the frontier");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_solve_round: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exv_round(p, hint, cube_off, cubes, len, bits, closed, budget, status, model, work, first, cube_status, len_out, bits_out, closed_out,
+                     cube_work, cube_replay, stream);
 }
 
 extern "C" int pdp_exact_min_unsat_split(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, int32_t *cost,

@@ -62,6 +62,12 @@ ROUND_BUDGET = 1 << 18
 ROUNDS_MAX_GIVE = 8
 ROUNDS_WAVES_PER_SIMD = 3
 DEFAULT_BUDGET = 1 << 32     # PDP_EXACT_DEFAULT_BUDGET
+# solve_items(split='rounds'): the same three for the deciding search (the library's PDP_EXACT_SOLVE_ROUND_BUDGET).  Chosen from the sweep
+# in profiles/exact_time.txt (tools/exact_time.py srsweep); SOLVE_ROUNDS_WAVES_PER_SIMD is k_exact_solve_round's
+# occupancy by registers (resources)
+SOLVE_ROUND_BUDGET = 1 << 18
+SOLVE_ROUNDS_MAX_GIVE = 8
+SOLVE_ROUNDS_WAVES_PER_SIMD = 4
 # min_unsat(split='auto'): the reads per instance of the plain first branch and bound.  Chosen from the sweep in profiles/exact_time.txt
 # (tools/exact_time.py xsweep)
 AUTO_MIN_STAGE1_BUDGET = 1 << 26
@@ -310,8 +316,58 @@ def split_solve(prob, part, budget, hint, split, device):
     return st, model, wk, du
 
 
+def solve_rounds_give(open_cubes, device):
+    """split='rounds' of the deciding search: rounds_give's rule with k_exact_solve_round's occupancy -- the smallest g with open_cubes *
+    (1 + g) >= AUTO_CUBES_PER_WAVE cubes per resident wave, 0 once the frontier fills the GPU -- capped by SOLVE_ROUNDS_MAX_GIVE and by the
+    2^22 cubes of a frontier"""
+    waves = torch.cuda.get_device_properties(device).multi_processor_count * 4 * SOLVE_ROUNDS_WAVES_PER_SIMD
+    target = AUTO_CUBES_PER_WAVE * waves
+    open_cubes = max(1, int(open_cubes))
+    give = -(-target // open_cubes) - 1
+    return max(0, min(give, SOLVE_ROUNDS_MAX_GIVE, native.COUNT_ROUNDS_MAX_CUBES // open_cubes - 1))
+
+
+def solve_rounds(prob, part, budget, hint, round_budget, give, rounds, device):
+    """The deciding search of one problem in rounds (Problem.exact_solve_round; ``part``: its loader items, or a callable that returns
+    them, read only where an instance has more than 1023 variables): numpy (status, model, work, rounds_used int32).  Every round runs
+    every open cube for ``round_budget`` reads past its replay (None or 0: SOLVE_ROUND_BUDGET) and cuts the frontier it leaves again,
+    ``give`` levels per stopped cube (None: solve_rounds_give of the open cubes, every round).  ``budget`` is the total of reads per
+    instance over all rounds and cubes (0: the library's default budget): an instance whose work has reached it leaves the frontier with
+    status -1.  ``rounds``: at most so many rounds (None: until no cube is open); instances that are still open then end with status -1
+    as well.  An instance of more than 1023 variables has no cube: it goes to the plain call, with ``budget``, and uses 0 rounds."""
+    total = budget if budget > 0 else DEFAULT_BUDGET
+    state = prob.exact_solve_begin(hint)
+    done = 0
+    while state.cubes and (rounds is None or done < rounds):
+        prob.exact_solve_round(state, round_budget or SOLVE_ROUND_BUDGET, solve_rounds_give(state.cubes, device) if give is None else give)
+        done += 1
+        per = state.cube_off[1:] - state.cube_off[:-1]
+        spent = (state.work >= total) & (per > 0)
+        if bool(spent.any()):
+            # out of reads: the instance's cubes leave the frontier, its status stays -1
+            keep = ~torch.repeat_interleave(spent, per)
+            state.len, state.bits, state.closed = state.len[keep], state.bits[keep], state.closed[keep]
+            state.cube_off = torch.cat([state.cube_off[:1], torch.cumsum(torch.where(spent, torch.zeros_like(per), per), 0)])
+    st, model, wk, used = state.status.cpu().numpy(), state.model.cpu().numpy(), state.work.cpu().numpy(), state.rounds.cpu().numpy()
+    wide = [int(j) for j in np.nonzero(st == -2)[0]]
+    if wide:
+        part = part() if callable(part) else part
+        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+        sub = _problem([part[j] for j in wide], device)
+        hint2 = None if hint is None else torch.cat([hint[voff[j]:voff[j + 1]] for j in wide])
+        r = [t.cpu().numpy() for t in sub.exact_solve(budget, hints=hint2)]
+        del sub
+        off = 0
+        for k, j in enumerate(wide):
+            n = int(voff[j + 1] - voff[j])
+            st[j], wk[j] = r[0][k], r[2][k]
+            model[voff[j]:voff[j + 1]] = r[1][off:off + n]
+            off += n
+    return st, model, wk, used
+
+
 def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, learn=False, arena=0, certify=False, proofs=False, cores=False,
-                assume=None, split=None):
+                assume=None, split=None, round_budget=None, rounds=None):
     """Solve loader items ((n, m, graph_map, edge_feature, label, misc) tuples: dataset.instance_from_clauses, dataset.random_ksat_items,
     dataset.parse_line, raw_item).  Returns numpy (status int8 [N] in {1, 0, -1}, models: a float32 0/1 array of n_i values per instance,
     work int64 [N]).  Instances are packed into problems of at most ``max_edges`` edges; nothing couples two instances.
@@ -337,8 +393,20 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
     (``proofs``: that refutation's lemmas).  ``cores`` under assumptions is not available.
     ``split``: the plain search (with ``hints`` if given) of every instance spread over 2^split waves (pdp_exact_solve_split; an int from 0
     to 16), or 'auto': see split_solve.  Status and models are those of the call without ``split`` while no cube runs out of ``budget``,
-    which then applies to every cube; work is the sum over the cubes that count.  Not with ``learn``, ``certify`` or ``assume``."""
-    split = _check_split(split)
+    which then applies to every cube; work is the sum over the cubes that count.  Not with ``learn``, ``certify`` or ``assume``.
+    ``split='rounds'``: see solve_rounds -- the search in rounds of ``round_budget`` reads per cube, at most ``rounds`` of them, the open
+    part of every tree cut again between two rounds to fill the GPU.  ``budget`` is then the total of reads per instance over all rounds
+    and cubes; status is that of the call without ``split`` while the total is not reached, every model satisfies its instance, and which
+    model comes back is not promised.  There is no check pass: a complete hint is followed, not tested first."""
+    by_rounds = isinstance(split, str) and split == 'rounds'
+    if not by_rounds:
+        split = _check_split(split)
+        if round_budget is not None or rounds is not None:
+            raise ValueError("round_budget and rounds belong to split='rounds'")
+    else:
+        for name, x in (('round_budget', round_budget), ('rounds', rounds)):
+            if x is not None and (isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1):
+                raise ValueError("%s must be None or a positive integer, got %r" % (name, x))
     if split is not None and (learn or certify or assume is not None):
         raise ValueError("split spreads the plain search: pass it without learn, certify and assume")
     learn = learn or certify or assume is not None
@@ -415,6 +483,8 @@ def solve_items(items, budget=0, device=None, max_edges=MAX_EDGES, hints=None, l
                 st, model, wk, vd, lem, cor = _certified_part(prob, part, names, budget, hint, arena, device, cores)
                 for j, i in enumerate(seg):
                     verdict[i], lemmas[i], core[i] = vd[j], lem[j], cor[j]
+            elif by_rounds:
+                st, model, wk, _ = solve_rounds(prob, part, budget, hint, round_budget, None, rounds, device)
             elif split is not None:
                 st, model, wk, _ = split_solve(prob, part, budget, hint, split, device)
             else:
@@ -1051,17 +1121,20 @@ def _label(s):
     return True if s == 1 else (False if s == 0 else None)
 
 
-def label_clause_lists(instances, budget=0, device=None, max_edges=MAX_EDGES, learn=False, arena=0, certify=False, split=None):
+def label_clause_lists(instances, budget=0, device=None, max_edges=MAX_EDGES, learn=False, arena=0, certify=False, split=None,
+                       round_budget=None, rounds=None):
     """The batched labeller: [(n, clauses), ...] (clauses: lists of signed 1-based ints) -> [True / False / None, ...].
-    ``certify``: only checked answers become labels (solve_items); an answer that is not certified is None.  ``split``: solve_items'."""
+    ``certify``: only checked answers become labels (solve_items); an answer that is not certified is None.  ``split``, ``round_budget``
+    and ``rounds``: solve_items'."""
     out = solve_items([raw_item(n, clauses) for n, clauses in instances], budget=budget, device=device, max_edges=max_edges,
-                      learn=learn, arena=arena, certify=certify, split=split)
+                      learn=learn, arena=arena, certify=certify, split=split, round_budget=round_budget, rounds=rounds)
     if certify:
         return [_label(int(s)) if v == 1 else None for s, v in zip(out[0], out[3])]
     return [_label(int(s)) for s in out[0]]
 
 
-def is_sat(var_num, iclause_list, budget=0, learn=False, arena=0, certify=False, split=None):
+def is_sat(var_num, iclause_list, budget=0, learn=False, arena=0, certify=False, split=None, round_budget=None, rounds=None):
     """The reference's labelling hook (generator.py:15-17) for one instance: True, False, or None when the budget ran out.  ``split``
-    (an int depth or 'auto'): the one instance's search spread over the GPU (solve_items)."""
-    return label_clause_lists([(var_num, iclause_list)], budget=budget, learn=learn, arena=arena, certify=certify, split=split)[0]
+    (an int depth, 'auto' or 'rounds'): the one instance's search spread over the GPU (solve_items)."""
+    return label_clause_lists([(var_num, iclause_list)], budget=budget, learn=learn, arena=arena, certify=certify, split=split,
+                              round_budget=round_budget, rounds=rounds)[0]

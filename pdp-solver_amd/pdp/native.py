@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_min_unsat_split', 'pdp_exact_min_unsat_split_cubes', 'pdp_exact_mass',
     'pdp_exact_mass_split', 'pdp_exact_mass_split_cubes', 'pdp_exact_nearest',
     'pdp_exact_nearest_split', 'pdp_exact_nearest_split_cubes',
-    'pdp_exact_count_frontier_words', 'pdp_exact_count_round', 'pdp_exact_count_expand',
+    'pdp_exact_count_frontier_words', 'pdp_exact_count_round', 'pdp_exact_count_expand', 'pdp_exact_solve_round',
 ]
 
 
@@ -272,6 +272,47 @@ class CountState(object):
         cubes = int(self.len.numel())
         sizes = {'cube_off': (problem.B + 1,), 'len': (cubes,), 'count': (problem.B,), 'true_count': (problem.V,), 'work': (problem.B,),
                  'leaves': (problem.B,), 'status': (problem.B,), 'rounds': (problem.B,)}
+        words = C.c_int32()
+        check(lib().pdp_exact_count_frontier_words(problem._h, C.byref(words)))
+        sizes['bits'] = sizes['closed'] = (cubes, words.value)
+        for f in self.FIELDS:
+            t = getattr(self, f)
+            if not torch.is_tensor(t) or t.device != problem.device or t.dtype != kinds[f] or tuple(t.shape) != sizes[f] or not t.is_contiguous():
+                raise NativeError("state.%s must be a contiguous %s tensor of shape %s on %s" % (f, kinds[f], sizes[f], problem.device))
+        if cubes > COUNT_ROUNDS_MAX_CUBES:
+            raise NativeError("state holds %d cubes; a frontier holds at most 2^22" % cubes)
+
+
+class SolveState(object):
+    """A resumable deciding search (Problem.exact_solve_begin / exact_solve_round): plain tensors, so it can be saved, moved with cpu() /
+    to() and continued on another Problem built from the same items.  The frontier is CountState's: cube_off int64 [B+1], len int32
+    [cubes], bits and closed int32 [cubes, words].  hint float32 [V]: the phase hints of every round (NaN: none).  status int8 [B]: -1
+    cubes are open, 1 satisfiable, 0 unsatisfiable, -2 not searched (more than 1023 variables); model float32 [V]: the model of an
+    instance of status 1, zeros elsewhere; work int64 [B]: the reads of all its cubes and rounds; rounds int32 [B]: the rounds the
+    instance had a cube in."""
+    FIELDS = ('cube_off', 'len', 'bits', 'closed', 'hint', 'status', 'model', 'work', 'rounds')
+
+    @property
+    def cubes(self):
+        return int(self.len.numel())
+
+    def to(self, device):
+        "a copy on ``device``"
+        s = SolveState()
+        for f in self.FIELDS:
+            setattr(s, f, getattr(self, f).to(device).clone())
+        return s
+
+    def cpu(self):
+        return self.to('cpu')
+
+    def validate(self, problem):
+        "what the library cannot see from raw pointers: devices, dtypes and shapes (the frontier's contents are checked on the GPU)"
+        kinds = {'cube_off': torch.int64, 'len': torch.int32, 'bits': torch.int32, 'closed': torch.int32, 'hint': torch.float32,
+                 'status': torch.int8, 'model': torch.float32, 'work': torch.int64, 'rounds': torch.int32}
+        cubes = int(self.len.numel())
+        sizes = {'cube_off': (problem.B + 1,), 'len': (cubes,), 'hint': (problem.V,), 'status': (problem.B,), 'model': (problem.V,),
+                 'work': (problem.B,), 'rounds': (problem.B,)}
         words = C.c_int32()
         check(lib().pdp_exact_count_frontier_words(problem._h, C.byref(words)))
         sizes['bits'] = sizes['closed'] = (cubes, words.value)
@@ -855,6 +896,71 @@ class Problem(object):
             return made
         return made, (ran, cube_status, rec[0], rec[1], rec[2], rec[3], len_out, bits_out, closed_out)
 
+    def exact_solve_begin(self, hints=None):
+        """The state of a resumable deciding search (pdp_exact_solve_round): the root frontier -- one cube of length 0 per instance of at
+        most 1023 variables -- status -1 (open), or -2 where the instance is not searched, zeroed models and work.  ``hints`` (float32, V
+        elements, on the problem's device; None: none) are kept on the state and steer every round.  See SolveState."""
+        if hints is not None:
+            if not torch.is_tensor(hints) or hints.dtype != torch.float32 or hints.numel() != self.V or hints.device != self.device:
+                raise ValueError("hints must be a float32 tensor of %d elements (one per variable) on %s, got %s"
+                                 % (self.V, self.device, '%s of %d on %s' % (hints.dtype, hints.numel(), hints.device)
+                                    if torch.is_tensor(hints) else type(hints).__name__))
+        c = self.exact_count_begin()
+        s = SolveState()
+        s.cube_off, s.len, s.bits, s.closed, s.status, s.work, s.rounds = c.cube_off, c.len, c.bits, c.closed, c.status, c.work, c.rounds
+        s.hint = (torch.full((self.V,), float('nan'), dtype=torch.float32, device=self.device) if hints is None
+                  else hints.reshape(-1).contiguous().clone())
+        s.model = torch.zeros(self.V, dtype=torch.float32, device=self.device)
+        return s
+
+    def exact_solve_round(self, state, budget=0, give=0, stats=False):
+        """One round of a resumable deciding search (pdp_exact_solve_round, then pdp_exact_count_expand): every open cube of ``state`` runs
+        for ``budget`` clause-literal reads past the replay of its path (0: the library default); an instance one of whose cubes found a
+        model becomes status 1 with that model and leaves the frontier, one whose cubes all ended without one becomes 0, and the
+        checkpoints of the others are cut into up to ``give`` children and a remainder each.  Advances ``state`` in place and returns the
+        number of open cubes.  Once decided, status is exact_solve's; with ``give`` 0 throughout, status and model are exact_solve's with
+        the state's hints bit for bit wherever its check pass does not accept them; with more, which model comes back is not promised.
+        ``stats``: also the round's records (cube_off int64 [B+1] of the frontier that ran, cube_status int8 [cubes] 1 / 0 / -1 / -2
+        dropped, cube_work and cube_replay int64 [cubes], the checkpoints len_out int32 [cubes], bits_out and closed_out int32 [cubes,
+        words], and first int32 [B]: the instance's lowest cube that answered 1, -1 none).  The state may come from another Problem of the
+        same items.  A malformed state raises before anything is searched or written.  More than 2^22 cubes after the expansion raises;
+        lower ``give``.  Synchronises the current stream twice."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads per cube (0: the library default), got %r" % (budget,))
+        if isinstance(give, bool) or not isinstance(give, numbers.Integral) or not 0 <= give <= COUNT_ROUNDS_MAX_N:
+            raise ValueError("give must be an integer from 0 to %d, got %r" % (COUNT_ROUNDS_MAX_N, give))
+        if not isinstance(state, SolveState):
+            raise ValueError("state must come from exact_solve_begin, got %s" % type(state).__name__)
+        state.validate(self)
+        dev = self.device
+        cubes, words = int(state.len.numel()), int(state.bits.size(1))
+        cube_status = torch.empty(cubes, dtype=torch.int8, device=dev)
+        len_out = torch.empty(cubes, dtype=torch.int32, device=dev)
+        bits_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        closed_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        first = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
+        rec = [torch.empty(cubes, dtype=torch.int64, device=dev) if stats else None for _ in range(2)]
+        check(lib().pdp_exact_solve_round(self._h, ptr(state.hint), ptr(state.cube_off), C.c_int64(cubes), ptr(state.len), ptr(state.bits),
+                                          ptr(state.closed), C.c_int64(int(budget)), ptr(state.status), ptr(state.model), ptr(state.work),
+                                          ptr(first), ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out), ptr(rec[0]),
+                                          ptr(rec[1]), _stream()))
+        capacity = min(cubes * (1 + int(give)), COUNT_ROUNDS_MAX_CUBES)
+        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=dev)
+        len_new = torch.empty(capacity, dtype=torch.int32, device=dev)
+        bits_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
+        closed_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
+        made = C.c_int64()
+        ran = state.cube_off
+        check(lib().pdp_exact_count_expand(self._h, ptr(ran), C.c_int64(cubes), ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out),
+                                           C.c_int32(int(give)), C.c_int64(capacity), ptr(cube_off), ptr(len_new), ptr(bits_new),
+                                           ptr(closed_new), C.byref(made), _stream()))
+        made = int(made.value)
+        state.rounds += (ran[1:] > ran[:-1]).to(torch.int32)
+        state.cube_off, state.len, state.bits, state.closed = cube_off, len_new[:made], bits_new[:made], closed_new[:made]
+        if not stats:
+            return made
+        return made, (ran, cube_status, rec[0], rec[1], len_out, bits_out, closed_out, first)
+
     def exact_mass_split(self, weights, budget=0, depth=None, stats=False):
         """exact_mass with the search of instance b spread over 2^depth[b] waves (pdp_exact_mass_split): (status, mass, true_mass,
         open_mass, work) as exact_mass's.  ``budget`` applies to every cube; at status -1 the probability lies in [mass, mass + open_mass];
@@ -1093,7 +1199,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split, exact_nearest_split, exact_mass_split and exact_count_round (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split, exact_nearest_split, exact_mass_split, exact_count_round and exact_solve_round (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

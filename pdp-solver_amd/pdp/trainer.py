@@ -160,7 +160,10 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         "min_unsat_proved" mean the same, which minimiser "min_unsat_solution" is and "min_unsat_work" depend on the timing of the cubes, and a
         row searched at a depth above 0 gains "min_unsat_split_depth" after "min_unsat_work".  With config['complete_split'] (a depth 0..16, or -1: exact.split_solve's 'auto') the same search runs
         with every instance spread over 2^depth waves (pdp_exact_solve_split): "complete" and the solution are unchanged, "work" is the sum over
-        the cubes, and a row searched at a depth above 0 gains "split_depth" after "work".  With config['complete_count'] every row whose "complete" is 1 gains "model_count" (pdp_exact_count within
+        the cubes, and a row searched at a depth above 0 gains "split_depth" after "work".  With config['complete_rounds'] (log2 of the reads per cube
+        and round, or -1: the default) the search runs in rounds instead (exact.solve_rounds, pdp_exact_solve_round; no check pass, so the
+        solution of a row PDP had solved is a model the hints lead to, not always PDP's own): the budget is the total per row over all
+        rounds and cubes, and every row that had a cube gains "complete_rounds" after "work".  With config['complete_count'] every row whose "complete" is 1 gains "model_count" (pdp_exact_count within
         the same budget: an int while it is exact, a float above 2^53), "model_count_log2", "model_count_proved" (1: the number of models, 0: the budget
         ran out, a lower bound), "marginals" (per variable, the share of the counted models in which it is true), "marginal_gap" (the mean
         over the variables of |the soft prediction - marginal|) and "count_work"; marginals and marginal_gap are left out where nothing was
@@ -201,7 +204,7 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             handle = native.Problem(graph_map, batch_variable_map, batch_function_map, edge_feature, batch_size=len(rows))
         hint = prediction[0].detach().reshape(-1).to(torch.float32).contiguous()
         budget = int(self._config.get('complete_budget', 0) or 0)
-        certified = split_depth = None
+        certified = split_depth = used_rounds = None
         if self._config.get('complete_certify'):
             # the learning search with its lemma log, every answer checked (pdp_exact_check); a proof that did not fit its region is
             # logged once more into regions of the size the first run reported; a refuted answer raises
@@ -224,6 +227,14 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                 handle, lambda: exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows)), budget, hint,
                 'auto' if split < 0 else split, hint.device)
             solution = solution.astype(int)
+        elif self._config.get('complete_rounds') is not None:
+            # config['complete_rounds']: the same search in rounds of 2^N reads per cube (pdp_exact_solve_round); -1: the default
+            from pdp import exact
+            per_round = int(self._config['complete_rounds'])
+            status, solution, work, used_rounds = exact.solve_rounds(
+                handle, lambda: exact.items_of(graph_map, batch_variable_map, batch_function_map, edge_feature, len(rows)), budget, hint,
+                None if per_round < 0 else 1 << per_round, None, None, hint.device)
+            solution = solution.astype(int)
         else:
             status, solution, work = handle.exact_solve(budget, hints=hint, learn=bool(self._config.get('complete_learn')))
             status, work = status.cpu().numpy(), work.cpu().numpy()
@@ -232,6 +243,8 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
             row['complete'], row['pdp_solved'], row['work'] = int(status[i]), row['solved'], int(work[i])
             if split_depth is not None and split_depth[i] > 0:
                 row['split_depth'] = int(split_depth[i])
+            if used_rounds is not None and used_rounds[i] > 0:
+                row['complete_rounds'] = int(used_rounds[i])
             if certified is not None:
                 row['certified'] = int(certified[i])
                 if cores[i] is not None:

@@ -21,7 +21,10 @@ the exact number of its models (pdp_exact_count), "model_count_log2", "model_cou
 from them) and "count_work"; ``--complete-split N`` (with ``--complete``, not with ``--complete-learn`` or ``--complete-certify``) spreads the
 search of every instance over 2^N waves (pdp_exact_solve_split; -1: a plain first stage, then a depth chosen from the number of
 undecided instances): the same "complete" and solution, "work" summed over the cubes, and "split_depth" on the rows searched at a depth
-above 0; ``--complete-count-split N`` (with ``--complete-count``) does the same for the count (pdp_exact_count_split; -1: a plain first count,
+above 0; ``--complete-rounds N`` (with ``--complete``, not with ``--complete-split``, ``--complete-learn`` or ``--complete-certify``) runs
+that search in rounds of 2^N reads per cube (pdp_exact_solve_round; -1: the default) and cuts the open part of every tree again between
+two rounds: the same "complete", a model of the instance as the solution, ``--complete-budget`` as the total per row, "work" summed over
+rounds and cubes, and "complete_rounds" on every row searched this way; ``--complete-count-split N`` (with ``--complete-count``) does the same for the count (pdp_exact_count_split; -1: a plain first count,
 then the instances that ran out once more at a depth chosen from their number): the same counts and marginals, "count_work" summed over
 the cubes, and "count_split_depth" on the rows counted at a depth above 0; ``--complete-count-rounds N`` (with ``--complete-count``, not
 with ``--complete-count-split``) counts in rounds of 2^N reads per cube (pdp_exact_count_round; -1: the default) and cuts the open part of
@@ -170,6 +173,12 @@ def main(argv=None):
                         '(pdp_exact_solve_split), N from 0 to 16, or -1: a plain first stage, then the undecided instances at a depth that fills the GPU; '
                         'the same "complete" and solution, "work" summed over the cubes, "split_depth" on the rows searched at a depth above 0; '
                         'not with --complete-learn or --complete-certify', type=int, default=None)
+    parser.add_argument('--complete-rounds', dest='complete_rounds', help='With --complete: run the exact search in rounds of 2^N reads per cube '
+                        '(pdp_exact_solve_round), N from 0 to 40, or -1 for the default; between two rounds the open part of every search tree is '
+                        'cut again to fill the GPU, and --complete-budget is the total of reads per row over all rounds and cubes; the same '
+                        '"complete", a model of the instance as the solution (not always the plain search\'s), "work" summed over the rounds and '
+                        'cubes, "complete_rounds" on every row searched this way; not with --complete-split, --complete-learn or '
+                        '--complete-certify', type=int, default=None)
     parser.add_argument('--complete-count-split', dest='complete_count_split', help='With --complete --complete-count: spread the count of every '
                         'satisfiable row over 2^N waves (pdp_exact_count_split), N from 0 to 16, or -1: a plain first count, then the rows that ran '
                         'out of its reads once more at a depth that fills the GPU; the same counts and marginals, "count_work" summed over the cubes, '
@@ -236,6 +245,15 @@ def main(argv=None):
             parser.error("--complete-split spreads the plain search: give it without --complete-learn and --complete-certify")
         if not -1 <= args['complete_split'] <= 16:
             parser.error("--complete-split takes a depth from 0 to 16, or -1 for a depth chosen from the undecided instances")
+    if args['complete_rounds'] is not None:
+        if not args['complete']:
+            parser.error("--complete-rounds runs the search of --complete in rounds: give --complete as well")
+        if args['complete_split'] is not None:
+            parser.error("--complete-rounds cuts the search between its rounds: give it without --complete-split")
+        if args['complete_learn'] or args['complete_certify']:
+            parser.error("--complete-rounds runs the plain search: give it without --complete-learn and --complete-certify")
+        if not -1 <= args['complete_rounds'] <= 40:
+            parser.error("--complete-rounds takes log2 of the reads per cube and round, from 0 to 40, or -1 for the default")
     if args['complete_count_split'] is not None:
         if not args['complete_count']:
             parser.error("--complete-count-split spreads the count of --complete-count: give --complete-count as well")

@@ -67,6 +67,13 @@ rounds times that one call alone (a fresh process per measurement of an alternat
 on row ``ca`` over round budgets 2^16 .. 2^24 and ROUNDS_MAX_GIVE = 1 / 4 / 8 / 16.  ``crd`` = row ``cd`` with PDP_CSD_BUDGET reads per
 instance in all (default and cap 2^28): complete counts and lower bounds next to the plain count under the same budget.
 
+Rounds solve rows (pdp_exact_solve_round; never part of the default): ``sra`` = the instance of row (c) with the largest plain work alone
+(PDP_SR_PICK=<index> names it without the plain run of the row): host wall time of solve_items plain, split=12 and split='rounds';
+``srb`` / ``src`` / ``srd`` = rows (b) / (c) / (d) whole: plain, split='auto' and split='rounds', equal status asserted, the reads against
+the plain search's and the rounds used; PDP_SOLVE_ONLY=plain / auto / split:12 / rounds times that one call alone (a fresh process per
+measurement of an alternating comparison), PDP_SR_ROUND_BUDGET=<N> a round budget of 2^N in place of the default.  ``srsweep`` = solve_items(split='rounds') on row (b) over round budgets 2^14 .. 2^22 and
+SOLVE_ROUNDS_MAX_GIVE = 1 / 4 / 8 / 16.
+
 Split minimum rows (pdp_exact_min_unsat_split; never part of the default): ``xsa`` / ``xsb`` = the 1 / 8 instances of row ``xa`` with the largest
 plain work as a batch of their own, same incumbents: kernel time of pdp_exact_min_unsat and of the split call at depths 4 / 8 / 12 on the
 same problem (each after an untimed call with a budget of one read), proved counts, costs, the reads against the plain call's, the
@@ -813,6 +820,70 @@ def run_count_rounds(key):
         _rounds_line(tag, ms, out, plain[3].sum())
 
 
+SOLVE_ROUNDS_ROWS = ('sra', 'srb', 'src', 'srsweep', 'srd')
+
+
+def _solve_line(tag, ms, out, plain_work, used=None):
+    print("    %s: wall %.1f ms  SAT %d  UNSAT %d  undecided %d  reads %d (%.3f of the plain search's)%s"
+          % (tag, ms, int((out[0] == 1).sum()), int((out[0] == 0).sum()), int((out[0] == -1).sum()), int(out[2].sum()),
+             float(out[2].sum()) / max(1.0, float(plain_work)), "" if used is None else "  rounds max %d  median %d" % (int(used.max()), int(np.median(used)))),
+          flush=True)
+
+
+def run_solve_rounds(key):
+    """sra / srb / src / srd: host wall time of solve_items plain, split=12 (sra) or split='auto', and split='rounds' on the same items, equal
+    status asserted; PDP_SOLVE_ONLY=plain / auto / split:<depth> / rounds times that one call alone (a fresh process per measurement of an
+    alternating comparison); PDP_SR_PICK=<index> names the instance of sra (else it is found by a plain run of row c), PDP_SR_ROUND_BUDGET=<N>
+    sets the round budget of 'rounds' to 2^N.  srsweep: the round budget and the give cap on row b."""
+    from pdp import exact
+    only = os.environ.get('PDP_SOLVE_ONLY')
+    title, make = ROWS[{'sra': 'c', 'srb': 'b', 'src': 'c', 'srsweep': 'b', 'srd': 'd'}[key]]
+    items = make()
+    exact.solve_items(items[:8], budget=1, split=1)                                  # the context, the library and the kernels are loaded
+    exact.solve_items(items[:8], budget=1, split='rounds')
+    if key == 'sra':
+        pick = os.environ.get('PDP_SR_PICK')
+        pick = int(np.argmax(exact.solve_items(items)[2])) if pick is None else int(pick)
+        items, title = [items[pick]], 'instance %d of %s' % (pick, title)
+    per_round = os.environ.get('PDP_SR_ROUND_BUDGET')                               # log2 of the reads per cube and round; unset: the default
+    per_round = None if per_round is None else 1 << int(per_round)
+    used = []
+    real = exact.solve_rounds
+
+    def keep(*a, **kw):
+        out = real(*a, **kw)
+        used.append(out[3])
+        return out
+    exact.solve_rounds = keep
+    calls = {'plain': lambda: exact.solve_items(items), 'auto': lambda: exact.solve_items(items, split='auto'),
+             'rounds': lambda: exact.solve_items(items, split='rounds', round_budget=per_round), 'split:12': lambda: exact.solve_items(items, split=12)}
+    if only:
+        ms, out = _wall(calls[only])
+        print("(%s, %s alone) %d instances, %s" % (key, only, len(items), title), flush=True)
+        _solve_line("solve_items", ms, out, out[2].sum(), np.concatenate(used) if used else None)
+        return
+    ms0, plain = _wall(calls['plain'])
+    print("(%s) %d instances, %s: plain solve_items wall %.1f ms  SAT %d  UNSAT %d  undecided %d  reads %d  largest %d"
+          % (key, len(items), title, ms0, int((plain[0] == 1).sum()), int((plain[0] == 0).sum()), int((plain[0] == -1).sum()), int(plain[2].sum()),
+             int(plain[2].max())), flush=True)
+    if key == 'srsweep':
+        default_cap = exact.SOLVE_ROUNDS_MAX_GIVE
+        for cap in (1, 4, 8, 16):
+            exact.SOLVE_ROUNDS_MAX_GIVE = cap
+            for lg in (14, 16, 18, 20, 22):
+                del used[:]
+                ms, out = _wall(lambda: exact.solve_items(items, split='rounds', round_budget=1 << lg))
+                assert np.array_equal(out[0], plain[0]), "split='rounds' answers differently"
+                _solve_line("give cap %2d, round budget 2^%d" % (cap, lg), ms, out, plain[2].sum(), np.concatenate(used))
+        exact.SOLVE_ROUNDS_MAX_GIVE = default_cap
+        return
+    for tag in (('split:12',) if key == 'sra' else ('auto',)) + ('rounds',):
+        del used[:]
+        ms, out = _wall(calls[tag])
+        assert np.array_equal(out[0], plain[0]), "%s answers differently" % tag
+        _solve_line(tag, ms, out, plain[2].sum(), np.concatenate(used) if used else None)
+
+
 MIN_SPLIT_ROWS = ('xsa', 'xsb', 'xsauto', 'xsweep')
 
 
@@ -1310,6 +1381,9 @@ if __name__ == '__main__':
             continue
         if k in MIN_SPLIT_ROWS:
             run_min_split(k)
+            continue
+        if k in SOLVE_ROUNDS_ROWS:
+            run_solve_rounds(k)
             continue
         if k in SPLIT_ROWS or k == 'sweep':
             run_split(k) if k in SPLIT_ROWS else run_split_sweep()
