@@ -715,6 +715,47 @@ int pdp_exact_solve_round(pdp_problem *p, const float *hint, const int64_t *cube
                           int32_t *first, int8_t *cube_status, int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out,
                           int64_t *cube_work, int64_t *cube_replay, void *stream);
 
+/* pdp_exact_nearest as a sequence of rounds over the same frontier, with the bound exchanged between two rounds (plain Python, normative:
+ * tests/exact_nearest_rounds_model.py).  The frontier (cube_off, len, bits, closed, the pairs,
+ * pdp_exact_count_frontier_words), its check and the checkpoints are pdp_exact_count_round's, and the next frontier comes from
+ * pdp_exact_count_expand, called as it is with this call's cube_status (it expands the cubes of status -1).
+ *   Search of a cube.  pdp_exact_nearest's branch and bound without its check pass, with plen = len and ub = cost[b] as it stood when the
+ *   round began (-1: infinite).  A decision that opens level L <= plen takes the hint's polarity for bit 0 and the other one for bit 1, and
+ *   carries the flipped mark iff closed.  A bit-1 decision adds the variable's penalty to dist; if that reaches ub the state is pruned at
+ *   once, before any pass.  A prune is pdp_exact_nearest's chronological backtracking (a flip whose penalty alone reaches ub is skipped
+ *   and the level undone); it pops closed levels, and a flip of an open level L sets plen = min(plen, L).  A state without an open clause
+ *   and dist < ub is accepted wherever it is met, also at a level < plen: ub = cube_cost = dist, one improvement, the cube's model = the
+ *   assignment with the unassigned variables at their hint values; ub == 0 ends the cube, otherwise the state is pruned.  ub appears in
+ *   the prune only -- the units are always forced and the branching variable does not read it -- so a path is replayed in the same tree
+ *   under any bound: identically, or pruned earlier.  hint [V] may be NULL (all false), penalty [V] may be NULL (all 1).
+ *   Budget of a round (reads per cube; budget <= 0: PDP_EXACT_NEAREST_ROUND_BUDGET) and checkpoint: pdp_exact_count_round's, word for
+ *   word.  cube_status [cubes] = 1 (ended: nothing below the bound it ran under is left in it; len_out 0 and a row of zeros) or -1
+ *   (stopped, with a checkpoint; it may have improved as well).  cube_cost [cubes] = the cube's last accepted cost, -1: none.
+ *   Outcome, per instance that has a cube.  best = the minimum of the cube_cost >= 0.  If cost[b] < 0 or best < cost[b]: cost[b] = best,
+ *   first[b] = the lowest cube, counted from cube_off[b], whose cube_cost is best, and model (its slice of [V]) = that cube's; else
+ *   first[b] = -1 and cost and model stay.  work[b] and improvements[b] (in/out) take the integer sums over the cubes.  status[b] = 1 if
+ *   cost[b] == 0, and the instance's stopped cubes get cube_status -2 ("dropped": the expansion leaves nothing of them, their checkpoints
+ *   stay as written); else, if no cube stopped, 1 where cost[b] >= 0 and 0 where no model was ever met; else -1: cost is an upper bound
+ *   that model attains, or -1.  An instance without a cube is not touched in any output.  cost, model, work and improvements are in/out:
+ *   the caller starts them at -1, zeros (or a model it has checked and that model's distance), 0 and 0.  cube_cost, cube_work,
+ *   cube_replay and cube_improvements [cubes] may be NULL.
+ * No word is shared between two cubes inside a round and the only atomic is the counter that hands out cube ids, so every output, record
+ * and frontier word is a function of the instances, hint, penalties, frontier, incoming cost and budget alone.  With one cube per
+ * instance throughout (give 0) status, cost, model and the summed improvements are pdp_exact_nearest's bit for bit wherever that call's
+ * check pass does not accept the hint, and the sum of cube_work - cube_replay over the rounds is its work less the check pass's reads;
+ * where it accepts, the search follows the hint to cost 0 and model = the thresholded hint with one improvement.  With more cubes status
+ * and cost are the same once the frontier is empty, and which minimiser comes back depends on budget and give.  One wave takes one cube at
+ * a time; an accepted leaf leaves its assignment as a row of bytes in [cubes][n_max] on the handle; a last kernel writes the outcome, one
+ * wave per instance.  The refusals are pdp_exact_solve_round's (PDP_ERR_INVALID naming the cube or instance, before anything is searched
+ * or written), plus a penalty outside [0, 2^20] on an instance that has a cube.  R != 1 -> PDP_ERR_UNSUPPORTED.  Routing, slab and
+ * working arrays are pdp_exact_solve's.  The call synchronises the stream once (the checks' verdicts). */
+#define PDP_EXACT_NEAREST_ROUND_BUDGET (((int64_t)1) << 18)
+int pdp_exact_nearest_round(pdp_problem *p, const float *hint, const int32_t *penalty, const int64_t *cube_off, int64_t cubes,
+                            const int32_t *len, const uint32_t *bits, const uint32_t *closed, int64_t budget, int8_t *status, int64_t *cost,
+                            float *model, int64_t *work, int32_t *improvements, int32_t *first, int8_t *cube_status, int32_t *len_out,
+                            uint32_t *bits_out, uint32_t *closed_out, int64_t *cube_cost, int64_t *cube_work, int64_t *cube_replay,
+                            int32_t *cube_improvements, void *stream);
+
 /* The models of given ranks in pdp_exact_count's own order (plain Python, normative: tests/exact_rank_model.py).  The
  * counting search meets its leaves in a fixed depth-first order and a leaf with f unassigned variables stands for 2^f models, so "count
  * before the leaf + offset inside it" numbers every model of an instance exactly once.  Instance b asks for K_b = rank_off[b+1] -
@@ -849,7 +890,7 @@ int pdp_exact_nearest_split_cubes(pdp_problem *p, int64_t *cube_off, int8_t *cub
                                   int32_t *cube_improvements, void *stream);
 
 /* *grid_host (a host int32) = the workgroups of the last launch that pdp_exact_solve, pdp_exact_solve_hinted, pdp_exact_solve_learn,
- * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split, pdp_exact_nearest_split, pdp_exact_mass_split, pdp_exact_count_round and pdp_exact_solve_round (their cube kernels:
+ * pdp_exact_solve_learn_proof, pdp_exact_solve_learn_assume, pdp_exact_min_unsat, pdp_exact_nearest, pdp_exact_count, pdp_exact_mass, pdp_exact_models_at, pdp_exact_solve_split, pdp_exact_count_split, pdp_exact_min_unsat_split, pdp_exact_nearest_split, pdp_exact_mass_split, pdp_exact_count_round, pdp_exact_solve_round and pdp_exact_nearest_round (their cube kernels:
  * min(cubes, CUs * resident workgroups per CU)), pdp_exact_check or pdp_exact_trim issued without an error on the problem; 0 before the first, and a call that fails
  * leaves the value.  Each of them launches min(B, CUs * resident workgroups per CU) workgroups of one wave that take instance after
  * instance from one counter; the environment variable PDP_EXACT_GRID=<v>, read at every launch, lowers that to min(grid, v) for an

@@ -171,7 +171,8 @@ struct pdp_problem {
     // and the route bytes [B]; exq.cubes = a round's per-cube records (count, work, leaves, replay, true_count rows, status) or an
     // expansion's scan (first new cube of every old one, the new cube_off); exq_nmax = the most variables of a searched instance.
     // pdp_exact_solve_round (exv_round) uses the same check words, route bytes and exq_nmax, and exq.cubes for its own records (work,
-    // replay, model rows of bytes)
+    // replay, model rows of bytes), and so does pdp_exact_nearest_round (exw_round: cost, work, replay, improvements, model rows), whose
+    // penalty check owns word 6 of the check's block
     pdp_exact_cubes exq; int exq_ready, exq_nmax;
     // k-th models of the counting search (pdp_exact.hip::exr_launch): ex_prepare's routing and slab; the rows' byte offsets [B+1] and the
     // validation words of the last call, one block allocated on first use

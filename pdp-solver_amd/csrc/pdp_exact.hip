@@ -38,7 +38,8 @@
 // pdp_exact_nearest_split (behind pdp_exact_min_unsat_split) cuts it into cubes that share the 64-bit ub[b]; a start model seeds it.
 // pdp_exact_count_round / pdp_exact_count_expand (near the end) run the count as a sequence of launches over a frontier of path
 // cubes, two bits per decision level, that is checkpointed at a budget stop and cut again between two launches; its cubes share nothing.
-// pdp_exact_solve_round (the very last kernels) runs the hinted deciding search over the same frontier, with the same check and expansion.
+// pdp_exact_solve_round (behind them) runs the hinted deciding search over the same frontier, with the same check and expansion.
+// pdp_exact_nearest_round (the very last kernels) does the same for the nearest-model search and hands every cube its instance's cost.
 #include "pdp_common.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -5209,6 +5210,317 @@ int exv_round(pdp_problem *p, const float *hint, const int64_t *cube_off, int64_
     return PDP_OK;
 }
 
+// ---- pdp_exact_nearest_round: the nearest-model search as a sequence of rounds that share their bound between two launches ---------------
+// (specification: include/pdp_hip.h; plain Python: tests/exact_nearest_rounds_model.py).  The frontier, its check kernel
+// and the expansion are the count's, called as they are.  ex_search_near_path is ex_search_path's structure with ex_search_near's
+// accounting: dist is the sum over the trail of exd_cost, restored through ExdCredit / exd_backtrack, the penalty and the hint code stay
+// in pend bits 10-31 and 8-9, and ub -- cost[b] when the round began -- appears in the prune only, so a path is replayed in the same
+// tree under any bound.  A round is four launches on one stream: the frontier check, the penalty range (one workgroup, no atomics;
+// both verdicts are read in the one synchronisation), the cubes (one counter hands out cube ids, one wave per cube; every cube leaves
+// its record, its checkpoint and, at every leaf it accepts, its assignment as a row of bytes), the finish (one wave per instance that
+// has a cube: the minimum of the cubes' costs, the lowest cube that holds it, its model, the sums, and -2 for the stopped cubes of an
+// instance that reached cost 0).  The state, the slab (ex_lds_layout), the routing and the HBM arrays are k_exact's.  No cube reads a
+// word of another.
+constexpr int EXW_BAD_PEN = 6;                  // word of the check's info block that the penalty kernel owns (EXQ_TOTAL is the last of the count's)
+static_assert(EXW_BAD_PEN > EXQ_TOTAL && EXW_BAD_PEN < EXQ_INFO, "the penalty verdict needs a word of its own");
+
+__device__ __forceinline__ int64_t exw_min64(int64_t x)
+{
+    for (int o = 32; o > 0; o >>= 1) { const int64_t y = (int64_t)__shfl_xor((long long)x, o); x = y < x ? y : x; }
+    return x;
+}
+
+// info[EXW_BAD_PEN] = the lowest instance that has a cube and a penalty outside [0, 2^20] (EXS_NONE: none), by one workgroup: a wave
+// per instance in turn, a lane per variable, the waves' minima through LDS.  It reads cube_off [B+1] and penalty [V] only, which are
+// the caller's whatever the frontier check finds.
+__global__ void __launch_bounds__(EXQ_NT) k_exact_nearest_round_check(PView pv, const int64_t *cube_off, const int32_t *penalty, int64_t *info)
+{
+    __shared__ int low[EXQ_NT / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    int mine = EXS_NONE;
+    for (int b = wave; b < pv.B; b += EXQ_NT / 64) {
+        if (cube_off[b + 1] <= cube_off[b]) continue;               // wave-uniform
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        int bad = 0;
+        for (int v = lane; v < n; v += 64) { const int32_t q = penalty[v0 + v]; bad |= q < 0 || q > EXD_MAX_PENALTY; }
+        if (__ballot(bad) != 0ull && mine == EXS_NONE) mine = b;
+    }
+    if (lane == 0) low[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int first = EXS_NONE;
+        for (int w = 0; w < EXQ_NT / 64; ++w) first = low[w] < first ? low[w] : first;
+        info[EXW_BAD_PEN] = first;
+    }
+}
+
+// The nearest-model search of one path cube by the calling wave, under the bound `ub` (EXD_INF: none).  Returns 1 (the cube has ended:
+// nothing below the bound it ran under is left in it) or -1 (budget spent: levels 1 .. *level_out are open, *plen_out of them still as
+// the path has them).  *cost_out = the cost of the last leaf it accepted (EXDS_NO_COST: none), whose assignment `row` holds.  The budget
+// is ex_search_count_path's.  A path decision on its other polarity adds its penalty at once; a state that reaches ub that way is pruned
+// before any pass and before the budget is tested (`prune` carried into the next turn of the loop).
+template <bool HBM, typename LitT, typename PtrT>
+__device__ int ex_search_near_path(const ExInst<LitT, PtrT> &X, int64_t budget, const ExPath &Q, int64_t ub, uint8_t *row, int *level_out,
+                                   int *plen_out, int64_t *work_out, int64_t *replay_out, int64_t *cost_out, int *improved_out)
+{
+    const int lane = (int)threadIdx.x;
+    constexpr int INF = 0x7fffffff;
+    int level = 0, tlen = 0, plen = Q.len, improved = 0;
+    int64_t work = 0, base = -1, dist = 0, accepted = EXDS_NO_COST;
+    int result = -1;
+    bool fresh = true, prune = false;
+    ExNoCredit none;
+    for (;;) {
+        int wmin = INF;
+        if (!prune) {
+            if (fresh) {
+                if (base < 0 && level >= plen) base = work;
+                if (base >= 0 && work - base >= budget) break;
+                fresh = false;
+            }
+            const ExPass P = ex_propagate(X);
+            work += ex_sum(P.reads);
+            prune = __ballot(P.conflict) != 0ull;
+            const bool any_unit = __ballot(P.unit) != 0ull;
+            if (any_unit) {
+                ex_sync<HBM>();
+                const int from = tlen;
+                const bool both = ex_assign_pending<HBM, true>(X, tlen);
+                prune = prune || both;
+                dist += ex_sum64(exd_span(X, from, tlen));          // the units assigned against the hint
+            }
+            prune = prune || dist >= ub;
+            if (!prune) {
+                if (any_unit) continue;
+                wmin = ex_min(P.wmin);
+                if (wmin == INF) {
+                    // a leaf below ub, inside the path too: the cube's new incumbent; an unassigned variable takes the hint's value
+                    ub = dist; accepted = dist;
+                    ++improved;
+                    for (int v = lane; v < X.n; v += EX_NT) {
+                        const uint32_t x = X.val[v];
+                        row[v] = (x ? x : ((X.pend[v] >> EX_HINT_SHIFT) & 3u)) == 1u ? 1 : 0;
+                    }
+                    if (ub == 0) { result = 1; break; }
+                    prune = true;
+                }
+            }
+        }
+        if (prune) {
+            prune = false;
+            if (!exd_backtrack<HBM>(X, level, tlen, dist, ub)) { result = 1; break; }
+            plen = level < plen ? level : plen;                     // `level` was flipped: the path beyond it no longer applies
+            fresh = true;
+            continue;
+        }
+        const unsigned long long best = ex_branch<HBM, EX_PHASE_INCUMBENT>(X, wmin, work);
+        if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
+        exq_decide<HBM>(X, Q, plen, best, level, tlen, none);
+        if (level <= plen && exq_bit(Q.bits, level) != 0u) {
+            // against the hint: its penalty counts at once
+            const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
+            dist += (int64_t)(X.pend[v] >> EXD_PEN_SHIFT);
+            prune = dist >= ub;
+        }
+        fresh = true;
+    }
+    *level_out = result == -1 ? level : 0; *plen_out = plen;
+    *work_out = work; *replay_out = base < 0 ? work : base; *cost_out = accepted; *improved_out = improved;
+    return result;
+}
+
+struct ExwParams {
+    int B;
+    uint32_t total;             // cubes of the round
+    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
+    int64_t budget;             // per cube, past its replay
+    const float *hint;          // [V] the point the distance is measured from (NULL: all false)
+    const int32_t *penalty;     // [V] (NULL: all 1)
+    const uint8_t *route;       // [B] 1: the HBM route
+    const int64_t *cube_off;    // [B+1] first cube id of every instance
+    const int32_t *len;         // [total]
+    const uint32_t *bits, *closed;      // [total][words]
+    int words;
+    int8_t *cube_status;        // [total] 1 / -1; the finish kernel turns the -1 of an instance at cost 0 into -2
+    int32_t *len_out; uint32_t *bits_out, *closed_out;      // the checkpoints, shaped as the inputs
+    int64_t *cube_cost, *cube_work, *cube_replay; int32_t *cube_improvements;       // [total]
+    uint8_t *rows;              // [total][n_max] the assignment of the last leaf every cube accepted
+    int n_max;
+    int8_t *status; int64_t *cost; float *model; int64_t *work; int32_t *improvements; int32_t *first;     // per instance
+    ExHbm h;
+};
+
+// cube q of instance I.b under the bound ub: copy the instance (ex_fill), clear the state (pend starts as the hint's codes and the
+// penalties), search along the path; then the cube's record and its checkpoint by ex_solve_count_path's ballots.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ void ex_solve_near_path(const ExwParams &xp, const Inst &I, ExInst<LitT, PtrT> X, uint32_t q, int64_t ub)
+{
+    const int lane = (int)threadIdx.x;
+    ex_fill<HBM>(I, X);
+    for (int v = lane; v < I.n; v += EX_NT) {
+        const uint32_t code = (xp.hint && xp.hint[I.v0 + v] > 0.5f) ? 1u : 2u;          // NaN compares false
+        const uint32_t w = xp.penalty ? (uint32_t)xp.penalty[I.v0 + v] : 1u;
+        X.val[v] = 0; X.pend[v] = (w << EXD_PEN_SHIFT) | (code << EX_HINT_SHIFT); X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
+    }
+    ex_sync<HBM>();
+    const size_t row = (size_t)q * (size_t)xp.words;
+    const ExPath Q{xp.bits + row, xp.closed + row, xp.len[q]};
+    int64_t work = 0, replay = 0, cost = EXDS_NO_COST;
+    int level = 0, plen = 0, improved = 0;
+    const int st = ex_search_near_path<HBM>(X, xp.budget, Q, ub, xp.rows + (size_t)q * (size_t)xp.n_max, &level, &plen, &work, &replay, &cost,
+                                            &improved);
+    for (int w = 0; w < xp.words; w += 2) {
+        const int L = 32 * w + lane + 1;
+        const uint32_t mark = L <= level ? X.dvar[L] >> 31 : 0u;
+        const bool path = L <= plen && L <= level;
+        const uint32_t pb = path ? exq_bit(Q.bits, L) : 0u, pc = path ? exq_bit(Q.closed, L) : 0u;
+        const unsigned long long bb = __ballot((pb | (mark & (pc ^ 1u))) != 0u), cc = __ballot(mark != 0u);
+        if (lane == 0) {
+            xp.bits_out[row + w] = (uint32_t)bb; xp.closed_out[row + w] = (uint32_t)cc;
+            if (w + 1 < xp.words) { xp.bits_out[row + w + 1] = (uint32_t)(bb >> 32); xp.closed_out[row + w + 1] = (uint32_t)(cc >> 32); }
+        }
+    }
+    if (lane == 0) {
+        xp.cube_status[q] = (int8_t)st;
+        xp.len_out[q] = level;
+        xp.cube_cost[q] = cost;
+        xp.cube_work[q] = work;
+        xp.cube_replay[q] = replay;
+        xp.cube_improvements[q] = improved;
+    }
+    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+}
+
+__global__ void __launch_bounds__(EX_NT) k_exact_nearest_round(PView pv, ExwParams xp)
+{
+    extern __shared__ __align__(16) unsigned char ex_slab[];
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= xp.total) break;
+        const int lo = exs_instance(xp.cube_off, xp.B, q);
+        const int64_t seen = xp.cost[lo];                           // the instance's cost when the round began: the finish kernel writes it
+        const int64_t ub = seen < 0 ? EXD_INF : seen;
+        const Inst I = load_inst(pv, lo);
+        // the checks have passed: every cube's instance has at most 1023 variables and penalties in range.  Both arms end in the barrier
+        // of ex_solve_near_path and fall through to the end of the loop body (see k_exact_count)
+        if (xp.route[lo]) ex_solve_near_path<true>(xp, I, ex_bind_hbm(xp.h, I), q, ub);
+        else ex_solve_near_path<false>(xp, I, ex_bind_lds(ex_slab, I), q, ub);
+    }
+}
+
+// The outcome of every instance that has a cube, one wave per instance: best = the minimum of the cubes' costs, first = the lowest cube,
+// counted from the instance's own first one, that holds it.  Where best is below cost[b] (or there was none) the instance takes it with
+// that cube's row as its model (one lane per variable); else first = -1 and cost and model stay.  Status 1 at cost 0, the instance's
+// stopped cubes rewritten to -2; else 1 / 0 (a model was met / none) when no cube stopped, else -1.  work and improvements take the
+// cubes' sums as integer wave sums.
+__global__ void __launch_bounds__(EX_NT) k_exact_nearest_round_finish(PView pv, ExwParams xp)
+{
+    const int lane = (int)threadIdx.x;
+    for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
+        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        if (nc == 0) continue;                                      // wave-uniform
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        int64_t w = 0, best = EXD_INF;
+        int imp = 0, open = 0;
+        for (int64_t j = lane; j < nc; j += EX_NT) {
+            const int64_t c = xp.cube_cost[c0 + j];
+            w += xp.cube_work[c0 + j];
+            imp += xp.cube_improvements[c0 + j];
+            open |= xp.cube_status[c0 + j] == -1;
+            if (c >= 0 && c < best) best = c;
+        }
+        w = exs_sum64(w);
+        imp = ex_sum(imp);
+        best = exw_min64(best);
+        int64_t cost = xp.cost[b];
+        const bool better = best != EXD_INF && (cost < 0 || best < cost);
+        int at = EXS_NONE;
+        if (better) {
+            for (int64_t j = lane; j < nc && at == EXS_NONE; j += EX_NT)
+                if (xp.cube_cost[c0 + j] == best) at = (int)j;
+            at = ex_min(at);
+            const uint8_t *row = xp.rows + (size_t)(c0 + at) * (size_t)xp.n_max;
+            for (int v = lane; v < n; v += EX_NT) xp.model[v0 + v] = row[v] ? 1.0f : 0.0f;
+            cost = best;
+        }
+        const bool stopped = __ballot(open) != 0ull;
+        if (cost == 0) {
+            for (int64_t j = lane; j < nc; j += EX_NT)
+                if (xp.cube_status[c0 + j] == -1) xp.cube_status[c0 + j] = -2;
+        }
+        if (lane == 0) {
+            xp.status[b] = (int8_t)(cost == 0 ? 1 : (stopped ? -1 : (cost >= 0 ? 1 : 0)));
+            xp.cost[b] = cost;
+            xp.first[b] = better ? at : -1;
+            xp.work[b] += w;
+            xp.improvements[b] += imp;
+        }
+    }
+}
+
+int exw_round(pdp_problem *p, const float *hint, const int32_t *penalty, const int64_t *cube_off, int64_t cubes, const int32_t *len,
+              const uint32_t *bits, const uint32_t *closed, int64_t budget, int8_t *status, int64_t *cost, float *model, int64_t *work,
+              int32_t *improvements, int32_t *first, int8_t *cube_status, int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out,
+              int64_t *cube_cost, int64_t *cube_work, int64_t *cube_replay, int32_t *cube_improvements, void *stream)
+{
+    const char *name = "pdp_exact_nearest_round";
+    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
+    if (cubes < 0 || cubes > EXS_MAX_CUBES) {
+        pdp_set_error("%s: %lld cubes; a frontier holds 0 .. 2^22", name, (long long)cubes);
+        return PDP_ERR_INVALID;
+    }
+    if (cubes * (int64_t)p->exq_nmax > EXV_MAX_ROW_BYTES) {
+        pdp_set_error("%s: the per-cube model rows (%lld cubes x %d variables) pass 2^31 bytes; split the batch", name, (long long)cubes,
+                      p->exq_nmax);
+        return PDP_ERR_INVALID;
+    }
+    const hipStream_t st = ST(stream);
+    int64_t info[EXQ_INFO];
+    exq_check_launch(p, cube_off, cubes, len, bits, closed, st);
+    PDP_LAUNCH_CHECK();
+    if (penalty) {
+        hipLaunchKernelGGL(k_exact_nearest_round_check, dim3(1), dim3(EXQ_NT), 0, st, make_view(p), cube_off, penalty, exq_info(p));
+        PDP_LAUNCH_CHECK();
+    }
+    PDP_HIP_CHECK(hipMemcpyAsync(info, exq_info(p), EXQ_INFO * 8, hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));
+    { const int st_ = exq_verdict(name, info); if (st_ != PDP_OK) return st_; }
+    if (penalty && info[EXW_BAD_PEN] != EXS_NONE) {
+        pdp_set_error("%s: instance %lld has a cube and a penalty outside 0 .. 2^20", name, (long long)info[EXW_BAD_PEN]);
+        return PDP_ERR_INVALID;
+    }
+    if (cubes == 0) return PDP_OK;
+    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax, B = p->B;
+    // per-cube records: cost [total] | work [total] | replay [total] | improvements [total] (padded to 8 bytes) | model rows [total][n_max]
+    const size_t imp_bytes = (total * 4 + 7) & ~(size_t)7;
+    { const int st_ = exs_records(p->exq, total * 24 + imp_bytes + total * nmax); if (st_ != PDP_OK) return st_; }
+    ExwParams xp;
+    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
+    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_NEAREST_ROUND_BUDGET;
+    xp.hint = hint; xp.penalty = penalty;
+    xp.route = exq_route(p); xp.cube_off = cube_off; xp.len = len; xp.bits = bits; xp.closed = closed; xp.words = exq_words(p);
+    xp.cube_status = cube_status; xp.len_out = len_out; xp.bits_out = bits_out; xp.closed_out = closed_out;
+    xp.cube_cost = (int64_t *)p->exq.cubes;
+    xp.cube_work = (int64_t *)(p->exq.cubes + total * 8);
+    xp.cube_replay = (int64_t *)(p->exq.cubes + total * 16);
+    xp.cube_improvements = (int32_t *)(p->exq.cubes + total * 24);
+    xp.rows = (uint8_t *)(p->exq.cubes + total * 24 + imp_bytes);
+    xp.n_max = (int)nmax;
+    xp.status = status; xp.cost = cost; xp.model = model; xp.work = work; xp.improvements = improvements; xp.first = first;
+    xp.h = ex_hbm(p);
+    { const int st_ = ex_launch_persistent(p, k_exact_nearest_round, xp, (int64_t)total, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(k_exact_nearest_round_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    if (cube_cost) PDP_HIP_CHECK(hipMemcpyAsync(cube_cost, xp.cube_cost, total * 8, hipMemcpyDeviceToDevice, st));
+    if (cube_work) PDP_HIP_CHECK(hipMemcpyAsync(cube_work, xp.cube_work, total * 8, hipMemcpyDeviceToDevice, st));
+    if (cube_replay) PDP_HIP_CHECK(hipMemcpyAsync(cube_replay, xp.cube_replay, total * 8, hipMemcpyDeviceToDevice, st));
+    if (cube_improvements) PDP_HIP_CHECK(hipMemcpyAsync(cube_improvements, xp.cube_improvements, total * 4, hipMemcpyDeviceToDevice, st));
+    return PDP_OK;
+}
+
 } // namespace
 
 extern "C" int pdp_exact_solve(pdp_problem *p, int64_t budget, int8_t *status, float *model, int64_t *work, void *stream)
@@ -5471,6 +5783,23 @@ extern "C" int pdp_exact_solve_round(pdp_problem *p, const float *hint, const in
     }
     return exv_round(p, hint, cube_off, cubes, len, bits, closed, budget, status, model, work, first, cube_status, len_out, bits_out, closed_out,
                      cube_work, cube_replay, stream);
+}
+
+extern "C" int pdp_exact_nearest_round(pdp_problem *p, const float *hint, const int32_t *penalty, const int64_t *cube_off, int64_t cubes,
+                                       const int32_t *len, const uint32_t *bits, const uint32_t *closed, int64_t budget, int8_t *status,
+                                       int64_t *cost, float *model, int64_t *work, int32_t *improvements, int32_t *first, int8_t *cube_status,
+                                       int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out, int64_t *cube_cost, int64_t *cube_work,
+                                       int64_t *cube_replay, int32_t *cube_improvements, void *stream)
+{
+    PDP_REQUIRE(p && cube_off && status && cost && model && work && improvements && first, "NULL argument");
+    PDP_REQUIRE(cubes <= 0 || (len && bits && closed && cube_status && len_out && bits_out && closed_out), "NULL argument");
+    PDP_REQUIRE(cubes <= 0 || (bits_out != bits && closed_out != closed && len_out != len), "pdp_exact_nearest_round: the checkpoints must not alias the frontier");
+    if (p->R != 1) {
+        pdp_set_error("pdp_exact_nearest_round: a replicated problem (R = %d) is not supported; solve the unreplicated batch", p->R);
+        return PDP_ERR_UNSUPPORTED;
+    }
+    return exw_round(p, hint, penalty, cube_off, cubes, len, bits, closed, budget, status, cost, model, work, improvements, first, cube_status,
+                     len_out, bits_out, closed_out, cube_cost, cube_work, cube_replay, cube_improvements, stream);
 }
 
 extern "C" int pdp_exact_min_unsat_split(pdp_problem *p, const float *hint, const int8_t *depth, int64_t budget, int8_t *status, int32_t *cost,

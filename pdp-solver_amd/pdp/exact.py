@@ -78,6 +78,12 @@ AUTO_MASS_STAGE1_BUDGET = 1 << 26
 # (tools/exact_time.py nssweep: the fastest of 2^18 / 2^22 / 2^26 on row nd; on row na, whose instances finish near 2^22 reads, it makes
 # 'auto' 2.0 times the plain call where 2^26 is free: DESIGN.md §9.16 weighs the two)
 AUTO_NEAREST_STAGE1_BUDGET = 1 << 22
+# nearest_model_rounds: the reads per cube and round (the library's PDP_EXACT_NEAREST_ROUND_BUDGET), the most levels a stopped
+# cube gives away in one expansion, and k_exact_nearest_round's occupancy by registers (resources and measured;
+# tools/exact_time.py nrsweep sweeps the first two)
+NEAREST_ROUND_BUDGET = 1 << 18
+NEAREST_ROUNDS_MAX_GIVE = 8
+NEAREST_ROUNDS_WAVES_PER_SIMD = 4
 
 
 def raw_item(n, clauses, label=-1.0, name=""):
@@ -646,6 +652,69 @@ def nearest_split(prob, part, budget, hint, pen, start, split, device):
     return st, co, model, wk, du, sc
 
 
+def nearest_rounds_give(open_cubes, device):
+    """split='rounds' of the nearest-model search: rounds_give's rule with k_exact_nearest_round's occupancy -- the smallest g with
+    open_cubes * (1 + g) >= AUTO_CUBES_PER_WAVE cubes per resident wave, 0 once the frontier fills the GPU -- capped by
+    NEAREST_ROUNDS_MAX_GIVE and by the 2^22 cubes of a frontier"""
+    waves = torch.cuda.get_device_properties(device).multi_processor_count * 4 * NEAREST_ROUNDS_WAVES_PER_SIMD
+    target = AUTO_CUBES_PER_WAVE * waves
+    open_cubes = max(1, int(open_cubes))
+    give = -(-target // open_cubes) - 1
+    return max(0, min(give, NEAREST_ROUNDS_MAX_GIVE, native.COUNT_ROUNDS_MAX_CUBES // open_cubes - 1))
+
+
+def nearest_rounds_drop_spent(state, total):
+    """The total budget of nearest_rounds, between two rounds: the cubes of every instance whose work has reached ``total`` (an int, or an
+    int64 tensor of one value per instance on the state's device) leave the frontier of the NearestState; the instance's status stays -1
+    and it keeps its cost and model.  Returns the number of instances that left."""
+    per = state.cube_off[1:] - state.cube_off[:-1]
+    spent = (state.work >= total) & (per > 0)
+    left = int(spent.sum().item())
+    if left:
+        keep = ~torch.repeat_interleave(spent, per)
+        state.len, state.bits, state.closed = state.len[keep].contiguous(), state.bits[keep].contiguous(), state.closed[keep].contiguous()
+        state.cube_off = torch.cat([state.cube_off[:1], torch.cumsum(torch.where(spent, torch.zeros_like(per), per), 0)])
+    return left
+
+
+def nearest_rounds(prob, part, budget, hint, pen, start, round_budget, give, rounds, device):
+    """The nearest-model search of one problem in rounds (Problem.exact_nearest_round; ``part``: its loader items, or a callable that
+    returns them, read only where an instance has more than 1023 variables; ``hint``, ``pen``, ``start``: tensors of V values, the last
+    two or None): numpy (status, cost, model, work, rounds_used int32).  Every round runs every open cube for ``round_budget`` reads past
+    its replay (None or 0: NEAREST_ROUND_BUDGET) under its instance's best cost so far and cuts the frontier it leaves again, ``give``
+    levels per stopped cube (None: nearest_rounds_give of the open cubes, every round).  ``budget`` is the total of reads per instance
+    over all rounds and cubes (0: the library's default budget): an instance whose work has reached it leaves the frontier with status
+    -1 and keeps its cost and model.  ``rounds``: at most so many rounds (None: until no cube is open); instances that are still open
+    then end with status -1 as well.  ``start`` is checked on the GPU and seeds the cost where it is a model.  An instance of more than
+    1023 variables has no cube: it goes to the plain call, with ``budget``, and uses 0 rounds.  An instance with a penalty outside
+    [0, 2^20] has status -3, cost 0 and a model of zeros, as in the plain call."""
+    total = budget if budget > 0 else DEFAULT_BUDGET
+    state = prob.exact_nearest_begin(hint, pen, start)
+    done = 0
+    while state.cubes and (rounds is None or done < rounds):
+        prob.exact_nearest_round(state, round_budget or NEAREST_ROUND_BUDGET, nearest_rounds_give(state.cubes, device) if give is None else give)
+        done += 1
+        nearest_rounds_drop_spent(state, total)
+    st, co, model = state.status.cpu().numpy(), state.cost.cpu().numpy(), state.model.cpu().numpy()
+    wk, used = state.work.cpu().numpy(), state.rounds.cpu().numpy()
+    co[st == -3] = 0
+    wide = [int(j) for j in np.nonzero(st == -2)[0]]
+    if wide:
+        part = part() if callable(part) else part
+        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+        sub = _problem([part[j] for j in wide], device)
+        cut = lambda t: None if t is None else torch.cat([t[int(voff[j]):int(voff[j + 1])] for j in wide])
+        r = [t.cpu().numpy() for t in sub.exact_nearest(cut(hint), cut(pen), budget)]
+        del sub
+        off = 0
+        for k, j in enumerate(wide):
+            n = int(voff[j + 1] - voff[j])
+            st[j], co[j], wk[j] = r[0][k], r[1][k], r[3][k]
+            model[voff[j]:voff[j + 1]] = r[2][off:off + n]
+            off += n
+    return st, co, model, wk, used
+
+
 def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges=MAX_EDGES, split=None, start=None, depths=False):
     """The model of every loader item (as solve_items takes them) nearest to its hint, by branch and bound (pdp_exact_nearest; DESIGN.md
     §9.15).  Returns numpy (status int8 [N]: 1 cost is the minimum over the models, 0 the instance has no model, -1 the budget ran out and
@@ -659,8 +728,28 @@ def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges
     which minimiser the model is and work depend on the timing of the cubes.  ``start``: per instance a model the caller already has
     (an array of n_i values, thresholded like a hint) or None, or None for all; the search of that instance starts below its distance,
     computed and checked on the GPU, and an array that is not a model is ignored.  Giving one turns on the split call (at depth 0 without
-    ``split``).  ``depths``: also return depth_used int8 [N].  Without ``split`` and ``start`` the call is pdp_exact_nearest's."""
-    split = _check_split(split)
+    ``split``).  ``depths``: also return depth_used int8 [N].  Without ``split`` and ``start`` the call is pdp_exact_nearest's.  The
+    search in rounds is a call of its own, nearest_model_rounds: ``split='rounds'`` is refused here as it always was."""
+    return _nearest_model(items, hints, penalties, budget, device, max_edges, _check_split(split), start, depths, None, None)
+
+
+def nearest_model_rounds(items, hints, penalties=None, budget=0, device=None, max_edges=MAX_EDGES, start=None, round_budget=None, rounds=None,
+                         depths=False):
+    """nearest_model in rounds (nearest_rounds, pdp_exact_nearest_round): the same arguments and the same four outputs.
+    Every round runs every open cube for ``round_budget`` reads past its replay (None: NEAREST_ROUND_BUDGET), at most ``rounds`` of them
+    (None: until no cube is open); between two rounds the open part of every tree is cut again and the best cost of an instance is handed
+    to all its cubes.  ``budget`` is the total of reads per instance over all rounds and cubes; a proved cost is nearest_model's minimum,
+    every output is a function of the inputs, and which minimiser the model is depends on ``round_budget``.  ``start`` seeds the cost
+    where it is a model.  ``depths``: also return the rounds every instance had a cube in (int32 [N])."""
+    for name, x in (('round_budget', round_budget), ('rounds', rounds)):
+        if x is not None and (isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 1):
+            raise ValueError("%s must be None or a positive integer, got %r" % (name, x))
+    return _nearest_model(items, hints, penalties, budget, device, max_edges, 'rounds', start, depths, round_budget, rounds)
+
+
+def _nearest_model(items, hints, penalties, budget, device, max_edges, split, start, depths, round_budget, rounds):
+    "nearest_model and nearest_model_rounds (``split`` 'rounds'), segment by segment"
+    by_rounds = isinstance(split, str) and split == 'rounds'
     native.require_gpu()
     for name, per in (('hints', hints), ('penalties', penalties), ('start', start)):
         if per is None:
@@ -679,7 +768,7 @@ def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges
     status = np.ones(N, dtype=np.int8)
     cost = np.zeros(N, dtype=np.int64)
     work = np.zeros(N, dtype=np.int64)
-    used = np.zeros(N, dtype=np.int8)
+    used = np.zeros(N, dtype=np.int32 if by_rounds else np.int8)
     models = [None] * N
     for seg in _segments(items, max_edges):
         part = [items[i] for i in seg]
@@ -712,7 +801,10 @@ def nearest_model(items, hints, penalties=None, budget=0, device=None, max_edges
                 # a value that does not fit int32 is out of range either way: -1 stands for it
                 allp = np.concatenate(pens)
                 pen = torch.from_numpy(np.where((allp < 0) | (allp > MAX_PENALTY), -1, allp).astype(np.int32)).to(device)
-            if split is None and start is None:
+            if by_rounds:
+                first = None if begin is None else torch.from_numpy(np.concatenate(begin)).to(device)
+                st, co, model, wk, du = nearest_rounds(prob, part, budget, hint, pen, first, round_budget, None, rounds, device)
+            elif split is None and start is None:
                 st, co, model, wk = [t.cpu().numpy() for t in prob.exact_nearest(hint, pen, budget)]
                 du = np.zeros(len(part), dtype=np.int8)
             else:

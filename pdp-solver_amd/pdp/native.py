@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     'pdp_exact_mass_split', 'pdp_exact_mass_split_cubes', 'pdp_exact_nearest',
     'pdp_exact_nearest_split', 'pdp_exact_nearest_split_cubes',
     'pdp_exact_count_frontier_words', 'pdp_exact_count_round', 'pdp_exact_count_expand', 'pdp_exact_solve_round',
+    'pdp_exact_nearest_round',
 ]
 
 
@@ -241,6 +242,7 @@ class Decimator(object):
 
 COUNT_ROUNDS_MAX_N = 1023           # pdp_exact_count_round searches instances of up to this many variables, as pdp_exact_count
 COUNT_ROUNDS_MAX_CUBES = 1 << 22    # cubes of one frontier
+EXACT_NEAREST_MAX_PENALTY = 1 << 20 # pdp_exact_nearest and pdp_exact_nearest_round: a penalty is an integer in [0, 2^20]
 
 
 class CountState(object):
@@ -313,6 +315,50 @@ class SolveState(object):
         cubes = int(self.len.numel())
         sizes = {'cube_off': (problem.B + 1,), 'len': (cubes,), 'hint': (problem.V,), 'status': (problem.B,), 'model': (problem.V,),
                  'work': (problem.B,), 'rounds': (problem.B,)}
+        words = C.c_int32()
+        check(lib().pdp_exact_count_frontier_words(problem._h, C.byref(words)))
+        sizes['bits'] = sizes['closed'] = (cubes, words.value)
+        for f in self.FIELDS:
+            t = getattr(self, f)
+            if not torch.is_tensor(t) or t.device != problem.device or t.dtype != kinds[f] or tuple(t.shape) != sizes[f] or not t.is_contiguous():
+                raise NativeError("state.%s must be a contiguous %s tensor of shape %s on %s" % (f, kinds[f], sizes[f], problem.device))
+        if cubes > COUNT_ROUNDS_MAX_CUBES:
+            raise NativeError("state holds %d cubes; a frontier holds at most 2^22" % cubes)
+
+
+class NearestState(object):
+    """A resumable nearest-model search (Problem.exact_nearest_begin / exact_nearest_round): plain tensors, so it can be saved, moved with
+    cpu() / to() and continued on another Problem built from the same items.  The frontier is CountState's: cube_off int64 [B+1], len
+    int32 [cubes], bits and closed int32 [cubes, words].  hint float32 [V]: the point the distance is measured from (> 0.5 true, every
+    other value false); penalty int32 [V]: what a variable costs where it differs.  status int8 [B]: -1 cubes are open, 1 cost is the
+    minimum (or 0 was reached), 0 the instance has no model, -2 not searched (more than 1023 variables), -3 a penalty outside [0, 2^20];
+    cost int64 [B]: the distance of model, an upper bound while the status is -1, -1: no model yet; model float32 [V]; work int64 [B]:
+    the reads of all its cubes and rounds; improvements int32 [B]: the leaves its cubes accepted; rounds int32 [B]: the rounds the
+    instance had a cube in."""
+    FIELDS = ('cube_off', 'len', 'bits', 'closed', 'hint', 'penalty', 'status', 'cost', 'model', 'work', 'improvements', 'rounds')
+
+    @property
+    def cubes(self):
+        return int(self.len.numel())
+
+    def to(self, device):
+        "a copy on ``device``"
+        s = NearestState()
+        for f in self.FIELDS:
+            setattr(s, f, getattr(self, f).to(device).clone())
+        return s
+
+    def cpu(self):
+        return self.to('cpu')
+
+    def validate(self, problem):
+        "what the library cannot see from raw pointers: devices, dtypes and shapes (the frontier's contents are checked on the GPU)"
+        kinds = {'cube_off': torch.int64, 'len': torch.int32, 'bits': torch.int32, 'closed': torch.int32, 'hint': torch.float32,
+                 'penalty': torch.int32, 'status': torch.int8, 'cost': torch.int64, 'model': torch.float32, 'work': torch.int64,
+                 'improvements': torch.int32, 'rounds': torch.int32}
+        cubes = int(self.len.numel())
+        sizes = {'cube_off': (problem.B + 1,), 'len': (cubes,), 'hint': (problem.V,), 'penalty': (problem.V,), 'status': (problem.B,),
+                 'cost': (problem.B,), 'model': (problem.V,), 'work': (problem.B,), 'improvements': (problem.B,), 'rounds': (problem.B,)}
         words = C.c_int32()
         check(lib().pdp_exact_count_frontier_words(problem._h, C.byref(words)))
         sizes['bits'] = sizes['closed'] = (cubes, words.value)
@@ -961,6 +1007,104 @@ class Problem(object):
             return made
         return made, (ran, cube_status, rec[0], rec[1], len_out, bits_out, closed_out, first)
 
+    def exact_nearest_begin(self, hints=None, penalties=None, start=None):
+        """The state of a resumable nearest-model search (pdp_exact_nearest_round): the root frontier -- one cube of length 0 per instance
+        of at most 1023 variables whose penalties all lie in [0, 2^20] -- status -1 (open), -2 where the instance is not searched or -3
+        where a penalty is out of range, cost -1, zeroed models, work and improvements.  ``hints`` (float32, V elements, on the problem's
+        device; None: all false) and ``penalties`` (int32, V elements; None: all 1) are kept on the state and used by every round.
+        ``start`` (float32, V elements; None: none): a model of every instance the caller already has, thresholded like the hints.  It is
+        checked, not trusted: its unsatisfied clauses are counted by cnf_eval on this handle and its distance is summed in int64, and
+        only where it is a model of an instance that has a cube does it seed cost and model.  See NearestState."""
+        for name, t, dtype in (('hints', hints, torch.float32), ('penalties', penalties, torch.int32), ('start', start, torch.float32)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != dtype or t.numel() != self.V or t.device != self.device:
+                raise ValueError("%s must be a %s tensor of %d elements (one per variable) on %s, got %s"
+                                 % (name, dtype, self.V, self.device,
+                                    '%s of %d on %s' % (t.dtype, t.numel(), t.device) if torch.is_tensor(t) else type(t).__name__))
+        dev = self.device
+        c = self.exact_count_begin()
+        s = NearestState()
+        s.hint = torch.zeros(self.V, dtype=torch.float32, device=dev) if hints is None else hints.reshape(-1).contiguous().clone()
+        s.penalty = torch.ones(self.V, dtype=torch.int32, device=dev) if penalties is None else penalties.reshape(-1).contiguous().clone()
+        owner = self.export_graph()[1].to(torch.int64).reshape(-1)                # the instance of every variable
+        out_of_range = ((s.penalty < 0) | (s.penalty > EXACT_NEAREST_MAX_PENALTY)).to(torch.int64)
+        bad = torch.zeros(self.B, dtype=torch.int64, device=dev).index_add_(0, owner, out_of_range) > 0
+        s.status = torch.where(bad, torch.full_like(c.status, -3), c.status)
+        has = s.status == -1
+        s.cube_off = torch.zeros(self.B + 1, dtype=torch.int64, device=dev)
+        s.cube_off[1:] = torch.cumsum(has.to(torch.int64), 0)
+        cubes = int(s.cube_off[-1].item())
+        s.len, s.bits, s.closed = c.len[:cubes].clone(), c.bits[:cubes].clone(), c.closed[:cubes].clone()
+        s.cost = torch.full((self.B,), -1, dtype=torch.int64, device=dev)
+        s.model = torch.zeros(self.V, dtype=torch.float32, device=dev)
+        s.work, s.rounds = c.work, c.rounds
+        s.improvements = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        if start is not None:
+            x = (start.reshape(-1) > 0.5)
+            unsat = self.cnf_eval(x.to(torch.float32).contiguous())[1].reshape(-1)
+            differs = (x != (s.hint > 0.5)).to(torch.int64) * s.penalty.to(torch.int64)
+            far = torch.zeros(self.B, dtype=torch.int64, device=dev).index_add_(0, owner, differs)
+            seeded = has & (unsat == 0)
+            s.cost = torch.where(seeded, far, s.cost)
+            s.model = torch.where(seeded[owner], x.to(torch.float32), s.model)
+        return s
+
+    def exact_nearest_round(self, state, budget=0, give=0, stats=False):
+        """One round of a resumable nearest-model search (pdp_exact_nearest_round, then pdp_exact_count_expand): every open cube of
+        ``state`` runs for ``budget`` clause-literal reads past the replay of its path (0: the library default) under the bound
+        state.cost of its instance as it stands when the round begins; the instance takes the minimum of its cubes' costs and the model
+        of the lowest cube that holds it, so the next round hands every cube the best bound any of them found.  An instance that reaches
+        cost 0, or whose cubes have all ended, becomes status 1 (0 where no model was ever met) and leaves the frontier; the checkpoints of
+        the others are cut into up to ``give`` children and a remainder each.  Advances ``state`` in place and returns the number of
+        open cubes.  After every round cost is -1 or attained by model, and it never rises.  Once the frontier is empty, status and cost
+        are exact_nearest's; with ``give`` 0 throughout so are model and improvements, bit for bit, wherever its check pass does not
+        accept the hints (where it does: cost 0, model = the thresholded hints, one improvement).  Every output is a function of the
+        state, ``budget`` and ``give`` alone.  ``stats``: also the round's records (cube_off int64 [B+1] of the frontier that ran,
+        cube_status int8 [cubes] 1 ended / -1 stopped / -2 dropped, cube_cost int64 [cubes] (-1: none), cube_work and cube_replay int64
+        [cubes], cube_improvements int32 [cubes], the checkpoints len_out int32 [cubes], bits_out and closed_out int32 [cubes, words],
+        and first int32 [B]: the instance's lowest cube that holds its new cost, -1: the cost did not fall).  The state may come from
+        another Problem of the same items.  A malformed state, or a penalty out of range on an instance that has a cube, raises before
+        anything is searched or written.  More than 2^22 cubes after the expansion raises; lower ``give``.  Synchronises the current
+        stream twice."""
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads per cube (0: the library default), got %r" % (budget,))
+        if isinstance(give, bool) or not isinstance(give, numbers.Integral) or not 0 <= give <= COUNT_ROUNDS_MAX_N:
+            raise ValueError("give must be an integer from 0 to %d, got %r" % (COUNT_ROUNDS_MAX_N, give))
+        if not isinstance(state, NearestState):
+            raise ValueError("state must come from exact_nearest_begin, got %s" % type(state).__name__)
+        state.validate(self)
+        dev = self.device
+        cubes, words = int(state.len.numel()), int(state.bits.size(1))
+        cube_status = torch.empty(cubes, dtype=torch.int8, device=dev)
+        len_out = torch.empty(cubes, dtype=torch.int32, device=dev)
+        bits_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        closed_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        first = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
+        rec = [torch.empty(cubes, dtype=torch.int64, device=dev) if stats else None for _ in range(3)]
+        rec_imp = torch.empty(cubes, dtype=torch.int32, device=dev) if stats else None
+        check(lib().pdp_exact_nearest_round(self._h, ptr(state.hint), ptr(state.penalty), ptr(state.cube_off), C.c_int64(cubes), ptr(state.len),
+                                            ptr(state.bits), ptr(state.closed), C.c_int64(int(budget)), ptr(state.status), ptr(state.cost),
+                                            ptr(state.model), ptr(state.work), ptr(state.improvements), ptr(first), ptr(cube_status),
+                                            ptr(len_out), ptr(bits_out), ptr(closed_out), ptr(rec[0]), ptr(rec[1]), ptr(rec[2]), ptr(rec_imp),
+                                            _stream()))
+        capacity = min(cubes * (1 + int(give)), COUNT_ROUNDS_MAX_CUBES)
+        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=dev)
+        len_new = torch.empty(capacity, dtype=torch.int32, device=dev)
+        bits_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
+        closed_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
+        made = C.c_int64()
+        ran = state.cube_off
+        check(lib().pdp_exact_count_expand(self._h, ptr(ran), C.c_int64(cubes), ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out),
+                                           C.c_int32(int(give)), C.c_int64(capacity), ptr(cube_off), ptr(len_new), ptr(bits_new),
+                                           ptr(closed_new), C.byref(made), _stream()))
+        made = int(made.value)
+        state.rounds += (ran[1:] > ran[:-1]).to(torch.int32)
+        state.cube_off, state.len, state.bits, state.closed = cube_off, len_new[:made], bits_new[:made], closed_new[:made]
+        if not stats:
+            return made
+        return made, (ran, cube_status, rec[0], rec[1], rec[2], rec_imp, len_out, bits_out, closed_out, first)
+
     def exact_mass_split(self, weights, budget=0, depth=None, stats=False):
         """exact_mass with the search of instance b spread over 2^depth[b] waves (pdp_exact_mass_split): (status, mass, true_mass,
         open_mass, work) as exact_mass's.  ``budget`` applies to every cube; at status -1 the probability lies in [mass, mass + open_mass];
@@ -1199,7 +1343,7 @@ class Problem(object):
         return verdict, fail_at, work, core, keep, n_core, n_keep
 
     def exact_last_grid(self):
-        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split, exact_nearest_split, exact_mass_split, exact_count_round and exact_solve_round (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
+        """Workgroups of the last launch of exact_solve, exact_solve_split, exact_count_split, exact_min_unsat_split, exact_nearest_split, exact_mass_split, exact_count_round, exact_solve_round and exact_nearest_round (their cube kernels), exact_min_unsat, exact_nearest, exact_count, exact_mass, exact_models_at, exact_solve_proof, exact_check or exact_trim on this problem (pdp_exact_last_grid), 0 before the
         first; PDP_EXACT_GRID=<v> in the environment lowers a launch to min(grid, v).  A host read: it does not synchronise."""
         out = C.c_int32(-1)
         check(lib().pdp_exact_last_grid(self._h, C.byref(out)))

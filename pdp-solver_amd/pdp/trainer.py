@@ -193,7 +193,10 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
         with every row spread over 2^depth waves that share the best cost found (pdp_exact_nearest_split), from the complete search's model
         as its start model: "nearest", "nearest_proved" and "nearest_solution" mean the same, which nearest model comes back and
         "nearest_work" (the sum over the cubes) depend on the timing of the cubes, and a row searched at a depth above 0 gains
-        "nearest_split_depth" after "nearest_work"."""
+        "nearest_split_depth" after "nearest_work".  With config['complete_nearest_rounds'] (log2 of the reads per cube and round, or -1: the
+        default) it runs in rounds instead (exact.nearest_rounds, pdp_exact_nearest_round), again from the complete search's model: the
+        budget is the total per row over all rounds and cubes, every output is a function of the inputs, and every row gains
+        "nearest_rounds" after "nearest_work"."""
         rows, offs = self._prediction_rows(model, prediction, graph_map, batch_variable_map, batch_function_map, edge_feature, graph_feat, label,
                                            misc_data)
         sat_problem = getattr(model, '_last_problem', None)
@@ -367,16 +370,26 @@ class SatFactorGraphTrainer(FactorGraphTrainerBase):
                 # The model the complete search has just found is the start model: the cubes look below its distance only.
                 nsplit = self._config.get('complete_nearest_split')
                 nsplit = None if nsplit is None else ('auto' if int(nsplit) < 0 else int(nsplit))
-                begin = None if nsplit is None else [np.asarray(rows[i]['solution'], dtype=np.float32) for i in sat_rows]
-                st, cost, models, nwork, ndepth = exact.nearest_model([items[i] for i in sat_rows], [pred[offs[i]:offs[i + 1]] for i in sat_rows],
-                                                                      budget=budget, device=hint.device, split=nsplit, start=begin, depths=True)
+                # config['complete_nearest_rounds']: the same search in rounds of 2^N reads per cube (pdp_exact_nearest_round); -1: the default
+                nrounds = self._config.get('complete_nearest_rounds')
+                begin = None if nsplit is None and nrounds is None else [np.asarray(rows[i]['solution'], dtype=np.float32) for i in sat_rows]
+                near, nhints = [items[i] for i in sat_rows], [pred[offs[i]:offs[i + 1]] for i in sat_rows]
+                if nrounds is not None:
+                    st, cost, models, nwork, ndepth = exact.nearest_model_rounds(near, nhints, budget=budget, device=hint.device, start=begin,
+                                                                                 round_budget=None if int(nrounds) < 0 else 1 << int(nrounds),
+                                                                                 depths=True)
+                else:
+                    st, cost, models, nwork, ndepth = exact.nearest_model(near, nhints, budget=budget, device=hint.device, split=nsplit,
+                                                                          start=begin, depths=True)
                 for k, i in enumerate(sat_rows):
                     row = rows[i]
                     if cost[k] >= 0:
                         row['nearest'] = int(cost[k])
                     row['nearest_proved'] = int(st[k] == 1)
                     row['nearest_solution'], row['nearest_work'] = models[k].astype(int).tolist(), int(nwork[k])
-                    if ndepth[k] > 0:
+                    if nrounds is not None:
+                        row['nearest_rounds'] = int(ndepth[k])
+                    elif ndepth[k] > 0:
                         row['nearest_split_depth'] = int(ndepth[k])
                 if hasattr(self, '_nearest_stats'):
                     self._nearest_stats[0] += int((st == 1).sum()); self._nearest_stats[1] += len(sat_rows)

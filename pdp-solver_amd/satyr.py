@@ -49,7 +49,11 @@ satisfiable row "nearest", the fewest variables in which a model of the instance
 budget ran out and it is an upper bound), "nearest_solution" (that model) and "nearest_work"; a row PDP solved gets "nearest" 0; ``--complete-nearest-split N`` (with
 ``--complete-nearest``) spreads that branch and bound over 2^N waves per row that share the best cost found (pdp_exact_nearest_split; -1: a
 plain first stage, then the rows left unproved once more at a depth chosen from their number, starting below the cost they hold): the
-budget applies per cube, "nearest_work" is summed over the cubes, and "nearest_split_depth" appears on the rows searched at a depth above 0.
+budget applies per cube, "nearest_work" is summed over the cubes, and "nearest_split_depth" appears on the rows searched at a depth above 0;
+``--complete-nearest-rounds N`` (with ``--complete-nearest``, not with ``--complete-nearest-split``) runs that branch and bound in rounds of
+2^N reads per cube (pdp_exact_nearest_round; -1: the default), cuts the open part of every tree again between two rounds and hands every
+cube the best cost its row has met, from the complete search's model as the start model: the same "nearest" where it is proved,
+``--complete-budget`` as the total per row, "nearest_work" summed over rounds and cubes, and "nearest_rounds" after "nearest_work".
 ``-c/--cpu_mode`` is rejected: the hot path has no CPU fallback.  Launched through ``python -m torch.distributed.run --nproc-per-node N``
 it runs one process per GPU on a shard of the input each and reduces the result once over RCCL.
 """
@@ -218,6 +222,12 @@ def main(argv=None):
                         '"nearest_split_depth" on the rows searched at a depth above 0.  The model --complete found is always the start model of '
                         'that search, so N = 0 is not the call without the flag: the start model is checked first and its reads are part of '
                         '"nearest_work"', type=int, default=None)
+    parser.add_argument('--complete-nearest-rounds', dest='complete_nearest_rounds', help='With --complete --complete-nearest: run the branch '
+                        'and bound of every satisfiable row in rounds of 2^N reads per cube (pdp_exact_nearest_round), N from 0 to 40, or -1 for '
+                        'the default; between two rounds the open part of every search tree is cut again to fill the GPU and every cube is '
+                        'handed the best cost its row has met, and --complete-budget is the total of reads per row over all rounds and cubes; '
+                        'the model --complete found is the start model; the same "nearest" where it is proved, "nearest_work" summed over the '
+                        'rounds and cubes, "nearest_rounds" after "nearest_work"; not with --complete-nearest-split', type=int, default=None)
     parser.add_argument('--split-forward', dest='split_forward', help='On several ranks: spread EVERY forward over all GPUs (one contiguous instance range '
                         'per rank) and keep the couplings of the reference -- its batch-wide reductions are completed across the ranks chunk by chunk; '
                         'p-d-p, -b 1; the rows are those of the single-process run', action='store_true')
@@ -281,6 +291,13 @@ def main(argv=None):
             parser.error("--complete-nearest-split spreads the search of --complete-nearest: give --complete-nearest as well")
         if not -1 <= args['complete_nearest_split'] <= 16:
             parser.error("--complete-nearest-split takes a depth from 0 to 16, or -1 for a depth chosen from the rows left unproved")
+    if args['complete_nearest_rounds'] is not None:
+        if not args['complete_nearest']:
+            parser.error("--complete-nearest-rounds runs the search of --complete-nearest in rounds: give --complete-nearest as well")
+        if args['complete_nearest_split'] is not None:
+            parser.error("--complete-nearest-rounds cuts the search between its rounds: give it without --complete-nearest-split")
+        if not -1 <= args['complete_nearest_rounds'] <= 40:
+            parser.error("--complete-nearest-rounds takes log2 of the reads per cube and round, from 0 to 40, or -1 for the default")
     if args['complete_sample'] is not None:
         if not args['complete_count']:
             parser.error("--complete-sample draws from the models --complete-count counts: give --complete-count as well")

@@ -107,7 +107,8 @@ Split nearest rows (pdp_exact_nearest_split; never part of the default): ``nsa``
 leaves at an upper bound as a batch of their own, 2^28 reads per instance and per cube: kernel time of pdp_exact_nearest and of the split
 call at depths 4 / 8 / 12 (``nsb`` also with the plain call's models as start models), proved counts, reads, the largest cube's share and
 the cubes that accepted nothing; equal costs wherever both prove are asserted.  ``nsauto`` / ``nsd`` = rows ``na`` / ``nd`` whole, host
-wall time of exact.nearest_model against nearest_model(split='auto'); ``nssweep`` = row ``nd`` over AUTO_NEAREST_STAGE1_BUDGET.
+wall time of exact.nearest_model against nearest_model(split='auto'); ``nssweep`` = row ``nd`` over AUTO_NEAREST_STAGE1_BUDGET;
+``nra`` / ``nrb`` / ``nrd`` / ``nrauto`` / ``nrsweep`` = the nearest-model search in rounds (run_nearest_rounds).
 
 Split mass rows (pdp_exact_mass_split; never part of the default): ``zsa`` / ``zsb`` = the 1 / 8 instances of row ``ca`` with the largest plain
 work at weights 0.5 as a batch of their own: kernel time of pdp_exact_mass and of the split call at depths 4 / 8 / 12 on the same problem
@@ -1283,6 +1284,25 @@ def _nearest_problem(sub, hints):
     return p, torch.from_numpy(np.concatenate(hints)).to(p.device)
 
 
+def _nearest_left():
+    """(title, the instances row nd leaves at an upper bound at 2^28 reads, their hints); PDP_NS_CACHE=<path> keeps them for the next process"""
+    import pickle
+    cache = os.environ.get('PDP_NS_CACHE')
+    if cache and os.path.exists(cache):
+        with open(cache, 'rb') as f:
+            return pickle.load(f)
+    title, sub, hints = _nearest_batch('d')
+    p, hint = _nearest_problem(sub, hints)
+    st = p.exact_nearest(hint, None, ND_BUDGET)[0].cpu().numpy()
+    left = np.nonzero(st == -1)[0]
+    del p
+    out = title, [sub[i] for i in left], [hints[i] for i in left]
+    if cache:
+        with open(cache, 'wb') as f:
+            pickle.dump(out, f)
+    return out
+
+
 def run_nearest_split(key):
     """nsa / nsb: the first / all of the instances row nd leaves at an upper bound, as a batch of their own at 2^28 reads per instance and
     per cube: pdp_exact_nearest next to pdp_exact_nearest_split at depths 4 / 8 / 12 (PDP_NS_DEPTHS=4,8 picks others), nsb also with the
@@ -1292,21 +1312,7 @@ def run_nearest_split(key):
     nearest_model(split='auto').  nssweep: the same on row nd over AUTO_NEAREST_STAGE1_BUDGET = 2^18 / 2^22 / 2^26."""
     from pdp import exact
     if key in ('nsa', 'nsb'):
-        import pickle
-        cache = os.environ.get('PDP_NS_CACHE')
-        if cache and os.path.exists(cache):
-            with open(cache, 'rb') as f:
-                title, part, ph = pickle.load(f)
-        else:
-            title, sub, hints = _nearest_batch('d')
-            p, hint = _nearest_problem(sub, hints)
-            st = p.exact_nearest(hint, None, ND_BUDGET)[0].cpu().numpy()
-            left = np.nonzero(st == -1)[0]
-            del p
-            part, ph = [sub[i] for i in left], [hints[i] for i in left]
-            if cache:
-                with open(cache, 'wb') as f:
-                    pickle.dump((title, part, ph), f)
+        title, part, ph = _nearest_left()
         if key == 'nsa':
             part, ph = part[:1], ph[:1]
         q, h = _nearest_problem(part, ph)
@@ -1355,9 +1361,103 @@ def run_nearest_split(key):
                             sorted(set(got[4][got[4] > 0].tolist())), int(got[3].sum())), flush=True)
 
 
+NEAREST_ROUNDS_ROWS = ('nra', 'nrb', 'nrd', 'nrauto', 'nrsweep')
+
+
+def _nearest_line(tag, ms, out, sub, hints, base_reads, used=None):
+    "one line of run_nearest_rounds; every model returned is checked against its clauses (pdp_cnf_eval) and its cost against its distance"
+    st, co, models, wk = out[:4]
+    found = co >= 0
+    if found.any():
+        q, _ = _nearest_problem(sub, hints)
+        ok = q.cnf_eval(torch.from_numpy(np.concatenate(models)).to(q.device).contiguous())[0].cpu().numpy().reshape(-1)
+        assert (ok[found] == 1).all(), tag + ": a model returned leaves a clause unsatisfied"
+        ham = np.array([int(((m > 0.5) != (np.asarray(h) > 0.5)).sum()) for m, h in zip(models, hints)])
+        assert (ham[found] == co[found]).all(), tag + ": cost is not the distance of the model returned"
+    print("    %s: wall %.1f ms  proved %d  upper bound %d  nothing found %d  reads %d (%.3f of the plain call's)  cost sum over the rows with a "
+          "model %d%s" % (tag, ms, int((st == 1).sum()), int(((st == -1) & found).sum()), int(((st == -1) & ~found).sum()), int(wk.sum()),
+                          float(wk.sum()) / max(1.0, float(base_reads)), int(co[found].sum()),
+                          "" if used is None else "  rounds %s" % _q(used)), flush=True)
+
+
+def run_nearest_rounds(key):
+    """nra / nrb: the first / all of the instances row nd leaves at an upper bound (as nsa / nsb), host wall time of exact.nearest_model plain
+    at 2^28 reads, split=8 / split=12 at 2^28 reads per cube, and nearest_model_rounds at a total of 2^28 reads per instance; wherever two calls
+    prove, their costs are asserted equal.  PDP_NR_ONLY=plain / split:<depth> / rounds times that one call alone (a fresh process per
+    measurement of an alternating comparison; 'plain' and 'split:<depth>' use nothing that the rounds added, so the same file measures an
+    older tree); PDP_NR_ROUND_BUDGET=<N> sets the round budget to 2^N and PDP_NR_TOTAL=<N> the total per instance to 2^N;
+    PDP_NS_CACHE=<path> keeps the batch.  nrd / nrauto: rows nd (2^28 reads) / na whole: plain, split='auto' and nearest_model_rounds.  nrsweep:
+    the round budget 2^14 .. 2^22 and the give caps 1 / 4 / 8 / 16 on nrb's batch."""
+    from pdp import exact
+    only = os.environ.get('PDP_NR_ONLY')
+    per_round = os.environ.get('PDP_NR_ROUND_BUDGET')
+    per_round = None if per_round is None else 1 << int(per_round)
+    total = os.environ.get('PDP_NR_TOTAL')
+    if key in ('nrd', 'nrauto'):
+        title, sub, hints = _nearest_batch('d' if key == 'nrd' else 'a')
+        budget = ND_BUDGET if key == 'nrd' else 0
+    else:
+        title, sub, hints = _nearest_left()
+        title, budget = 'row nd (%s) left at an upper bound' % title, ND_BUDGET
+        if key == 'nra':
+            sub, hints = sub[:1], hints[:1]
+    total = budget if total is None else 1 << int(total)
+    exact.nearest_model(sub[:8], hints[:8], budget=1, split=1)                           # the context, the library and the kernels are loaded
+    if only is None or only == 'rounds':
+        exact.nearest_model_rounds(sub[:8], hints[:8], budget=1)
+    used = []
+    real = getattr(exact, 'nearest_rounds', None)
+
+    def keep(*a, **kw):
+        out = real(*a, **kw)
+        used.append(out[4])
+        return out
+    if real is not None:
+        exact.nearest_rounds = keep
+    calls = {'plain': lambda: exact.nearest_model(sub, hints, budget=budget),
+             'auto': lambda: exact.nearest_model(sub, hints, budget=budget, split='auto'),
+             'rounds': lambda: exact.nearest_model_rounds(sub, hints, budget=total, round_budget=per_round)}
+    for d in (8, 12):
+        calls['split:%d' % d] = lambda d=d: exact.nearest_model(sub, hints, budget=budget, split=d)
+    print("(%s%s) %d instances, %s, hints = p-d-p forward, 2^%d reads per instance (plain), per cube (split) or in all (rounds: 2^%d)"
+          % (key, ', %s alone' % only if only else '', len(sub), title, (budget or 1 << 32).bit_length() - 1, (total or 1 << 32).bit_length() - 1),
+          flush=True)
+    if only:
+        ms, out = _wall(calls[only])
+        _nearest_line(only, ms, out, sub, hints, out[3].sum(), np.concatenate(used) if used else None)
+        return
+    ms0, plain = _wall(calls['plain'])
+    _nearest_line('plain', ms0, plain, sub, hints, plain[3].sum())
+
+    def agrees(out, tag):
+        both = (plain[0] == 1) & (out[0] == 1)
+        assert np.array_equal(out[1][both], plain[1][both]), tag + ": a proved cost differs from the plain call's"
+        assert np.array_equal(out[0][(plain[0] == 0) | (out[0] == 0)], plain[0][(plain[0] == 0) | (out[0] == 0)]), tag + ": a model appears or is lost"
+
+    if key == 'nrsweep':
+        default_cap = exact.NEAREST_ROUNDS_MAX_GIVE
+        for cap in (1, 4, 8, 16):
+            exact.NEAREST_ROUNDS_MAX_GIVE = cap
+            for lg in (14, 16, 18, 20, 22):
+                del used[:]
+                ms, out = _wall(lambda: exact.nearest_model_rounds(sub, hints, budget=total, round_budget=1 << lg))
+                agrees(out, 'rounds')
+                _nearest_line("give cap %2d, round budget 2^%d" % (cap, lg), ms, out, sub, hints, plain[3].sum(), np.concatenate(used))
+        exact.NEAREST_ROUNDS_MAX_GIVE = default_cap
+        return
+    for tag in (('split:8', 'split:12') if key in ('nra', 'nrb') else ('auto',)) + ('rounds',):
+        del used[:]
+        ms, out = _wall(calls[tag])
+        agrees(out, tag)
+        _nearest_line(tag, ms, out, sub, hints, plain[3].sum(), np.concatenate(used) if used else None)
+
+
 if __name__ == '__main__':
     native.require_gpu()
     for k in (sys.argv[1:] or sorted(ROWS)):
+        if k in NEAREST_ROUNDS_ROWS:
+            run_nearest_rounds(k)
+            continue
         if k in NEAREST_SPLIT_ROWS:
             run_nearest_split(k)
             continue
