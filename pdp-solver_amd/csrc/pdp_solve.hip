@@ -101,6 +101,7 @@ struct SolveParams {
     int lds_tickets;            // LDS-resident kernel, pass 1: 0 = instance blockIdx.x, else the number of instances the workgroups draw tickets for
     uint8_t *ghost_flag;        // LDS-resident kernel: [B] 2 = an instance that left inactive with iterations to come failed its ghost sweep (lds_ghost_bad)
     uint32_t *team_ws;          // [team_count][PDP_TEAM_WORDS], zeroed before every launch
+    int no_clean_trips;         // PDP_SOLVE_NO_CLEAN_TRIPS=1: under an edge mask every E2 trip of the LDS-resident kernel applies it (A/B switch)
 };
 
 // Device-side control of the chunked persistent solve: the host enqueues every launch of a call up front and reads
@@ -147,7 +148,8 @@ __host__ __device__ inline BlobLayout blob_layout(int n, int m, int ne)
     return b;
 }
 
-__device__ __forceinline__ size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+constexpr size_t PDP_CARVE_ALIGN = 16;    // granularity of carve(): every LDS piece starts at a multiple of it (the dynamic LDS base is 16-byte aligned)
+__device__ __forceinline__ size_t align16(size_t x) { return (x + (PDP_CARVE_ALIGN - 1)) & ~(PDP_CARVE_ALIGN - 1); }
 
 template <class T>
 __device__ __forceinline__ T *carve(unsigned char *&p, size_t count)
@@ -881,9 +883,9 @@ __device__ __forceinline__ LView make_lview(const LdsArrays &L, int b, int n, in
 __device__ unsigned long long g_phase_cycles[40];
 // per-phase sums stay in registers and are flushed once per launch: one atomic per phase and iteration from 5000 workgroups
 // onto the same 16 words more than doubled the kernel time
-#define PROF_DECL unsigned long long _t0 = __builtin_readcyclecounter(), _t1; uint32_t _acc[20] = {0};
+#define PROF_DECL unsigned long long _t0 = __builtin_readcyclecounter(), _t1; uint32_t _acc[22] = {0};
 #define PROF_MARK(i) do { _t1 = __builtin_readcyclecounter(); _acc[i] += (uint32_t)(_t1 - _t0); _t0 = _t1; } while (0)
-#define PROF_FLUSH() do { if (threadIdx.x == 0) { _Pragma("unroll") for (int _i = 0; _i < 20; ++_i) if (_acc[_i]) atomicAdd(&g_phase_cycles[_i < 13 ? _i : _i + 11], (unsigned long long)_acc[_i]); } } while (0)
+#define PROF_FLUSH() do { if (threadIdx.x == 0) { _Pragma("unroll") for (int _i = 0; _i < 22; ++_i) if (_acc[_i]) atomicAdd(&g_phase_cycles[_i < 13 ? _i : _i + 11], (unsigned long long)_acc[_i]); } } while (0)
 extern "C" int pdp_debug_phase_cycles(unsigned long long *out_host, int reset)
 {
     if (hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_phase_cycles), sizeof(unsigned long long) * 40) != hipSuccess) return 1;
@@ -1154,6 +1156,7 @@ struct ColdShared {
     int red[PDP_RED_SMALL];          // scratch of the general simplification routines
 };
 typedef __attribute__((address_space(3))) unsigned char lds_u8;
+typedef const __attribute__((address_space(3))) float lds_cf32;
 __device__ __forceinline__ uint32_t lds_offset_of(const void *p)
 {
     uint32_t off = (uint32_t)(uintptr_t)(lds_u8 *)p;
@@ -1618,6 +1621,23 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
     if (tid == 0) { s_cold.is_sat = hdr.is_sat; s_flag_or[0] = 0; s_flag_or[1] = 0; s_sat_count = 0; s_risk = 0xffffffffu; }
     __syncthreads();
 
+    // Does every slot that this wave takes in E2 (slots k nt + tid) have its edge-mask bit?  Then the wave's E2 multiplies by 1.0f three times
+    // per slot -- x * 1 is x bit for bit, NaN payloads and -0 included -- and runs without the mask (see there).  One wave-uniform flag; the
+    // mask bits change at a refresh only (P7 renews the flag) and come with the record: rebuilt here from the loaded words, one ballot per
+    // launch, rather than carried in the record's header (a flag there would be per instance, not per wave, and needs the writer's reduction).
+    // (One flag per TRIP and a scalar branch in every trip was measured too: the branch splits the trip's basic block, and the call lost
+    //  0.06-0.10 ms where this form gains -- profiles/EXPERIMENTS.md.)  Forced instantiations keep the masked trip (their register budget is spent).
+    int em_all_ones = 0;
+    if constexpr (!FORCE) {
+        bool lost = false;
+        for (int p = tid; p < ne; p += nt) lost = lost || !(pcc[p] & PC_EM);
+        em_all_ones = (__builtin_amdgcn_ballot_w64(lost) == 0ull) ? 1 : 0;
+    }
+    // E2's trips of this wave: slots k nt + tid, k < e2_trips; in the last of them only the lanes whose slot exists
+    const int wave_first = UNI(tid - lane);
+    const int e2_trips = wave_first < ne ? (ne - 1 - wave_first) / nt + 1 : 0;
+    const bool in_last_trip = tid + (e2_trips - 1) * nt < ne;
+
     // P4's work item of this lane -- (variable, half row) -- is topology: fetched once per launch instead of through two dependent LDS round
     // trips (vord -> v_ptr) in every sweep, when every item has a lane of its own (2 n <= threads).  Two registers: lo | hi, v | degree.
     const bool p4_cached = 2 * n <= nt;
@@ -1852,42 +1872,57 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
         float nan_acc = 0.0f;
         const uint32_t log_em_or = use_em ? 0u : PC_EM;      // without an edge mask every slot counts
         // one slot's update: reads the slot's words, the three row sums and its own logs, stores the new survey and returns the new values
-        struct SlotNew { float qu, eta, eta_old, total; uint16_t cw; };
+        // (MASKED: the trip applies the edge mask, returned as 1.0f / 0.0f)
+        struct SlotNew { float qu, eta, eta_old, total, em; };
         const float *const S_ = L.S, *const PN_ = L.PN, *const EX_ = L.EX;
-        auto slot_update = [&](int p) __attribute__((always_inline)) {
-            const uint16_t pw = pvv[p], cw = pcc[p];
-            const int v = pw & VM, c = cw & 0x3fff;
-            const float s = slot_sign(pw);
+        // Without a force the four row-sum reads of a slot go through byte addresses formed here, not through indices: bit 14 of the slot word
+        // is zero then, so 2 v + [negative literal] is the 16-bit word rotated left by one (two operations), the slot's own sum is at
+        // PN + 4 * that, the opposite sum at that address ^ 4 (carve_all hands out 16-byte aligned pieces, so bit 2 of the address is bit 0 of
+        // the index), exp of the opposite sum at the same address + (EX - PN), a scalar.
+        static_assert(PDP_CARVE_ALIGN % 8 == 0, "the opposite row sum is read at (address of the own one) ^ 4: PN must start at a multiple of 8 bytes");
+        const uint32_t pn_at = (uint32_t)(uintptr_t)(lds_u8 *)PN_, s_at = (uint32_t)(uintptr_t)(lds_u8 *)S_;
+        const uint32_t ex_from_pn = (uint32_t)(uintptr_t)(lds_u8 *)EX_ - pn_at;
+        auto slot_update = [&](int p, auto masked) __attribute__((always_inline)) {
+            constexpr bool MASKED = decltype(masked)::value;
+            const uint32_t pw = pvv[p], cw = pcc[p];
             const float eta_old = Eold[p];
             const float xp = X[p];
-            const float agg = S_[c] - xp;                       // the reference's 0 + S is a no-op: a sum that starts at +0 is never -0
-            const float force = FORCE ? frc_of(pw) : 0.0f;
-            // The reference's (0.5 (1 + s)) * pos + (0.5 (1 - s)) * neg has coefficients 1 and 0: one product is the sum itself, the other an
-            // exact zero.  R1 stores P / N so that they are never -0 (sums that start at +0), never infinite (sums of clamped logs) and NaN
-            // only together (each gets 0 * the other): x + (+-0) == x then, so the expression is the SELECTED sum -- and with the pair
-            // {P, N} per variable the selection on the slot's sign bit is the index 2 v + [negative literal]: no coefficient arithmetic, no select.
-            // (with a force: the pair in one read and two selects, as before the pair layout -- the index form costs those instantiations scratch)
-            const uint32_t iv = ((uint32_t)v << 1) | ((uint32_t)pw >> 15);
-            const bool neg_lit = (pw & 0x8000u) != 0;
-            float2 pn = make_float2(0.0f, 0.0f);
-            if constexpr (FORCE) pn = reinterpret_cast<const float2 *>(PN_)[v];
-            float same = FORCE ? (neg_lit ? pn.y : pn.x) : PN_[iv];
-            same = same - Y[p];
-            // without an external force both log terms are log(1) = +0: adding it can only turn a -0 into +0, which exp ignores
-            if constexpr (FORCE) same = same + ((force == s) ? L1 : L0);
-            float opp = FORCE ? (neg_lit ? pn.x : pn.y) : PN_[iv ^ 1u];
-            if constexpr (FORCE) opp = opp + ((force == -s) ? L1 : L0);
+            float agg, same, opp, eopp = 0.0f;
+            if constexpr (FORCE) {
+                const int v = pw & VM, c = cw & 0x3fff;
+                const float s = slot_sign((uint16_t)pw);
+                agg = S_[c] - xp;                               // the reference's 0 + S is a no-op: a sum that starts at +0 is never -0
+                const float force = frc_of((uint16_t)pw);
+                // The reference's (0.5 (1 + s)) * pos + (0.5 (1 - s)) * neg has coefficients 1 and 0: one product is the sum itself, the other an
+                // exact zero.  R1 stores P / N so that they are never -0 (sums that start at +0), never infinite (sums of clamped logs) and NaN
+                // only together (each gets 0 * the other): x + (+-0) == x then, so the expression is the SELECTED sum -- and with the pair
+                // {P, N} per variable the selection on the slot's sign bit is the index 2 v + [negative literal]: no coefficient arithmetic, no select.
+                // (with a force: the pair in one read and two selects, as before the pair layout -- the index form costs those instantiations scratch)
+                const bool neg_lit = (pw & 0x8000u) != 0;
+                const float2 pn = reinterpret_cast<const float2 *>(PN_)[v];
+                same = (neg_lit ? pn.y : pn.x) - Y[p];
+                same = same + ((force == s) ? L1 : L0);
+                opp = (neg_lit ? pn.x : pn.y) + ((force == -s) ? L1 : L0);
+            } else {
+                uint32_t iv;                                    // (the word beside itself, then bits 15 .. 30; kept opaque: the optimiser would fold the
+                                                                //  field extract into the address's shift and mask, one operation more)
+                asm("v_bfe_u32 %0, %1, 15, 16" : "=v"(iv) : "v"(__builtin_amdgcn_perm(pw, pw, 0x01000100u)));
+                const uint32_t a_same = pn_at + (iv << 2);
+                agg = *(lds_cf32 *)(uintptr_t)(s_at + ((cw & 0x3fffu) << 2)) - xp;
+                // without an external force both log terms are log(1) = +0: adding it can only turn a -0 into +0, which exp ignores
+                same = *(lds_cf32 *)(uintptr_t)a_same - Y[p];
+                opp = *(lds_cf32 *)(uintptr_t)(a_same ^ 4u);
+                eopp = *(lds_cf32 *)(uintptr_t)(a_same + ex_from_pn);   // (exp(opp) is one of the two exps R1 took for the variable: three exps per slot)
+            }
 #ifndef PDP_E2_PACKED_EXPS
             // (four scalar chains: a packed fp32 instruction holds the SIMD as long as two plain ones and waits a state behind the packed step it
             //  depends on, so the 4-vector form buys nothing here -- measured in round 5: -2.3 % on the launch, the logs likewise -1.8 %)
             const float so = same + opp;
-            // (without a force exp(opp) is one of the two exps R1 took for the variable: three exps per slot)
-            float eopp;
-            if constexpr (FORCE) eopp = exp1_sum(opp); else eopp = EX_[iv];
+            if constexpr (FORCE) eopp = exp1_sum(opp);
             const f4v ex = {exp1_sum(agg), exp1_sum(so), exp1_sum(same), eopp};
 #else
             f4v ex = exp4_sum((f4v){agg, same + opp, same, FORCE ? opp : same});     // A/B switch: 3 + 1 without a force
-            if constexpr (!FORCE) ex.w = EX_[iv];
+            if constexpr (!FORCE) ex.w = eopp;
 #endif
             // mask * new + (1 - mask) * old with mask == 1: (+0) * old + new as ONE fused operation -- the product is an exact zero (or NaN),
             // so fusing rounds nothing differently; the unfused form is a multiply and an add per slot
@@ -1898,34 +1933,54 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
             const float total = (qu + qs) + dc;
             const float qu_new = __builtin_fmaf(1.0f - 1.0f, xp, qu / total);      // (+0) * log(old q_u): NaN iff the old q_u is NaN or infinite
             Enew[p] = eta_new;
-            return SlotNew{qu_new, eta_new, eta_old, total, cw};
+            // (a masked trip without a force runs under an edge mask: the slot's own bit; with a force the sweeps without one take this body too)
+            return SlotNew{qu_new, eta_new, eta_old, total, MASKED ? bit15_to_float((uint16_t)(FORCE ? (cw | log_em_or) : cw)) : 1.0f};
         };
-        auto slot_logs = [&](int p, const SlotNew &r) __attribute__((always_inline)) {
+        auto slot_logs = [&](int p, const SlotNew &r, auto masked) __attribute__((always_inline)) {
+            constexpr bool MASKED = decltype(masked)::value;
 #ifndef PDP_E2_PACKED_LOGS
             // (the two logs as scalar chains: the survey's log runs beside the division it does not depend on, and neither waits a state between
             //  dependent packed steps -- measured in round 5 against the 2-vector form: -1.8 % on the launch)
-            const float em = bit15_to_float((uint16_t)(r.cw | log_em_or));
-            Y[p] = pdp_safe_log_fin(1.0f - r.eta, PDP_SP_EPS) * em;      // (needs the survey only: runs beside the division)
-            X[p] = pdp_safe_log_fin(r.qu, PDP_SP_EPS) * em;
+            float y = pdp_safe_log_fin(1.0f - r.eta, PDP_SP_EPS);           // (needs the survey only: runs beside the division)
+            float x = pdp_safe_log_fin(r.qu, PDP_SP_EPS);
+            if constexpr (MASKED) { y = y * r.em; x = x * r.em; }
+            Y[p] = y; X[p] = x;
 #else
-            const f2v lg = log2_fin((f2v){r.qu, 1.0f - r.eta}, PDP_SP_EPS) * bit15_to_float((uint16_t)(r.cw | log_em_or));
+            f2v lg = log2_fin((f2v){r.qu, 1.0f - r.eta}, PDP_SP_EPS);
+            if constexpr (MASKED) lg = lg * r.em;
             X[p] = lg.x; Y[p] = lg.y;
 #endif
         };
+        // A wave whose slots all have their mask bit (its flag, formed at the load and at every refresh), and every wave while the problem has no
+        // edge mask yet, runs the unmasked body: the same stored bits, five vector instructions per slot less.  One scalar branch per sweep;
+        // with PDP_SOLVE_NO_CLEAN_TRIPS=1 only the sweeps without an edge mask take it, and with a force every trip is a masked one.
+        const std::true_type masked_trip; const std::false_type clean_trip;
+        const bool wave_clean = !FORCE && (!use_em || (em_all_ones && !sp.no_clean_trips));
         if (PROF_SKIP(4)) { }
         else if (fuse_logs) {
             // (the logs of a trip riding in the NEXT trip, so that their dependent chain of ~20 packed steps interleaves with that trip's loads, exps
             //  and division in one basic block, was measured in round 5: +3 % on the launch)
-            for (int p = tid; p < ne; p += nt) {
-                const SlotNew r = slot_update(p);
-                QU[p] = pdp_abs(r.eta_old - r.eta) * bit15_to_float((uint16_t)(r.cw | log_em_or));   // |delta eta| * edge mask (pdp_decimate.py:135-141)
-                slot_logs(p, r);
+            auto trip = [&](int p, auto masked) __attribute__((always_inline)) {
+                const SlotNew r = slot_update(p, masked);
+                float d = pdp_abs(r.eta_old - r.eta);
+                if constexpr (decltype(masked)::value) d = d * r.em;
+                QU[p] = d;                                  // |delta eta| * edge mask (pdp_decimate.py:135-141)
+                slot_logs(p, r, masked);
+                if constexpr (!decltype(masked)::value) PROF_COUNT(20);      // (the profile counts thread 0's trips: clean ones, all of them)
+                PROF_COUNT(21);
+            };
+            if constexpr (FORCE) {
+                for (int p = tid; p < ne; p += nt) trip(p, masked_trip);
+            } else {
+                // (counted in scalar registers: see e2_trips)
+                if (wave_clean) { for (int k = 0, p = tid; k < e2_trips; ++k, p += nt) if (k + 1 < e2_trips || in_last_trip) trip(p, clean_trip); }
+                else { for (int k = 0, p = tid; k < e2_trips; ++k, p += nt) if (k + 1 < e2_trips || in_last_trip) trip(p, masked_trip); }
             }
         } else {
             // (a launch's last sweep is of this form: the smallest normalisation of the instance goes to the dispatch order of the next launch)
             float tmin = PDP_INF;
-            for (int p = tid; p < ne; p += nt) {
-                const SlotNew r = slot_update(p);
+            auto trip = [&](int p, auto masked) __attribute__((always_inline)) {
+                const SlotNew r = slot_update(p, masked);
                 tmin = (r.total < tmin) ? r.total : tmin;
                 QU[p] = r.qu;
                 if (!has_prev) {
@@ -1935,9 +1990,16 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
                 } else {
                     const float pe = prev_from_global ? sp.prev_slots[G.e0 + p] : r.eta_old;
                     float d = pdp_abs(pe - r.eta);
-                    if (use_em) d = d * bit15_to_float(r.cw);
-                    Y[p] = d;                               // the smooth-max weights exp(30 d) are only built when P4 cannot decide without them
+                    if constexpr (decltype(masked)::value) { if (use_em) d = d * r.em; }
+                    Y[p] = d;                              // the smooth-max weights exp(30 d) are only built when P4 cannot decide without them
                 }
+            };
+            if constexpr (FORCE) {
+                for (int p = tid; p < ne; p += nt) trip(p, masked_trip);
+            } else {
+                // (counted in scalar registers: see e2_trips)
+                if (wave_clean) { for (int k = 0, p = tid; k < e2_trips; ++k, p += nt) if (k + 1 < e2_trips || in_last_trip) trip(p, clean_trip); }
+                else { for (int k = 0, p = tid; k < e2_trips; ++k, p += nt) if (k + 1 < e2_trips || in_last_trip) trip(p, masked_trip); }
             }
             if (sp.risk && t + 1 == T) {
                 tmin = wave_reduce(tmin, OpMinLess(), PDP_INF);
@@ -2169,12 +2231,21 @@ __global__ void __launch_bounds__(1024, PDP_SOLVE_WAVES_PER_SIMD) k_sp_solve_lds
             const bool recount = sp.check_termination && (decimated || rf_changed || nsat < 0);
             if (refresh) {
                 const float *const av = L.av, *const af = L.af;
-                for (int p = tid; p < ne; p += nt) {
+                auto refresh_slot = [&](int p) __attribute__((always_inline)) {
                     const uint16_t cw = pcc[p];
                     const float a = 0.0f + av[pvv[p] & VM];
                     const float b = 0.0f + af[cw & 0x3fff];
                     const bool em = (a * b) == 1.0f;
                     pcc[p] = (uint16_t)((cw & ~PC_EM) | (em ? PC_EM : 0));
+                    return em;
+                };
+                if constexpr (FORCE) {
+                    for (int p = tid; p < ne; p += nt) refresh_slot(p);
+                } else {
+                    // (the wave's flag "no slot of mine is masked" follows the new bits)
+                    bool lost = false;
+                    for (int p = tid; p < ne; p += nt) lost = !refresh_slot(p) || lost;
+                    em_all_ones = (__builtin_amdgcn_ballot_w64(lost) == 0ull) ? 1 : 0;
                 }
                 use_em = 1; em_dirty = 1; mask_fix = logs_ready;
                 PROF_COUNT(17);
@@ -2976,6 +3047,7 @@ static int sp_solve_resident(pdp_problem *p, pdp_solve_args *a, hipStream_t st, 
     sp.no_scorer_reuse = getenv("PDP_SOLVE_NO_SCORER_REUSE") ? 1 : 0;
     sp.no_event_look = getenv("PDP_SOLVE_NO_EVENT_LOOK") ? 1 : 0;
     sp.rf_no_fused_step = getenv("PDP_SOLVE_RF_NO_FUSED_STEP") ? 1 : 0;
+    sp.no_clean_trips = getenv("PDP_SOLVE_NO_CLEAN_TRIPS") ? 1 : 0;
     if (rf || force) {
         // the external force as a 2-bit code in the slot word (0, +1, -1, NaN; any other value raises the violation flag: the call fails over
         // to the step-wise loop, which takes the column as it is).  The SP triple only reads it (one column for all chunks).

@@ -35,4 +35,5 @@ for i, nm in ((16, "scorer edge logs"), (17, "scorer sums+score+flags"), (18, "a
     print("  decimation: %-26s %12d cycles  %5.1f%% of P6" % (nm, out[i], 100.0 * out[i] / max(1, out[6])))
 print("  decimations followed by the general unit propagation: %d, by the general peel: %d" % (out[22], out[23]))
 print("clause counts %d, mask refreshes %d" % (out[27], out[28]))
+print("E2 trips of the fused form (thread 0 of every workgroup): %d, of them without the edge mask %d (%.1f%%)" % (out[32], out[31], 100.0 * out[31] / max(1, out[32])))
 print("instance-iterations %d, exact smooth-max passes %d, decimations on the neighbourhood path %d, on the general path %d" % (out[12], out[9], out[10], out[11]))
