@@ -170,14 +170,15 @@ struct pdp_problem {
     // resumable counts (pdp_exact.hip::exq_prepare, on exn_prepare's routing and slab): exq.blob = the check's words, the HBM route's T [V]
     // and the route bytes [B]; exq.cubes = a round's per-cube records (count, work, leaves, replay, true_count rows, status) or an
     // expansion's scan (first new cube of every old one, the new cube_off); exq_nmax = the most variables of a searched instance.
-    // pdp_exact_solve_round (exv_round) uses the same check words, route bytes and exq_nmax, and exq.cubes for its own records (work,
-    // replay, model rows of bytes), and so does pdp_exact_nearest_round (exw_round: cost, work, replay, improvements, model rows), whose
-    // penalty check owns word 6 of the check's block
+    // The three round calls share one scaffold (exq_round_begin, exq_round_params, exq_round_launch): pdp_exact_solve_round (exv_round)
+    // uses the same check words, route bytes and exq_nmax, and exq.cubes for its own records (work, replay, model rows of bytes), and
+    // so does pdp_exact_nearest_round (exw_round: cost, work, replay, improvements, model rows), whose penalty check owns word 6 of
+    // the check's block
     pdp_exact_cubes exq; int exq_ready, exq_nmax;
     // k-th models of the counting search (pdp_exact.hip::exr_launch): ex_prepare's routing and slab; the rows' byte offsets [B+1] and the
     // validation words of the last call, one block allocated on first use
     char *exr_blob;
-    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_min, k_exact_nearest, k_exact_count, k_exact_learn, k_exact_check, k_exact_trim, k_exact_split, k_exact_count_split, k_exact_min_split, k_exact_models, k_exact_mass, k_exact_mass_split or k_exact_count_round on this problem (0: none yet)
+    int32_t ex_last_grid;       // workgroups of the last launch of k_exact, k_exact_min, k_exact_nearest, k_exact_count, k_exact_learn, k_exact_check, k_exact_trim, k_exact_split, k_exact_count_split, k_exact_min_split, k_exact_models, k_exact_mass, k_exact_mass_split, k_exact_count_round, k_exact_solve_round or k_exact_nearest_round on this problem (0: none yet)
     uint32_t *team_ws;          // barrier counters and reduction mailboxes of the workgroup teams (k_sp_solve<NT, true>)
     hipStream_t res_side_stream; hipEvent_t res_side_ev[2];   // the big instances' launches overlap the LDS-resident kernel on a stream of their own
     float *nws[4]; size_t nws_floats[4];             // neural workspaces (grow on demand)

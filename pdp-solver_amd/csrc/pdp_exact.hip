@@ -194,6 +194,17 @@ __device__ __forceinline__ unsigned long long ex_max64(unsigned long long x)
     return x;
 }
 
+__device__ __forceinline__ int64_t ex_sum64(int64_t x)
+{
+    for (int o = 32; o > 0; o >>= 1) x += (int64_t)__shfl_xor((long long)x, o);
+    return x;
+}
+__device__ __forceinline__ int64_t ex_min64(int64_t x)
+{
+    for (int o = 32; o > 0; o >>= 1) { const int64_t y = (int64_t)__shfl_xor((long long)x, o); x = y < x ? y : x; }
+    return x;
+}
+
 constexpr uint32_t EX_HINT_SHIFT = 8;            // bits 8-9 of pend[v]: the hint code of v (0 none, 1 true, 2 false); bits 0-1 are the unit bits
 
 // ---- the blocks every DPLL search below is built from, each written once ---------------------------------------------------------------
@@ -859,12 +870,6 @@ struct ExdParams {
     const float *hint;          // [V] the point the distance is measured from (NULL: all false)
     const int32_t *penalty;     // [V] (NULL: all 1)
 };
-
-__device__ __forceinline__ int64_t ex_sum64(int64_t x)
-{
-    for (int o = 32; o > 0; o >>= 1) x += (int64_t)__shfl_xor((long long)x, o);
-    return x;
-}
 
 // what the assigned variable u adds to dist: its penalty where its value is not the hint's
 template <typename LitT, typename PtrT>
@@ -2944,12 +2949,6 @@ __global__ void __launch_bounds__(EX_NT) k_exact_split(PView pv, ExsParams xp)
     }
 }
 
-__device__ __forceinline__ int64_t exs_sum64(int64_t x)
-{
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
 // The instance's answer from its cubes' records, one wave per instance: first = best[b]; the work of cubes 0..first (all, when no cube
 // answered 1) plus the check pass's reads; status 1, or 0 when every cube answered 0, else -1; the model of cube `first` expanded from its
 // row (a depth-0 instance's single cube wrote its slice itself), the hints where the check pass accepted, 0 elsewhere.
@@ -2971,7 +2970,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact_split_finish(PView pv, ExsParam
             int64_t sum = 0;
             int open = 0;
             for (int64_t j = lane; j <= last; j += EX_NT) { sum += xp.cube_work[c0 + j]; open |= xp.cube_status[c0 + j] != 0; }
-            w += exs_sum64(sum);
+            w += ex_sum64(sum);
             st = found ? 1 : (__ballot(open) != 0ull ? -1 : 0);
             if (depth > 0) {
                 const uint32_t *row = xp.rows + (size_t)(c0 + last) * (size_t)xp.words;
@@ -3147,8 +3146,8 @@ __global__ void __launch_bounds__(EX_NT) k_exact_count_split_finish(PView pv, Ex
             for (int t = 0; t < lim; ++t) count = count + s_count[t];
             __syncthreads();
         }
-        w = exs_sum64(w);
-        lv = exs_sum64(lv);
+        w = ex_sum64(w);
+        lv = ex_sum64(lv);
         const bool any_open = __ballot(open) != 0ull;
         for (int vb = 0; vb < n; vb += EX_NT) {
             const int v = vb + lane;
@@ -3622,8 +3621,8 @@ __global__ void __launch_bounds__(EX_NT) k_exact_min_split_finish(PView pv, Exms
             open |= xp.cube_status[c0 + j] != 1;
             if (at == EXS_NONE && xp.cube_cost[c0 + j] == best) at = (int)j;
         }
-        sum = exs_sum64(sum);
-        imp = exs_sum64(imp);
+        sum = ex_sum64(sum);
+        imp = ex_sum64(imp);
         at = ex_min(at);
         const bool all_done = __ballot(open) == 0ull;
         if (depth > 0 && at != EXS_NONE) {
@@ -3844,8 +3843,8 @@ __global__ void __launch_bounds__(EX_NT) k_exact_near_split_finish(PView pv, Exd
             open |= xp.cube_status[c0 + j] != 1;
             if (at == EXS_NONE && xp.cube_cost[c0 + j] == best) at = (int)j;
         }
-        sum = exs_sum64(sum);
-        imp = exs_sum64(imp);
+        sum = ex_sum64(sum);
+        imp = ex_sum64(imp);
         at = ex_min(at);
         const bool all_done = __ballot(open) == 0ull, bad = reads < 0;
         if (depth > 0 && at != EXS_NONE) {
@@ -4352,8 +4351,8 @@ __global__ void __launch_bounds__(EX_NT) k_exact_mass_split_finish(PView pv, Exz
             for (int t = 0; t < lim; ++t) { mass = mass + s_mass[t]; open_mass = open_mass + s_open[t]; }
             __syncthreads();
         }
-        w = exs_sum64(w);
-        lv = exs_sum64(lv);
+        w = ex_sum64(w);
+        lv = ex_sum64(lv);
         const bool any_open = __ballot(open) != 0ull;
         const bool bad_weight = xp.cube_status[c0] == (int8_t)-3;   // one address for the whole wave
         for (int vb = 0; vb < n; vb += EX_NT) {
@@ -4441,9 +4440,14 @@ int exzs_launch(pdp_problem *p, const float *weights, const int8_t *depth, int64
 // order, sequentially).  The state, the slab (exn_lds_layout), the routing and the HBM arrays are k_exact_count's; the HBM route's T is an
 // array of this call's own, because true_count holds the running total here.  An expansion is the check, a scan by one workgroup (the
 // first new cube of every old one) and the rows written by one wave per old cube.  No wave waits for, or reads a word of, another.
+// pdp_exact_solve_round and pdp_exact_nearest_round below run on the same scaffold, written once here: ExPath, ExWalk (the replay and
+// the budget), exq_decide, ExRound, exq_checkpoint, exq_cubes, and on the host exq_round_begin, exq_round_params, exq_round_launch.
 constexpr int EXQ_NT = 1024;                    // the check and the scan: one workgroup each
 constexpr int EXQ_INFO = 8;                     // words of the check (EXQ_BAD_*) and of the scan (EXQ_TOTAL)
 enum { EXQ_BAD_OFF = 0, EXQ_BAD_WIDE, EXQ_BAD_HBM, EXQ_BAD_LEN, EXQ_BAD_PAIR, EXQ_TOTAL };
+constexpr int EXW_BAD_PEN = 6;                  // word of the check's info block that the penalty kernel owns (EXQ_TOTAL is the last of the count's)
+static_assert(EXW_BAD_PEN > EXQ_TOTAL && EXW_BAD_PEN < EXQ_INFO, "the penalty verdict needs a word of its own");
+constexpr int64_t EXV_MAX_ROW_BYTES = (int64_t)1 << 31;         // of the byte rows (models) that the deciding and nearest-model rounds keep per cube
 
 // What a cube of a round knows: its path (rows of `words` words, level L at bit (L - 1) % 32 of word (L - 1) / 32) and its length.
 struct ExPath { const uint32_t *bits, *closed; int len; };
@@ -4465,8 +4469,31 @@ __device__ __forceinline__ bool exq_owns_leaf(const ExPath &Q, int level, int pl
     return any == 0u;
 }
 
-// The decision push of a path cube: ex_decide where a level L <= plen takes the polarity its path bit asks for (0: the key's, 1: the
-// other) and is recorded as already flipped iff the path has it closed.
+// The cursor of a path cube, shared by the three path searches: levels 1 .. plen are still as the path has them, and the budget is
+// tested only where a node begins (`fresh`), on the reads made since the first node that began with level >= plen (`base`; -1: still
+// replaying), so the replay of a path is free.
+struct ExWalk {
+    int plen;
+    int64_t base = -1;
+    bool fresh = true;
+    // where a node begins: has the cube spent its budget?  Elsewhere false.
+    __device__ __forceinline__ bool spent(int level, int64_t work, int64_t budget)
+    {
+        if (!fresh) return false;
+        if (base < 0 && level >= plen) base = work;
+        if (base >= 0 && work - base >= budget) return true;
+        fresh = false;
+        return false;
+    }
+    // `level` was flipped: the path beyond it no longer applies
+    __device__ __forceinline__ void flipped(int level) { plen = level < plen ? level : plen; fresh = true; }
+    __device__ __forceinline__ void opened() { fresh = true; }
+    __device__ __forceinline__ int64_t replay(int64_t work) const { return base < 0 ? work : base; }
+};
+
+// The decision of a path cube: a level L <= plen takes the polarity its path bit asks for (0: the key's, 1: the other) and is recorded
+// as already flipped iff the path has it closed.  The push itself repeats ex_decide's four lines on purpose: moved into a helper of
+// both, they were scheduled differently in the split kernels, which this section leaves instruction-identical.
 template <bool HBM, typename LitT, typename PtrT, typename Credit>
 __device__ __forceinline__ void exq_decide(const ExInst<LitT, PtrT> &X, const ExPath &Q, int plen, unsigned long long best, int &level,
                                            int &tlen, const Credit &credit)
@@ -4486,25 +4513,20 @@ __device__ __forceinline__ void exq_decide(const ExInst<LitT, PtrT> &X, const Ex
 }
 
 // The counting search of one path cube by the calling wave.  Returns 1 (the cube is exhausted) or -1 (budget spent: levels 1 .. *level_out
-// are open, *plen_out of them still as the path has them).  The budget is tested only where a node begins (`fresh`), on the reads made
-// since the first node that began with level >= plen (`base`; -1: still replaying).
+// are open, *plen_out of them still as the path has them).
 template <bool HBM, typename LitT, typename PtrT>
 __device__ int ex_search_count_path(const ExInst<LitT, PtrT> &X, const ExnAcc &A, int64_t budget, const ExPath &Q, int *level_out,
                                     int *plen_out, int64_t *work_out, int64_t *replay_out, double *count_out, int64_t *leaves_out)
 {
     constexpr int INF = 0x7fffffff;
-    int level = 0, tlen = 0, plen = Q.len;
-    int64_t work = 0, leaves = 0, base = -1;
+    int level = 0, tlen = 0;
+    int64_t work = 0, leaves = 0;
     double count = 0.0;
     int result = -1;
-    bool fresh = true;
+    ExWalk W{Q.len};
     ExnCredit credit{A, count, 0.0};
     for (;;) {
-        if (fresh) {
-            if (base < 0 && level >= plen) base = work;
-            if (base >= 0 && work - base >= budget) break;
-            fresh = false;
-        }
+        if (W.spent(level, work, budget)) break;
         const ExPass P = ex_propagate(X);
         work += ex_sum(P.reads);
         bool any_conflict = __ballot(P.conflict) != 0ull;
@@ -4520,7 +4542,7 @@ __device__ int ex_search_count_path(const ExInst<LitT, PtrT> &X, const ExnAcc &A
             wmin = ex_min(P.wmin);
             if (wmin == INF) {
                 // a leaf: every clause has a true literal and the unassigned variables are free; then as after a conflict
-                if (level >= plen || exq_owns_leaf(Q, level, plen)) {
+                if (level >= W.plen || exq_owns_leaf(Q, level, W.plen)) {
                     count = count + ldexp(1.0, X.n - tlen);
                     ++leaves;
                 }
@@ -4529,27 +4551,27 @@ __device__ int ex_search_count_path(const ExInst<LitT, PtrT> &X, const ExnAcc &A
         }
         if (any_conflict) {
             if (!ex_backtrack<HBM>(X, level, tlen, credit)) { result = 1; break; }
-            plen = level < plen ? level : plen;                     // `level` was flipped: the path beyond it no longer applies
-            fresh = true;
+            W.flipped(level);
             continue;
         }
         const unsigned long long best = ex_branch<HBM, EX_PHASE_COUNT>(X, wmin, work);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        exq_decide<HBM>(X, Q, plen, best, level, tlen, credit);
-        fresh = true;
+        exq_decide<HBM>(X, Q, W.plen, best, level, tlen, credit);
+        W.opened();
     }
-    *level_out = result == 1 ? 0 : level; *plen_out = plen;
+    *level_out = result == 1 ? 0 : level; *plen_out = W.plen;
     // the end flush of ex_search_count; dvar keeps the levels' marks for the checkpoint
     for (; level >= 0; --level) {
         const int from = level > 0 ? X.mark[level] : 0;
         exn_credit(X, A, from, tlen, count - A.snap[level]);
         tlen = from;
     }
-    *work_out = work; *replay_out = base < 0 ? work : base; *count_out = count; *leaves_out = leaves;
+    *work_out = work; *replay_out = W.replay(work); *count_out = count; *leaves_out = leaves;
     return result;
 }
 
-struct ExqParams {
+// What the cube launch of every round call knows: the frontier that runs, the checkpoints and the records that all three searches leave.
+struct ExRound {
     int B;
     uint32_t total;             // cubes of the round
     uint32_t *next;             // the "next cube" counter (zeroed before the launch)
@@ -4559,21 +4581,86 @@ struct ExqParams {
     const int32_t *len;         // [total]
     const uint32_t *bits, *closed;      // [total][words]
     int words;
-    int8_t *cube_status;        // [total] 1 / -1
+    int8_t *cube_status;        // [total] what the search returned; a finish kernel may turn the -1 of an answered instance into -2
     int32_t *len_out; uint32_t *bits_out, *closed_out;      // the checkpoints, shaped as the inputs
-    double *cube_count;         // [total]
-    int64_t *cube_work, *cube_leaves, *cube_replay;         // [total]
-    double *rows;               // [total][n_max] true_count of every cube whose count is not 0.0
-    int n_max;
-    double *count, *true_count; int64_t *work, *leaves;     // the running totals (in/out)
+    int64_t *cube_work, *cube_replay;   // [total]
+    int n_max;                  // the width of the family's per-cube rows
     ExHbm h;
+};
+
+__device__ __forceinline__ ExPath exq_path(const ExRound &r, uint32_t q)
+{
+    const size_t row = (size_t)q * (size_t)r.words;
+    return ExPath{r.bits + row, r.closed + row, r.len[q]};
+}
+
+// What every path search leaves of cube q: its status, work and replay, and its checkpoint: one lane per level, the row's words from
+// ballots, written by lane 0 with plain stores.  A level is closed iff it carries the flipped mark; it is on its other polarity iff
+// its path bit says so (levels 1 .. plen are still as the path has them) or it was flipped in this round (marked, and not closed by the
+// path).  Ends in the barrier after which the slab is reused by the wave's next cube.
+template <bool HBM, typename LitT, typename PtrT>
+__device__ __forceinline__ void exq_checkpoint(const ExInst<LitT, PtrT> &X, const ExPath &Q, const ExRound &r, uint32_t q, int st, int level,
+                                               int plen, int64_t work, int64_t replay)
+{
+    const int lane = (int)threadIdx.x;
+    const size_t row = (size_t)q * (size_t)r.words;
+    for (int w = 0; w < r.words; w += 2) {
+        const int L = 32 * w + lane + 1;
+        const uint32_t mark = L <= level ? X.dvar[L] >> 31 : 0u;
+        const bool path = L <= plen && L <= level;
+        const uint32_t pb = path ? exq_bit(Q.bits, L) : 0u, pc = path ? exq_bit(Q.closed, L) : 0u;
+        const unsigned long long bb = __ballot((pb | (mark & (pc ^ 1u))) != 0u), cc = __ballot(mark != 0u);
+        if (lane == 0) {
+            r.bits_out[row + w] = (uint32_t)bb; r.closed_out[row + w] = (uint32_t)cc;
+            if (w + 1 < r.words) { r.bits_out[row + w + 1] = (uint32_t)(bb >> 32); r.closed_out[row + w + 1] = (uint32_t)(cc >> 32); }
+        }
+    }
+    if (lane == 0) {
+        r.cube_status[q] = (int8_t)st;
+        r.len_out[q] = level;
+        r.cube_work[q] = work;
+        r.cube_replay[q] = replay;
+    }
+    ex_sync<HBM>();
+}
+
+// The cube loop of every round kernel: one counter hands out cube ids, and the calling wave runs body(route, I, q) on each it draws,
+// route a std::bool_constant (true: the HBM route).  The check has passed, so every cube's instance has at most 1023 variables.  Both
+// arms end in the barrier of exq_checkpoint and fall through to the end of the loop body (see k_exact_count).
+template <typename Body>
+__device__ __forceinline__ void exq_cubes(const PView &pv, const ExRound &r, Body body)
+{
+    for (;;) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(r.next, 1u);
+        q = __shfl(q, 0);
+        if (q >= r.total) break;
+        const int lo = exs_instance(r.cube_off, r.B, q);
+        const Inst I = load_inst(pv, lo);
+        if (r.route[lo]) body(std::true_type{}, I, q);
+        else body(std::false_type{}, I, q);
+    }
+}
+
+// the working arrays of a cube's instance on either route
+template <bool HBM>
+__device__ __forceinline__ auto exq_bind(const ExRound &r, unsigned char *slab, const Inst &I)
+{
+    if constexpr (HBM) return ex_bind_hbm(r.h, I);
+    else return ex_bind_lds(slab, I);
+}
+
+struct ExqParams {
+    ExRound r;                  // cube_status: 1 / -1
+    double *cube_count;         // [total]
+    int64_t *cube_leaves;       // [total]
+    double *rows;               // [total][n_max] true_count of every cube whose count is not 0.0
+    double *count, *true_count; int64_t *work, *leaves;     // the running totals (in/out)
     double *h_T, *h_F, *h_snap; // the HBM route's accumulators: T [V] of this call's own, F and snap as ExnParams
 };
 
 // cube q of instance I.b: copy the instance (ex_fill), clear the state, search along the path; then the cube's record, its row of
-// per-variable counts unless its count is 0.0, and its checkpoint: one lane per level, the row's words from ballots, written by lane 0
-// with plain stores.  A level is closed iff it carries the flipped mark; it is on its other polarity iff its path bit says so (levels
-// 1 .. plen are still as the path has them) or it was flipped in this round (marked, and not closed by the path).
+// per-variable counts unless its count is 0.0, and its checkpoint.
 template <bool HBM, typename LitT, typename PtrT>
 __device__ void ex_solve_count_path(const ExqParams &xp, const Inst &I, ExInst<LitT, PtrT> X, const ExnAcc A, uint32_t q)
 {
@@ -4585,62 +4672,33 @@ __device__ void ex_solve_count_path(const ExqParams &xp, const Inst &I, ExInst<L
     }
     if (lane == 0) A.snap[0] = 0.0;
     ex_sync<HBM>();
-    const size_t row = (size_t)q * (size_t)xp.words;
-    const ExPath Q{xp.bits + row, xp.closed + row, xp.len[q]};
+    const ExPath Q = exq_path(xp.r, q);
     int64_t work = 0, replay = 0, leaves = 0;
     double count = 0.0;
     int level = 0, plen = 0;
-    const int st = ex_search_count_path<HBM>(X, A, xp.budget, Q, &level, &plen, &work, &replay, &count, &leaves);
+    const int st = ex_search_count_path<HBM>(X, A, xp.r.budget, Q, &level, &plen, &work, &replay, &count, &leaves);
     ex_sync<HBM>();                                                 // T and F are read by other lanes than wrote them
     if (count != 0.0) {
-        double *out = xp.rows + (size_t)q * (size_t)xp.n_max;
+        double *out = xp.rows + (size_t)q * (size_t)xp.r.n_max;
         for (int v = lane; v < I.n; v += EX_NT) {
             const double t = A.T[v];
             out[v] = t + (count - t - A.F[v]) * 0.5;
         }
     }
-    for (int w = 0; w < xp.words; w += 2) {
-        const int L = 32 * w + lane + 1;
-        const uint32_t mark = L <= level ? X.dvar[L] >> 31 : 0u;
-        const bool path = L <= plen && L <= level;
-        const uint32_t pb = path ? exq_bit(Q.bits, L) : 0u, pc = path ? exq_bit(Q.closed, L) : 0u;
-        const unsigned long long bb = __ballot((pb | (mark & (pc ^ 1u))) != 0u), cc = __ballot(mark != 0u);
-        if (lane == 0) {
-            xp.bits_out[row + w] = (uint32_t)bb; xp.closed_out[row + w] = (uint32_t)cc;
-            if (w + 1 < xp.words) { xp.bits_out[row + w + 1] = (uint32_t)(bb >> 32); xp.closed_out[row + w + 1] = (uint32_t)(cc >> 32); }
-        }
-    }
-    if (lane == 0) {
-        xp.cube_status[q] = (int8_t)st;
-        xp.len_out[q] = level;
-        xp.cube_count[q] = count;
-        xp.cube_work[q] = work;
-        xp.cube_leaves[q] = leaves;
-        xp.cube_replay[q] = replay;
-    }
-    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+    if (lane == 0) { xp.cube_count[q] = count; xp.cube_leaves[q] = leaves; }
+    exq_checkpoint<HBM>(X, Q, xp.r, q, st, level, plen, work, replay);
 }
 
 __global__ void __launch_bounds__(EX_NT) k_exact_count_round(PView pv, ExqParams xp)
 {
     extern __shared__ __align__(16) unsigned char ex_slab[];
-    for (;;) {
-        uint32_t q = 0;
-        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
-        q = __shfl(q, 0);
-        if (q >= xp.total) break;
-        const int lo = exs_instance(xp.cube_off, xp.B, q);
-        const Inst I = load_inst(pv, lo);
-        // the check has passed: every cube's instance has at most 1023 variables.  Both arms end in the barrier of ex_solve_count_path
-        // and fall through to the end of the loop body (see k_exact_count)
-        if (xp.route[lo]) {
-            ExnAcc A;
-            A.T = xp.h_T + I.v0; A.F = xp.h_F + I.v0; A.snap = xp.h_snap + I.v0 + I.b;
-            ex_solve_count_path<true>(xp, I, ex_bind_hbm(xp.h, I), A, q);
-        } else {
-            ex_solve_count_path<false>(xp, I, ex_bind_lds(ex_slab, I), exn_bind_lds(ex_slab, I), q);
-        }
-    }
+    exq_cubes(pv, xp.r, [&](auto route, const Inst &I, uint32_t q) {
+        constexpr bool HBM = decltype(route)::value;
+        ExnAcc A;
+        if constexpr (HBM) { A.T = xp.h_T + I.v0; A.F = xp.h_F + I.v0; A.snap = xp.h_snap + I.v0 + I.b; }
+        else A = exn_bind_lds(ex_slab, I);
+        ex_solve_count_path<HBM>(xp, I, exq_bind<HBM>(xp.r, ex_slab, I), A, q);
+    });
 }
 
 // The running totals of every instance take its cubes' records and rows, one wave per instance: k_exact_count_split_finish's order
@@ -4651,7 +4709,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact_count_round_accumulate(PView pv
     __shared__ double s_count[EX_NT];
     const int lane = (int)threadIdx.x;
     for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
-        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        const int64_t c0 = xp.r.cube_off[b], nc = xp.r.cube_off[b + 1] - c0;
         if (nc == 0) continue;                                      // wave-uniform, before any barrier of the body
         const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
         double count = xp.count[b];
@@ -4660,14 +4718,14 @@ __global__ void __launch_bounds__(EX_NT) k_exact_count_round_accumulate(PView pv
             const int64_t j = base + lane;
             const bool in = j < nc;
             s_count[lane] = in ? xp.cube_count[c0 + j] : 0.0;
-            if (in) { w += xp.cube_work[c0 + j]; lv += xp.cube_leaves[c0 + j]; }
+            if (in) { w += xp.r.cube_work[c0 + j]; lv += xp.cube_leaves[c0 + j]; }
             __syncthreads();
             const int lim = (int)(nc - base < EX_NT ? nc - base : EX_NT);
             for (int t = 0; t < lim; ++t) count = count + s_count[t];
             __syncthreads();
         }
-        w = exs_sum64(w);
-        lv = exs_sum64(lv);
+        w = ex_sum64(w);
+        lv = ex_sum64(lv);
         for (int vb = 0; vb < n; vb += EX_NT) {
             const int v = vb + lane;
             double acc = v < n ? xp.true_count[v0 + v] : 0.0;
@@ -4681,7 +4739,7 @@ __global__ void __launch_bounds__(EX_NT) k_exact_count_round_accumulate(PView pv
 #pragma unroll
                     for (int u = 0; u < EXNS_ROWS_IN_FLIGHT; ++u) {
                         const bool take = t + u < lim && s_count[t + u] != 0.0 && v < n;
-                        r[u] = take ? xp.rows[(size_t)(c0 + base + t + u) * (size_t)xp.n_max + (size_t)v] : 0.0;
+                        r[u] = take ? xp.rows[(size_t)(c0 + base + t + u) * (size_t)xp.r.n_max + (size_t)v] : 0.0;
                     }
 #pragma unroll
                     for (int u = 0; u < EXNS_ROWS_IN_FLIGHT; ++u)
@@ -4735,6 +4793,30 @@ __global__ void __launch_bounds__(EXQ_NT) k_exact_count_round_check(PView pv, co
     }
     __syncthreads();
     if (t < EXQ_TOTAL) info[t] = bad[t];
+}
+
+// The second check of a nearest-model round: info[EXW_BAD_PEN] = the lowest instance that has a cube and a penalty outside [0, 2^20]
+// (EXS_NONE: none), by one workgroup: a wave per instance in turn, a lane per variable, the waves' minima through LDS.  It reads
+// cube_off [B+1] and penalty [V] only, which are the caller's whatever the frontier check finds.
+__global__ void __launch_bounds__(EXQ_NT) k_exact_nearest_round_check(PView pv, const int64_t *cube_off, const int32_t *penalty, int64_t *info)
+{
+    __shared__ int low[EXQ_NT / 64];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    int mine = EXS_NONE;
+    for (int b = wave; b < pv.B; b += EXQ_NT / 64) {
+        if (cube_off[b + 1] <= cube_off[b]) continue;               // wave-uniform
+        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
+        int bad = 0;
+        for (int v = lane; v < n; v += 64) { const int32_t q = penalty[v0 + v]; bad |= q < 0 || q > EXD_MAX_PENALTY; }
+        if (__ballot(bad) != 0ull && mine == EXS_NONE) mine = b;
+    }
+    if (lane == 0) low[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int first = EXS_NONE;
+        for (int w = 0; w < EXQ_NT / 64; ++w) first = low[w] < first ? low[w] : first;
+        info[EXW_BAD_PEN] = first;
+    }
 }
 
 // The scan of an expansion, by one workgroup; it returns at once unless the check before it found nothing.  Old cube c becomes
@@ -4854,14 +4936,20 @@ inline int exq_words(const pdp_problem *p) { return std::max(1, (p->exq_nmax + 3
 inline int64_t *exq_info(const pdp_problem *p) { return (int64_t *)p->exq.blob; }
 inline const uint8_t *exq_route(const pdp_problem *p) { return (const uint8_t *)(p->exq.blob + EXQ_INFO * 8 + (p->ex_nbig > 0 ? (size_t)p->V * 8 : 0)); }
 
-// what the host can refuse before a kernel looks at the frontier
-int exq_sizes(const pdp_problem *p, const char *name, int64_t cubes)
+// what the host can refuse before a kernel looks at the frontier.  `model_rows`: the per-cube rows are the byte rows of the deciding
+// and nearest-model rounds, not the count's doubles.
+int exq_sizes(const pdp_problem *p, const char *name, int64_t cubes, bool model_rows = false)
 {
     if (cubes < 0 || cubes > EXS_MAX_CUBES) {
         pdp_set_error("%s: %lld cubes; a frontier holds 0 .. 2^22", name, (long long)cubes);
         return PDP_ERR_INVALID;
     }
-    if (cubes * (int64_t)p->exq_nmax * 8 > EXNS_MAX_ROW_BYTES) {
+    if (model_rows && cubes * (int64_t)p->exq_nmax > EXV_MAX_ROW_BYTES) {
+        pdp_set_error("%s: the per-cube model rows (%lld cubes x %d variables) pass 2^31 bytes; split the batch", name, (long long)cubes,
+                      p->exq_nmax);
+        return PDP_ERR_INVALID;
+    }
+    if (!model_rows && cubes * (int64_t)p->exq_nmax * 8 > EXNS_MAX_ROW_BYTES) {
         pdp_set_error("%s: the per-cube rows (%lld cubes x %d variables x 8 bytes) pass 2^31 bytes; split the batch", name, (long long)cubes,
                       p->exq_nmax);
         return PDP_ERR_INVALID;
@@ -4904,49 +4992,94 @@ int exq_verdict(const char *name, const int64_t info[EXQ_INFO])
     return PDP_OK;
 }
 
+// The frontier a round call is given and the checkpoints it writes, as the caller's pointers.
+struct ExFrontier { const int64_t *cube_off; int64_t cubes; const int32_t *len; const uint32_t *bits, *closed; };
+struct ExCheckpoints { int8_t *cube_status; int32_t *len_out; uint32_t *bits_out, *closed_out; };
+
+// The head of every round call, before anything is searched or written: the routing, what the host can refuse, the frontier check and,
+// with `penalty`, the penalty range, both verdicts read in the call's one synchronisation.
+int exq_round_begin(pdp_problem *p, const char *name, bool model_rows, const int64_t *cube_off, int64_t cubes, const int32_t *len,
+                    const uint32_t *bits, const uint32_t *closed, const int32_t *penalty, hipStream_t st)
+{
+    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
+    { const int st_ = exq_sizes(p, name, cubes, model_rows); if (st_ != PDP_OK) return st_; }
+    int64_t info[EXQ_INFO];
+    exq_check_launch(p, cube_off, cubes, len, bits, closed, st);
+    PDP_LAUNCH_CHECK();
+    if (penalty) {
+        hipLaunchKernelGGL(k_exact_nearest_round_check, dim3(1), dim3(EXQ_NT), 0, st, make_view(p), cube_off, penalty, exq_info(p));
+        PDP_LAUNCH_CHECK();
+    }
+    PDP_HIP_CHECK(hipMemcpyAsync(info, exq_info(p), EXQ_INFO * 8, hipMemcpyDeviceToHost, st));
+    PDP_HIP_CHECK(hipStreamSynchronize(st));
+    { const int st_ = exq_verdict(name, info); if (st_ != PDP_OK) return st_; }
+    if (penalty && info[EXW_BAD_PEN] != EXS_NONE) {
+        pdp_set_error("%s: instance %lld has a cube and a penalty outside 0 .. 2^20", name, (long long)info[EXW_BAD_PEN]);
+        return PDP_ERR_INVALID;
+    }
+    return PDP_OK;
+}
+
+// What the three cube launches share; the work and replay records lie at the family's own byte offsets of p->exq.cubes.
+ExRound exq_round_params(pdp_problem *p, const ExFrontier &f, int64_t budget, const ExCheckpoints &c, size_t work_at, size_t replay_at)
+{
+    ExRound r;
+    r.B = p->B; r.total = (uint32_t)f.cubes; r.next = p->ex_next;
+    r.budget = budget;
+    r.route = exq_route(p); r.cube_off = f.cube_off; r.len = f.len; r.bits = f.bits; r.closed = f.closed; r.words = exq_words(p);
+    r.cube_status = c.cube_status; r.len_out = c.len_out; r.bits_out = c.bits_out; r.closed_out = c.closed_out;
+    r.cube_work = (int64_t *)(p->exq.cubes + work_at);
+    r.cube_replay = (int64_t *)(p->exq.cubes + replay_at);
+    r.n_max = p->exq_nmax;
+    r.h = ex_hbm(p);
+    return r;
+}
+
+// The two searching launches of a round: the cubes, persistent, then the per-instance kernel, one wave per instance of a flat grid.
+template <typename Params>
+int exq_round_launch(pdp_problem *p, void (*cubes)(PView, Params), void (*finish)(PView, Params), const Params &xp, size_t lds_bytes,
+                     hipStream_t st)
+{
+    { const int st_ = ex_launch_persistent(p, cubes, xp, (int64_t)xp.r.total, lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    const int64_t flat = std::min<int64_t>((int64_t)p->B, (int64_t)pdp_device_cus() * 16);
+    hipLaunchKernelGGL(finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
+    PDP_LAUNCH_CHECK();
+    return PDP_OK;
+}
+
+// a per-cube record the caller may ask for (NULL: not wanted)
+inline hipError_t exq_record(void *dst, const void *src, size_t bytes, hipStream_t st)
+{
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
+}
+
 int exq_round(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int32_t *len, const uint32_t *bits, const uint32_t *closed,
               int64_t budget, double *count, double *true_count, int64_t *work, int64_t *leaves, int8_t *cube_status, int32_t *len_out,
               uint32_t *bits_out, uint32_t *closed_out, double *cube_count, int64_t *cube_work, int64_t *cube_leaves, int64_t *cube_replay,
               void *stream)
 {
     const char *name = "pdp_exact_count_round";
-    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
-    { const int st_ = exq_sizes(p, name, cubes); if (st_ != PDP_OK) return st_; }
     const hipStream_t st = ST(stream);
-    int64_t info[EXQ_INFO];
-    exq_check_launch(p, cube_off, cubes, len, bits, closed, st);
-    PDP_LAUNCH_CHECK();
-    PDP_HIP_CHECK(hipMemcpyAsync(info, exq_info(p), EXQ_INFO * 8, hipMemcpyDeviceToHost, st));
-    PDP_HIP_CHECK(hipStreamSynchronize(st));
-    { const int st_ = exq_verdict(name, info); if (st_ != PDP_OK) return st_; }
+    { const int st_ = exq_round_begin(p, name, false, cube_off, cubes, len, bits, closed, nullptr, st); if (st_ != PDP_OK) return st_; }
     if (cubes == 0) return PDP_OK;
-    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax, B = p->B;
+    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax;
     // per-cube records: count [total] | work [total] | leaves [total] | replay [total] | rows [total][n_max] | status [total]
     { const int st_ = exs_records(p->exq, total * 32 + total * nmax * 8 + total); if (st_ != PDP_OK) return st_; }
     ExqParams xp;
-    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_ROUND_BUDGET;
-    xp.route = exq_route(p); xp.cube_off = cube_off; xp.len = len; xp.bits = bits; xp.closed = closed; xp.words = exq_words(p);
-    xp.cube_status = cube_status; xp.len_out = len_out; xp.bits_out = bits_out; xp.closed_out = closed_out;
+    xp.r = exq_round_params(p, {cube_off, cubes, len, bits, closed}, budget > 0 ? budget : (int64_t)PDP_EXACT_ROUND_BUDGET,
+                            {cube_status, len_out, bits_out, closed_out}, total * 8, total * 24);
     xp.cube_count = (double *)p->exq.cubes;
-    xp.cube_work = (int64_t *)(p->exq.cubes + total * 8);
     xp.cube_leaves = (int64_t *)(p->exq.cubes + total * 16);
-    xp.cube_replay = (int64_t *)(p->exq.cubes + total * 24);
     xp.rows = (double *)(p->exq.cubes + total * 32);
-    xp.n_max = (int)nmax;
     xp.count = count; xp.true_count = true_count; xp.work = work; xp.leaves = leaves;
-    xp.h = ex_hbm(p);
     xp.h_T = p->ex_nbig > 0 ? (double *)(p->exq.blob + EXQ_INFO * 8) : nullptr;
     xp.h_F = p->exn_blob ? (double *)p->exn_blob : nullptr;
     xp.h_snap = p->exn_blob ? (double *)(p->exn_blob + (size_t)p->V * 8) : nullptr;
-    { const int st_ = ex_launch_persistent(p, k_exact_count_round, xp, (int64_t)total, p->exn_lds_bytes, st); if (st_ != PDP_OK) return st_; }
-    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
-    hipLaunchKernelGGL(k_exact_count_round_accumulate, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
-    if (cube_count) PDP_HIP_CHECK(hipMemcpyAsync(cube_count, xp.cube_count, total * 8, hipMemcpyDeviceToDevice, st));
-    if (cube_work) PDP_HIP_CHECK(hipMemcpyAsync(cube_work, xp.cube_work, total * 8, hipMemcpyDeviceToDevice, st));
-    if (cube_leaves) PDP_HIP_CHECK(hipMemcpyAsync(cube_leaves, xp.cube_leaves, total * 8, hipMemcpyDeviceToDevice, st));
-    if (cube_replay) PDP_HIP_CHECK(hipMemcpyAsync(cube_replay, xp.cube_replay, total * 8, hipMemcpyDeviceToDevice, st));
+    { const int st_ = exq_round_launch(p, k_exact_count_round, k_exact_count_round_accumulate, xp, p->exn_lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    PDP_HIP_CHECK(exq_record(cube_count, xp.cube_count, total * 8, st));
+    PDP_HIP_CHECK(exq_record(cube_work, xp.r.cube_work, total * 8, st));
+    PDP_HIP_CHECK(exq_record(cube_leaves, xp.cube_leaves, total * 8, st));
+    PDP_HIP_CHECK(exq_record(cube_replay, xp.r.cube_replay, total * 8, st));
     return PDP_OK;
 }
 
@@ -4993,34 +5126,28 @@ int exq_expand(pdp_problem *p, const int64_t *cube_off, int64_t cubes, const int
 }
 
 // ---- pdp_exact_solve_round: the deciding search as a sequence of rounds over the same frontier ------------------------------------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_solve_rounds_model.py).  The frontier, its check kernel and
-// the expansion are the count's, called as they are.  ex_search_path is pdp_exact_solve_hinted's search without its check pass, from the
-// shared blocks, with exq_decide's decision and the round budget of ex_search_count_path; a state without an open clause answers 1
+// (specification: include/pdp_hip.h; plain Python: tests/exact_solve_rounds_model.py).  The round scaffold (frontier,
+// check, cursor, decision, checkpoint, cube loop, host head and tail, expansion) is the one above.  ex_search_path is
+// pdp_exact_solve_hinted's search without its check pass, from the shared blocks; a state without an open clause answers 1
 // wherever it is met.  A round is three launches on one stream: the check, the cubes (one counter hands out cube ids, one wave per
 // cube; every cube leaves its record, its checkpoint and, where it answered 1, its model as a row of bytes), the finish (one wave per
 // instance that has a cube: the lowest cube that answered 1 gives the model, the stopped cubes of such an instance become -2 so that the
 // expansion leaves nothing of them).  The state, the slab (ex_lds_layout), the routing and the HBM arrays are k_exact's.  No cube reads a
 // word of another: a cube of a satisfiable instance runs out its round even if a sibling has a model already.
-constexpr int64_t EXV_MAX_ROW_BYTES = (int64_t)1 << 31;
 
 // The deciding search of one path cube by the calling wave.  Returns 1 (val holds a model), 0 (the cube has none) or -1 (budget spent:
-// levels 1 .. *level_out are open, *plen_out of them still as the path has them).  The budget is ex_search_count_path's: tested only where
-// a node begins (`fresh`), on the reads made since the first node that began with level >= plen (`base`; -1: still replaying).
+// levels 1 .. *level_out are open, *plen_out of them still as the path has them).
 template <bool HBM, typename LitT, typename PtrT>
 __device__ int ex_search_path(const ExInst<LitT, PtrT> &X, int64_t budget, const ExPath &Q, int *level_out, int *plen_out, int64_t *work_out,
                               int64_t *replay_out)
 {
-    int level = 0, tlen = 0, plen = Q.len;
-    int64_t work = 0, base = -1;
+    int level = 0, tlen = 0;
+    int64_t work = 0;
     int result = -1;
-    bool fresh = true;
+    ExWalk W{Q.len};
     ExNoCredit none;
     for (;;) {
-        if (fresh) {
-            if (base < 0 && level >= plen) base = work;
-            if (base >= 0 && work - base >= budget) break;
-            fresh = false;
-        }
+        if (W.spent(level, work, budget)) break;
         const ExPass P = ex_propagate(X);
         work += ex_sum(P.reads);
         bool any_conflict = __ballot(P.conflict) != 0ull;
@@ -5032,8 +5159,7 @@ __device__ int ex_search_path(const ExInst<LitT, PtrT> &X, int64_t budget, const
         }
         if (any_conflict) {
             if (!ex_backtrack<HBM>(X, level, tlen, none)) { result = 0; break; }
-            plen = level < plen ? level : plen;                     // `level` was flipped: the path beyond it no longer applies
-            fresh = true;
+            W.flipped(level);
             continue;
         }
         if (any_unit) continue;
@@ -5041,36 +5167,25 @@ __device__ int ex_search_path(const ExInst<LitT, PtrT> &X, int64_t budget, const
         if (wmin == 0x7fffffff) { result = 1; break; }              // no open clause: a model, inside the path too
         const unsigned long long best = ex_branch<HBM, EX_PHASE_HINT>(X, wmin, work);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        exq_decide<HBM>(X, Q, plen, best, level, tlen, none);
-        fresh = true;
+        exq_decide<HBM>(X, Q, W.plen, best, level, tlen, none);
+        W.opened();
     }
-    *level_out = result == -1 ? level : 0; *plen_out = plen;
-    *work_out = work; *replay_out = base < 0 ? work : base;
+    *level_out = result == -1 ? level : 0; *plen_out = W.plen;
+    *work_out = work; *replay_out = W.replay(work);
     return result;
 }
 
 struct ExvParams {
-    int B;
-    uint32_t total;             // cubes of the round
-    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
-    int64_t budget;             // per cube, past its replay
+    ExRound r;                  // cube_status: 1 / 0 / -1; the finish kernel turns the -1 of an answered instance into -2
     const float *hint;          // [V] phase hints (NULL: none)
-    const uint8_t *route;       // [B] 1: the HBM route
-    const int64_t *cube_off;    // [B+1] first cube id of every instance
-    const int32_t *len;         // [total]
-    const uint32_t *bits, *closed;      // [total][words]
-    int words;
-    int8_t *cube_status;        // [total] 1 / 0 / -1; the finish kernel turns the -1 of an answered instance into -2
-    int32_t *len_out; uint32_t *bits_out, *closed_out;      // the checkpoints, shaped as the inputs
-    int64_t *cube_work, *cube_replay;   // [total]
     uint8_t *rows;              // [total][n_max] the assignment of every cube that answered 1
-    int n_max;
     int8_t *status; float *model; int64_t *work; int32_t *first;    // per instance (status and work in/out)
-    ExHbm h;
 };
 
 // cube q of instance I.b: copy the instance (ex_fill), clear the state (pend starts as the hint codes), search along the path; then the
-// cube's record, its model row where it answered 1, and its checkpoint by ex_solve_count_path's ballots.
+// cube's record, its model row where it answered 1, and its checkpoint.  The hint-code expression is written out as in ex_solve, the
+// learning and the split search: a helper shared with them changed the instruction order of those kernels (profiles/exact_time.txt,
+// "scaffold compile"), and ex_solve_near_path's rule is another one (NaN is false there: a distance has no "no hint").
 template <bool HBM, typename LitT, typename PtrT>
 __device__ void ex_solve_path(const ExvParams &xp, const Inst &I, ExInst<LitT, PtrT> X, uint32_t q)
 {
@@ -5082,50 +5197,24 @@ __device__ void ex_solve_path(const ExvParams &xp, const Inst &I, ExInst<LitT, P
         X.val[v] = 0; X.pend[v] = code << EX_HINT_SHIFT; X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
     }
     ex_sync<HBM>();
-    const size_t row = (size_t)q * (size_t)xp.words;
-    const ExPath Q{xp.bits + row, xp.closed + row, xp.len[q]};
+    const ExPath Q = exq_path(xp.r, q);
     int64_t work = 0, replay = 0;
     int level = 0, plen = 0;
-    const int st = ex_search_path<HBM>(X, xp.budget, Q, &level, &plen, &work, &replay);
+    const int st = ex_search_path<HBM>(X, xp.r.budget, Q, &level, &plen, &work, &replay);
     if (st == 1) {
-        uint8_t *out = xp.rows + (size_t)q * (size_t)xp.n_max;
+        uint8_t *out = xp.rows + (size_t)q * (size_t)xp.r.n_max;
         for (int v = lane; v < I.n; v += EX_NT) out[v] = X.val[v] == 1 ? 1 : 0;
     }
-    for (int w = 0; w < xp.words; w += 2) {
-        const int L = 32 * w + lane + 1;
-        const uint32_t mark = L <= level ? X.dvar[L] >> 31 : 0u;
-        const bool path = L <= plen && L <= level;
-        const uint32_t pb = path ? exq_bit(Q.bits, L) : 0u, pc = path ? exq_bit(Q.closed, L) : 0u;
-        const unsigned long long bb = __ballot((pb | (mark & (pc ^ 1u))) != 0u), cc = __ballot(mark != 0u);
-        if (lane == 0) {
-            xp.bits_out[row + w] = (uint32_t)bb; xp.closed_out[row + w] = (uint32_t)cc;
-            if (w + 1 < xp.words) { xp.bits_out[row + w + 1] = (uint32_t)(bb >> 32); xp.closed_out[row + w + 1] = (uint32_t)(cc >> 32); }
-        }
-    }
-    if (lane == 0) {
-        xp.cube_status[q] = (int8_t)st;
-        xp.len_out[q] = level;
-        xp.cube_work[q] = work;
-        xp.cube_replay[q] = replay;
-    }
-    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+    exq_checkpoint<HBM>(X, Q, xp.r, q, st, level, plen, work, replay);
 }
 
 __global__ void __launch_bounds__(EX_NT) k_exact_solve_round(PView pv, ExvParams xp)
 {
     extern __shared__ __align__(16) unsigned char ex_slab[];
-    for (;;) {
-        uint32_t q = 0;
-        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
-        q = __shfl(q, 0);
-        if (q >= xp.total) break;
-        const int lo = exs_instance(xp.cube_off, xp.B, q);
-        const Inst I = load_inst(pv, lo);
-        // the check has passed: every cube's instance has at most 1023 variables.  Both arms end in the barrier of ex_solve_path and fall
-        // through to the end of the loop body (see k_exact_count)
-        if (xp.route[lo]) ex_solve_path<true>(xp, I, ex_bind_hbm(xp.h, I), q);
-        else ex_solve_path<false>(xp, I, ex_bind_lds(ex_slab, I), q);
-    }
+    exq_cubes(pv, xp.r, [&](auto route, const Inst &I, uint32_t q) {
+        constexpr bool HBM = decltype(route)::value;
+        ex_solve_path<HBM>(xp, I, exq_bind<HBM>(xp.r, ex_slab, I), q);
+    });
 }
 
 // The outcome of every instance that has a cube, one wave per instance: first = the lowest cube, counted from the instance's own first
@@ -5135,25 +5224,25 @@ __global__ void __launch_bounds__(EX_NT) k_exact_solve_round_finish(PView pv, Ex
 {
     const int lane = (int)threadIdx.x;
     for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
-        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        const int64_t c0 = xp.r.cube_off[b], nc = xp.r.cube_off[b + 1] - c0;
         if (nc == 0) continue;                                      // wave-uniform
         const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
         int64_t w = 0;
         int at = EXS_NONE, open = 0;
         for (int64_t j = lane; j < nc; j += EX_NT) {
-            const int st = (int)xp.cube_status[c0 + j];
-            w += xp.cube_work[c0 + j];
+            const int st = (int)xp.r.cube_status[c0 + j];
+            w += xp.r.cube_work[c0 + j];
             if (st == 1 && at == EXS_NONE) at = (int)j;
             open |= st == -1;
         }
-        w = exs_sum64(w);
+        w = ex_sum64(w);
         at = ex_min(at);
         const bool found = at != EXS_NONE, stopped = __ballot(open) != 0ull;
         if (found) {
-            const uint8_t *row = xp.rows + (size_t)(c0 + at) * (size_t)xp.n_max;
+            const uint8_t *row = xp.rows + (size_t)(c0 + at) * (size_t)xp.r.n_max;
             for (int v = lane; v < n; v += EX_NT) xp.model[v0 + v] = row[v] ? 1.0f : 0.0f;
             for (int64_t j = lane; j < nc; j += EX_NT)
-                if (xp.cube_status[c0 + j] == -1) xp.cube_status[c0 + j] = -2;
+                if (xp.r.cube_status[c0 + j] == -1) xp.r.cube_status[c0 + j] = -2;
         }
         if (lane == 0) {
             xp.status[b] = (int8_t)(found ? 1 : (stopped ? -1 : 0));
@@ -5168,51 +5257,27 @@ int exv_round(pdp_problem *p, const float *hint, const int64_t *cube_off, int64_
               int32_t *len_out, uint32_t *bits_out, uint32_t *closed_out, int64_t *cube_work, int64_t *cube_replay, void *stream)
 {
     const char *name = "pdp_exact_solve_round";
-    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
-    if (cubes < 0 || cubes > EXS_MAX_CUBES) {
-        pdp_set_error("%s: %lld cubes; a frontier holds 0 .. 2^22", name, (long long)cubes);
-        return PDP_ERR_INVALID;
-    }
-    if (cubes * (int64_t)p->exq_nmax > EXV_MAX_ROW_BYTES) {
-        pdp_set_error("%s: the per-cube model rows (%lld cubes x %d variables) pass 2^31 bytes; split the batch", name, (long long)cubes,
-                      p->exq_nmax);
-        return PDP_ERR_INVALID;
-    }
     const hipStream_t st = ST(stream);
-    int64_t info[EXQ_INFO];
-    exq_check_launch(p, cube_off, cubes, len, bits, closed, st);
-    PDP_LAUNCH_CHECK();
-    PDP_HIP_CHECK(hipMemcpyAsync(info, exq_info(p), EXQ_INFO * 8, hipMemcpyDeviceToHost, st));
-    PDP_HIP_CHECK(hipStreamSynchronize(st));
-    { const int st_ = exq_verdict(name, info); if (st_ != PDP_OK) return st_; }
+    { const int st_ = exq_round_begin(p, name, true, cube_off, cubes, len, bits, closed, nullptr, st); if (st_ != PDP_OK) return st_; }
     if (cubes == 0) return PDP_OK;
-    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax, B = p->B;
+    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax;
     // per-cube records: work [total] | replay [total] | model rows [total][n_max]
     { const int st_ = exs_records(p->exq, total * 16 + total * nmax); if (st_ != PDP_OK) return st_; }
     ExvParams xp;
-    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_SOLVE_ROUND_BUDGET;
+    xp.r = exq_round_params(p, {cube_off, cubes, len, bits, closed}, budget > 0 ? budget : (int64_t)PDP_EXACT_SOLVE_ROUND_BUDGET,
+                            {cube_status, len_out, bits_out, closed_out}, 0, total * 8);
     xp.hint = hint;
-    xp.route = exq_route(p); xp.cube_off = cube_off; xp.len = len; xp.bits = bits; xp.closed = closed; xp.words = exq_words(p);
-    xp.cube_status = cube_status; xp.len_out = len_out; xp.bits_out = bits_out; xp.closed_out = closed_out;
-    xp.cube_work = (int64_t *)p->exq.cubes;
-    xp.cube_replay = (int64_t *)(p->exq.cubes + total * 8);
     xp.rows = (uint8_t *)(p->exq.cubes + total * 16);
-    xp.n_max = (int)nmax;
     xp.status = status; xp.model = model; xp.work = work; xp.first = first;
-    xp.h = ex_hbm(p);
-    { const int st_ = ex_launch_persistent(p, k_exact_solve_round, xp, (int64_t)total, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
-    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
-    hipLaunchKernelGGL(k_exact_solve_round_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
-    if (cube_work) PDP_HIP_CHECK(hipMemcpyAsync(cube_work, xp.cube_work, total * 8, hipMemcpyDeviceToDevice, st));
-    if (cube_replay) PDP_HIP_CHECK(hipMemcpyAsync(cube_replay, xp.cube_replay, total * 8, hipMemcpyDeviceToDevice, st));
+    { const int st_ = exq_round_launch(p, k_exact_solve_round, k_exact_solve_round_finish, xp, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    PDP_HIP_CHECK(exq_record(cube_work, xp.r.cube_work, total * 8, st));
+    PDP_HIP_CHECK(exq_record(cube_replay, xp.r.cube_replay, total * 8, st));
     return PDP_OK;
 }
 
 // ---- pdp_exact_nearest_round: the nearest-model search as a sequence of rounds that share their bound between two launches ---------------
-// (specification: include/pdp_hip.h; plain Python: tests/exact_nearest_rounds_model.py).  The frontier, its check kernel
-// and the expansion are the count's, called as they are.  ex_search_near_path is ex_search_path's structure with ex_search_near's
+// (specification: include/pdp_hip.h; plain Python: tests/exact_nearest_rounds_model.py).  The round scaffold is the one
+// above (see pdp_exact_count_round).  ex_search_near_path is ex_search_path's structure with ex_search_near's
 // accounting: dist is the sum over the trail of exd_cost, restored through ExdCredit / exd_backtrack, the penalty and the hint code stay
 // in pend bits 10-31 and 8-9, and ub -- cost[b] when the round began -- appears in the prune only, so a path is replayed in the same
 // tree under any bound.  A round is four launches on one stream: the frontier check, the penalty range (one workgroup, no atomics;
@@ -5221,63 +5286,27 @@ int exv_round(pdp_problem *p, const float *hint, const int64_t *cube_off, int64_
 // has a cube: the minimum of the cubes' costs, the lowest cube that holds it, its model, the sums, and -2 for the stopped cubes of an
 // instance that reached cost 0).  The state, the slab (ex_lds_layout), the routing and the HBM arrays are k_exact's.  No cube reads a
 // word of another.
-constexpr int EXW_BAD_PEN = 6;                  // word of the check's info block that the penalty kernel owns (EXQ_TOTAL is the last of the count's)
-static_assert(EXW_BAD_PEN > EXQ_TOTAL && EXW_BAD_PEN < EXQ_INFO, "the penalty verdict needs a word of its own");
-
-__device__ __forceinline__ int64_t exw_min64(int64_t x)
-{
-    for (int o = 32; o > 0; o >>= 1) { const int64_t y = (int64_t)__shfl_xor((long long)x, o); x = y < x ? y : x; }
-    return x;
-}
-
-// info[EXW_BAD_PEN] = the lowest instance that has a cube and a penalty outside [0, 2^20] (EXS_NONE: none), by one workgroup: a wave
-// per instance in turn, a lane per variable, the waves' minima through LDS.  It reads cube_off [B+1] and penalty [V] only, which are
-// the caller's whatever the frontier check finds.
-__global__ void __launch_bounds__(EXQ_NT) k_exact_nearest_round_check(PView pv, const int64_t *cube_off, const int32_t *penalty, int64_t *info)
-{
-    __shared__ int low[EXQ_NT / 64];
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    int mine = EXS_NONE;
-    for (int b = wave; b < pv.B; b += EXQ_NT / 64) {
-        if (cube_off[b + 1] <= cube_off[b]) continue;               // wave-uniform
-        const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
-        int bad = 0;
-        for (int v = lane; v < n; v += 64) { const int32_t q = penalty[v0 + v]; bad |= q < 0 || q > EXD_MAX_PENALTY; }
-        if (__ballot(bad) != 0ull && mine == EXS_NONE) mine = b;
-    }
-    if (lane == 0) low[wave] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int first = EXS_NONE;
-        for (int w = 0; w < EXQ_NT / 64; ++w) first = low[w] < first ? low[w] : first;
-        info[EXW_BAD_PEN] = first;
-    }
-}
-
 // The nearest-model search of one path cube by the calling wave, under the bound `ub` (EXD_INF: none).  Returns 1 (the cube has ended:
 // nothing below the bound it ran under is left in it) or -1 (budget spent: levels 1 .. *level_out are open, *plen_out of them still as
-// the path has them).  *cost_out = the cost of the last leaf it accepted (EXDS_NO_COST: none), whose assignment `row` holds.  The budget
-// is ex_search_count_path's.  A path decision on its other polarity adds its penalty at once; a state that reaches ub that way is pruned
-// before any pass and before the budget is tested (`prune` carried into the next turn of the loop).
+// the path has them).  *cost_out = the cost of the last leaf it accepted (EXDS_NO_COST: none), whose assignment `row` holds.  A path
+// decision on its other polarity adds its penalty at once; a state that reaches ub that way is pruned before any pass and before the
+// budget is tested (`prune` carried into the next turn of the loop).
 template <bool HBM, typename LitT, typename PtrT>
 __device__ int ex_search_near_path(const ExInst<LitT, PtrT> &X, int64_t budget, const ExPath &Q, int64_t ub, uint8_t *row, int *level_out,
                                    int *plen_out, int64_t *work_out, int64_t *replay_out, int64_t *cost_out, int *improved_out)
 {
     const int lane = (int)threadIdx.x;
     constexpr int INF = 0x7fffffff;
-    int level = 0, tlen = 0, plen = Q.len, improved = 0;
-    int64_t work = 0, base = -1, dist = 0, accepted = EXDS_NO_COST;
+    int level = 0, tlen = 0, improved = 0;
+    int64_t work = 0, dist = 0, accepted = EXDS_NO_COST;
     int result = -1;
-    bool fresh = true, prune = false;
+    bool prune = false;
+    ExWalk W{Q.len};
     ExNoCredit none;
     for (;;) {
         int wmin = INF;
         if (!prune) {
-            if (fresh) {
-                if (base < 0 && level >= plen) base = work;
-                if (base >= 0 && work - base >= budget) break;
-                fresh = false;
-            }
+            if (W.spent(level, work, budget)) break;
             const ExPass P = ex_propagate(X);
             work += ex_sum(P.reads);
             prune = __ballot(P.conflict) != 0ull;
@@ -5309,53 +5338,43 @@ __device__ int ex_search_near_path(const ExInst<LitT, PtrT> &X, int64_t budget, 
         if (prune) {
             prune = false;
             if (!exd_backtrack<HBM>(X, level, tlen, dist, ub)) { result = 1; break; }
-            plen = level < plen ? level : plen;                     // `level` was flipped: the path beyond it no longer applies
-            fresh = true;
+            W.flipped(level);
             continue;
         }
         const unsigned long long best = ex_branch<HBM, EX_PHASE_INCUMBENT>(X, wmin, work);
         if (best == 0ull) break;            // unreachable (an open clause of width wmin has wmin >= 2 unassigned literals); never index with it
-        exq_decide<HBM>(X, Q, plen, best, level, tlen, none);
-        if (level <= plen && exq_bit(Q.bits, level) != 0u) {
+        exq_decide<HBM>(X, Q, W.plen, best, level, tlen, none);
+        if (level <= W.plen && exq_bit(Q.bits, level) != 0u) {
             // against the hint: its penalty counts at once
             const int v = (int)(0x7fffffffu - (uint32_t)((best >> 1) & 0x7fffffffull));
             dist += (int64_t)(X.pend[v] >> EXD_PEN_SHIFT);
             prune = dist >= ub;
         }
-        fresh = true;
+        W.opened();
     }
-    *level_out = result == -1 ? level : 0; *plen_out = plen;
-    *work_out = work; *replay_out = base < 0 ? work : base; *cost_out = accepted; *improved_out = improved;
+    *level_out = result == -1 ? level : 0; *plen_out = W.plen;
+    *work_out = work; *replay_out = W.replay(work); *cost_out = accepted; *improved_out = improved;
     return result;
 }
 
 struct ExwParams {
-    int B;
-    uint32_t total;             // cubes of the round
-    uint32_t *next;             // the "next cube" counter (zeroed before the launch)
-    int64_t budget;             // per cube, past its replay
+    ExRound r;                  // cube_status: 1 / -1; the finish kernel turns the -1 of an instance at cost 0 into -2
     const float *hint;          // [V] the point the distance is measured from (NULL: all false)
     const int32_t *penalty;     // [V] (NULL: all 1)
-    const uint8_t *route;       // [B] 1: the HBM route
-    const int64_t *cube_off;    // [B+1] first cube id of every instance
-    const int32_t *len;         // [total]
-    const uint32_t *bits, *closed;      // [total][words]
-    int words;
-    int8_t *cube_status;        // [total] 1 / -1; the finish kernel turns the -1 of an instance at cost 0 into -2
-    int32_t *len_out; uint32_t *bits_out, *closed_out;      // the checkpoints, shaped as the inputs
-    int64_t *cube_cost, *cube_work, *cube_replay; int32_t *cube_improvements;       // [total]
+    int64_t *cube_cost; int32_t *cube_improvements;         // [total]
     uint8_t *rows;              // [total][n_max] the assignment of the last leaf every cube accepted
-    int n_max;
     int8_t *status; int64_t *cost; float *model; int64_t *work; int32_t *improvements; int32_t *first;     // per instance
-    ExHbm h;
 };
 
-// cube q of instance I.b under the bound ub: copy the instance (ex_fill), clear the state (pend starts as the hint's codes and the
-// penalties), search along the path; then the cube's record and its checkpoint by ex_solve_count_path's ballots.
+// cube q of instance I.b under the bound cost[I.b] as it stood when the round began (the finish kernel writes it): copy the instance
+// (ex_fill), clear the state (pend starts as the hint's codes and the penalties, which the check has found in range), search along
+// the path; then the cube's record and its checkpoint.
 template <bool HBM, typename LitT, typename PtrT>
-__device__ void ex_solve_near_path(const ExwParams &xp, const Inst &I, ExInst<LitT, PtrT> X, uint32_t q, int64_t ub)
+__device__ void ex_solve_near_path(const ExwParams &xp, const Inst &I, ExInst<LitT, PtrT> X, uint32_t q)
 {
     const int lane = (int)threadIdx.x;
+    const int64_t seen = xp.cost[I.b];
+    const int64_t ub = seen < 0 ? EXD_INF : seen;
     ex_fill<HBM>(I, X);
     for (int v = lane; v < I.n; v += EX_NT) {
         const uint32_t code = (xp.hint && xp.hint[I.v0 + v] > 0.5f) ? 1u : 2u;          // NaN compares false
@@ -5363,51 +5382,22 @@ __device__ void ex_solve_near_path(const ExwParams &xp, const Inst &I, ExInst<Li
         X.val[v] = 0; X.pend[v] = (w << EXD_PEN_SHIFT) | (code << EX_HINT_SHIFT); X.cnt[2 * v] = 0u; X.cnt[2 * v + 1] = 0u;
     }
     ex_sync<HBM>();
-    const size_t row = (size_t)q * (size_t)xp.words;
-    const ExPath Q{xp.bits + row, xp.closed + row, xp.len[q]};
+    const ExPath Q = exq_path(xp.r, q);
     int64_t work = 0, replay = 0, cost = EXDS_NO_COST;
     int level = 0, plen = 0, improved = 0;
-    const int st = ex_search_near_path<HBM>(X, xp.budget, Q, ub, xp.rows + (size_t)q * (size_t)xp.n_max, &level, &plen, &work, &replay, &cost,
-                                            &improved);
-    for (int w = 0; w < xp.words; w += 2) {
-        const int L = 32 * w + lane + 1;
-        const uint32_t mark = L <= level ? X.dvar[L] >> 31 : 0u;
-        const bool path = L <= plen && L <= level;
-        const uint32_t pb = path ? exq_bit(Q.bits, L) : 0u, pc = path ? exq_bit(Q.closed, L) : 0u;
-        const unsigned long long bb = __ballot((pb | (mark & (pc ^ 1u))) != 0u), cc = __ballot(mark != 0u);
-        if (lane == 0) {
-            xp.bits_out[row + w] = (uint32_t)bb; xp.closed_out[row + w] = (uint32_t)cc;
-            if (w + 1 < xp.words) { xp.bits_out[row + w + 1] = (uint32_t)(bb >> 32); xp.closed_out[row + w + 1] = (uint32_t)(cc >> 32); }
-        }
-    }
-    if (lane == 0) {
-        xp.cube_status[q] = (int8_t)st;
-        xp.len_out[q] = level;
-        xp.cube_cost[q] = cost;
-        xp.cube_work[q] = work;
-        xp.cube_replay[q] = replay;
-        xp.cube_improvements[q] = improved;
-    }
-    ex_sync<HBM>();                                                 // the slab is reused by the wave's next cube
+    const int st = ex_search_near_path<HBM>(X, xp.r.budget, Q, ub, xp.rows + (size_t)q * (size_t)xp.r.n_max, &level, &plen, &work, &replay,
+                                            &cost, &improved);
+    if (lane == 0) { xp.cube_cost[q] = cost; xp.cube_improvements[q] = improved; }
+    exq_checkpoint<HBM>(X, Q, xp.r, q, st, level, plen, work, replay);
 }
 
 __global__ void __launch_bounds__(EX_NT) k_exact_nearest_round(PView pv, ExwParams xp)
 {
     extern __shared__ __align__(16) unsigned char ex_slab[];
-    for (;;) {
-        uint32_t q = 0;
-        if (threadIdx.x == 0) q = atomicAdd(xp.next, 1u);
-        q = __shfl(q, 0);
-        if (q >= xp.total) break;
-        const int lo = exs_instance(xp.cube_off, xp.B, q);
-        const int64_t seen = xp.cost[lo];                           // the instance's cost when the round began: the finish kernel writes it
-        const int64_t ub = seen < 0 ? EXD_INF : seen;
-        const Inst I = load_inst(pv, lo);
-        // the checks have passed: every cube's instance has at most 1023 variables and penalties in range.  Both arms end in the barrier
-        // of ex_solve_near_path and fall through to the end of the loop body (see k_exact_count)
-        if (xp.route[lo]) ex_solve_near_path<true>(xp, I, ex_bind_hbm(xp.h, I), q, ub);
-        else ex_solve_near_path<false>(xp, I, ex_bind_lds(ex_slab, I), q, ub);
-    }
+    exq_cubes(pv, xp.r, [&](auto route, const Inst &I, uint32_t q) {
+        constexpr bool HBM = decltype(route)::value;
+        ex_solve_near_path<HBM>(xp, I, exq_bind<HBM>(xp.r, ex_slab, I), q);
+    });
 }
 
 // The outcome of every instance that has a cube, one wave per instance: best = the minimum of the cubes' costs, first = the lowest cube,
@@ -5419,21 +5409,21 @@ __global__ void __launch_bounds__(EX_NT) k_exact_nearest_round_finish(PView pv, 
 {
     const int lane = (int)threadIdx.x;
     for (int b = (int)blockIdx.x; b < pv.B; b += (int)gridDim.x) {
-        const int64_t c0 = xp.cube_off[b], nc = xp.cube_off[b + 1] - c0;
+        const int64_t c0 = xp.r.cube_off[b], nc = xp.r.cube_off[b + 1] - c0;
         if (nc == 0) continue;                                      // wave-uniform
         const int v0 = pv.inst_v0[b], n = pv.inst_v0[b + 1] - v0;
         int64_t w = 0, best = EXD_INF;
         int imp = 0, open = 0;
         for (int64_t j = lane; j < nc; j += EX_NT) {
             const int64_t c = xp.cube_cost[c0 + j];
-            w += xp.cube_work[c0 + j];
+            w += xp.r.cube_work[c0 + j];
             imp += xp.cube_improvements[c0 + j];
-            open |= xp.cube_status[c0 + j] == -1;
+            open |= xp.r.cube_status[c0 + j] == -1;
             if (c >= 0 && c < best) best = c;
         }
-        w = exs_sum64(w);
+        w = ex_sum64(w);
         imp = ex_sum(imp);
-        best = exw_min64(best);
+        best = ex_min64(best);
         int64_t cost = xp.cost[b];
         const bool better = best != EXD_INF && (cost < 0 || best < cost);
         int at = EXS_NONE;
@@ -5441,14 +5431,14 @@ __global__ void __launch_bounds__(EX_NT) k_exact_nearest_round_finish(PView pv, 
             for (int64_t j = lane; j < nc && at == EXS_NONE; j += EX_NT)
                 if (xp.cube_cost[c0 + j] == best) at = (int)j;
             at = ex_min(at);
-            const uint8_t *row = xp.rows + (size_t)(c0 + at) * (size_t)xp.n_max;
+            const uint8_t *row = xp.rows + (size_t)(c0 + at) * (size_t)xp.r.n_max;
             for (int v = lane; v < n; v += EX_NT) xp.model[v0 + v] = row[v] ? 1.0f : 0.0f;
             cost = best;
         }
         const bool stopped = __ballot(open) != 0ull;
         if (cost == 0) {
             for (int64_t j = lane; j < nc; j += EX_NT)
-                if (xp.cube_status[c0 + j] == -1) xp.cube_status[c0 + j] = -2;
+                if (xp.r.cube_status[c0 + j] == -1) xp.r.cube_status[c0 + j] = -2;
         }
         if (lane == 0) {
             xp.status[b] = (int8_t)(cost == 0 ? 1 : (stopped ? -1 : (cost >= 0 ? 1 : 0)));
@@ -5466,58 +5456,26 @@ int exw_round(pdp_problem *p, const float *hint, const int32_t *penalty, const i
               int64_t *cube_cost, int64_t *cube_work, int64_t *cube_replay, int32_t *cube_improvements, void *stream)
 {
     const char *name = "pdp_exact_nearest_round";
-    { const int st_ = exq_prepare(p); if (st_ != PDP_OK) return st_; }
-    if (cubes < 0 || cubes > EXS_MAX_CUBES) {
-        pdp_set_error("%s: %lld cubes; a frontier holds 0 .. 2^22", name, (long long)cubes);
-        return PDP_ERR_INVALID;
-    }
-    if (cubes * (int64_t)p->exq_nmax > EXV_MAX_ROW_BYTES) {
-        pdp_set_error("%s: the per-cube model rows (%lld cubes x %d variables) pass 2^31 bytes; split the batch", name, (long long)cubes,
-                      p->exq_nmax);
-        return PDP_ERR_INVALID;
-    }
     const hipStream_t st = ST(stream);
-    int64_t info[EXQ_INFO];
-    exq_check_launch(p, cube_off, cubes, len, bits, closed, st);
-    PDP_LAUNCH_CHECK();
-    if (penalty) {
-        hipLaunchKernelGGL(k_exact_nearest_round_check, dim3(1), dim3(EXQ_NT), 0, st, make_view(p), cube_off, penalty, exq_info(p));
-        PDP_LAUNCH_CHECK();
-    }
-    PDP_HIP_CHECK(hipMemcpyAsync(info, exq_info(p), EXQ_INFO * 8, hipMemcpyDeviceToHost, st));
-    PDP_HIP_CHECK(hipStreamSynchronize(st));
-    { const int st_ = exq_verdict(name, info); if (st_ != PDP_OK) return st_; }
-    if (penalty && info[EXW_BAD_PEN] != EXS_NONE) {
-        pdp_set_error("%s: instance %lld has a cube and a penalty outside 0 .. 2^20", name, (long long)info[EXW_BAD_PEN]);
-        return PDP_ERR_INVALID;
-    }
+    { const int st_ = exq_round_begin(p, name, true, cube_off, cubes, len, bits, closed, penalty, st); if (st_ != PDP_OK) return st_; }
     if (cubes == 0) return PDP_OK;
-    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax, B = p->B;
+    const size_t total = (size_t)cubes, nmax = (size_t)p->exq_nmax;
     // per-cube records: cost [total] | work [total] | replay [total] | improvements [total] (padded to 8 bytes) | model rows [total][n_max]
     const size_t imp_bytes = (total * 4 + 7) & ~(size_t)7;
     { const int st_ = exs_records(p->exq, total * 24 + imp_bytes + total * nmax); if (st_ != PDP_OK) return st_; }
     ExwParams xp;
-    xp.B = p->B; xp.total = (uint32_t)total; xp.next = p->ex_next;
-    xp.budget = budget > 0 ? budget : (int64_t)PDP_EXACT_NEAREST_ROUND_BUDGET;
+    xp.r = exq_round_params(p, {cube_off, cubes, len, bits, closed}, budget > 0 ? budget : (int64_t)PDP_EXACT_NEAREST_ROUND_BUDGET,
+                            {cube_status, len_out, bits_out, closed_out}, total * 8, total * 16);
     xp.hint = hint; xp.penalty = penalty;
-    xp.route = exq_route(p); xp.cube_off = cube_off; xp.len = len; xp.bits = bits; xp.closed = closed; xp.words = exq_words(p);
-    xp.cube_status = cube_status; xp.len_out = len_out; xp.bits_out = bits_out; xp.closed_out = closed_out;
     xp.cube_cost = (int64_t *)p->exq.cubes;
-    xp.cube_work = (int64_t *)(p->exq.cubes + total * 8);
-    xp.cube_replay = (int64_t *)(p->exq.cubes + total * 16);
     xp.cube_improvements = (int32_t *)(p->exq.cubes + total * 24);
     xp.rows = (uint8_t *)(p->exq.cubes + total * 24 + imp_bytes);
-    xp.n_max = (int)nmax;
     xp.status = status; xp.cost = cost; xp.model = model; xp.work = work; xp.improvements = improvements; xp.first = first;
-    xp.h = ex_hbm(p);
-    { const int st_ = ex_launch_persistent(p, k_exact_nearest_round, xp, (int64_t)total, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
-    const int64_t flat = std::min<int64_t>((int64_t)B, (int64_t)pdp_device_cus() * 16);
-    hipLaunchKernelGGL(k_exact_nearest_round_finish, dim3((unsigned)flat), dim3(EX_NT), 0, st, make_view(p), xp);
-    PDP_LAUNCH_CHECK();
-    if (cube_cost) PDP_HIP_CHECK(hipMemcpyAsync(cube_cost, xp.cube_cost, total * 8, hipMemcpyDeviceToDevice, st));
-    if (cube_work) PDP_HIP_CHECK(hipMemcpyAsync(cube_work, xp.cube_work, total * 8, hipMemcpyDeviceToDevice, st));
-    if (cube_replay) PDP_HIP_CHECK(hipMemcpyAsync(cube_replay, xp.cube_replay, total * 8, hipMemcpyDeviceToDevice, st));
-    if (cube_improvements) PDP_HIP_CHECK(hipMemcpyAsync(cube_improvements, xp.cube_improvements, total * 4, hipMemcpyDeviceToDevice, st));
+    { const int st_ = exq_round_launch(p, k_exact_nearest_round, k_exact_nearest_round_finish, xp, p->ex_lds_bytes, st); if (st_ != PDP_OK) return st_; }
+    PDP_HIP_CHECK(exq_record(cube_cost, xp.cube_cost, total * 8, st));
+    PDP_HIP_CHECK(exq_record(cube_work, xp.r.cube_work, total * 8, st));
+    PDP_HIP_CHECK(exq_record(cube_replay, xp.r.cube_replay, total * 8, st));
+    PDP_HIP_CHECK(exq_record(cube_improvements, xp.cube_improvements, total * 4, st));
     return PDP_OK;
 }
 

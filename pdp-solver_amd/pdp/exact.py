@@ -306,31 +306,63 @@ def split_solve(prob, part, budget, hint, split, device):
     du = np.zeros(len(st), dtype=np.int8)
     again = [int(j) for j in np.nonzero(st == -1)[0]]
     if again:
-        part = part() if callable(part) else part
-        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
-        sub = _problem([part[j] for j in again], device)
-        hint2 = None if hint is None else torch.cat([hint[voff[j]:voff[j + 1]] for j in again])
-        r = [t.cpu().numpy() for t in sub.exact_solve_split(budget, hints=hint2, depth=auto_depth(len(again), device), stats=True)[:5]]
-        del sub
-        off = 0
-        for k, j in enumerate(again):
-            n = int(voff[j + 1] - voff[j])
-            st[j], du[j] = r[0][k], r[4][k]
-            wk[j] += r[2][k]
-            model[voff[j]:voff[j + 1]] = r[1][off:off + n]
-            off += n
+        depth = auto_depth(len(again), device)
+        r = _on_their_own(part, again, device, lambda sub, cut: sub.exact_solve_split(budget, hints=cut(hint), depth=depth, stats=True)[:5],
+                          {1: model})
+        st[again], du[again] = r[0], r[4]
+        wk[again] += r[2]
     return st, model, wk, du
+
+
+def _on_their_own(part, which, device, call, per_variable):
+    """Instances ``which`` (ascending indices) of a problem as a problem of their own.  ``part``: the loader items, or a callable that
+    returns them.  call(sub, cut) runs on the new problem, cut(t) being the values of a per-variable tensor (or None) that belong to
+    it; its tensors come back as numpy arrays.  ``per_variable`` {index of a result: array of the whole problem}: those results are
+    written back into the instances' slices."""
+    part = part() if callable(part) else part
+    voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
+    sub = _problem([part[j] for j in which], device)
+    r = [t.cpu().numpy() for t in call(sub, lambda t: None if t is None else torch.cat([t[int(voff[j]):int(voff[j + 1])] for j in which]))]
+    del sub
+    off = 0
+    for j in which:
+        n = int(voff[j + 1] - voff[j])
+        for k, whole in per_variable.items():
+            whole[voff[j]:voff[j + 1]] = r[k][off:off + n]
+        off += n
+    return r
+
+
+def _rounds_give(open_cubes, device, waves_per_simd, max_give):
+    """The levels every stopped cube gives away so that ``open_cubes`` of them become AUTO_CUBES_PER_WAVE cubes per resident wave of a
+    round kernel that holds ``waves_per_simd``: the smallest g with open_cubes * (1 + g) >= that target, 0 once the frontier fills the
+    GPU, capped by ``max_give`` and by the 2^22 cubes of a frontier"""
+    waves = torch.cuda.get_device_properties(device).multi_processor_count * 4 * waves_per_simd
+    target = AUTO_CUBES_PER_WAVE * waves
+    open_cubes = max(1, int(open_cubes))
+    give = -(-target // open_cubes) - 1
+    return max(0, min(give, max_give, native.COUNT_ROUNDS_MAX_CUBES // open_cubes - 1))
+
+
+def _drop_spent(state, total):
+    """The total budget of a search in rounds, between two rounds: the cubes of every instance whose work has reached ``total`` (an int,
+    or an int64 tensor of one value per instance on the state's device) leave the frontier; what the state holds of the instance
+    stays.  Returns (the mask of the instances that left, their number); the number is the one host synchronisation."""
+    per = state.cube_off[1:] - state.cube_off[:-1]
+    spent = (state.work >= total) & (per > 0)
+    left = int(spent.sum().item())
+    if left:
+        keep = ~torch.repeat_interleave(spent, per)
+        state.len, state.bits, state.closed = state.len[keep].contiguous(), state.bits[keep].contiguous(), state.closed[keep].contiguous()
+        state.cube_off = torch.cat([state.cube_off[:1], torch.cumsum(torch.where(spent, torch.zeros_like(per), per), 0)])
+    return spent, left
 
 
 def solve_rounds_give(open_cubes, device):
     """split='rounds' of the deciding search: rounds_give's rule with k_exact_solve_round's occupancy -- the smallest g with open_cubes *
     (1 + g) >= AUTO_CUBES_PER_WAVE cubes per resident wave, 0 once the frontier fills the GPU -- capped by SOLVE_ROUNDS_MAX_GIVE and by the
     2^22 cubes of a frontier"""
-    waves = torch.cuda.get_device_properties(device).multi_processor_count * 4 * SOLVE_ROUNDS_WAVES_PER_SIMD
-    target = AUTO_CUBES_PER_WAVE * waves
-    open_cubes = max(1, int(open_cubes))
-    give = -(-target // open_cubes) - 1
-    return max(0, min(give, SOLVE_ROUNDS_MAX_GIVE, native.COUNT_ROUNDS_MAX_CUBES // open_cubes - 1))
+    return _rounds_give(open_cubes, device, SOLVE_ROUNDS_WAVES_PER_SIMD, SOLVE_ROUNDS_MAX_GIVE)
 
 
 def solve_rounds(prob, part, budget, hint, round_budget, give, rounds, device):
@@ -347,28 +379,12 @@ def solve_rounds(prob, part, budget, hint, round_budget, give, rounds, device):
     while state.cubes and (rounds is None or done < rounds):
         prob.exact_solve_round(state, round_budget or SOLVE_ROUND_BUDGET, solve_rounds_give(state.cubes, device) if give is None else give)
         done += 1
-        per = state.cube_off[1:] - state.cube_off[:-1]
-        spent = (state.work >= total) & (per > 0)
-        if bool(spent.any()):
-            # out of reads: the instance's cubes leave the frontier, its status stays -1
-            keep = ~torch.repeat_interleave(spent, per)
-            state.len, state.bits, state.closed = state.len[keep], state.bits[keep], state.closed[keep]
-            state.cube_off = torch.cat([state.cube_off[:1], torch.cumsum(torch.where(spent, torch.zeros_like(per), per), 0)])
+        _drop_spent(state, total)                                                 # out of reads: the status stays -1
     st, model, wk, used = state.status.cpu().numpy(), state.model.cpu().numpy(), state.work.cpu().numpy(), state.rounds.cpu().numpy()
     wide = [int(j) for j in np.nonzero(st == -2)[0]]
     if wide:
-        part = part() if callable(part) else part
-        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
-        sub = _problem([part[j] for j in wide], device)
-        hint2 = None if hint is None else torch.cat([hint[voff[j]:voff[j + 1]] for j in wide])
-        r = [t.cpu().numpy() for t in sub.exact_solve(budget, hints=hint2)]
-        del sub
-        off = 0
-        for k, j in enumerate(wide):
-            n = int(voff[j + 1] - voff[j])
-            st[j], wk[j] = r[0][k], r[2][k]
-            model[voff[j]:voff[j + 1]] = r[1][off:off + n]
-            off += n
+        r = _on_their_own(part, wide, device, lambda sub, cut: sub.exact_solve(budget, hints=cut(hint)), {1: model})
+        st[wide], wk[wide] = r[0], r[2]
     return st, model, wk, used
 
 
@@ -656,25 +672,14 @@ def nearest_rounds_give(open_cubes, device):
     """split='rounds' of the nearest-model search: rounds_give's rule with k_exact_nearest_round's occupancy -- the smallest g with
     open_cubes * (1 + g) >= AUTO_CUBES_PER_WAVE cubes per resident wave, 0 once the frontier fills the GPU -- capped by
     NEAREST_ROUNDS_MAX_GIVE and by the 2^22 cubes of a frontier"""
-    waves = torch.cuda.get_device_properties(device).multi_processor_count * 4 * NEAREST_ROUNDS_WAVES_PER_SIMD
-    target = AUTO_CUBES_PER_WAVE * waves
-    open_cubes = max(1, int(open_cubes))
-    give = -(-target // open_cubes) - 1
-    return max(0, min(give, NEAREST_ROUNDS_MAX_GIVE, native.COUNT_ROUNDS_MAX_CUBES // open_cubes - 1))
+    return _rounds_give(open_cubes, device, NEAREST_ROUNDS_WAVES_PER_SIMD, NEAREST_ROUNDS_MAX_GIVE)
 
 
 def nearest_rounds_drop_spent(state, total):
     """The total budget of nearest_rounds, between two rounds: the cubes of every instance whose work has reached ``total`` (an int, or an
     int64 tensor of one value per instance on the state's device) leave the frontier of the NearestState; the instance's status stays -1
     and it keeps its cost and model.  Returns the number of instances that left."""
-    per = state.cube_off[1:] - state.cube_off[:-1]
-    spent = (state.work >= total) & (per > 0)
-    left = int(spent.sum().item())
-    if left:
-        keep = ~torch.repeat_interleave(spent, per)
-        state.len, state.bits, state.closed = state.len[keep].contiguous(), state.bits[keep].contiguous(), state.closed[keep].contiguous()
-        state.cube_off = torch.cat([state.cube_off[:1], torch.cumsum(torch.where(spent, torch.zeros_like(per), per), 0)])
-    return left
+    return _drop_spent(state, total)[1]
 
 
 def nearest_rounds(prob, part, budget, hint, pen, start, round_budget, give, rounds, device):
@@ -700,18 +705,8 @@ def nearest_rounds(prob, part, budget, hint, pen, start, round_budget, give, rou
     co[st == -3] = 0
     wide = [int(j) for j in np.nonzero(st == -2)[0]]
     if wide:
-        part = part() if callable(part) else part
-        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
-        sub = _problem([part[j] for j in wide], device)
-        cut = lambda t: None if t is None else torch.cat([t[int(voff[j]):int(voff[j + 1])] for j in wide])
-        r = [t.cpu().numpy() for t in sub.exact_nearest(cut(hint), cut(pen), budget)]
-        del sub
-        off = 0
-        for k, j in enumerate(wide):
-            n = int(voff[j + 1] - voff[j])
-            st[j], co[j], wk[j] = r[0][k], r[1][k], r[3][k]
-            model[voff[j]:voff[j + 1]] = r[2][off:off + n]
-            off += n
+        r = _on_their_own(part, wide, device, lambda sub, cut: sub.exact_nearest(cut(hint), cut(pen), budget), {2: model})
+        st[wide], co[wide], wk[wide] = r[0], r[1], r[3]
     return st, co, model, wk, used
 
 
@@ -833,18 +828,10 @@ def count_split(prob, part, budget, split, device):
     du = np.zeros(len(st), dtype=np.int8)
     again = [int(j) for j in np.nonzero(st == -1)[0]]
     if again:
-        part = part() if callable(part) else part
-        voff = np.concatenate([[0], np.cumsum([int(it[0]) for it in part])])
-        sub = _problem([part[j] for j in again], device)
-        r = [t.cpu().numpy() for t in sub.exact_count_split(budget, depth=auto_depth(len(again), device), stats=True)[:6]]
-        del sub
-        off = 0
-        for k, j in enumerate(again):
-            n = int(voff[j + 1] - voff[j])
-            st[j], co[j], du[j] = r[0][k], r[1][k], r[5][k]
-            wk[j] += r[3][k]
-            tc[voff[j]:voff[j + 1]] = r[2][off:off + n]
-            off += n
+        depth = auto_depth(len(again), device)
+        r = _on_their_own(part, again, device, lambda sub, cut: sub.exact_count_split(budget, depth=depth, stats=True)[:6], {2: tc})
+        st[again], co[again], du[again] = r[0], r[1], r[5]
+        wk[again] += r[3]
     return st, co, tc, wk, du
 
 
@@ -852,11 +839,7 @@ def rounds_give(open_cubes, device):
     """split='rounds': the levels every stopped cube gives away so that ``open_cubes`` of them become AUTO_CUBES_PER_WAVE cubes per resident
     wave of k_exact_count_round -- the smallest g with open_cubes * (1 + g) >= that target, 0 once the frontier fills the GPU -- capped
     by ROUNDS_MAX_GIVE and by the 2^22 cubes of a frontier"""
-    waves = torch.cuda.get_device_properties(device).multi_processor_count * 4 * ROUNDS_WAVES_PER_SIMD
-    target = AUTO_CUBES_PER_WAVE * waves
-    open_cubes = max(1, int(open_cubes))
-    give = -(-target // open_cubes) - 1
-    return max(0, min(give, ROUNDS_MAX_GIVE, native.COUNT_ROUNDS_MAX_CUBES // open_cubes - 1))
+    return _rounds_give(open_cubes, device, ROUNDS_WAVES_PER_SIMD, ROUNDS_MAX_GIVE)
 
 
 def count_rounds(prob, part, budget, round_budget, give, rounds, device):
@@ -873,14 +856,7 @@ def count_rounds(prob, part, budget, round_budget, give, rounds, device):
     while state.cubes and (rounds is None or done < rounds):
         prob.exact_count_round(state, round_budget or ROUND_BUDGET, rounds_give(state.cubes, device) if give is None else give)
         done += 1
-        per = state.cube_off[1:] - state.cube_off[:-1]
-        spent = (state.work >= total) & (per > 0)
-        if bool(spent.any()):
-            # out of reads: the instance's cubes leave the frontier, its totals stay as the lower bound they are
-            keep = ~torch.repeat_interleave(spent, per)
-            ended |= spent
-            state.len, state.bits, state.closed = state.len[keep], state.bits[keep], state.closed[keep]
-            state.cube_off = torch.cat([state.cube_off[:1], torch.cumsum(torch.where(spent, torch.zeros_like(per), per), 0)])
+        ended |= _drop_spent(state, total)[0]                                     # out of reads: the totals stay as the lower bound they are
     status = torch.where(ended, torch.full_like(state.status, -1), state.status)
     return (status.cpu().numpy(), state.count.cpu().numpy(), state.true_count.cpu().numpy(), state.work.cpu().numpy(),
             state.rounds.cpu().numpy())

@@ -245,13 +245,13 @@ COUNT_ROUNDS_MAX_CUBES = 1 << 22    # cubes of one frontier
 EXACT_NEAREST_MAX_PENALTY = 1 << 20 # pdp_exact_nearest and pdp_exact_nearest_round: a penalty is an integer in [0, 2^20]
 
 
-class CountState(object):
-    """A resumable count (Problem.exact_count_begin / exact_count_round): plain tensors, so it can be saved, moved with cpu() / to() and
-    continued on another Problem built from the same items.  The frontier: cube_off int64 [B+1], len int32 [cubes], bits and closed int32
-    [cubes, words] (two bits per decision level, include/pdp_hip.h).  The running totals: count float64 [B], true_count float64 [V],
-    work and leaves int64 [B].  status int8 [B]: 1 complete, -1 cubes are open (count is a lower bound), -2 not searched; rounds int32
-    [B]: the rounds the instance had a cube in."""
-    FIELDS = ('cube_off', 'len', 'bits', 'closed', 'count', 'true_count', 'work', 'leaves', 'status', 'rounds')
+class _RoundState(object):
+    """What the three resumable states share: plain tensors named by FIELDS, KINDS[field] = (dtype, shape kind), the shape kinds being
+    'B', 'V', 'B+1', 'cubes' and 'cubes x words'."""
+    FIELDS = ()
+    KINDS = {}
+    FRONTIER = {'cube_off': (torch.int64, 'B+1'), 'len': (torch.int32, 'cubes'), 'bits': (torch.int32, 'cubes x words'),
+                'closed': (torch.int32, 'cubes x words')}
 
     @property
     def cubes(self):
@@ -259,7 +259,7 @@ class CountState(object):
 
     def to(self, device):
         "a copy on ``device``"
-        s = CountState()
+        s = type(self)()
         for f in self.FIELDS:
             setattr(s, f, getattr(self, f).to(device).clone())
         return s
@@ -269,23 +269,31 @@ class CountState(object):
 
     def validate(self, problem):
         "what the library cannot see from raw pointers: devices, dtypes and shapes (the frontier's contents are checked on the GPU)"
-        kinds = {'cube_off': torch.int64, 'len': torch.int32, 'bits': torch.int32, 'closed': torch.int32, 'count': torch.float64,
-                 'true_count': torch.float64, 'work': torch.int64, 'leaves': torch.int64, 'status': torch.int8, 'rounds': torch.int32}
         cubes = int(self.len.numel())
-        sizes = {'cube_off': (problem.B + 1,), 'len': (cubes,), 'count': (problem.B,), 'true_count': (problem.V,), 'work': (problem.B,),
-                 'leaves': (problem.B,), 'status': (problem.B,), 'rounds': (problem.B,)}
         words = C.c_int32()
         check(lib().pdp_exact_count_frontier_words(problem._h, C.byref(words)))
-        sizes['bits'] = sizes['closed'] = (cubes, words.value)
+        shapes = {'B': (problem.B,), 'V': (problem.V,), 'B+1': (problem.B + 1,), 'cubes': (cubes,), 'cubes x words': (cubes, words.value)}
         for f in self.FIELDS:
             t = getattr(self, f)
-            if not torch.is_tensor(t) or t.device != problem.device or t.dtype != kinds[f] or tuple(t.shape) != sizes[f] or not t.is_contiguous():
-                raise NativeError("state.%s must be a contiguous %s tensor of shape %s on %s" % (f, kinds[f], sizes[f], problem.device))
+            kind, size = self.KINDS[f][0], shapes[self.KINDS[f][1]]
+            if not torch.is_tensor(t) or t.device != problem.device or t.dtype != kind or tuple(t.shape) != size or not t.is_contiguous():
+                raise NativeError("state.%s must be a contiguous %s tensor of shape %s on %s" % (f, kind, size, problem.device))
         if cubes > COUNT_ROUNDS_MAX_CUBES:
             raise NativeError("state holds %d cubes; a frontier holds at most 2^22" % cubes)
 
 
-class SolveState(object):
+class CountState(_RoundState):
+    """A resumable count (Problem.exact_count_begin / exact_count_round): plain tensors, so it can be saved, moved with cpu() / to() and
+    continued on another Problem built from the same items.  The frontier: cube_off int64 [B+1], len int32 [cubes], bits and closed int32
+    [cubes, words] (two bits per decision level, include/pdp_hip.h).  The running totals: count float64 [B], true_count float64 [V],
+    work and leaves int64 [B].  status int8 [B]: 1 complete, -1 cubes are open (count is a lower bound), -2 not searched; rounds int32
+    [B]: the rounds the instance had a cube in."""
+    FIELDS = ('cube_off', 'len', 'bits', 'closed', 'count', 'true_count', 'work', 'leaves', 'status', 'rounds')
+    KINDS = dict(_RoundState.FRONTIER, count=(torch.float64, 'B'), true_count=(torch.float64, 'V'), work=(torch.int64, 'B'),
+                 leaves=(torch.int64, 'B'), status=(torch.int8, 'B'), rounds=(torch.int32, 'B'))
+
+
+class SolveState(_RoundState):
     """A resumable deciding search (Problem.exact_solve_begin / exact_solve_round): plain tensors, so it can be saved, moved with cpu() /
     to() and continued on another Problem built from the same items.  The frontier is CountState's: cube_off int64 [B+1], len int32
     [cubes], bits and closed int32 [cubes, words].  hint float32 [V]: the phase hints of every round (NaN: none).  status int8 [B]: -1
@@ -293,40 +301,11 @@ class SolveState(object):
     instance of status 1, zeros elsewhere; work int64 [B]: the reads of all its cubes and rounds; rounds int32 [B]: the rounds the
     instance had a cube in."""
     FIELDS = ('cube_off', 'len', 'bits', 'closed', 'hint', 'status', 'model', 'work', 'rounds')
-
-    @property
-    def cubes(self):
-        return int(self.len.numel())
-
-    def to(self, device):
-        "a copy on ``device``"
-        s = SolveState()
-        for f in self.FIELDS:
-            setattr(s, f, getattr(self, f).to(device).clone())
-        return s
-
-    def cpu(self):
-        return self.to('cpu')
-
-    def validate(self, problem):
-        "what the library cannot see from raw pointers: devices, dtypes and shapes (the frontier's contents are checked on the GPU)"
-        kinds = {'cube_off': torch.int64, 'len': torch.int32, 'bits': torch.int32, 'closed': torch.int32, 'hint': torch.float32,
-                 'status': torch.int8, 'model': torch.float32, 'work': torch.int64, 'rounds': torch.int32}
-        cubes = int(self.len.numel())
-        sizes = {'cube_off': (problem.B + 1,), 'len': (cubes,), 'hint': (problem.V,), 'status': (problem.B,), 'model': (problem.V,),
-                 'work': (problem.B,), 'rounds': (problem.B,)}
-        words = C.c_int32()
-        check(lib().pdp_exact_count_frontier_words(problem._h, C.byref(words)))
-        sizes['bits'] = sizes['closed'] = (cubes, words.value)
-        for f in self.FIELDS:
-            t = getattr(self, f)
-            if not torch.is_tensor(t) or t.device != problem.device or t.dtype != kinds[f] or tuple(t.shape) != sizes[f] or not t.is_contiguous():
-                raise NativeError("state.%s must be a contiguous %s tensor of shape %s on %s" % (f, kinds[f], sizes[f], problem.device))
-        if cubes > COUNT_ROUNDS_MAX_CUBES:
-            raise NativeError("state holds %d cubes; a frontier holds at most 2^22" % cubes)
+    KINDS = dict(_RoundState.FRONTIER, hint=(torch.float32, 'V'), status=(torch.int8, 'B'), model=(torch.float32, 'V'),
+                 work=(torch.int64, 'B'), rounds=(torch.int32, 'B'))
 
 
-class NearestState(object):
+class NearestState(_RoundState):
     """A resumable nearest-model search (Problem.exact_nearest_begin / exact_nearest_round): plain tensors, so it can be saved, moved with
     cpu() / to() and continued on another Problem built from the same items.  The frontier is CountState's: cube_off int64 [B+1], len
     int32 [cubes], bits and closed int32 [cubes, words].  hint float32 [V]: the point the distance is measured from (> 0.5 true, every
@@ -336,38 +315,9 @@ class NearestState(object):
     the reads of all its cubes and rounds; improvements int32 [B]: the leaves its cubes accepted; rounds int32 [B]: the rounds the
     instance had a cube in."""
     FIELDS = ('cube_off', 'len', 'bits', 'closed', 'hint', 'penalty', 'status', 'cost', 'model', 'work', 'improvements', 'rounds')
-
-    @property
-    def cubes(self):
-        return int(self.len.numel())
-
-    def to(self, device):
-        "a copy on ``device``"
-        s = NearestState()
-        for f in self.FIELDS:
-            setattr(s, f, getattr(self, f).to(device).clone())
-        return s
-
-    def cpu(self):
-        return self.to('cpu')
-
-    def validate(self, problem):
-        "what the library cannot see from raw pointers: devices, dtypes and shapes (the frontier's contents are checked on the GPU)"
-        kinds = {'cube_off': torch.int64, 'len': torch.int32, 'bits': torch.int32, 'closed': torch.int32, 'hint': torch.float32,
-                 'penalty': torch.int32, 'status': torch.int8, 'cost': torch.int64, 'model': torch.float32, 'work': torch.int64,
-                 'improvements': torch.int32, 'rounds': torch.int32}
-        cubes = int(self.len.numel())
-        sizes = {'cube_off': (problem.B + 1,), 'len': (cubes,), 'hint': (problem.V,), 'penalty': (problem.V,), 'status': (problem.B,),
-                 'cost': (problem.B,), 'model': (problem.V,), 'work': (problem.B,), 'improvements': (problem.B,), 'rounds': (problem.B,)}
-        words = C.c_int32()
-        check(lib().pdp_exact_count_frontier_words(problem._h, C.byref(words)))
-        sizes['bits'] = sizes['closed'] = (cubes, words.value)
-        for f in self.FIELDS:
-            t = getattr(self, f)
-            if not torch.is_tensor(t) or t.device != problem.device or t.dtype != kinds[f] or tuple(t.shape) != sizes[f] or not t.is_contiguous():
-                raise NativeError("state.%s must be a contiguous %s tensor of shape %s on %s" % (f, kinds[f], sizes[f], problem.device))
-        if cubes > COUNT_ROUNDS_MAX_CUBES:
-            raise NativeError("state holds %d cubes; a frontier holds at most 2^22" % cubes)
+    KINDS = dict(_RoundState.FRONTIER, hint=(torch.float32, 'V'), penalty=(torch.int32, 'V'), status=(torch.int8, 'B'),
+                 cost=(torch.int64, 'B'), model=(torch.float32, 'V'), work=(torch.int64, 'B'), improvements=(torch.int32, 'B'),
+                 rounds=(torch.int32, 'B'))
 
 
 class Problem(object):
@@ -905,24 +855,45 @@ class Problem(object):
         cube_replay int64 [cubes], and the checkpoints len_out int32 [cubes], bits_out and closed_out int32 [cubes, words]).  The state
         may come from another Problem of the same items.  A malformed state raises before anything is searched or written.  More than
         2^22 cubes after the expansion raises; lower ``give``.  Synchronises the current stream twice."""
-        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
-            raise ValueError("budget must be an integer number of clause-literal reads per cube (0: the library default), got %r" % (budget,))
-        if isinstance(give, bool) or not isinstance(give, numbers.Integral) or not 0 <= give <= COUNT_ROUNDS_MAX_N:
-            raise ValueError("give must be an integer from 0 to %d, got %r" % (COUNT_ROUNDS_MAX_N, give))
-        if not isinstance(state, CountState):
-            raise ValueError("state must come from exact_count_begin, got %s" % type(state).__name__)
-        state.validate(self)
+        self._round_args(state, CountState, 'exact_count_begin', budget, give)
         dev = self.device
-        cubes, words = int(state.len.numel()), int(state.bits.size(1))
-        cube_status = torch.empty(cubes, dtype=torch.int8, device=dev)
-        len_out = torch.empty(cubes, dtype=torch.int32, device=dev)
-        bits_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
-        closed_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        cubes = state.cubes
+        cube_status, len_out, bits_out, closed_out = out = self._round_buffers(state)
         rec = [torch.empty(cubes, dtype=torch.float64 if k == 0 else torch.int64, device=dev) if stats else None for k in range(4)]
         check(lib().pdp_exact_count_round(self._h, ptr(state.cube_off), C.c_int64(cubes), ptr(state.len), ptr(state.bits), ptr(state.closed),
                                           C.c_int64(int(budget)), ptr(state.count), ptr(state.true_count), ptr(state.work), ptr(state.leaves),
                                           ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out), ptr(rec[0]), ptr(rec[1]),
                                           ptr(rec[2]), ptr(rec[3]), _stream()))
+        made, ran = self._round_expand(state, *out, give)
+        open_ = state.cube_off[1:] > state.cube_off[:-1]
+        state.status = torch.where(state.status == -2, state.status, torch.where(open_, -1, 1).to(torch.int8))
+        if not stats:
+            return made
+        return made, (ran, cube_status, rec[0], rec[1], rec[2], rec[3], len_out, bits_out, closed_out)
+
+    def _round_args(self, state, cls, begin_name, budget, give):
+        "the refusals every round call makes before anything runs"
+        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
+            raise ValueError("budget must be an integer number of clause-literal reads per cube (0: the library default), got %r" % (budget,))
+        if isinstance(give, bool) or not isinstance(give, numbers.Integral) or not 0 <= give <= COUNT_ROUNDS_MAX_N:
+            raise ValueError("give must be an integer from 0 to %d, got %r" % (COUNT_ROUNDS_MAX_N, give))
+        if not isinstance(state, cls):
+            raise ValueError("state must come from %s, got %s" % (begin_name, type(state).__name__))
+        state.validate(self)
+
+    def _round_buffers(self, state):
+        "what every round writes per cube: (cube_status, len_out, bits_out, closed_out), the checkpoints shaped as the frontier"
+        dev = self.device
+        cubes, words = int(state.len.numel()), int(state.bits.size(1))
+        return (torch.empty(cubes, dtype=torch.int8, device=dev), torch.empty(cubes, dtype=torch.int32, device=dev),
+                torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes],
+                torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes])
+
+    def _round_expand(self, state, cube_status, len_out, bits_out, closed_out, give):
+        """The tail of every round (pdp_exact_count_expand): the checkpoints of the cubes that stopped become the state's frontier, each
+        cut into up to ``give`` children and a remainder.  Returns (open cubes, the cube_off of the frontier that ran)."""
+        dev = self.device
+        cubes, words = int(state.len.numel()), int(state.bits.size(1))
         capacity = min(cubes * (1 + int(give)), COUNT_ROUNDS_MAX_CUBES)
         cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=dev)
         len_new = torch.empty(capacity, dtype=torch.int32, device=dev)
@@ -936,11 +907,7 @@ class Problem(object):
         made = int(made.value)
         state.rounds += (ran[1:] > ran[:-1]).to(torch.int32)
         state.cube_off, state.len, state.bits, state.closed = cube_off, len_new[:made], bits_new[:made], closed_new[:made]
-        open_ = cube_off[1:] > cube_off[:-1]
-        state.status = torch.where(state.status == -2, state.status, torch.where(open_, -1, 1).to(torch.int8))
-        if not stats:
-            return made
-        return made, (ran, cube_status, rec[0], rec[1], rec[2], rec[3], len_out, bits_out, closed_out)
+        return made, ran
 
     def exact_solve_begin(self, hints=None):
         """The state of a resumable deciding search (pdp_exact_solve_round): the root frontier -- one cube of length 0 per instance of at
@@ -971,38 +938,17 @@ class Problem(object):
         words], and first int32 [B]: the instance's lowest cube that answered 1, -1 none).  The state may come from another Problem of the
         same items.  A malformed state raises before anything is searched or written.  More than 2^22 cubes after the expansion raises;
         lower ``give``.  Synchronises the current stream twice."""
-        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
-            raise ValueError("budget must be an integer number of clause-literal reads per cube (0: the library default), got %r" % (budget,))
-        if isinstance(give, bool) or not isinstance(give, numbers.Integral) or not 0 <= give <= COUNT_ROUNDS_MAX_N:
-            raise ValueError("give must be an integer from 0 to %d, got %r" % (COUNT_ROUNDS_MAX_N, give))
-        if not isinstance(state, SolveState):
-            raise ValueError("state must come from exact_solve_begin, got %s" % type(state).__name__)
-        state.validate(self)
+        self._round_args(state, SolveState, 'exact_solve_begin', budget, give)
         dev = self.device
-        cubes, words = int(state.len.numel()), int(state.bits.size(1))
-        cube_status = torch.empty(cubes, dtype=torch.int8, device=dev)
-        len_out = torch.empty(cubes, dtype=torch.int32, device=dev)
-        bits_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
-        closed_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        cubes = state.cubes
+        cube_status, len_out, bits_out, closed_out = out = self._round_buffers(state)
         first = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
         rec = [torch.empty(cubes, dtype=torch.int64, device=dev) if stats else None for _ in range(2)]
         check(lib().pdp_exact_solve_round(self._h, ptr(state.hint), ptr(state.cube_off), C.c_int64(cubes), ptr(state.len), ptr(state.bits),
                                           ptr(state.closed), C.c_int64(int(budget)), ptr(state.status), ptr(state.model), ptr(state.work),
                                           ptr(first), ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out), ptr(rec[0]),
                                           ptr(rec[1]), _stream()))
-        capacity = min(cubes * (1 + int(give)), COUNT_ROUNDS_MAX_CUBES)
-        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=dev)
-        len_new = torch.empty(capacity, dtype=torch.int32, device=dev)
-        bits_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
-        closed_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
-        made = C.c_int64()
-        ran = state.cube_off
-        check(lib().pdp_exact_count_expand(self._h, ptr(ran), C.c_int64(cubes), ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out),
-                                           C.c_int32(int(give)), C.c_int64(capacity), ptr(cube_off), ptr(len_new), ptr(bits_new),
-                                           ptr(closed_new), C.byref(made), _stream()))
-        made = int(made.value)
-        state.rounds += (ran[1:] > ran[:-1]).to(torch.int32)
-        state.cube_off, state.len, state.bits, state.closed = cube_off, len_new[:made], bits_new[:made], closed_new[:made]
+        made, ran = self._round_expand(state, *out, give)
         if not stats:
             return made
         return made, (ran, cube_status, rec[0], rec[1], len_out, bits_out, closed_out, first)
@@ -1067,19 +1013,10 @@ class Problem(object):
         another Problem of the same items.  A malformed state, or a penalty out of range on an instance that has a cube, raises before
         anything is searched or written.  More than 2^22 cubes after the expansion raises; lower ``give``.  Synchronises the current
         stream twice."""
-        if isinstance(budget, bool) or not isinstance(budget, numbers.Integral):
-            raise ValueError("budget must be an integer number of clause-literal reads per cube (0: the library default), got %r" % (budget,))
-        if isinstance(give, bool) or not isinstance(give, numbers.Integral) or not 0 <= give <= COUNT_ROUNDS_MAX_N:
-            raise ValueError("give must be an integer from 0 to %d, got %r" % (COUNT_ROUNDS_MAX_N, give))
-        if not isinstance(state, NearestState):
-            raise ValueError("state must come from exact_nearest_begin, got %s" % type(state).__name__)
-        state.validate(self)
+        self._round_args(state, NearestState, 'exact_nearest_begin', budget, give)
         dev = self.device
-        cubes, words = int(state.len.numel()), int(state.bits.size(1))
-        cube_status = torch.empty(cubes, dtype=torch.int8, device=dev)
-        len_out = torch.empty(cubes, dtype=torch.int32, device=dev)
-        bits_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
-        closed_out = torch.empty(max(cubes, 1), words, dtype=torch.int32, device=dev)[:cubes]
+        cubes = state.cubes
+        cube_status, len_out, bits_out, closed_out = out = self._round_buffers(state)
         first = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
         rec = [torch.empty(cubes, dtype=torch.int64, device=dev) if stats else None for _ in range(3)]
         rec_imp = torch.empty(cubes, dtype=torch.int32, device=dev) if stats else None
@@ -1088,19 +1025,7 @@ class Problem(object):
                                             ptr(state.model), ptr(state.work), ptr(state.improvements), ptr(first), ptr(cube_status),
                                             ptr(len_out), ptr(bits_out), ptr(closed_out), ptr(rec[0]), ptr(rec[1]), ptr(rec[2]), ptr(rec_imp),
                                             _stream()))
-        capacity = min(cubes * (1 + int(give)), COUNT_ROUNDS_MAX_CUBES)
-        cube_off = torch.empty(self.B + 1, dtype=torch.int64, device=dev)
-        len_new = torch.empty(capacity, dtype=torch.int32, device=dev)
-        bits_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
-        closed_new = torch.empty(max(capacity, 1), words, dtype=torch.int32, device=dev)
-        made = C.c_int64()
-        ran = state.cube_off
-        check(lib().pdp_exact_count_expand(self._h, ptr(ran), C.c_int64(cubes), ptr(cube_status), ptr(len_out), ptr(bits_out), ptr(closed_out),
-                                           C.c_int32(int(give)), C.c_int64(capacity), ptr(cube_off), ptr(len_new), ptr(bits_new),
-                                           ptr(closed_new), C.byref(made), _stream()))
-        made = int(made.value)
-        state.rounds += (ran[1:] > ran[:-1]).to(torch.int32)
-        state.cube_off, state.len, state.bits, state.closed = cube_off, len_new[:made], bits_new[:made], closed_new[:made]
+        made, ran = self._round_expand(state, *out, give)
         if not stats:
             return made
         return made, (ran, cube_status, rec[0], rec[1], rec[2], rec_imp, len_out, bits_out, closed_out, first)
